@@ -51,11 +51,6 @@ import time
 
 import numpy as np
 
-# One HIP stream per batch in flight (4) + torch's streams: with the runtime's default of 4 hardware queues two
-# of them would share a queue and serialise.  Must be set before the HIP runtime initialises (i.e. before torch);
-# libilcc_hip.so does the same when it is loaded first.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -181,9 +176,10 @@ def generate(kind, n_frames, seed, workers):
 def ensure_world(args):
     """`--gpus N` means N ranks, one per device -- or the run fails.  Under a launcher (WORLD_SIZE set: the driver's
     `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`) the two numbers must agree.  A plain
-    `python bench.py --gpus N` with N > 1 replaces itself with that launcher command (rendezvous on 127.0.0.1), so the
-    flag can never silently run one rank and report n_gpus 1.  N ranks need N devices; ILCC_BENCH_SINGLE_DEVICE (the 1-GPU
-    test hook that puts every rank on device 0) lifts that."""
+    `python bench.py --gpus N` with N > 1 runs that launcher command as a child process (rendezvous on 127.0.0.1) and exits
+    with its status, so the flag can never silently run one rank and report n_gpus 1.  N ranks need N devices;
+    ILCC_BENCH_SINGLE_DEVICE (the 1-GPU test hook that puts every rank on device 0) lifts that.  This process never opens
+    the GPU itself: the device count comes from a short-lived child, so the launcher's ranks are the only GPU processes."""
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
     single = bool(os.environ.get("ILCC_BENCH_SINGLE_DEVICE"))
@@ -196,8 +192,9 @@ def ensure_world(args):
     if args.gpus == 1:
         return
     import socket
-    import torch
-    ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    import subprocess
+    ndev = int(subprocess.check_output([sys.executable, "-c", "import torch; print(torch.cuda.device_count() "
+                                        "if torch.cuda.is_available() else 0)"], text=True).split()[-1])
     if ndev < args.gpus and not single:
         raise SystemExit("bench.py: --gpus %d needs %d HIP devices, this node shows %d (one rank per device; "
                          "ILCC_BENCH_SINGLE_DEVICE=1 is the 1-GPU test hook)" % (args.gpus, args.gpus, ndev))
@@ -209,7 +206,8 @@ def ensure_world(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
     print("bench.py: --gpus %d without a launcher: re-executing as `%s`" % (args.gpus, " ".join(cmd[1:9])), file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd)
+    raise SystemExit(rc if rc >= 0 else 128 - rc)      # a rank killed by a signal: the shell's 128 + signal
 
 
 def main():
@@ -238,7 +236,13 @@ def main():
     ap.add_argument("--solver", choices=("grid", "reference"), default="grid",
                     help="reference: the TIMED region runs ILCC_SOLVER_REFERENCE_LOCAL (K7a instead of K6 + K7r) -- profiling runs of "
                          "that mode (tools/gpu_profile_reference.sh); the headline and the driver's run are `grid`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the compact result records of the last timed step (what the "
+                         "timed path hands its caller) to DIR/records.npy: [frames, record floats] float32, layout "
+                         "sharding.pack_records; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     ensure_world(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -478,6 +482,8 @@ def main():
             # tag = (rank * B + b) * F + f and a content check word per record (sharding.verify_records)
             assert gathered is not None and tuple(gathered.shape) == (world * FS, rec_w)
             verify_records(gathered.cpu().numpy(), np.arange(world * FS))
+    if args.dump_outputs and rank == 0:
+        dump_records(args.dump_outputs, gathered.cpu().numpy() if dist_on else np.concatenate(last))
     tm = est.timing()
 
     # ONE batch at a time (in flight 1, nothing else on the chip): the only exclusive launch durations.  roofline.frac is priced
@@ -895,6 +901,26 @@ def config5_leg(N, synth, inputs, device, steps=10):
             "hbm_frac": steps * F / dt * (16 * lidar.n_points + 12 * board.n_corners + 64) / 1e9 / HBM_PEAK_GBPS,
             "what": "configs[4], inputs resident, four batches in flight; frac = credited lane-instr of one batch's K6 launches / their "
                     "summed duration with ONE batch in flight / the 78.6 T issue peak"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_records(out_dir, records):
+    """--dump-outputs: the last timed step's compact records as out_dir/records.npy (float32).  When they exceed
+    DUMP_MAX_BYTES, a fixed, seeded sample of the frames is written instead, with the sampled frame indices (float64,
+    ascending) in out_dir/records_frames.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    records = np.ascontiguousarray(records, dtype=np.float32)
+    index_path = os.path.join(out_dir, "records_frames.npy")
+    if os.path.exists(index_path):
+        os.remove(index_path)
+    if records.nbytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (records[0].nbytes + 8)      # (room for both .npy headers)
+        frames = np.sort(np.random.default_rng(0).choice(len(records), keep, replace=False))
+        np.save(index_path, frames.astype(np.float64))
+        records = records[frames]
+    np.save(os.path.join(out_dir, "records.npy"), records)
 
 
 class Rec:

@@ -257,13 +257,11 @@ int32_t ilcc_extract_batch_device(ilcc_handle* h, const float* d_xyzi, const uin
                                   uint32_t n_frames, const float* d_clicks, ilcc_result* out);
 
 /* Asynchronous form of ilcc_extract_batch_device: enqueue the whole path for one batch and return;
- * up to 4 batches may be in flight per handle (each in its own buffers and stream; run the process with
- * GPU_MAX_HW_QUEUES >= 5, HIP's default of 4 makes two of the streams share a hardware queue), so the short
- * latency-bound stages of one batch overlap with the grid search of another.  *ticket identifies the
- * batch; ilcc_wait blocks until it is complete and copies its records to out (n_frames entries).
- * (The library never touches the environment: the HOST exports GPU_MAX_HW_QUEUES=8 before the HIP runtime starts --
- * the Python package does it on import, the C++ mains in host/ do it first thing in main().  The first use of the
- * fourth slot prints a one-time note when the variable is absent or below 5.)
+ * up to 4 batches may be in flight per handle (each in its own buffers and stream; streams that share one of the
+ * process's hardware queues serialise), so the short latency-bound stages of one batch overlap with the grid search
+ * of another.  *ticket identifies the batch; ilcc_wait blocks until it is complete and copies its records to out
+ * (n_frames entries).  (The library never touches the environment: the hardware-queue count is the host's setting.
+ * The first use of the fourth slot prints a one-time note when fewer than 5 queues are configured.)
  * Tickets must be waited for in submission order once all slots are taken (ILCC_CAPACITY otherwise).
  * The inputs must stay valid and unchanged until the matching ilcc_wait returns. */
 int32_t ilcc_submit_batch_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets,

@@ -21,8 +21,8 @@ using namespace ilcc;
 #define ILCC_SLOTS 4
 #endif
 constexpr int kSlots = ILCC_SLOTS;   // batches in flight per handle (submit/wait); slot 0 serves the synchronous calls.
-                            // Every slot has its own stream: the process needs GPU_MAX_HW_QUEUES >= 5 (HIP default: 4), otherwise two
-                            // slot streams share one hardware queue and serialise (measured: 113 k instead of 164 k frames/s)
+                            // Every slot has its own stream: with fewer than 5 hardware queues in the process two slot
+                            // streams share one hardware queue and serialise (measured: 113 k instead of 164 k frames/s)
 
 // One in-flight batch: its own stream, events, stage buffers and pinned result staging.
 struct Slot {
@@ -273,10 +273,10 @@ void free_slot(Slot& sl) {
   sl = Slot{};
 }
 
-// The HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue
+// The HIP runtime maps streams onto the hardware queues GPU_MAX_HW_QUEUES allows and streams that share a queue
 // serialise: a fourth batch in flight only pays with >= 5 queues.  The variable is read when the runtime initialises and
-// belongs to the HOST process (the Python package exports it on import, the C++ mains in host/ first thing in main()):
-// the library only reads it, and says so once when the fourth slot is first used with fewer than 5 queues configured.
+// belongs to the HOST process: the library only reads it, and says so once when the fourth slot is first used with fewer
+// than 5 queues configured.
 void warn_hw_queues_once(int slot_index) {
   static std::once_flag once;   // handles of several threads (one per GPU) may reach this together
   if (slot_index < 3) return;
@@ -284,9 +284,10 @@ void warn_hw_queues_once(int slot_index) {
     const char* v = std::getenv("GPU_MAX_HW_QUEUES");
     if (v && std::atoi(v) >= 5) return;
     std::fprintf(stderr,
-                 "libilcc_hip: GPU_MAX_HW_QUEUES=%s: with fewer than 5 hardware queues the fourth batch in flight shares a "
-                 "queue with another one and serialises; keep at most 3 tickets outstanding or export GPU_MAX_HW_QUEUES=8 "
-                 "before the HIP runtime starts (the library does not modify the environment)\n", v ? v : "(unset: HIP's default is 4)");
+                 "libilcc_hip: GPU_MAX_HW_QUEUES=%s: "
+                 "with fewer than 5 hardware queues the fourth batch in flight shares a queue with another one and "
+                 "serialises; keep at most 3 tickets outstanding for full overlap (the library does not modify the "
+                 "environment)\n", v ? v : "(unset: HIP's default is 4)");
   });
 }
 

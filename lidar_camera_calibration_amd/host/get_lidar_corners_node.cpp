@@ -186,7 +186,6 @@ class CornerNode {
 }  // namespace
 
 int main(int argc, char** argv) {
-  (void)setenv("GPU_MAX_HW_QUEUES", "8", /*overwrite=*/0);   // host-side, before the HIP runtime starts (include/ilcc_hip.h)
   ros::init(argc, argv, "lidar_corners");
   ros::NodeHandle nh;
   CornerNode node(nh);

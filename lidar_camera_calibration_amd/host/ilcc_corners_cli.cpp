@@ -18,9 +18,6 @@
 using namespace ilcc_host;
 
 int main(int argc, char** argv) {
-  // the library keeps up to four batches in flight on four HIP streams: more hardware queues than HIP's default of 4,
-  // exported by the HOST before the runtime starts (include/ilcc_hip.h, ilcc_submit_batch_device); never overrides the user
-  (void)setenv("GPU_MAX_HW_QUEUES", "8", /*overwrite=*/0);
   std::string cloud_path, bag_path, topic = "/velodyne_points", yaml_path, out_path, solver = "grid";
   PointXYZI click{0, 0, 0, 0};
   int device = -1;

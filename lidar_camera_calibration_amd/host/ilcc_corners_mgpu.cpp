@@ -163,7 +163,6 @@ int run_rank(RankJob* j) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  (void)setenv("GPU_MAX_HW_QUEUES", "8", /*overwrite=*/0);   // host-side, before the first HIP call (include/ilcc_hip.h)
   bool accept_ambiguous = false, accept_low_coverage = false;
   const char* prog = argv[0];
   while (argc > 1 && std::strncmp(argv[1], "--", 2) == 0) {

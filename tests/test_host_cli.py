@@ -220,14 +220,29 @@ def _bench(env_extra, args, launcher=None, timeout=300, with_stderr=False):
     return (json.loads(lines[0]), r.stderr) if with_stderr else json.loads(lines[0])
 
 
-def test_bench_multi_rank_path_with_one_rccl_rank():
+def test_bench_multi_rank_path_with_one_rccl_rank(tmp_path):
     """bench.py's N > 1 code path -- process group over RCCL (backend "nccl"), records packed on the GPU, ONE gather per
     step on a side stream, rank 0 verifying tags + content checks of what arrived -- forced with a single rank, so that
-    RCCL itself is exercised on the 1-GPU box."""
+    RCCL itself is exercised on the 1-GPU box.  --dump-outputs then writes the gathered records of the last step."""
     out = _bench({"ILCC_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29611"},
-                 ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs", "--batches-per-step", "2", "--frames-per-batch", "256"])
+                 ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs", "--batches-per-step", "2", "--frames-per-batch", "256",
+                  "--dump-outputs", str(tmp_path)])
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["value"] > 1000
     assert out["config"]["frames_per_step_per_gpu"] == 512
+    rec = np.load(tmp_path / "records.npy")
+    assert rec.dtype == np.float32 and rec.shape == (512, 20 + 3 * synth.Board().n_corners)
+    assert np.array_equal(rec[:, 16], np.arange(512, dtype=np.float32))        # tags: frame order of the step
+
+
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the compact records the timed path handed back in its last step, as DIR/records.npy; --steps is
+    the number of timed steps and ms_per_step the time of one."""
+    out = _bench({}, ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs", "--frames-per-batch", "64",
+                      "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    rec = np.load(tmp_path / "records.npy")
+    assert rec.dtype == np.float32 and rec.shape == (64, 20 + 3 * synth.Board().n_corners)
+    assert (rec[:, 0] == N.OK).sum() >= 48 and out["frames_ok"] == "%d/64" % (rec[:, 0] == N.OK).sum()
 
 
 def test_bench_two_ranks_on_one_device_over_gloo():

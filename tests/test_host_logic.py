@@ -112,6 +112,28 @@ def test_bench_reads_its_roofline_inputs_from_committed_profiles():
     assert bench.k6_pmc(2, 100) is None          # no file for that batch size: traffic is null, never a scaled guess
 
 
+def test_bench_dump_keeps_a_seeded_sample_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs writes every record while they fit in DUMP_MAX_BYTES, else the same seeded sample of frames each time,
+    with their indices beside them."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rec = np.arange(1000 * 25, dtype=np.float32).reshape(1000, 25)
+    bench.dump_records(str(tmp_path / "all"), rec)
+    assert np.array_equal(np.load(tmp_path / "all" / "records.npy"), rec) and not (tmp_path / "all" / "records_frames.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40000 + 4096)
+    for d in ("a", "b"):
+        bench.dump_records(str(tmp_path / d), rec)
+    got, frames = np.load(tmp_path / "a" / "records.npy"), np.load(tmp_path / "a" / "records_frames.npy")
+    assert got.dtype == np.float32 and frames.dtype == np.float64 and len(frames) == 40000 // (100 + 8)
+    assert np.all(np.diff(frames) > 0) and np.array_equal(got, rec[frames.astype(np.int64)])
+    assert got.nbytes + frames.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(frames, np.load(tmp_path / "b" / "records_frames.npy"))
+    bench.dump_records(str(tmp_path / "a"), rec[:10])                 # a later run that fits leaves no stale index behind
+    assert not (tmp_path / "a" / "records_frames.npy").exists()
+
+
 def test_k6_credit_matches_the_isa():
     """bench.py credits each executed K6 evaluation with the VALU instruction count of the term: the constants there, the
     committed profiles/r06_k6_isa_count.json and a fresh run of tools/k6_isa_count.sh on the current source (hipcc -S,

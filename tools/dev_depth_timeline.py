@@ -3,7 +3,6 @@ thing in question: under it the depth cliff disappears).  Uses ilcc_debug_timeli
 to one reference event) and the host's own clock around submit / wait.
 usage: [ILCC_HIP_LIB=build/ab/libilcc_hip_s8.so] python tools/dev_depth_timeline.py DEPTH [steps=40] [out.json] [config=2|5]"""
 import ctypes as C, json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import bench
