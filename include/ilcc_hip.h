@@ -350,8 +350,10 @@ int32_t ilcc_grid_cost(ilcc_handle* h, const float* yz, const uint8_t* label, ui
                        int32_t use_oob, float* cost_out, int32_t* best_index, float* best_cost);
 
 /* The GRID solver as the pipeline runs it on a SMALL batch -- walk layout, the three launches that locate the minimum (seed,
- * refinement, anchor rounds; batches of >= 512 frames fuse them into k6_locate, whose equality with the three launches is a test
- * of its own: test_fused_locate_equals_the_three_launches), common pre-pass, full pass with its near-tie list, then the refinement
+ * refinement, anchor rounds; batches of >= 512 frames fuse them into k6_locate.  The two paths give the same final results -- the
+ * full pass is exact for any bound it is given, test_fused_locate_equals_the_three_launches -- but not the same bound: the fused
+ * path keeps an 8 x 8 refinement window on grids whose seed stride is wider than 8 translations, where the launches widen it to
+ * 16 x 16, and runs one anchor round against kAnchorRounds), common pre-pass, full pass with its near-tie list, then the refinement
  * with the near-tie recount and its first-round shortcut -- on caller-supplied labelled points (host buffers).  Out: the grid argmin and its fp32 cost, the refined lattice point (units of step / refine_div from the
  * grid's minima), phase, fixed-point costs (units of 2^-40) of the result and of the cheapest neighbouring basin, rounds, hops,
  * ILCC_FLAG_* and the near-tie count.  Test/diagnostic entry (adversarial inputs for the fp32 ranking). */

@@ -578,7 +578,7 @@ void seeded_by_full_table_records(Ctx& full, const ilcc_handle* h, GridPartial* 
 // Locating the minimum with three kinds of launches (batches too small for k6_locate's one workgroup per frame): seed over the
 // decimated tables, refinement around its argmin (both on the walk's prefix, with a bound word of their own: their sums are not
 // costs of complete candidates), then kAnchorRounds anchor rounds on every point, which publish the frame's real bound.
-int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, Ctx& full) {
+int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, const LocatePlan& lp, Ctx& full) {
   Ctx seed = c;
   seed.cth = h->d_cth2;
   seed.sth = h->d_sth2;
@@ -591,9 +591,9 @@ int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStrea
   seed.partial = sl.d_partial2;
   // the "nearest to zero" indices of the decimated tables (the kernel reads ay[c_ty] / az[c_tz] for its rim test and
   // uses all three for the tie-break distance: they must index THIS launch's tables, not the full ones)
-  seed.c_th = std::min(std::max(c.c_th / std::max(1, h->seed_stride_th), 0), h->n_th2 - 1);
-  seed.c_ty = std::min(c.c_ty / std::max(1, h->seed_stride_t), h->n_ty2 - 1);
-  seed.c_tz = std::min(c.c_tz / std::max(1, h->seed_stride_t), h->n_tz2 - 1);
+  seed.c_th = lp.c_th2;
+  seed.c_ty = lp.c_ty2;
+  seed.c_tz = lp.c_tz2;
   seed.walk_limit = (uint32_t)ILCC_SEED_POINTS;
   seed.grid_bound = sl.d_bound_sub;
   launch_grid_cost(seed, s, /*use_oob=*/1, nullptr, true);
@@ -607,11 +607,8 @@ int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStrea
   refine.seed_stride_t = h->seed_stride_t;
   refine.seed_stride_th = h->seed_stride_th;
   refine.seed_off_th = h->seed_stride_th / 2;
-#ifndef ILCC_REFINE_WIDE
-#define ILCC_REFINE_WIDE 1
-#endif
-  refine.refine_window = (ILCC_REFINE_WIDE && h->seed_stride_t > 2 * kTileA) ? 4 : 2;   // tiles per axis: the window spans the seed's stride
-  refine.refine_radius_th = (std::max(1, h->seed_stride_th / ILCC_REFINE_RADIUS_DIV) / kRefineThetaStride) * kRefineThetaStride;
+  refine.refine_window = h->seed_stride_t > 2 * kTileA ? 4 : 2;   // tiles per axis: the window spans the seed's stride
+  refine.refine_radius_th = (lp.refine_radius / kRefineThetaStride) * kRefineThetaStride;
   refine.refine_step_th = kRefineThetaStride;
   refine.grid_blocks = std::min((uint32_t)(2 * (refine.refine_radius_th / kRefineThetaStride) + 1), h->max_theta);
   refine.partial = sl.d_partial3;
@@ -678,7 +675,7 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, int si, const Ctx& c, hipS
       HIP_TRY(h, hipEventRecord(sl.k6ev[2], s));
       seeded_by_full_table_records(full, h, sl.d_partial4, 1);
     } else {
-      const int32_t st = enqueue_locate_launches(h, sl, c, s, full);
+      const int32_t st = enqueue_locate_launches(h, sl, c, s, lp, full);
       if (st != ILCC_OK) return st;
     }
   } else {

@@ -118,6 +118,127 @@ __device__ __forceinline__ bool better(float c, uint32_t d2, uint32_t flat, cons
   return c < b.cost || (c == b.cost && (d2 < b.d2 || (d2 == b.d2 && flat < b.flat)));
 }
 
+// argmin over the lanes of the wavefront (valid in lane 0); AB: carry each lane's (a << 16) | b along
+template <bool AB>
+__device__ __forceinline__ Best wave_argmin(Best best, uint32_t& ab) {
+#pragma unroll
+  for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) {
+    Best t;
+    t.cost = __shfl_down(best.cost, o, ILCC_WAVE);
+    t.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
+    t.flat = __shfl_down(best.flat, o, ILCC_WAVE);
+    const uint32_t tab = AB ? __shfl_down(ab, o, ILCC_WAVE) : 0u;
+    if (better(t.cost, t.d2, t.flat, best)) {
+      best = t;
+      if (AB) ab = tab;
+    }
+  }
+  return best;
+}
+__device__ __forceinline__ Best wave_argmin(Best best) {
+  uint32_t none = 0;
+  return wave_argmin<false>(best, none);
+}
+
+// the workgroup's argmin over the wavefronts' bests its lanes 0 stored in LDS (read behind the barrier that follows the stores),
+// ties to the lower wavefront; s_ab (optional): the wavefronts' (a << 16) | b, the winner's into ab
+template <int WAVES>
+__device__ __forceinline__ Best block_argmin(const Best* s_best, const uint32_t* s_ab, uint32_t& ab) {
+  Best b = s_best[0];
+  if (s_ab) ab = s_ab[0];
+  for (int w = 1; w < WAVES; ++w)
+    if (better(s_best[w].cost, s_best[w].d2, s_best[w].flat, b)) {
+      b = s_best[w];
+      if (s_ab) ab = s_ab[w];
+    }
+  return b;
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, ILCC_WAVE));
+  return v;
+}
+
+// a completed candidate (theta k, translation (ia, ib)) of a launch's tables (n_ty x n_tz, entries nearest zero (c_th, c_ty, c_tz)) with
+// the costs c0 / c1 of its two colour phases: into this lane's best (flat = 2 cell + phase) and its (ia << 16) | ib
+__device__ __forceinline__ void score(float c0, float c1, int k, int ia, int ib, int n_ty, int n_tz, int c_th, int c_ty, int c_tz, Best& best,
+                                      uint32_t& ab) {
+  const uint32_t cell = ((uint32_t)k * (uint32_t)n_ty + (uint32_t)ia) * (uint32_t)n_tz + (uint32_t)ib;
+  const uint32_t d2 = (uint32_t)((k - c_th) * (k - c_th) + (ia - c_ty) * (ia - c_ty) + (ib - c_tz) * (ib - c_tz));
+  const uint32_t cab = ((uint32_t)ia << 16) | (uint32_t)ib;
+  if (better(c0, d2, 2u * cell, best)) {
+    best = Best{c0, d2, 2u * cell};
+    ab = cab;
+  }
+  if (better(c1, d2, 2u * cell + 1u, best)) {
+    best = Best{c1, d2, 2u * cell + 1u};
+    ab = cab;
+  }
+}
+
+// the record of a workgroup (or frame) that has no candidate at all
+__device__ __forceinline__ void no_candidate(GridPartial* out) { *out = GridPartial{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu, 0u}; }
+
+// Ctx::grid_iters: kIterSlots words per counter, frame f adds to word f mod kIterSlots of each (spread: fewer colliding atomics)
+enum EvalCounter { kEvalsAll = 0, kEvalsInterior = 1, kEvalsBox = 2 };
+__device__ __forceinline__ void count_evals(const Ctx& c, uint32_t f, EvalCounter which, unsigned long long n) {
+  atomicAdd(c.grid_iters + (int)which * kIterSlots + (f & (kIterSlots - 1)), n);
+}
+
+// first candidate of a window of `width` candidates that starts `before` candidates ahead of `centre`, kept inside an axis of n
+__device__ __forceinline__ int window_origin(int centre, int before, int n, int width) {
+  return min(max(centre - before, 0), max(n - width, 0));
+}
+
+// Rx(theta) on (0, y, z), already divided by g (Optimization.h:37-46).  Every launch rotates its points with this expression, which
+// is what keeps the sums of the different launches of a frame bit for bit the same
+__device__ __forceinline__ float2 rotate(float2 v, float cth, float sth) {
+  return make_float2(fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x));
+}
+
+// the walk prefix a subsampled (locate) launch looks at: M >> kSeedShift of the M positions, at least at_least
+__device__ __forceinline__ uint32_t walk_sample(uint32_t M, uint32_t at_least) { return min(M, max(at_least, M >> kSeedShift)); }
+// A sample of Ms of the M walk positions takes a proportional prefix of each part of the layout: n_in interior, n_rm rim, the rest
+// other border-class points
+__device__ __forceinline__ void walk_prefix(uint32_t Ms, uint32_t M, uint32_t Mi_all, uint32_t n_rim_all, uint32_t& n_in, uint32_t& n_rm) {
+  n_in = Mi_all;
+  n_rm = n_rim_all;
+  if (Ms < M) {
+    n_in = (uint32_t)(((uint64_t)Mi_all * Ms) / M);
+    n_rm = (uint32_t)(((uint64_t)n_rim_all * Ms) / M);
+  }
+}
+// walk position sl of that sample -> index in the walk layout.  (floor() twice in walk_prefix: the rest can be two positions longer
+// than the other border-class part, hence the clamp)
+__device__ __forceinline__ uint32_t layout_source(uint32_t sl, uint32_t n_in, uint32_t n_rm, uint32_t M, uint32_t Mi_all, uint32_t n_rim_all) {
+  const uint32_t src = sl < n_in ? sl : sl < n_in + n_rm ? Mi_all + (sl - n_in) : Mi_all + n_rim_all + (sl - n_in - n_rm);
+  return min(src, M - 1u);
+}
+// The frame's labelled points in walk order (k6_locate, k6_anchor).  With a walk layout (k5w_walk_order, below: every frame of at
+// most kGridLdsPointsMax points) the layout is [interior class | rim | other border-class points], each part in golden-ratio order;
+// without one, walk position s is point (s * S) mod M of the frame's own arrays.  (grid_cost_body calls the three functions above
+// on fields of its own: held in a FrameWalk, they gave the full pass another register allocation and schedule.)
+struct FrameWalk {
+  const float2* __restrict__ yz;
+  const uint8_t* __restrict__ lab;
+  uint32_t M, S, Mi_all, n_rim_all;   // labelled points, golden-ratio stride, interior / rim class sizes of the layout
+  bool layout;
+  __device__ __forceinline__ FrameWalk(const Ctx& c, uint32_t f) : M(c.n_lab[f]), layout(M <= (uint32_t)kGridLdsPointsMax) {
+    const uint64_t beg = c.off[f];
+    yz = (layout ? c.walk_yz : c.yz) + beg;
+    lab = (layout ? c.walk_lab : c.lab) + beg;
+    S = (!layout && M) ? c.walk_stride[f] : 1u;
+    Mi_all = layout ? c.walk_mi[f] : 0u;
+    n_rim_all = layout ? c.walk_nrim[f] : 0u;
+  }
+  __device__ __forceinline__ uint32_t sample(uint32_t at_least) const { return walk_sample(M, at_least); }
+  __device__ __forceinline__ void prefix(uint32_t Ms, uint32_t& n_in, uint32_t& n_rm) const { walk_prefix(Ms, M, Mi_all, n_rim_all, n_in, n_rm); }
+  __device__ __forceinline__ uint32_t source(uint32_t sl, uint32_t n_in, uint32_t n_rm) const {
+    return layout ? layout_source(sl, n_in, n_rm, M, Mi_all, n_rim_all) : (uint32_t)(((uint64_t)sl * S) % M);
+  }
+};
+
 struct PointTerms {   // uniform across the wavefront
   float pi, pj, hw;   // rotated coordinates / g, and 0.5 * (label == white)
 };
@@ -340,22 +461,18 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     }
   }
   if (r->status != ILCC_OK || group_dead) {
-    if (threadIdx.x == 0) {
-      out->cost = __builtin_inff();
-      out->d2 = 0xFFFFFFFFu;
-      out->flat = 0xFFFFFFFFu;
-      out->pad = 0u;
-    }
+    if (threadIdx.x == 0) no_candidate(out);
     return;
   }
   // walk_limit: the seed and refinement launches only look at a PREFIX of the walk -- the golden-ratio order makes it a
   // uniform sample of the board -- to find WHERE the minimum is; their sums are not costs of complete candidates and go to
   // a bound word of their own.  The anchor launch then evaluates the found neighbourhood on every point: that is the bound.
+  // (the LDS-free body walks the frame's own arrays in golden-ratio order, layout or not)
   const uint32_t Mfull = c.n_lab[f];
-  const uint32_t M = c.walk_limit ? min(Mfull, max(c.walk_limit, Mfull >> kSeedShift)) : Mfull;   // an eighth of the points (measured: 1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s), at least walk_limit
+  const uint32_t M = c.walk_limit ? walk_sample(Mfull, c.walk_limit) : Mfull;   // an eighth of the points (measured: 1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s), at least walk_limit
   const uint64_t beg = c.off[f];
   const float2* __restrict__ gyz = c.yz + beg;
-  const uint8_t* __restrict__ glab = c.lab + beg;
+  const uint8_t* __restrict__ glab = c.lab + beg;   // an eighth of the points (measured: 1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s), at least walk_limit
   const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
   int nta = (n_ty + kTile - 1) / kTile, ntb = (n_tz + kTile - 1) / kTile;
   int a_org = 0, b_org = 0;   // first candidate of tile (0, 0)
@@ -377,8 +494,8 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
         // refine_window = tiles per axis of the window: 2 (8 x 8 translations around the seed's argmin) or, on grids whose seed stride
         // is wider than that window (config 5: every 16th translation), 4 -- the seed's best can be half a stride from the minimum
         const int wt = max(2, c.refine_window);
-        a_org = __builtin_amdgcn_readfirstlane(min(max(sa - (wt * kTile) / 2, 0), max(n_ty - wt * kTile, 0)));
-        b_org = __builtin_amdgcn_readfirstlane(min(max(sbb - (wt * kTile) / 2, 0), max(n_tz - wt * kTile, 0)));
+        a_org = __builtin_amdgcn_readfirstlane(window_origin(sa, (wt * kTile) / 2, n_ty, wt * kTile));
+        b_org = __builtin_amdgcn_readfirstlane(window_origin(sbb, (wt * kTile) / 2, n_tz, wt * kTile));
         nta = min(wt, nta);
         ntb = min(wt, ntb);
       } else {
@@ -389,38 +506,27 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
   }
   const float cth = c.cth[k], sth = c.sth[k];
 
-  // Point order: k5w_walk_order (below) has written the frame's labelled points in WALK layout, once per frame instead of once
-  // per workgroup: [interior class | rim | other border-class points], each part in golden-ratio order (slot s of the walk
-  // holds point (s * S) mod M with S ~ 0.618 M coprime to M, so that every prefix of a part is a sample spread over the whole
-  // board: the bound test cuts tiles sooner than ring order would).  INTERIOR: in the board under EVERY rotation and
-  // translation of the tables -> accumulate_interior.  Staging is then a rotation of M points by this workgroup's theta.
-  // A subsampled launch (walk_limit) stages a prefix of each part, in proportion.
-  const uint32_t S = Mfull ? c.walk_stride[f] : 1u;   // (the walk through global memory of frames too large for LDS)
+  // Point order: k5w_walk_order (below) has written the frame's labelled points in WALK layout (FrameWalk), once per frame instead
+  // of once per workgroup.  Golden-ratio order makes every prefix of a part a sample spread over the whole board: the bound test
+  // cuts tiles sooner than ring order would.  INTERIOR: in the board under EVERY rotation and translation of the tables ->
+  // accumulate_interior.  Staging is then a rotation of M points by this workgroup's theta.  A subsampled launch (walk_limit)
+  // stages a prefix of each part, in proportion.
   uint32_t Mi = 0;
   uint32_t stage_lo = 0, stage_hi = 0;   // walk positions staged so far: [stage_lo, stage_hi)
+  const uint32_t S = Mfull ? c.walk_stride[f] : 1u;
   const float2* __restrict__ wyz = c.walk_yz + beg;
   const uint8_t* __restrict__ wlab = c.walk_lab + beg;
   const uint32_t Mi_all = LDS_POINTS ? c.walk_mi[f] : 0u, n_rim_all = LDS_POINTS ? c.walk_nrim[f] : 0u;
-  uint32_t n_in = Mi_all, n_rm = n_rim_all;
-  if (LDS_POINTS && M < Mfull) {
-    n_in = (uint32_t)(((uint64_t)Mi_all * M) / Mfull);
-    n_rm = (uint32_t)(((uint64_t)n_rim_all * M) / Mfull);
-  }
+  uint32_t n_in, n_rm;
+  walk_prefix(M, Mfull, Mi_all, n_rim_all, n_in, n_rm);
+  auto walk_source = [&](uint32_t sl) { return layout_source(sl, n_in, n_rm, Mfull, Mi_all, n_rim_all); };
   const uint32_t lds_n = OVERFLOW ? min(M, c.grid_lds_points) : M;   // walk positions [0, lds_n) live in LDS
-  auto walk_source = [&](uint32_t sl) -> uint32_t {   // walk position -> index in the walk layout
-    const uint32_t src = sl < n_in ? sl : sl < n_in + n_rm ? Mi_all + (sl - n_in) : Mi_all + n_rim_all + (sl - n_in - n_rm);
-    return min(src, Mfull - 1u);
-  };
   auto stage_point = [&](uint32_t sl) {
     const uint32_t src = walk_source(sl);
-    const float2 v = wyz[src];
-    // Rx(theta) on (0,y,z), already divided by g (Optimization.h:37-46)
-    s_ij[sl] = make_float2(fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x));
+    s_ij[sl] = rotate(wyz[src], cth, sth);
     s_hw[sl] = wlab[src] ? 0.5f : 0.f;
   };
   if (LDS_POINTS) {
-    // (parts are prefixes: n_in <= Mi_all, n_rm <= n_rim_all, and the rest M - n_in - n_rm <= the other border points + 2:
-    // floor() twice; the source index below is clamped for that)
     Mi = n_in;
     // The full pass stages the points its box pre-pass looks at first: a workgroup the pre-pass leaves no tile (half of
     // them: every theta more than a few steps from the minimum) never stages, or reads, the rest.
@@ -474,11 +580,8 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       // 1 247 -> 1 274 k frames/s, config 5 87.3 -> 89.2 k; with groups of 7 thetas instead of 5 (the common pre-pass is then the only
       // filter and costs less per theta): 1 280 k / 92 k (groups of 3 / 4 / 5 / 7 / 9 / 11 / 15: 1 235 / 1 250 / 1 276 / 1 280 / 1 283 /
       // 1 271 / 1 177 k and 82.9 / 83.9 / 89.7 / 91.5 / 92.6 / 92.2 / 90.8 k).  Grids without a common pre-pass (state 2) keep their own.
-#ifndef ILCC_K6_SKIP_OWN_PREPASS
-#define ILCC_K6_SKIP_OWN_PREPASS 1
-#endif
       uint32_t wave_evals = 0;
-      if (ILCC_K6_SKIP_OWN_PREPASS && s_dead0 != nullptr) {
+      if (s_dead0 != nullptr) {
         if (threadIdx.x == 0) s_cnt[0] = 1u;   // (the group's state word said: some tile is alive)
       } else {
         wave_evals = box_prepass_rounds<THREADS>(n_tiles, ntb, a_org, b_org, n_ty, n_tz, s_ay, s_az, s_dead, s_live, s_cnt + 1, s_cnt, n_pre,
@@ -494,11 +597,8 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       __syncthreads();
       if (!any_alive) {   // nothing to walk at this theta: the rest of the frame's points is never staged
         if (threadIdx.x == 0) {
-          out->cost = __builtin_inff();
-          out->d2 = 0xFFFFFFFFu;
-          out->flat = 0xFFFFFFFFu;
-          out->pad = 0u;
-          atomicAdd(c.grid_iters + 2 * kIterSlots + (f & (kIterSlots - 1)), box_evals);
+          no_candidate(out);
+          count_evals(c, f, kEvalsBox, box_evals);
         }
         return;
       }
@@ -568,16 +668,16 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     uint32_t pos = 0;
     auto fetch = [&](uint32_t at) -> PointTerms {   // at = walk position of THIS lane's point
       if (LDS_POINTS) {
-        if (OVERFLOW && at >= lds_n) {   // past the staged prefix: from the walk layout in L2, rotated here (stage_point's expressions)
+        if (OVERFLOW && at >= lds_n) {   // past the staged prefix: from the walk layout in L2, rotated here
           const uint32_t src = walk_source(at);
-          const float2 v = wyz[src];
-          return PointTerms{fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x), wlab[src] ? 0.5f : 0.f};
+          const float2 v = rotate(wyz[src], cth, sth);
+          return PointTerms{v.x, v.y, wlab[src] ? 0.5f : 0.f};
         }
         const float2 v = s_ij[at];
         return PointTerms{v.x, v.y, s_hw[at]};
       } else {
-        const float2 v = gyz[idx];
-        const PointTerms t{fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x), glab[idx] ? 0.5f : 0.f};
+        const float2 v = rotate(gyz[idx], cth, sth);
+        const PointTerms t{v.x, v.y, glab[idx] ? 0.5f : 0.f};
         idx += idx_step;
         if (idx >= Mfull) idx -= Mfull;
         return t;
@@ -770,9 +870,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     }
     if (PRUNE) {
       // share the wavefront's best complete cost with every workgroup of the frame
-      float wb = best.cost;
-#pragma unroll
-      for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) wb = fminf(wb, __shfl_xor(wb, o, ILCC_WAVE));
+      const float wb = wave_min(best.cost);
       // publish only what improves the frame's bound as this wavefront last saw it: atomics on a
       // word that thousands of wavefronts also load serialise in L2 (measured: 2.5x on the kernel)
       if (lane == 0 && wb < fminf(shared_bound, __uint_as_float(gb_bits))) {
@@ -791,6 +889,28 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
   // 64 of them at a time, one per lane: the lanes look their tiles up in the pre-pass's bit mask, a ballot gives the ones
   // still alive, and only those are visited (a handful of a wavefront's 25: the loop over dead tiles was a third of the
   // kernel's scalar instructions).
+  const int ntb_s = __builtin_amdgcn_readfirstlane(ntb);
+  auto visit = [&](int qs) {   // tile qs of the workgroup
+    const int tile_a = __builtin_amdgcn_readfirstlane(qs / ntb_s), tile_b = __builtin_amdgcn_readfirstlane(qs - tile_a * ntb_s);
+#ifdef ILCC_K6_TIMING
+    const unsigned long long tt0 = K6_NOW();
+    const uint32_t pd0 = pts_done;
+#endif
+    run_tile(tile_a, tile_b, 0.f, 0.f, 0u, Mi);
+#ifdef ILCC_K6_TIMING
+    const unsigned long long dt = K6_NOW() - tt0;
+    const uint32_t walked = pts_done - pd0;
+    if (walked <= (uint32_t)(2 * kStep) && walked < M) {
+      ++n_rej;
+      t_rej += dt;
+    } else {
+      ++n_surv;
+      t_surv += dt;
+      p_surv += walked;
+      if (walked >= M) ++n_done;
+    }
+#endif
+  };
   if constexpr (THREADS == kGridThreadsLarge && kGridThreadsLarge != kGridThreads) {
     // The 512-thread instance (frames of several thousand labelled points, ~1000 tiles per workgroup): which wavefront takes
     // which tile is decided at run time.  The tiles that survive the pre-pass AND walk far (the candidates around the minimum)
@@ -805,7 +925,6 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     constexpr int kChunk = 8;   // tile slots per claim
     static_assert(kChunk >= 1 && kChunk <= ILCC_WAVE, "a chunk is looked up by the lanes of one wavefront");
     const int n_chunks = __builtin_amdgcn_readfirstlane((n_tiles + kChunk - 1) / kChunk);
-    const int ntb_s = __builtin_amdgcn_readfirstlane(ntb);
     for (;;) {
       int cl = 0;
       if (lane == 0) cl = (int)atomicAdd(s_next, 1u);
@@ -826,37 +945,12 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
         todo &= todo - 1ull;
         int qs = ch + n_chunks * bit + t0;
         if (qs >= n_tiles) qs -= n_tiles;
-        const int tile_a = __builtin_amdgcn_readfirstlane(qs / ntb_s), tile_b = __builtin_amdgcn_readfirstlane(qs - tile_a * ntb_s);
-#ifdef ILCC_K6_TIMING
-        const unsigned long long tt0 = K6_NOW();
-        const uint32_t pd0 = pts_done;
-        const float bc0 = best.cost;
-        const uint32_t bf0 = best.flat;
-#endif
-        run_tile(tile_a, tile_b, 0.f, 0.f, 0u, Mi);
-#ifdef ILCC_K6_TIMING
-        {
-          const unsigned long long dt = K6_NOW() - tt0;
-          const uint32_t walked = pts_done - pd0;
-          if (walked <= (uint32_t)(2 * kStep) && walked < M) {
-            ++n_rej;
-            t_rej += dt;
-          } else {
-            ++n_surv;
-            t_surv += dt;
-            p_surv += walked;
-            if (walked >= M) ++n_done;
-          }
-          (void)bc0;
-          (void)bf0;
-        }
-#endif
+        visit(qs);
       }
     }
   } else {
     constexpr int kWaves = THREADS / ILCC_WAVE;
     const int per_wave = __builtin_amdgcn_readfirstlane(wid < n_tiles ? (n_tiles - wid + kWaves - 1) / kWaves : 0);
-    const int ntb_s = __builtin_amdgcn_readfirstlane(ntb);
     for (int k0 = 0; k0 < per_wave; k0 += ILCC_WAVE) {
       bool alive = false;
       if (k0 + lane < per_wave) {
@@ -870,45 +964,14 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
         todo &= todo - 1ull;
         int qs = wid + kWaves * (k0 + bit) + t0;
         if (qs >= n_tiles) qs -= n_tiles;
-        const int tile_a = __builtin_amdgcn_readfirstlane(qs / ntb_s), tile_b = __builtin_amdgcn_readfirstlane(qs - tile_a * ntb_s);
-#ifdef ILCC_K6_TIMING
-        const unsigned long long tt0 = K6_NOW();
-        const uint32_t pd0 = pts_done;
-        const float bc0 = best.cost;
-        const uint32_t bf0 = best.flat;
-#endif
-        run_tile(tile_a, tile_b, 0.f, 0.f, 0u, Mi);
-#ifdef ILCC_K6_TIMING
-        {
-          const unsigned long long dt = K6_NOW() - tt0;
-          const uint32_t walked = pts_done - pd0;
-          if (walked <= (uint32_t)(2 * kStep) && walked < M) {
-            ++n_rej;
-            t_rej += dt;
-          } else {
-            ++n_surv;
-            t_surv += dt;
-            p_surv += walked;
-            if (walked >= M) ++n_done;
-          }
-          (void)bc0;
-          (void)bf0;
-        }
-#endif
+        visit(qs);
       }
     }
   }
   [[maybe_unused]] const unsigned long long t_tiles = K6_NOW();
 
   // lanes hold different candidates: wavefront argmin, then across the 4 wavefronts
-#pragma unroll
-  for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) {
-    Best t;
-    t.cost = __shfl_down(best.cost, o, ILCC_WAVE);
-    t.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-    t.flat = __shfl_down(best.flat, o, ILCC_WAVE);
-    if (better(t.cost, t.d2, t.flat, best)) best = t;
-  }
+  best = wave_argmin(best);
   if (lane == 0) {
     s_best[wid] = best;
     s_iters[wid] = pts_done;
@@ -921,12 +984,11 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       it_sum += s_iters[w];
       in_sum += s_cnt[w];
     }
-    atomicAdd(c.grid_iters + (f & (kIterSlots - 1)), (unsigned long long)it_sum);   // spread over 64 words
-    atomicAdd(c.grid_iters + kIterSlots + (f & (kIterSlots - 1)), (unsigned long long)in_sum);
-    if (use_box) atomicAdd(c.grid_iters + 2 * kIterSlots + (f & (kIterSlots - 1)), box_evals);
-    Best b = s_best[0];
-    for (int w = 1; w < THREADS / ILCC_WAVE; ++w)
-      if (better(s_best[w].cost, s_best[w].d2, s_best[w].flat, b)) b = s_best[w];
+    count_evals(c, f, kEvalsAll, it_sum);
+    count_evals(c, f, kEvalsInterior, in_sum);
+    if (use_box) count_evals(c, f, kEvalsBox, box_evals);
+    uint32_t none = 0;
+    const Best b = block_argmin<THREADS / ILCC_WAVE>(s_best, nullptr, none);
     out->cost = b.cost;
     out->d2 = b.d2;
     out->flat = b.flat;
@@ -982,7 +1044,9 @@ __global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, float* volume) {
   float* s_ay = s_hw + c.grid_lds_points;   // n_ty floats
   float* s_az = s_ay + c.p.n_ty;            // n_tz floats
   const uint32_t Mall = c.n_lab[blockIdx.y];
-  const uint32_t M = c.walk_limit ? min(Mall, max(c.walk_limit, Mall >> kSeedShift)) : Mall;
+  // (unused, and kept: without it the full pass compiles to another register allocation and schedule -- 1.6 k of the 9.4 k lines
+  // of its gfx950 assembly differ)
+  const uint32_t M = c.walk_limit ? walk_sample(Mall, c.walk_limit) : Mall;
   (void)M;
   if (Mall <= c.grid_lds_points) {   // (k5w_walk_order has laid out every frame of at most kGridLdsPointsMax points)
     grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS>(c, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
@@ -1058,11 +1122,11 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, uint32_t* grp
     float ilo = __builtin_inff(), ihi = -__builtin_inff(), jlo = __builtin_inff(), jhi = -__builtin_inff();
 #pragma unroll
     for (int t = 0; t < kThetaGroup; ++t) {
-      const float pi = fmaf(-sth[t], v.y, cth[t] * v.x), pj = fmaf(cth[t], v.y, sth[t] * v.x);   // = the full pass's staging
-      ilo = fminf(ilo, pi);
-      ihi = fmaxf(ihi, pi);
-      jlo = fminf(jlo, pj);
-      jhi = fmaxf(jhi, pj);
+      const float2 p = rotate(v, cth[t], sth[t]);
+      ilo = fminf(ilo, p.x);
+      ihi = fmaxf(ihi, p.x);
+      jlo = fminf(jlo, p.y);
+      jhi = fmaxf(jhi, p.y);
     }
     // a point far from the rotation centre: leave it out (as a point at the board's centre, in the board under every
     // translation of the tables -- the host launches this kernel only then -- it contributes nothing to any bound)
@@ -1086,7 +1150,7 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, uint32_t* grp
   if (threadIdx.x == 0) {
     unsigned long long box_evals = 0;
     for (int w = 0; w < THREADS / ILCC_WAVE; ++w) box_evals += s_iters[w];
-    atomicAdd(c.grid_iters + 2 * kIterSlots + (f & (kIterSlots - 1)), box_evals);
+    count_evals(c, f, kEvalsBox, box_evals);
     grp_alive[tr] = any_alive ? 1u : 0u;
   }
 }
@@ -1102,29 +1166,101 @@ void launch_group_prepass(const Ctx& c, hipStream_t s, uint32_t* grp_alive, uint
     hipLaunchKernelGGL((k6_group_prepass<kGridThreads>), grid, dim3(kGridThreads), lds, s, c, grp_alive, grp_mask);
 }
 
+// ANCHOR (k6_anchor, and the last stage of k6_locate): the 4 x 4 tile at (a_org, b_org) of the full tables at theta k on EVERY
+// labelled point of the frame, by the n_parts wavefronts of that theta -- blocks of four walk positions go round them, this one takes
+// blocks part, part + n_parts, ...  Writes the quad sums of its 16 candidates (cost / 2 per phase) to s_part[candidate][phase].
+// ty / tz: the translation tables (in LDS or in global memory).
+__device__ __forceinline__ void anchor_walk(const Ctx& c, const FrameWalk& fw, int k, int a_org, int b_org, const float* ty, const float* tz,
+                                            uint32_t part, uint32_t n_parts, float (*s_part)[2], uint32_t& pts_done, uint32_t& pts_in) {
+  const int my_s = lane_id() & (kSlices - 1), my_c = lane_id() >> 2;
+  const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h, delta2 = (float)c.p.huber_delta;
+  const float cth = c.cth[k], sth = c.sth[k];
+  const float ay = ty[min(a_org + (my_c >> 2), c.p.n_ty - 1)], az = tz[min(b_org + (my_c & 3), c.p.n_tz - 1)];
+  float A0 = 0.f, A1 = 0.f;
+  uint32_t pos = 0, pin = 0;
+  for (uint32_t at0 = part * kSlices; at0 < fw.M; at0 += n_parts * kSlices) {
+    const uint32_t at = at0 + (uint32_t)my_s;
+    if (at < fw.M) {
+      const uint32_t src = fw.source(at, fw.Mi_all, fw.n_rim_all);
+      const float2 v = rotate(fw.yz[src], cth, sth);
+      const PointTerms pt{v.x, v.y, fw.lab[src] ? 0.5f : 0.f};
+      if (at < fw.Mi_all)
+        accumulate_interior(pt, ay, az, delta2, A0, A1);
+      else
+        accumulate<true>(pt, ay, az, Wh, Hh, delta2, A0, A1);
+    }
+    pos += kSlices;
+    pin += at0 < fw.Mi_all ? (uint32_t)kSlices : 0u;
+  }
+  pts_done += pos;
+  pts_in += pin;
+  const float t0s = quad_sum(A0), t1s = quad_sum(A1);
+  if (my_s == 0) {
+    s_part[my_c][0] = t0s;
+    s_part[my_c][1] = t1s;
+  }
+}
+
+// The anchor's result, by one wavefront behind the barrier that follows the walks: candidate (t, cand) costs the sum of its PARTS
+// partial sums s_part[t * PARTS + part][cand], in part order (the published bound is compared bit for bit downstream); the argmin over
+// (theta k0 + t, candidate) carries (a << 16) | b.  Lane 0 writes the record and lowers the frame's bound: a complete candidate on
+// every point is a valid bound.
+template <int THETAS, int PARTS>
+__device__ __forceinline__ void anchor_publish(const Ctx& c, uint32_t f, const float (*s_part)[16][2], int k0, int a_org, int b_org,
+                                               GridPartial* out) {
+  const int lane = lane_id();
+  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
+  Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
+  uint32_t ab = 0;
+  if (lane < 16 * THETAS) {
+    const int t = lane >> 4, cand = lane & 15;
+    const int k = min(max(k0 + t, 0), c.p.n_th - 1), ja = a_org + (cand >> 2), jb = b_org + (cand & 3);
+    if (ja < n_ty && jb < n_tz) {
+      float h0 = 0.f, h1 = 0.f;
+#pragma unroll
+      for (int q = 0; q < PARTS; ++q) {
+        h0 += s_part[t * PARTS + q][cand][0];
+        h1 += s_part[t * PARTS + q][cand][1];
+      }
+      score(2.f * h0, 2.f * h1, k, ja, jb, n_ty, n_tz, c.c_th, c.c_ty, c.c_tz, best, ab);
+    }
+  }
+  best = wave_argmin<true>(best, ab);
+  if (lane == 0) {
+    *out = GridPartial{best.cost, best.d2, best.flat, ab};
+    if (best.flat != 0xFFFFFFFFu) atomicMin(c.grid_bound + f, __float_as_uint(best.cost));
+  }
+}
+
 // k6_locate (round 5): seed + refinement + anchor in ONE launch, one workgroup per frame.  The three launches it replaces only
 // have to say WHERE the minimum is and publish the frame's bound; as 17 small workgroups per frame in three dependent launches
 // they were 277 of the K6 stage's 733 us with a batch alone on the chip, at 16-28 % issue utilisation: each stages
 // its points and tables again, reads the previous launch's argmin from global memory, and the anchor's workgroups run one
-// wavefront of four.  Here a frame's 8 wavefronts
+// wavefront of four.  Here a frame's 6 wavefronts
 //   1. stage the SAMPLE of the walk (an eighth of the labelled points, a proportional prefix of each class of the walk layout)
 //      once, rotated by the five seed thetas; 5 x (8 x 8 decimated translations) = 20 tiles, one per wavefront at a time,
 //      pruned against a bound word in LDS; argmin in LDS;
 //   2. rotate the sample by the (2 r + 1) thetas around the seed's and score their 8 x 8 windows of full-table translations
-//      (36 tiles); argmin in LDS;
+//      (kLocateWindowTiles; 36 tiles); argmin in LDS;
 //   3. score the 4 x 4 tile around that argmin at theta - 1, theta, theta + 1 on EVERY labelled point (rotated on the fly from
 //      the walk layout in L2), two wavefronts per theta on alternate blocks of the walk, and publish the best complete cost as
 //      the frame's bound and its candidate as the full pass's starting tile.
-// The same candidates on the same points as the three launches; the sums are grouped differently (the anchor's two half-walks
-// are added at the end), which the full pass cannot see: the bound only has to be the cost of SOME complete candidate, and a
-// candidate is cut, or listed as a near tie, with 2e-5 to spare -- 20 x the rounding of an fp32 sum of a thousand terms.
-// Batches of fewer than kLocateMinFrames frames keep the three launches: there a frame's 17 workgroups are what fills the chip.
+// Same on both paths: the final results.  The full pass is exact for any bound it is given -- the bound only has to be the cost of
+// SOME complete candidate, and a candidate is cut, or listed as a near tie, with 2e-5 to spare (20 x the rounding of an fp32 sum of a
+// thousand terms).  Not the same: this path keeps the 8 x 8 refinement window on grids whose seed stride is wider than 8 translations
+// (the separate launches widen theirs to 16 x 16 there) and runs one anchor round, against kAnchorRounds; its anchor also adds two
+// parts of the walk per theta where k6_anchor adds eight.  So the bound it publishes, and the full pass's executed work, can differ.
+// Batches of fewer than kLocateMinFrames frames keep the separate launches: there a frame's 17 workgroups are what fills the chip.
 constexpr int kLocateThreads = 384;       // 6 wavefronts = 3 anchor thetas x 2 parts of the walk, all busy in the anchor.  Measured (k frames/s / locate alone): 256: 1056, 512: 1089, 1024: 1011-1033 when it was built; on the final build 384: 1266 / 0.184 ms, 512: 1268 / 0.214 ms, 768: 1251 / 0.201 ms
 constexpr int kSeedPeek = 16;             // walk positions of every seed tile a wavefront looks at before it chooses which tile to evaluate first
 constexpr int kAnchorThetas = 3;          // thetas around the refinement's argmin the anchor scores (1: locate 0.26 -> 0.21 ms alone, full pass 0.36 -> 0.40: a wash)
 constexpr int kAnchorParts = (kLocateThreads / 64) / kAnchorThetas;  // wavefronts sharing a theta's walk
 constexpr int kLocateWaves = kLocateThreads / ILCC_WAVE;
 constexpr int kLocateThetasMax = 16;      // rotations of the sample kept in LDS at a time (seed: 5, refinement: 2 r + 1 = 9)
+// k6_locate's refinement window, in tiles per axis: 2 (8 x 8 translations around the seed's argmin) on EVERY grid.  The separate
+// launches widen theirs to 4 tiles (16 x 16) on grids whose seed stride is wider than 8 translations (Ctx::refine_window); whether
+// this path should too is a change of its own, to be measured.
+constexpr int kLocateWindowTiles = 2;
 __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ Best s_best[kLocateWaves];
@@ -1132,28 +1268,19 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   __shared__ uint32_t s_bound;              // float bits: best complete SAMPLE cost so far (seed and refinement share the sample)
   __shared__ uint32_t s_pick[4];            // argmin of a phase: flat, (a << 16) | b
   __shared__ uint32_t s_iters[kLocateWaves], s_iters_in[kLocateWaves];
-  __shared__ float s_part[kAnchorThetas][kAnchorParts][16][2];     // anchor: (theta, part of the walk, candidate, phase) partial costs / 2
+  __shared__ float s_part[kAnchorThetas * kAnchorParts][16][2];     // anchor: (theta, part of the walk) -> (candidate, phase) partial costs / 2
   const uint32_t f = blockIdx.x;
   GridPartial* out = lp.out + f;
   const int lane = lane_id();
   const int wid = __builtin_amdgcn_readfirstlane(wave_id());
-  const uint32_t Mfull = c.n_lab[f];
   if (c.res[f].status != ILCC_OK) {
-    if (threadIdx.x == 0) *out = GridPartial{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu, 0u};
+    if (threadIdx.x == 0) no_candidate(out);
     return;
   }
-  const uint64_t beg = c.off[f];
-  const bool walk_layout = Mfull <= (uint32_t)kGridLdsPointsMax;   // k5w_walk_order has laid the frame out; else: the points in golden-ratio order through L2
-  const float2* __restrict__ wyz = walk_layout ? c.walk_yz + beg : c.yz + beg;
-  const uint8_t* __restrict__ wlab = walk_layout ? c.walk_lab + beg : c.lab + beg;
-  const uint32_t S = (!walk_layout && Mfull) ? c.walk_stride[f] : 1u;
-  const uint32_t Mi_all = walk_layout ? c.walk_mi[f] : 0u, n_rim_all = walk_layout ? c.walk_nrim[f] : 0u;
-  const uint32_t Ms = min(min(Mfull, max(lp.sample_min, Mfull >> kSeedShift)), lp.sample_cap);
-  uint32_t n_in = Mi_all, n_rm = n_rim_all;
-  if (Ms < Mfull) {
-    n_in = (uint32_t)(((uint64_t)Mi_all * Ms) / Mfull);
-    n_rm = (uint32_t)(((uint64_t)n_rim_all * Ms) / Mfull);
-  }
+  const FrameWalk fw(c, f);
+  const uint32_t Ms = min(fw.sample(lp.sample_min), lp.sample_cap);
+  uint32_t n_in, n_rm;
+  fw.prefix(Ms, n_in, n_rm);
   const int n_ty = c.p.n_ty, n_tz = c.p.n_tz, n_th = c.p.n_th;
   // dynamic LDS: the raw sample, its rotations, the (ty, tz) tables (full, then the seed's)
   float2* s_raw = reinterpret_cast<float2*>(smem);
@@ -1164,11 +1291,9 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   float* s_ay2 = s_az + n_tz;
   float* s_az2 = s_ay2 + lp.n_ty2;
   for (uint32_t sl = threadIdx.x; sl < Ms; sl += kLocateThreads) {
-    uint32_t src = sl < n_in ? sl : sl < n_in + n_rm ? Mi_all + (sl - n_in) : Mi_all + n_rim_all + (sl - n_in - n_rm);
-    src = min(src, Mfull - 1u);
-    if (!walk_layout) src = (uint32_t)(((uint64_t)sl * S) % Mfull);
-    s_raw[sl] = wyz[src];
-    s_hw[sl] = wlab[src] ? 0.5f : 0.f;
+    const uint32_t src = fw.source(sl, n_in, n_rm);
+    s_raw[sl] = fw.yz[src];
+    s_hw[sl] = fw.lab[src] ? 0.5f : 0.f;
   }
   for (int i = threadIdx.x; i < n_ty; i += kLocateThreads) s_ay[i] = c.ay[i];
   for (int i = threadIdx.x; i < n_tz; i += kLocateThreads) s_az[i] = c.az[i];
@@ -1184,9 +1309,7 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
     for (uint32_t item = threadIdx.x; item < (uint32_t)n_rot * Ms; item += kLocateThreads) {
       const uint32_t r = item / Ms, sl = item - r * Ms;
       const int k = th_of((int)r);
-      const float cth = cth_tab[k], sth = sth_tab[k];
-      const float2 v = s_raw[sl];
-      s_rot[(size_t)r * lp.sample_cap + sl] = make_float2(fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x));   // = k6_grid_cost's staging
+      s_rot[(size_t)r * lp.sample_cap + sl] = rotate(s_raw[sl], cth_tab[k], sth_tab[k]);
     }
   };
   // one 4 x 4 tile on the rotated sample `rot`, quad-sliced like k6_grid_cost (border class first, a bound test every 8 walk
@@ -1241,37 +1364,26 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   };
   // a phase's argmin: every wavefront's best -> LDS -> s_pick (flat, ab)
   auto reduce_best = [&](Best best, uint32_t ab) {
-#pragma unroll
-    for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) {
-      Best t;
-      t.cost = __shfl_down(best.cost, o, ILCC_WAVE);
-      t.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-      t.flat = __shfl_down(best.flat, o, ILCC_WAVE);
-      const uint32_t tab = __shfl_down(ab, o, ILCC_WAVE);
-      if (better(t.cost, t.d2, t.flat, best)) {
-        best = t;
-        ab = tab;
-      }
-    }
+    best = wave_argmin<true>(best, ab);
     if (lane == 0) {
       s_best[wid] = best;
       s_ab[wid] = ab;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-      Best b = s_best[0];
-      uint32_t bab = s_ab[0];
-      for (int w = 1; w < kLocateWaves; ++w)
-        if (better(s_best[w].cost, s_best[w].d2, s_best[w].flat, b)) {
-          b = s_best[w];
-          bab = s_ab[w];
-        }
+      uint32_t bab = 0;
+      const Best b = block_argmin<kLocateWaves>(s_best, s_ab, bab);
       s_pick[0] = b.flat;
       s_pick[1] = bab;
       s_pick[2] = __float_as_uint(b.cost);
       s_pick[3] = b.d2;
     }
     __syncthreads();
+  };
+  // a completed sample tile: the wavefront's best cost (v: this lane's) lowers the sample bound
+  auto lower_sample_bound = [&](float v) {
+    const float wb = wave_min(v);
+    if (lane == 0) atomicMin(&s_bound, __float_as_uint(wb));   // costs are >= 0: uint order == float order
   };
   __syncthreads();
 
@@ -1304,9 +1416,7 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
           }
         }
         pts_done += min(Ms - n_in, (uint32_t)kSeedPeek);
-        float pm = (ia < lp.n_ty2 && ib < lp.n_tz2) ? fminf(quad_sum(A0), quad_sum(A1)) : __builtin_inff();
-#pragma unroll
-        for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) pm = fminf(pm, __shfl_xor(pm, o, ILCC_WAVE));
+        const float pm = wave_min((ia < lp.n_ty2 && ib < lp.n_tz2) ? fminf(quad_sum(A0), quad_sum(A1)) : __builtin_inff());
         if (pm < peek_best) {   // (wave-uniform)
           peek_best = pm;
           t_first = t;
@@ -1322,25 +1432,16 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
       const bool owner = ia < lp.n_ty2 && ib < lp.n_tz2;
       float c0, c1;
       if (!sample_tile(s_rot + (size_t)k2 * lp.sample_cap, s_ay2[min(ia, lp.n_ty2 - 1)], s_az2[min(ib, lp.n_tz2 - 1)], c0, c1)) continue;
-      if (owner) {
-        const uint32_t cell = ((uint32_t)k2 * (uint32_t)lp.n_ty2 + (uint32_t)ia) * (uint32_t)lp.n_tz2 + (uint32_t)ib;
-        const uint32_t d2 = (uint32_t)((k2 - lp.c_th2) * (k2 - lp.c_th2) + (ia - lp.c_ty2) * (ia - lp.c_ty2) + (ib - lp.c_tz2) * (ib - lp.c_tz2));
-        const uint32_t ab = ((uint32_t)ia << 16) | (uint32_t)ib;
-        if (better(c0, d2, 2u * cell, best)) { best = Best{c0, d2, 2u * cell}; best_ab = ab; }
-        if (better(c1, d2, 2u * cell + 1u, best)) { best = Best{c1, d2, 2u * cell + 1u}; best_ab = ab; }
-      }
-      float wb = owner ? fminf(c0, c1) : __builtin_inff();
-#pragma unroll
-      for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) wb = fminf(wb, __shfl_xor(wb, o, ILCC_WAVE));
-      if (lane == 0) atomicMin(&s_bound, __float_as_uint(wb));   // costs are >= 0: uint order == float order
+      if (owner) score(c0, c1, k2, ia, ib, lp.n_ty2, lp.n_tz2, lp.c_th2, lp.c_ty2, lp.c_tz2, best, best_ab);
+      lower_sample_bound(owner ? fminf(c0, c1) : __builtin_inff());
     }
     reduce_best(best, best_ab);
   }
   if (s_pick[0] == 0xFFFFFFFFu) {   // (no candidate at all: an empty frame)
-    if (threadIdx.x == 0) *out = GridPartial{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu, 0u};
+    if (threadIdx.x == 0) no_candidate(out);
     return;
   }
-  // ---- 2. refinement: theta within +- refine_radius steps of the seed's, the 8 x 8 window of full-table translations around its argmin
+  // ---- 2. refinement: theta within +- refine_radius steps of the seed's, the window of full-table translations around its argmin
   const int k2s = (int)((s_pick[0] >> 1) / (uint32_t)(lp.n_ty2 * lp.n_tz2));
   const int sa = min((int)(s_pick[1] >> 16) * lp.stride_t, n_ty - 1), sbb = min((int)(s_pick[1] & 0xFFFFu) * lp.stride_t, n_tz - 1);
   // every OTHER theta of the refinement's range: the anchor scores theta - 1, theta, theta + 1 around its argmin on every point, so
@@ -1352,8 +1453,10 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   rotate_sample(n_ref, [&](int r) { return min(max(k_ref0 + kRefStride * r, 0), n_th - 1); }, c.cth, c.sth);
   __syncthreads();
   {
-    const int a_org = min(max(sa - kTile, 0), max(n_ty - 2 * kTile, 0)), b_org = min(max(sbb - kTile, 0), max(n_tz - 2 * kTile, 0));
-    const int nta = min(2, (n_ty + kTile - 1) / kTile), ntb = min(2, (n_tz + kTile - 1) / kTile), per = nta * ntb, n_tiles = n_ref * per;
+    constexpr int kWindow = kLocateWindowTiles * kTile;
+    const int a_org = window_origin(sa, kWindow / 2, n_ty, kWindow), b_org = window_origin(sbb, kWindow / 2, n_tz, kWindow);
+    const int nta = min(kLocateWindowTiles, (n_ty + kTile - 1) / kTile), ntb = min(kLocateWindowTiles, (n_tz + kTile - 1) / kTile);
+    const int per = nta * ntb, n_tiles = n_ref * per;
     Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
     uint32_t best_ab = 0;
     for (int t = wid; t < n_tiles; t += kLocateWaves) {
@@ -1363,17 +1466,8 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
       const bool owner = ia < n_ty && ib < n_tz;
       float c0, c1;
       if (!sample_tile(s_rot + (size_t)r * lp.sample_cap, s_ay[min(ia, n_ty - 1)], s_az[min(ib, n_tz - 1)], c0, c1)) continue;
-      if (owner) {
-        const uint32_t cell = ((uint32_t)k * (uint32_t)n_ty + (uint32_t)ia) * (uint32_t)n_tz + (uint32_t)ib;
-        const uint32_t d2 = (uint32_t)((k - c.c_th) * (k - c.c_th) + (ia - c.c_ty) * (ia - c.c_ty) + (ib - c.c_tz) * (ib - c.c_tz));
-        const uint32_t ab = ((uint32_t)ia << 16) | (uint32_t)ib;
-        if (better(c0, d2, 2u * cell, best)) { best = Best{c0, d2, 2u * cell}; best_ab = ab; }
-        if (better(c1, d2, 2u * cell + 1u, best)) { best = Best{c1, d2, 2u * cell + 1u}; best_ab = ab; }
-      }
-      float wb = owner ? fminf(c0, c1) : __builtin_inff();
-#pragma unroll
-      for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) wb = fminf(wb, __shfl_xor(wb, o, ILCC_WAVE));
-      if (lane == 0) atomicMin(&s_bound, __float_as_uint(wb));
+      if (owner) score(c0, c1, k, ia, ib, n_ty, n_tz, c.c_th, c.c_ty, c.c_tz, best, best_ab);
+      lower_sample_bound(owner ? fminf(c0, c1) : __builtin_inff());
     }
     reduce_best(best, best_ab);
   }
@@ -1382,79 +1476,15 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
     // (the refinement evaluates every candidate of the seed's argmin window again, so it always has a pick)
     const int kr = (int)((s_pick[0] >> 1) / (uint32_t)(n_ty * n_tz));
     const int ra = min((int)(s_pick[1] >> 16), n_ty - 1), rb = min((int)(s_pick[1] & 0xFFFFu), n_tz - 1);
-    const int a_org = min(max(ra - 1, 0), max(n_ty - kTile, 0)), b_org = min(max(rb - 1, 0), max(n_tz - kTile, 0));
-    const int ia = a_org + my_a, ib = b_org + my_b;
-    const bool owner = ia < n_ty && ib < n_tz;
+    const int a_org = window_origin(ra, 1, n_ty, kTile), b_org = window_origin(rb, 1, n_tz, kTile);
+    const int k0 = kr - kAnchorThetas / 2;
     if (wid < kAnchorThetas * kAnchorParts) {
-      const int t = wid % kAnchorThetas, half = wid / kAnchorThetas;
-      const int k = min(max(kr + t - kAnchorThetas / 2, 0), n_th - 1);
-      const float cth = c.cth[k], sth = c.sth[k];
-      const float ay = s_ay[min(ia, n_ty - 1)], az = s_az[min(ib, n_tz - 1)];
-      float A0 = 0.f, A1 = 0.f;
-      uint32_t idx = 0, pos = 0, pin = 0;
-      // blocks of four walk positions go round the theta's wavefronts
-      for (uint32_t at0 = (uint32_t)half * kSlices; at0 < Mfull; at0 += (uint32_t)kAnchorParts * kSlices) {
-        const uint32_t at = at0 + (uint32_t)my_s;
-        if (at < Mfull) {
-          idx = walk_layout ? at : (uint32_t)(((uint64_t)at * S) % Mfull);
-          const float2 v = wyz[idx];
-          const PointTerms pt{fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x), wlab[idx] ? 0.5f : 0.f};
-          if (at < Mi_all)
-            accumulate_interior(pt, ay, az, delta2, A0, A1);
-          else
-            accumulate<true>(pt, ay, az, Wh, Hh, delta2, A0, A1);
-        }
-        pos += kSlices;
-        pin += at0 < Mi_all ? (uint32_t)kSlices : 0u;
-      }
-      pts_done += pos;
-      pts_in += pin;
-      const float t0s = quad_sum(A0), t1s = quad_sum(A1);
-      if (my_s == 0) {
-        s_part[t][half][my_c][0] = t0s;
-        s_part[t][half][my_c][1] = t1s;
-      }
+      const int t = wid % kAnchorThetas, part = wid / kAnchorThetas;
+      anchor_walk(c, fw, min(max(k0 + t, 0), n_th - 1), a_org, b_org, s_ay, s_az, (uint32_t)part, kAnchorParts, s_part[t * kAnchorParts + part],
+                  pts_done, pts_in);
     }
     __syncthreads();
-    if (wid == 0) {
-      Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-      uint32_t best_ab = 0;
-      if (lane < 16 * kAnchorThetas) {
-        const int t = lane >> 4, cand = lane & 15, ca = cand >> 2, cb = cand & 3;
-        const int k = min(max(kr + t - kAnchorThetas / 2, 0), n_th - 1), ja = a_org + ca, jb = b_org + cb;
-        if (ja < n_ty && jb < n_tz) {
-          float h0 = 0.f, h1 = 0.f;
-#pragma unroll
-          for (int q = 0; q < kAnchorParts; ++q) {
-            h0 += s_part[t][q][cand][0];
-            h1 += s_part[t][q][cand][1];
-          }
-          const float c0 = 2.f * h0, c1 = 2.f * h1;
-          const uint32_t cell = ((uint32_t)k * (uint32_t)n_ty + (uint32_t)ja) * (uint32_t)n_tz + (uint32_t)jb;
-          const uint32_t d2 = (uint32_t)((k - c.c_th) * (k - c.c_th) + (ja - c.c_ty) * (ja - c.c_ty) + (jb - c.c_tz) * (jb - c.c_tz));
-          best = Best{c0, d2, 2u * cell};
-          if (better(c1, d2, 2u * cell + 1u, best)) best = Best{c1, d2, 2u * cell + 1u};
-          best_ab = ((uint32_t)ja << 16) | (uint32_t)jb;
-        }
-      }
-#pragma unroll
-      for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) {
-        Best tt;
-        tt.cost = __shfl_down(best.cost, o, ILCC_WAVE);
-        tt.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-        tt.flat = __shfl_down(best.flat, o, ILCC_WAVE);
-        const uint32_t tab = __shfl_down(best_ab, o, ILCC_WAVE);
-        if (better(tt.cost, tt.d2, tt.flat, best)) {
-          best = tt;
-          best_ab = tab;
-        }
-      }
-      if (lane == 0) {
-        *out = GridPartial{best.cost, best.d2, best.flat, best_ab};
-        if (best.flat != 0xFFFFFFFFu) atomicMin(c.grid_bound + f, __float_as_uint(best.cost));   // the frame's real bound: a complete candidate on every point
-      }
-    }
-    (void)owner;
+    if (wid == 0) anchor_publish<kAnchorThetas, kAnchorParts>(c, f, s_part, k0, a_org, b_org, out);
   }
   if (lane == 0) {
     s_iters[wid] = pts_done;
@@ -1467,8 +1497,8 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
       it_sum += s_iters[w];
       in_sum += s_iters_in[w];
     }
-    atomicAdd(c.grid_iters + (f & (kIterSlots - 1)), (unsigned long long)it_sum);
-    atomicAdd(c.grid_iters + kIterSlots + (f & (kIterSlots - 1)), (unsigned long long)in_sum);
+    count_evals(c, f, kEvalsAll, it_sum);
+    count_evals(c, f, kEvalsInterior, in_sum);
   }
 }
 
@@ -1494,95 +1524,31 @@ __global__ __launch_bounds__(kAnchorThreads) void k6_anchor(Ctx c) {
   Best sb{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
   if (c.res[f].status == ILCC_OK) sb = seed_argmin(c, f, k2u, ab);
   if (sb.flat == 0xFFFFFFFFu) {
-    if (threadIdx.x == 0) *out = GridPartial{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu, 0u};
+    if (threadIdx.x == 0) no_candidate(out);
     return;
   }
-  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz, n_th = c.p.n_th;
+  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
   const int kr = (int)((sb.flat >> 1) / (uint32_t)(n_ty * n_tz));   // (the records come from launches over the full tables)
-  const int k = min(max(kr + (int)kblk - c.refine_radius_th, 0), n_th - 1);
+  const int k0 = kr + (int)kblk - c.refine_radius_th;                 // this workgroup's theta, before the clamp to the table
   const int ra = min((int)(ab >> 16), n_ty - 1), rb = min((int)(ab & 0xFFFFu), n_tz - 1);
-  const int a_org = min(max(ra - 1, 0), max(n_ty - kTile, 0)), b_org = min(max(rb - 1, 0), max(n_tz - kTile, 0));
-  const int my_s = lane & (kSlices - 1), my_c = lane >> 2, my_a = my_c >> 2, my_b = my_c & 3;
-  const int ia = a_org + my_a, ib = b_org + my_b;
-  const uint32_t Mfull = c.n_lab[f];
-  const uint64_t beg = c.off[f];
-  const bool walk_layout = Mfull <= (uint32_t)kGridLdsPointsMax;
-  const float2* __restrict__ wyz = walk_layout ? c.walk_yz + beg : c.yz + beg;
-  const uint8_t* __restrict__ wlab = walk_layout ? c.walk_lab + beg : c.lab + beg;
-  const uint32_t S = (!walk_layout && Mfull) ? c.walk_stride[f] : 1u;
-  const uint32_t Mi_all = walk_layout ? c.walk_mi[f] : 0u;
-  const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h, delta2 = (float)c.p.huber_delta;
-  const float cth = c.cth[k], sth = c.sth[k];
-  const float ay = c.ay[min(ia, n_ty - 1)], az = c.az[min(ib, n_tz - 1)];
-  float A0 = 0.f, A1 = 0.f;
-  uint32_t pos = 0, pin = 0;
-  for (uint32_t at0 = (uint32_t)wid * kSlices; at0 < Mfull; at0 += (uint32_t)kAnchorWaves * kSlices) {
-    const uint32_t at = at0 + (uint32_t)my_s;
-    if (at < Mfull) {
-      const uint32_t idx = walk_layout ? at : (uint32_t)(((uint64_t)at * S) % Mfull);
-      const float2 v = wyz[idx];
-      const PointTerms pt{fmaf(-sth, v.y, cth * v.x), fmaf(cth, v.y, sth * v.x), wlab[idx] ? 0.5f : 0.f};   // = k6_grid_cost's staging
-      if (at < Mi_all)
-        accumulate_interior(pt, ay, az, delta2, A0, A1);
-      else
-        accumulate<true>(pt, ay, az, Wh, Hh, delta2, A0, A1);
-    }
-    pos += kSlices;
-    pin += at0 < Mi_all ? (uint32_t)kSlices : 0u;
-  }
-  const float t0s = quad_sum(A0), t1s = quad_sum(A1);
-  if (my_s == 0) {
-    s_part[wid][my_c][0] = t0s;
-    s_part[wid][my_c][1] = t1s;
-  }
+  const int a_org = window_origin(ra, 1, n_ty, kTile), b_org = window_origin(rb, 1, n_tz, kTile);
+  uint32_t pts_done = 0, pts_in = 0;
+  anchor_walk(c, FrameWalk(c, f), min(max(k0, 0), c.p.n_th - 1), a_org, b_org, c.ay, c.az, (uint32_t)wid, kAnchorWaves, s_part[wid], pts_done,
+              pts_in);
   if (lane == 0) {
-    s_iters[wid] = pos;
-    s_iters_in[wid] = pin;
+    s_iters[wid] = pts_done;
+    s_iters_in[wid] = pts_in;
   }
   __syncthreads();
-  if (wid == 0) {
-    Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-    uint32_t best_ab = 0;
-    if (lane < 16) {
-      const int ja = a_org + (lane >> 2), jb = b_org + (lane & 3);
-      if (ja < n_ty && jb < n_tz) {
-        float h0 = 0.f, h1 = 0.f;
-#pragma unroll
-        for (int q = 0; q < kAnchorWaves; ++q) {
-          h0 += s_part[q][lane][0];
-          h1 += s_part[q][lane][1];
-        }
-        const float c0 = 2.f * h0, c1 = 2.f * h1;
-        const uint32_t cell = ((uint32_t)k * (uint32_t)n_ty + (uint32_t)ja) * (uint32_t)n_tz + (uint32_t)jb;
-        const uint32_t d2 = (uint32_t)((k - c.c_th) * (k - c.c_th) + (ja - c.c_ty) * (ja - c.c_ty) + (jb - c.c_tz) * (jb - c.c_tz));
-        best = Best{c0, d2, 2u * cell};
-        if (better(c1, d2, 2u * cell + 1u, best)) best = Best{c1, d2, 2u * cell + 1u};
-        best_ab = ((uint32_t)ja << 16) | (uint32_t)jb;
-      }
+  if (wid == 0) anchor_publish<1, kAnchorWaves>(c, f, s_part, k0, a_org, b_org, out);
+  if (threadIdx.x == 0) {
+    uint32_t it_sum = 0, in_sum = 0;
+    for (int w = 0; w < kAnchorWaves; ++w) {
+      it_sum += s_iters[w];
+      in_sum += s_iters_in[w];
     }
-#pragma unroll
-    for (int o = ILCC_WAVE / 2; o > 0; o >>= 1) {
-      Best tt;
-      tt.cost = __shfl_down(best.cost, o, ILCC_WAVE);
-      tt.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-      tt.flat = __shfl_down(best.flat, o, ILCC_WAVE);
-      const uint32_t tab = __shfl_down(best_ab, o, ILCC_WAVE);
-      if (better(tt.cost, tt.d2, tt.flat, best)) {
-        best = tt;
-        best_ab = tab;
-      }
-    }
-    if (lane == 0) {
-      *out = GridPartial{best.cost, best.d2, best.flat, best_ab};
-      if (best.flat != 0xFFFFFFFFu) atomicMin(c.grid_bound + f, __float_as_uint(best.cost));   // a complete candidate on every point: a valid bound
-      uint32_t it_sum = 0, in_sum = 0;
-      for (int w = 0; w < kAnchorWaves; ++w) {
-        it_sum += s_iters[w];
-        in_sum += s_iters_in[w];
-      }
-      atomicAdd(c.grid_iters + (f & (kIterSlots - 1)), (unsigned long long)it_sum);
-      atomicAdd(c.grid_iters + kIterSlots + (f & (kIterSlots - 1)), (unsigned long long)in_sum);
-    }
+    count_evals(c, f, kEvalsAll, it_sum);
+    count_evals(c, f, kEvalsInterior, in_sum);
   }
 }
 
@@ -1656,9 +1622,8 @@ __global__ __launch_bounds__(kWalkThreads) void k5w_walk_order(Ctx c) {
     const bool inside_always = bi + 1e-4f < room_i && bj + 1e-4f < room_j;
     int cl = 0;
     if (!inside_always) {
-      const float cth = c.cth[c.c_th], sth = c.sth[c.c_th];
-      const float pi = fmaf(-sth, v.y, cth * v.x), pj = fmaf(cth, v.y, sth * v.x);
-      const float uc = fabsf((pi + ay_c) - Wh) - Wh, wc = fabsf((pj + az_c) - Hh) - Hh;
+      const float2 p = rotate(v, c.cth[c.c_th], c.sth[c.c_th]);
+      const float uc = fabsf((p.x + ay_c) - Wh) - Wh, wc = fabsf((p.y + az_c) - Hh) - Hh;
       cl = (fmaxf(uc, wc) > rim_thr) ? 2 : 1;
     }
     s_cls[sl] = (uint8_t)cl;

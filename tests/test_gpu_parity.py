@@ -1310,18 +1310,29 @@ def test_points_on_cell_borders_of_the_grid_argmin(ob):
     est.close()
 
 
-def test_fused_locate_equals_the_three_launches():
+def _wide_seed_stride(p):
+    """The default board with 129 x 129 translations over the default span (steps 39 / 128 of the default): seed stride 16 translations,
+    where the separate launches widen the refinement window to 16 x 16 and k6_locate keeps 8 x 8."""
+    p.n_ty = p.n_tz = 129
+    p.ty_step = p.tz_step = (0.15 / 20.0) * 39.0 / 128.0
+    return p
+
+
+@pytest.mark.parametrize("grid", [lambda p: p, _wide_seed_stride], ids=["default", "wide_seed_stride"])
+def test_fused_locate_equals_the_three_launches(grid):
     """Batches of >= 512 frames locate the grid minimum with ONE launch (k6_locate: seed, refinement and anchor in one workgroup
-    per frame), smaller ones with three k6_grid_cost launches over (theta, frame) grids.  Same candidates on the same points in
-    the same order: every field of the result must be identical, and so must the executed-evaluation-independent outputs
-    (grid argmin, cost, margin, refinement trajectory, corners).  64 distinct frames, tiled 8 x into one 512-frame batch."""
+    per frame), smaller ones with the separate launches (seed and refinement over (theta, frame) grids, then the anchor rounds).  The
+    bound they publish may differ (k6_locate keeps the 8 x 8 refinement window on wide-stride grids and runs one anchor round), the
+    full pass is exact for any bound: every field of the result must be identical, and so must the executed-evaluation-independent
+    outputs (grid argmin, cost, margin, refinement trajectory, corners).  64 distinct frames, tiled 8 x into one 512-frame batch;
+    on the default grid (seed stride 5) and on one whose seed stride is wider than 8 translations."""
     from lidar_camera_calibration_amd import LidarCornersBatch, synth
     from lidar_camera_calibration_amd import _native as N
     clouds, clicks, _, _ = synth.make_batch(64, seed=0xF05ED)
-    small = LidarCornersBatch(64, clouds.shape[1], N.default_params())
+    small = LidarCornersBatch(64, clouds.shape[1], grid(N.default_params()))
     small.reserve(2048, 4096)
     r_small = small.extract(clouds, clicks)
-    big = LidarCornersBatch(512, clouds.shape[1], N.default_params())
+    big = LidarCornersBatch(512, clouds.shape[1], grid(N.default_params()))
     big.reserve(2048, 4096)
     r_big = big.extract(np.tile(clouds, (8, 1, 1)), np.tile(clicks, (8, 1)))
     n_ok = 0
