@@ -39,7 +39,7 @@ class Params(C.Structure):
         ("ty_min", C.c_double), ("ty_step", C.c_double),
         ("tz_min", C.c_double), ("tz_step", C.c_double),
         ("refine_div", C.c_int32), ("refine_max_rounds", C.c_int32),
-        ("refine_th_margin", C.c_int32), ("refine_pad_", C.c_int32),
+        ("refine_th_margin", C.c_int32), ("max_iterations", C.c_int32),
         ("ambiguity_eps", C.c_double),
         ("min_cell_coverage", C.c_double),
         ("ransac_probability", C.c_double),

@@ -32,6 +32,7 @@ void orc_default_params(orc_params* p) {
   p->ransac_thresh = 0.03; /* :201 */
   p->ransac_hyp = 50;           /* SACSegmentation: max_iterations_ (50) */
   p->ransac_probability = 0.99; /* SACSegmentation: probability_ (0.99) */
+  p->max_iterations = 50;       /* ceres::Solver::Options::max_num_iterations (50) */
   p->ransac_seed = 12345u; /* PCL seeds its sampler with 12345 when random=false */
   p->hist_bins = 100;      /* :226 */
   p->gray_rate = 2.5;      /* :371 */
@@ -1122,6 +1123,8 @@ static int dogleg_compute_step(dogleg_state* s, int32_t n, const double* J, cons
 static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* final_cost) {
   const int np = lsq_np(q);
   const int32_t n = lsq_nres(q);
+  /* the board solver takes its cap from the parameters; the 3-D/2-D pose solver keeps Ceres' default */
+  const int32_t max_iter = (q->kind == 0 && q->p) ? q->p->max_iterations : 50;
   if (n == 0) {
     *final_cost = 0;
     return 0;
@@ -1154,7 +1157,7 @@ static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* fi
   int invalid = 0;
   for (;;) {
     /* FinalizeIterationAndCheckIfMinimizerCanContinue */
-    if (iter >= 50) break;
+    if (iter >= max_iter) break;
     double gmax = 0;
     for (int c = 0; c < np; ++c) gmax = fmax(gmax, fabs(grad[c]));
     if (gmax <= 1e-10) break;

@@ -91,12 +91,15 @@ typedef struct orc_params {
   int32_t refine_div;        /* finest lattice = grid step / refine_div (power of two, default 16; 0: keep the grid argmin) */
   int32_t refine_max_rounds; /* bound on the 27-candidate rounds of one pattern search (default 64) */
   int32_t refine_th_margin;  /* the search may leave the grid's theta range by this many grid steps (default 32) */
-  int32_t refine_pad_;
+  int32_t max_iterations;    /* trust-region iterations per pass of the board solver (Ceres' max_num_iterations, default 50).
+                                Kept in the 4 bytes that pad refine_th_margin to ambiguity_eps's alignment, so that the
+                                struct's size and offsets -- which every binding of the library hard-codes -- do not change */
   double ambiguity_eps;      /* ORC_AMBIGUOUS when (best neighbouring basin - cost) / cost < eps (default 1.0: an alternative must cost at least twice as much; <= 0: never) */
   double min_cell_coverage;  /* ORC_FLAG_LOW_COVERAGE when fewer than this fraction of the board's squares hold a labelled point under the final pose (default 0.9; <= 0: never) */
   double ransac_probability; /* SACSegmentation::probability_ (PCL default 0.99): RANSAC stops once iterations >= log(1 - p) / log(1 - w^3),
                                 w = best inlier share so far (pcl::RandomSampleConsensus::computeModel); <= 0: ransac_hyp hypotheses, no early stop */
 } orc_params;
+_Static_assert(sizeof(orc_params) == 208, "orc_params layout is part of the library's ABI");
 
 typedef struct orc_result {
   int32_t status;

@@ -112,6 +112,86 @@ def test_functor_jacobian_matches_finite_differences(ob):
     assert checked > 100
 
 
+def _functor_numpy(th, y, z, W, H, g, tlw, lw, oob):
+    """VirtualboardError::operator() (Optimization.h:31-107) restated in numpy fp64 on arrays of points, with its Jacobian
+    under Jet semantics (floor / ceil carry no derivative): strict bounds, the both-even / both-odd colour rule, the
+    `> 0.5` ceil branch and the out-of-board term."""
+    c, s = math.cos(th[0]), math.sin(th[0])
+    r1 = c * y - s * z + th[1]
+    r2 = s * y + c * z + th[2]
+    i = (r1 + W * g / 2.0) / g
+    j = (r2 + H * g / 2.0) / g
+    di = np.stack([(-s * y - c * z) / g, np.full_like(y, 1.0 / g), np.zeros_like(y)], 1)
+    dj = np.stack([(c * y - s * z) / g, np.zeros_like(y), np.full_like(y, 1.0 / g)], 1)
+    inside = (i > 0) & (i < W) & (j > 0) & (j < H)
+    ifl, jfl = np.floor(i), np.floor(j)
+    i_even, j_even = ifl == np.floor(ifl / 2) * 2, jfl == np.floor(jfl / 2) * 2
+    white = np.where(i_even == j_even, bool(tlw), not tlw)
+    miss = inside & (white != bool(lw))
+    si_in = np.where(i - ifl > 0.5, -1.0, 1.0)
+    sj_in = np.where(j - jfl > 0.5, -1.0, 1.0)
+    e_in = np.where(i - ifl > 0.5, np.ceil(i) - i, i - ifl) + np.where(j - jfl > 0.5, np.ceil(j) - j, j - jfl)
+    near0_i, near0_j = np.abs(i) < np.abs(i - W), np.abs(j) < np.abs(j - H)
+    e_out = np.where(near0_i, np.abs(i), np.abs(i - W)) + np.where(near0_j, np.abs(j), np.abs(j - H))
+    si_out = np.where(near0_i, np.where(i < 0, -1.0, 1.0), np.where(i - W < 0, -1.0, 1.0))
+    sj_out = np.where(near0_j, np.where(j < 0, -1.0, 1.0), np.where(j - H < 0, -1.0, 1.0))
+    out = ~inside & bool(oob)
+    r = np.where(miss, e_in, np.where(out, e_out, 0.0))
+    si = np.where(miss, si_in, np.where(out, si_out, 0.0))
+    sj = np.where(miss, sj_in, np.where(out, sj_out, 0.0))
+    return r, si[:, None] * di + sj[:, None] * dj
+
+
+_BOARDS = [(6, 8), (7, 9), (9, 12), (5, 5), (2, 3), (17, 17)]
+
+
+@pytest.mark.parametrize("W,H", _BOARDS, ids=["%dx%d" % b for b in _BOARDS])
+def test_functor_matches_numpy_restatement_on_other_boards(ob, W, H):
+    """orc_residual and its Jacobian == the numpy restatement on even x even, odd x odd, odd x even and square boards, four
+    square sizes, both phases, both laser colours, out-of-board term on and off -- points spread over the board, its
+    outline and a band around it, a quarter of them snapped to within 1e-9 of a cell border."""
+    rng = np.random.default_rng(W * 100 + H)
+    n = 60
+    for g in (0.08, 0.10, 0.12, 0.25):
+        hw, hh = 0.5 * W * g, 0.5 * H * g
+        y = rng.uniform(-hw - 2 * g, hw + 2 * g, n)
+        z = rng.uniform(-hh - 2 * g, hh + 2 * g, n)
+        snap = rng.random(n) < 0.25
+        y = np.where(snap, np.round(y / g) * g + rng.choice([-1e-9, 1e-9], n), y)
+        for tlw in (0, 1):
+            for lw in (0, 1):
+                for oob in (0, 1):
+                    th = [rng.uniform(-0.2, 0.2), rng.uniform(-g, g), rng.uniform(-g, g)]
+                    r_np, j_np = _functor_numpy(th, y, z, W, H, g, tlw, lw, oob)
+                    for k in range(n):
+                        r, jac = ob.residual(th, y[k], z[k], W, H, g, tlw, lw, oob, want_jac=True)
+                        assert r == pytest.approx(r_np[k], abs=1e-9), (W, H, g, tlw, lw, oob, y[k], z[k])
+                        assert np.allclose(jac, j_np[k], atol=1e-6), (W, H, g, y[k], z[k], jac, j_np[k])
+
+
+@pytest.mark.parametrize("W,H", _BOARDS, ids=["%dx%d" % b for b in _BOARDS])
+def test_functor_half_turn_rule_follows_the_board_parity(ob, W, H):
+    """A half turn about the board centre maps square (a, b) to (W-1-a, H-1-b): the colours are kept when W + H is even
+    (even x even, odd x odd) and swapped when it is odd (odd x even) -- i.e. the turned point is scored with the other
+    phase.  Exactly one phase is a mismatch inside the board, and the period is 2g."""
+    rng = np.random.default_rng(W * 31 + H)
+    g = 0.12
+    keep = (W + H) % 2 == 0
+    n_in = 0
+    for _ in range(300):
+        yy, zz = rng.uniform(-0.5 * W * g, 0.5 * W * g), rng.uniform(-0.5 * H * g, 0.5 * H * g)
+        tlw, lw = int(rng.integers(2)), int(rng.integers(2))
+        ra = ob.residual([0, 0, 0], yy, zz, W, H, g, tlw, lw, 0)
+        rb = ob.residual([0, 0, 0], -yy, -zz, W, H, g, tlw if keep else 1 - tlw, lw, 0)
+        assert ra == pytest.approx(rb, abs=1e-9), (yy, zz, tlw, lw)
+        r1 = ob.residual([0, 0, 0], yy, zz, W, H, g, 1 - tlw, lw, 0)
+        assert (ra == 0.0) != (r1 == 0.0) or (ra == 0.0 and r1 == 0.0)
+        n_in += (ra > 0) != (r1 > 0)
+        if W >= 3 and abs(yy) < 0.5 * W * g - 2 * g:
+            assert ob.residual([0, 0, 0], yy + 2 * g, zz, W, H, g, tlw, lw, 0) == pytest.approx(ra, abs=1e-9)
+    assert n_in > 200
+
+
 # ----------------------------------------------------------------------------- bundled corner files
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 6])
 def test_fixture_files_are_exact_lattices(golden_dir, n):
@@ -378,6 +458,38 @@ def test_local_solver_reaches_zero_cost_on_clean_board(ob):
 
 
 # ----------------------------------------------------------------------------- GRID-mode refinement (specification)
+@pytest.mark.parametrize("bins", [1, 7, 4096])
+@pytest.mark.parametrize("rate", [1.2, 6.0])
+def test_gray_zone_matches_python_restatement_at_other_bins_and_rates(ob, bins, rate):
+    """calHist / get_gray_zone away from 100 bins and rate 2.5, on continuous and on integer (VLP-16 reflectivity)
+    intensities: one bin never finds both peaks (ILCC_DEGENERATE_HIST); 7 and 4096 bins follow the restatement."""
+    rng = np.random.default_rng(bins * 10 + int(rate * 10))
+    p = ob.default_params()
+    p.hist_bins, p.gray_rate = bins, rate
+    n_ok = 0
+    for trial in range(12):
+        n = int(rng.integers(900, 3000))
+        inten = np.concatenate([rng.normal(12, 4, n // 2), rng.normal(100, 8, n - n // 2),
+                                rng.uniform(12, 100, n // 10)]).clip(0, 255)
+        if trial % 2:
+            inten = np.round(inten)
+        inten = inten.astype(np.float32)
+        st, rl, gz = ob.gray_zone(inten, p)
+        ref = _gray_zone_python(inten, bins, rate)
+        if ref is None:
+            assert st == 4
+        else:
+            assert st == 0
+            n_ok += 1
+            assert gz[0] == pytest.approx(ref[0], rel=1e-12) and gz[1] == pytest.approx(ref[1], rel=1e-12)
+            assert gz[0] == pytest.approx(((rate - 1) * rl[0] + rl[1]) / rate, rel=1e-12)
+            assert gz[1] == pytest.approx((rl[0] + (rate - 1) * rl[1]) / rate, rel=1e-12)
+    if bins == 1:
+        assert n_ok == 0
+    else:
+        assert n_ok >= 6
+
+
 def _clean_board_points(p, th0, ty0, tz0, margin=0.12, step=0.03):
     """noise-free checker samples (topleftWhite = False) moved by a known board -> cloud motion"""
     g = p.grid_length
@@ -411,6 +523,29 @@ def test_fixed_point_cost_is_the_cost_and_ignores_summation_order(ob):
                 perm = rng.permutation(m)
                 assert ob.cost_q(th, y[perm], z[perm], lab[perm], p, ph, oob) == cq
     assert ob.cost_q([0.0, 0.0, 0.0], y[:0], z[:0], lab[:0], p, 0, 1) == 0
+
+
+@pytest.mark.parametrize("W,H,g", [(7, 9, 0.12), (9, 12, 0.10), (5, 5, 0.15), (2, 3, 0.25), (17, 17, 0.08)])
+@pytest.mark.parametrize("delta", [0.02, 0.5, 5.0])
+def test_fixed_point_cost_is_the_cost_on_other_boards_and_deltas(ob, W, H, g, delta):
+    """orc_cost_q on other boards and Huber deltas: within m/2 quanta of orc_cost (the fp64 functor with Ceres' sqrt-form
+    Huber), order-independent, and -- for the out-of-board term to matter -- points reach past the board's outline."""
+    p = ob.default_params()
+    p.board_w, p.board_h, p.grid_length, p.huber_delta = W, H, g, delta
+    rng = np.random.default_rng(W * H + int(delta * 100))
+    m = 1200
+    y = rng.uniform(-0.6 * W * g, 0.6 * W * g, m).astype(np.float32)
+    z = rng.uniform(-0.6 * H * g, 0.6 * H * g, m).astype(np.float32)
+    lab = rng.integers(0, 2, m).astype(np.int8)
+    for th in ([0.0, 0.0, 0.0], [0.11, -0.031, 0.052], [-0.2, 0.07, -0.09]):
+        for ph in (0, 1):
+            for oob in (0, 1):
+                cq = ob.cost_q(th, y, z, lab, p, ph, oob)
+                c = ob.cost(th, y, z, lab, p, ph, oob)
+                assert c > 0
+                assert abs(cq / ob.COST_Q_ONE - c) <= 0.5 * m / ob.COST_Q_ONE + 1e-12 * max(1.0, c)
+                perm = rng.permutation(m)
+                assert ob.cost_q(th, y[perm], z[perm], lab[perm], p, ph, oob) == cq
 
 
 def _neighbour_costs(ob, p, y, z, lab, lat, phase, stride=1):
