@@ -187,7 +187,8 @@ typedef struct ilcc_result {
 
 typedef struct ilcc_handle ilcc_handle;
 
-/* per-stage device time of the last batch call, ms (HIP events on the handle's stream) */
+/* per-stage device time of the last batch call, ms (HIP events on the batch's stream; grid_cost leaves out the wait for the
+ * previous batch's full pass) */
 typedef struct ilcc_timing {
   float roi_crop, cluster, ransac_plane, plane_frame_hist, grid_cost, refine_corners, total;
   uint32_t grid_cost_launches;   /* kernel launches accumulated since ilcc_reset_timing */
@@ -257,16 +258,17 @@ int32_t ilcc_extract_batch_device(ilcc_handle* h, const float* d_xyzi, const uin
                                   uint32_t n_frames, const float* d_clicks, ilcc_result* out);
 
 /* Asynchronous form of ilcc_extract_batch_device: enqueue the whole path for one batch and return;
- * up to 4 batches may be in flight per handle (each in its own buffers and stream; streams that share one of the
- * process's hardware queues serialise), so the short latency-bound stages of one batch overlap with the grid search
- * of another.  *ticket identifies the batch; ilcc_wait blocks until it is complete and copies its records to out
- * (n_frames entries).  (The library never touches the environment: the hardware-queue count is the host's setting.
- * The first use of the fourth slot prints a one-time note when fewer than 5 queues are configured.)
+ * up to 4 batches may be in flight per handle (each in its own buffers; the batches take the handle's three streams in
+ * turn, and a batch's grid-search full pass waits for the previous batch's), so the short latency-bound stages of one
+ * batch overlap with the grid search of another.  *ticket identifies the batch; ilcc_wait blocks until it is complete
+ * and copies its records to out (n_frames entries).  (The library never touches the environment: the hardware-queue
+ * count is the host's setting.  Three streams plus the host's own need 4 queues, HIP's default; ilcc_create prints a
+ * one-time note when fewer are configured.)
  * Tickets must be waited for in submission order once all slots are taken (ILCC_CAPACITY otherwise).
  * The inputs must stay valid and unchanged until the matching ilcc_wait returns. */
 int32_t ilcc_submit_batch_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets,
                                  uint32_t n_frames, const float* d_clicks, int32_t* ticket);
-/* The same with HOST inputs (SURVEY.md 8d counts this copy): the batch's H2D copy is enqueued on the slot's own
+/* The same with HOST inputs (SURVEY.md 8d counts this copy): the batch's H2D copy is enqueued on the batch's
  * stream in front of its kernels, so it overlaps with the kernels of the other batches in flight and the host never
  * blocks on it.  xyzi should be page-locked (hipHostMalloc / hipHostRegister / torch pin_memory): the copy of a
  * pageable buffer is staged by the runtime and serialises.  xyzi and clicks must stay valid until ilcc_wait. */

@@ -1,5 +1,5 @@
 // ilcc_api.cpp -- host side of the C-ABI (include/ilcc_hip.h): handle, HBM buffers, the stage
-// pipeline on one HIP stream, HIP-event timing, and the two file contracts of the path.
+// pipeline on the handle's three HIP streams, HIP-event timing, and the two file contracts of the path.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,15 +21,17 @@ using namespace ilcc;
 #define ILCC_SLOTS 4
 #endif
 constexpr int kSlots = ILCC_SLOTS;   // batches in flight per handle (submit/wait); slot 0 serves the synchronous calls.
-                            // Every slot has its own stream: with fewer than 5 hardware queues in the process two slot
-                            // streams share one hardware queue and serialise (measured: 113 k instead of 164 k frames/s)
+                            // A slot holds buffers, events and staging, no stream: the batches share the handle's kStreams
+                            // streams, so the hardware queues a handle needs do not grow with the batches in flight
+constexpr int kStreams = 3;   // the handle's streams: batch seq runs whole on S[seq mod 3]
 
-// One in-flight batch: its own stream, events, stage buffers and pinned result staging.
+// One in-flight batch: its events, stage buffers and pinned result staging.
 struct Slot {
-  hipStream_t stream = nullptr;
   hipEvent_t ev[10]{};   // 0..6 stage boundaries; 7, 8: end of K6's seed + refinement passes / start of its full pass; 9: behind K1's count pass
   hipEvent_t k6ev[4]{};  // inside the K6 stage: after K5w, after the seed launch, after the refinement launch, after the anchor launch (launch-by-launch event spans)
-  hipEvent_t k6_done = nullptr;
+  hipEvent_t done = nullptr;   // the batch's last command (what a wait synchronises on: never a whole shared stream)
+  hipEvent_t late = nullptr;   // behind what a wait enqueues itself (K9 into d_records, the late compact pack, ensure_full's copy)
+  hipEvent_t k6_done = nullptr;   // no timing: behind the full pass (the next batch's full pass waits for it)
   bool allocated = false;
   // device buffers
   float4* d_xyzi = nullptr;   // staging for host-input calls
@@ -81,9 +83,13 @@ struct ilcc_handle {
   uint32_t max_theta = 0;
   uint32_t crop_chunks_cap = 0;
   Slot slots[kSlots];
+  hipStream_t stream[kStreams]{};   // S0, S1, S2: created with the handle, shared by the slots
+  uint64_t seq = 0;     // batches enqueued so far: batch seq takes S[seq mod 3]
+  uint64_t stream_last[kStreams]{};   // per stream, 1 + seq of the last batch enqueued on it (0: none yet)
+  hipEvent_t entry_done = nullptr;    // no timing: behind the work of a diagnostic entry or a table upload
   int next_slot = 0;    // round robin for ilcc_submit_*
   int last_slot = -1;   // slot whose batch the fetch calls look at
-  int k6_last = -1;     // slot that issued the most recent K6 (K6 launches are chained: clean timing)
+  int k6_last = -1;     // slot that issued the most recent full pass (full passes are chained: they never share the chip)
   // candidate tables (shared by all slots, read-only while batches are in flight)
   float *d_cth = nullptr, *d_sth = nullptr, *d_ay = nullptr, *d_az = nullptr;
   // decimated subset of the same tables: seeding pass of K6's branch and bound
@@ -170,9 +176,17 @@ bool params_ok(const ilcc_params& p, std::string& why) {
   return true;
 }
 
+// a diagnostic entry or a table upload waits for its own work on an event behind it, never for the whole shared stream
+int32_t sync_own(ilcc_handle* h, hipStream_t s) {
+  HIP_TRY(h, hipEventRecord(h->entry_done, s));
+  HIP_TRY(h, hipEventSynchronize(h->entry_done));
+  return ILCC_OK;
+}
+
+// (only where no batch is in flight: a whole shared stream also holds the later batches)
 int32_t sync_all(ilcc_handle* h) {
-  for (Slot& sl : h->slots)
-    if (sl.allocated) HIP_TRY(h, hipStreamSynchronize(sl.stream));
+  for (hipStream_t s : h->stream)
+    if (s) HIP_TRY(h, hipStreamSynchronize(s));
   return ILCC_OK;
 }
 
@@ -182,7 +196,7 @@ int32_t upload_tables(ilcc_handle* h) {
     h->err = "grid axis longer than the handle's table capacity";
     return ILCC_CAPACITY;
   }
-  hipStream_t st = h->slots[0].stream;
+  hipStream_t st = h->stream[0];
   std::vector<float> cth(p.n_th), sth(p.n_th), ay(p.n_ty), az(p.n_tz);
   const double g = p.grid_length;
   for (int k = 0; k < p.n_th; ++k) {
@@ -245,12 +259,12 @@ int32_t upload_tables(ilcc_handle* h) {
       tab[i] = make_double2(std::cos(th), std::sin(th));
     }
     HIP_TRY(h, hipMemcpyAsync(h->d_th_lattice, tab.data(), sizeof(double2) * n, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipStreamSynchronize(st));   // tab is a local
+    const int32_t sst = sync_own(h, st);   // tab is a local
+    if (sst != ILCC_OK) return sst;
     h->hop_y = (int32_t)std::lround(p.grid_length / (p.ty_step / (double)div));
     h->hop_z = (int32_t)std::lround(p.grid_length / (p.tz_step / (double)div));
   }
-  HIP_TRY(h, hipStreamSynchronize(st));
-  return ILCC_OK;
+  return sync_own(h, st);
 }
 
 void free_slot(Slot& sl) {
@@ -268,26 +282,24 @@ void free_slot(Slot& sl) {
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : sl.k6ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (sl.done) (void)hipEventDestroy(sl.done);
+  if (sl.late) (void)hipEventDestroy(sl.late);
   if (sl.k6_done) (void)hipEventDestroy(sl.k6_done);
-  if (sl.stream) (void)hipStreamDestroy(sl.stream);
   sl = Slot{};
 }
 
-// The HIP runtime maps streams onto the hardware queues GPU_MAX_HW_QUEUES allows and streams that share a queue
-// serialise: a fourth batch in flight only pays with >= 5 queues.  The variable is read when the runtime initialises and
-// belongs to the HOST process: the library only reads it, and says so once when the fourth slot is first used with fewer
-// than 5 queues configured.
-void warn_hw_queues_once(int slot_index) {
+// The HIP runtime maps streams onto the hardware queues GPU_MAX_HW_QUEUES allows, and streams that share a queue
+// serialise.  A handle's three streams plus the host's own stream need 4 queues, HIP's default.  The variable is read when
+// the runtime initialises and belongs to the HOST process: the library only reads it, and says so once when it is below 4.
+void warn_hw_queues_once() {
   static std::once_flag once;   // handles of several threads (one per GPU) may reach this together
-  if (slot_index < 3) return;
   std::call_once(once, [] {
     const char* v = std::getenv("GPU_MAX_HW_QUEUES");
-    if (v && std::atoi(v) >= 5) return;
+    if (!v || std::atoi(v) >= kStreams + 1) return;
     std::fprintf(stderr,
-                 "libilcc_hip: GPU_MAX_HW_QUEUES=%s: "
-                 "with fewer than 5 hardware queues the fourth batch in flight shares a queue with another one and "
-                 "serialises; keep at most 3 tickets outstanding for full overlap (the library does not modify the "
-                 "environment)\n", v ? v : "(unset: HIP's default is 4)");
+                 "libilcc_hip: GPU_MAX_HW_QUEUES=%s: with fewer than %d hardware queues two of the handle's stage streams "
+                 "(or one and the host's stream) share a queue and serialise (the library does not modify the "
+                 "environment)\n", v, kStreams + 1);
   });
 }
 
@@ -339,12 +351,12 @@ int32_t size_group_prepass(ilcc_handle* h, Slot& sl) {
 
 int32_t alloc_slot(ilcc_handle* h, Slot& sl) {
   if (sl.allocated) return ILCC_OK;
-  warn_hw_queues_once((int)(&sl - h->slots));
   const uint64_t np = h->max_points;
   const uint32_t mf = h->max_frames;
-  HIP_TRY(h, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
   for (auto& ev : sl.ev) HIP_TRY(h, hipEventCreate(&ev));
   for (auto& ev : sl.k6ev) HIP_TRY(h, hipEventCreate(&ev));
+  HIP_TRY(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+  HIP_TRY(h, hipEventCreateWithFlags(&sl.late, hipEventDisableTiming));
   HIP_TRY(h, hipEventCreateWithFlags(&sl.k6_done, hipEventDisableTiming));
 #define ALLOC(ptr, bytes) HIP_TRY(h, hipMalloc((void**)&(ptr), (size_t)(bytes)))
   ALLOC(sl.d_xyzi, sizeof(float4) * np);
@@ -506,8 +518,26 @@ int32_t check_offsets(ilcc_handle* h, const uint64_t* offsets, uint32_t n_frames
   return ILCC_OK;
 }
 
-int32_t enqueue_impl(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames, const float* d_clicks,
-                     bool front_only, bool no_crop);
+// The next batch's stream: batch seq runs whole on S[seq mod 3]
+int take_stream(ilcc_handle* h) {
+  const int k = (int)(h->seq % kStreams);
+  h->stream_last[k] = ++h->seq;
+  return k;
+}
+
+// Where a wait launches what it needs once its batch is complete (K9 into d_records, the late compact pack, ensure_full's copy):
+// the stream whose last batch is the oldest.  A stream that holds no batch submitted after the waited one is idle.  With four
+// batches in flight on three streams every stream holds a later batch, and the launch waits for the rest of the oldest of them
+// (its chain wait, for the batch just finished, is already met; a younger one may still wait for full passes before it).
+hipStream_t late_stream(const ilcc_handle* h) {
+  int best = 0;
+  for (int k = 1; k < kStreams; ++k)
+    if (h->stream_last[k] < h->stream_last[best]) best = k;
+  return h->stream[best];
+}
+
+int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
+                     const float* d_clicks, bool front_only, bool no_crop);
 
 // K2's workgroup keeps bitmap + per-cell arrays + (up to cluster_lds_points) sorted points in LDS: when the cell arrays have
 // grown large (dense clouds), give up LDS points first -- frames of that size sort into HBM anyway
@@ -526,19 +556,19 @@ hipError_t copy_results_trimmed(ilcc_result* dst, const ilcc_result* d_src, uint
                           hipMemcpyDeviceToHost, s);
 }
 
-// enqueue the whole path for one batch on the slot's stream (no host synchronisation).  On a mid-pipeline failure the
-// kernels already queued may still be running on the slot's buffers: wait for them before handing the error back, so
-// that the next submit can reuse the slot.
-int32_t enqueue(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
+// enqueue the whole path for one batch on the stream (no host synchronisation).  On a mid-pipeline failure the kernels already
+// queued may still be running on the slot's buffers: wait for them before handing the error back, so that the next submit can
+// reuse the slot.  (The batch is the newest one: its stream holds nothing behind it.)
+int32_t enqueue(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
                 const float* d_clicks, bool front_only = false, bool no_crop = false) {
   if (h->poisoned) {
     h->err = "handle unusable: a failed ilcc_set_params could not restore the device tables";
     return ILCC_HIP_ERROR;
   }
-  const int32_t st = enqueue_impl(h, si, d_xyzi, offsets, n_frames, d_clicks, front_only, no_crop);
-  if (st != ILCC_OK && h->slots[si].stream) {
+  const int32_t st = enqueue_impl(h, si, s, d_xyzi, offsets, n_frames, d_clicks, front_only, no_crop);
+  if (st != ILCC_OK) {
     const std::string why = h->err;
-    (void)hipStreamSynchronize(h->slots[si].stream);
+    (void)hipStreamSynchronize(s);
     (void)hipGetLastError();
     h->slots[si].busy = false;
     h->err = why;
@@ -553,9 +583,6 @@ int32_t enqueue(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_t* of
 #endif
 #ifndef ILCC_BOX_POINTS
 #define ILCC_BOX_POINTS 48     // rim points a (frame, theta) workgroup's own box pre-pass looks at, at least
-#endif
-#ifndef ILCC_K6_CHAIN
-#define ILCC_K6_CHAIN 1        // 0: the full passes of different batches may share the chip (measured slower every round)
 #endif
 constexpr int kAnchorRadius = 1;   // the anchor scores 2 * 1 + 1 thetas around the refinement's argmin, one 4 x 4 tile each, on ALL points
 #ifndef ILCC_ANCHOR_ROUNDS
@@ -633,10 +660,11 @@ int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStrea
   return ILCC_OK;
 }
 
-// The grid search of one batch on its stream: K5w (walk layout), the launches that locate the minimum and publish the frame's bound
-// (k6_locate, or seed + refinement + anchor rounds), the common pre-pass, the full pass -- with the slot's K6 events recorded in
-// between.  chain: the full pass waits for the previous batch's (the pipeline; the diagnostic entry ilcc_grid_solve runs alone).
-int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, int si, const Ctx& c, hipStream_t s, uint32_t n_frames, bool chain) {
+// The grid search of one batch: K5w (walk layout), the launches that locate the minimum and publish the frame's bound (k6_locate,
+// or seed + refinement + anchor rounds), the common pre-pass, the full pass -- with the slot's K6 events recorded in between.
+// chain: the full pass waits for the previous batch's, on whichever stream that one runs (every batch; the diagnostic entry
+// ilcc_grid_solve runs alone).
+int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, uint32_t n_frames, bool chain) {
   const bool prune = h->p.grid_prune != 0;
   launch_walk_order(c, s);   // K5w: the labelled points in K6's walk layout, once per frame
   HIP_TRY(h, hipEventRecord(sl.k6ev[0], s));
@@ -686,8 +714,7 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, int si, const Ctx& c, hipS
   const GroupPrepassPlan gp = group_prepass_plan(h->p);
   full.box_points = gp.box ? (uint32_t)ILCC_BOX_POINTS : 0u;   // (eligibility: group_prepass_plan, which also sized the buffers)
   // k6_group_prepass: one box pre-pass for kThetaGroup consecutive thetas, launched HERE -- behind the anchor (it needs the
-  // frame's bound), in front of the wait for the previous batch's full pass, so it runs beside that pass like the other small
-  // launches.  Its buffers were sized for (max_frames, this grid) by alloc_slot / ilcc_set_params.
+  // frame's bound), in front of the full pass.  Its buffers were sized for (max_frames, this grid) by alloc_slot / ilcc_set_params.
   if (full.box_points != 0u && gp.on && (size_t)n_frames * gp.groups <= sl.grp_alive_cap &&
       (size_t)n_frames * gp.groups * gp.words <= sl.grp_mask_cap) {
     full.grp_count = gp.groups;
@@ -700,20 +727,23 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, int si, const Ctx& c, hipS
     if (h->group_prepass_skipped++ == 0) h->err = "note: k6_group_prepass skipped (mask buffers smaller than this batch needs): slower, results unaffected";
   }
   HIP_TRY(h, hipEventRecord(sl.ev[7], s));
-  // The FULL passes of different slots are chained so that they never share the chip (two passes side by side both run at half
-  // speed and every batch's front end waits longer for wave slots); the launches above are small and are left free to overlap
-  // with another batch's full pass, like K2 / K3 / K7.
-  if (chain && ILCC_K6_CHAIN && h->k6_last >= 0 && h->k6_last != si && h->slots[h->k6_last].busy)
+  // The FULL passes of consecutive batches are chained so that they never share the chip (two passes side by side both run at
+  // half speed and every batch's front end waits longer for wave slots); the launches above are small and are left free to
+  // overlap with another batch's full pass, like K2 / K3 / K7.
+  const int si = (int)(&sl - h->slots);
+  if (chain && h->k6_last >= 0 && h->k6_last != si && h->slots[h->k6_last].busy)
     HIP_TRY(h, hipStreamWaitEvent(s, h->slots[h->k6_last].k6_done, 0));
   HIP_TRY(h, hipEventRecord(sl.ev[8], s));
   full.tie_count = sl.d_tie_count;
   launch_grid_cost(full, s, /*use_oob=*/1, nullptr, prune);
-  HIP_TRY(h, hipEventRecord(sl.k6_done, s));
-  if (chain) h->k6_last = si;
+  if (chain) {
+    HIP_TRY(h, hipEventRecord(sl.k6_done, s));
+    h->k6_last = si;
+  }
   return ILCC_OK;
 }
 
-int32_t enqueue_impl(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
+int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
                      const float* d_clicks, bool front_only, bool no_crop) {
   Slot& sl = h->slots[si];
   uint64_t max_n = 0;
@@ -726,7 +756,6 @@ int32_t enqueue_impl(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_
   }
   sl.off.assign(offsets, offsets + n_frames + 1);
   sl.n_frames = n_frames;
-  hipStream_t s = sl.stream;
   std::memcpy(sl.h_off, sl.off.data(), sizeof(uint64_t) * (n_frames + 1));
   HIP_TRY(h, hipMemcpyAsync(sl.d_off, sl.h_off, sizeof(uint64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
   // (result records, component counters, K6 counters and near-tie counters are reset inside K1 / K2)
@@ -767,7 +796,7 @@ int32_t enqueue_impl(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_
   sl.grid = !front_only && h->p.solver == ILCC_SOLVER_GRID;
   HIP_TRY(h, hipEventRecord(sl.ev[4], s));
   if (sl.grid) {
-    const int32_t st = enqueue_grid_search(h, sl, si, c, s, n_frames, /*chain=*/true);
+    const int32_t st = enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/true);
     if (st != ILCC_OK) return st;
   }
   HIP_TRY(h, hipEventRecord(sl.ev[5], s));
@@ -794,16 +823,26 @@ int32_t enqueue_impl(ilcc_handle* h, int si, const float4* d_xyzi, const uint64_
   }
   launch_store_to_host(sl.d_iters, sl.h_iters_dev, sizeof(unsigned long long) * kBatchWords, s);
   HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(sl.done, s));
   sl.busy = true;
   sl.online = no_crop;
+  return ILCC_OK;
+}
+
+// What a wait launches for a batch that has completed (on late_stream) is waited for on its own event
+int32_t run_late(ilcc_handle* h, Slot& sl, hipStream_t s) {
+  HIP_TRY(h, hipEventRecord(sl.late, s));
+  HIP_TRY(h, hipEventSynchronize(sl.late));
   return ILCC_OK;
 }
 
 // the slot's full records in its pinned staging (they are there already unless the batch ran in ILCC_RESULTS_COMPACT mode)
 int32_t ensure_full(ilcc_handle* h, Slot& sl) {
   if (sl.h_res_valid) return ILCC_OK;
-  HIP_TRY(h, copy_results_trimmed(sl.h_res, sl.d_res, sl.n_frames, sl.rec_corners, sl.stream));
-  HIP_TRY(h, hipStreamSynchronize(sl.stream));
+  const hipStream_t s = late_stream(h);
+  HIP_TRY(h, copy_results_trimmed(sl.h_res, sl.d_res, sl.n_frames, sl.rec_corners, s));
+  const int32_t st = run_late(h, sl, s);
+  if (st != ILCC_OK) return st;
   sl.h_res_valid = true;
   return ILCC_OK;
 }
@@ -812,13 +851,17 @@ int32_t ensure_full(ilcc_handle* h, Slot& sl) {
 int32_t finish(ilcc_handle* h, int si, ilcc_result* out, float* out_compact = nullptr, float* d_records = nullptr,
                uint32_t n_corners = 0, uint32_t tag_base = 0) {
   Slot& sl = h->slots[si];
-  if (d_records) launch_pack_records(sl.d_res, sl.n_frames, n_corners, tag_base, d_records, sl.stream);   // same stream: after K7
+  HIP_TRY(h, hipEventSynchronize(sl.done));
   const uint32_t n_frames = sl.n_frames;
   const size_t rec_w = (size_t)ILCC_RECORD_HEADER + 3 * (size_t)sl.rec_corners;
-  if (out_compact && !sl.compact) {   // not enqueued with the batch: pack and copy now
-    launch_pack_records(sl.d_res, n_frames, sl.rec_corners, 0u, sl.h_rec_dev, sl.stream);
+  const bool pack_now = out_compact && !sl.compact;   // the compact records were not enqueued with the batch
+  const hipStream_t ls = late_stream(h);
+  if (d_records) launch_pack_records(sl.d_res, n_frames, n_corners, tag_base, d_records, ls);
+  if (pack_now) launch_pack_records(sl.d_res, n_frames, sl.rec_corners, 0u, sl.h_rec_dev, ls);
+  if (d_records || pack_now) {
+    const int32_t st = run_late(h, sl, ls);
+    if (st != ILCC_OK) return st;
   }
-  HIP_TRY(h, hipStreamSynchronize(sl.stream));
   sl.busy = false;
   sl.h_res_valid = !sl.compact;
   h->last_slot = si;
@@ -1115,6 +1158,12 @@ ilcc_handle* ilcc_create(int32_t device, const ilcc_params* p, uint32_t max_fram
   if ((e = hipMalloc((void**)&h->d_solve, sizeof(double) * 8)) != hipSuccess ||
       (e = hipMalloc((void**)&h->d_refine_io, sizeof(RefineOut))) != hipSuccess)
     return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
+  warn_hw_queues_once();
+  for (hipStream_t& s : h->stream)
+    if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess)
+      return fail(std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
+  if ((e = hipEventCreateWithFlags(&h->entry_done, hipEventDisableTiming)) != hipSuccess)
+    return fail(std::string("hipEventCreateWithFlags: ") + hipGetErrorString(e));
   if (alloc_slot(h, h->slots[0]) != ILCC_OK) return fail(h->err);   // further slots on first asynchronous use
   if (upload_tables(h) != ILCC_OK) return fail(h->err);
   return h;
@@ -1122,15 +1171,17 @@ ilcc_handle* ilcc_create(int32_t device, const ilcc_params* p, uint32_t max_fram
 
 void ilcc_destroy(ilcc_handle* h) {
   if (!h) return;
-  for (Slot& sl : h->slots) {
-    if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-    free_slot(sl);
-  }
+  for (hipStream_t s : h->stream)
+    if (s) (void)hipStreamSynchronize(s);
+  for (Slot& sl : h->slots) free_slot(sl);
+  for (hipStream_t s : h->stream)
+    if (s) (void)hipStreamDestroy(s);
   void* bufs[] = {h->d_cth, h->d_sth, h->d_ay, h->d_az, h->d_cth2, h->d_sth2, h->d_ay2, h->d_az2, h->d_solve, h->d_refine_io,
                   h->d_th_lattice};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (h->tl_ref) (void)hipEventDestroy(h->tl_ref);
+  if (h->entry_done) (void)hipEventDestroy(h->entry_done);
   delete h;
 }
 
@@ -1197,7 +1248,8 @@ int32_t ilcc_submit_batch_device(ilcc_handle* h, const float* d_xyzi, const uint
   }
   st = alloc_slot(h, sl);
   if (st != ILCC_OK) return st;
-  st = enqueue(h, si, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, d_clicks);
+  const hipStream_t s = h->stream[take_stream(h)];
+  st = enqueue(h, si, s, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, d_clicks);
   if (st != ILCC_OK) return st;
   *ticket = si;
   h->next_slot = (si + 1) % kSlots;
@@ -1218,11 +1270,12 @@ int32_t ilcc_submit_batch(ilcc_handle* h, const float* xyzi, const uint64_t* off
   }
   st = alloc_slot(h, sl);
   if (st != ILCC_OK) return st;
-  // the copy rides on the slot's stream: ordered before this batch's K1, concurrent with every other slot's kernels
+  const hipStream_t s = h->stream[take_stream(h)];
+  // the copy rides on the batch's front-end stream: ordered before this batch's K1, concurrent with the other batches' kernels
   if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, sl.stream));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, sl.stream));
-  st = enqueue(h, si, sl.d_xyzi, offsets, n_frames, sl.d_clicks);
+    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
+  st = enqueue(h, si, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks);
   if (st != ILCC_OK) return st;
   *ticket = si;
   h->next_slot = (si + 1) % kSlots;
@@ -1319,7 +1372,8 @@ int32_t ilcc_extract_batch_device(ilcc_handle* h, const float* d_xyzi, const uin
     h->err = "synchronous call while ticket 0 is in flight";
     return ILCC_BAD_ARGUMENT;
   }
-  st = enqueue(h, 0, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, d_clicks);
+  const hipStream_t s = h->stream[take_stream(h)];
+  st = enqueue(h, 0, s, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, d_clicks);
   if (st != ILCC_OK) return st;
   return finish(h, 0, out);
 }
@@ -1335,10 +1389,11 @@ int32_t ilcc_extract_batch(ilcc_handle* h, const float* xyzi, const uint64_t* of
     h->err = "synchronous call while ticket 0 is in flight";
     return ILCC_BAD_ARGUMENT;
   }
+  const hipStream_t s = h->stream[take_stream(h)];
   if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, sl.stream));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, sl.stream));
-  st = enqueue(h, 0, sl.d_xyzi, offsets, n_frames, sl.d_clicks);
+    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
+  st = enqueue(h, 0, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks);
   if (st != ILCC_OK) return st;
   return finish(h, 0, out);
 }
@@ -1376,10 +1431,11 @@ int32_t ilcc_chessboard_by_point_batch(ilcc_handle* h, const float* xyzi, const 
     h->err = "synchronous call while ticket 0 is in flight";
     return ILCC_BAD_ARGUMENT;
   }
+  const hipStream_t s = h->stream[take_stream(h)];
   if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, sl.stream));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, points, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, sl.stream));
-  st = enqueue(h, 0, sl.d_xyzi, offsets, n_frames, sl.d_clicks, /*front_only=*/true, /*no_crop=*/true);
+    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, points, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
+  st = enqueue(h, 0, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks, /*front_only=*/true, /*no_crop=*/true);
   if (st != ILCC_OK) return st;
   st = finish(h, 0, out);
   if (st != ILCC_OK) return st;
@@ -1387,8 +1443,8 @@ int32_t ilcc_chessboard_by_point_batch(ilcc_handle* h, const float* xyzi, const 
   return ILCC_OK;
 }
 
-// The same call in two halves, like ilcc_submit_batch / ilcc_wait: up to four calls in flight per handle, the H2D copy of one
-// overlapping the kernels of the others (the two tiers need no host decision in between: the second tier's kernels skip the
+// The same call in two halves, like ilcc_submit_batch / ilcc_wait: up to four calls in flight per handle, each whole on one of
+// the handle's three streams in turn, the H2D copy of one overlapping the kernels of the others (the two tiers need no host decision in between: the second tier's kernels skip the
 // frames the first has answered).  A tracker that hands over one scan at a time gains nothing; a recorded sequence does.
 int32_t ilcc_submit_chessboard_by_point(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
                                         const float* points, int32_t* ticket) {
@@ -1404,10 +1460,11 @@ int32_t ilcc_submit_chessboard_by_point(ilcc_handle* h, const float* xyzi, const
   }
   st = alloc_slot(h, sl);
   if (st != ILCC_OK) return st;
+  const hipStream_t s = h->stream[take_stream(h)];
   if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, sl.stream));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, points, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, sl.stream));
-  st = enqueue(h, si, sl.d_xyzi, offsets, n_frames, sl.d_clicks, /*front_only=*/true, /*no_crop=*/true);
+    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, points, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
+  st = enqueue(h, si, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks, /*front_only=*/true, /*no_crop=*/true);
   if (st != ILCC_OK) return st;
   *ticket = si;
   h->next_slot = (si + 1) % kSlots;
@@ -1508,7 +1565,7 @@ int64_t ilcc_fetch_walk(ilcc_handle* h, uint32_t frame, float* out_yz, uint8_t* 
 }
 
 // shared setup for the two single-kernel test entries: frame 0 of slot 0 = caller's labelled points
-static int32_t stage_labelled(ilcc_handle* h, const float* yz, const uint8_t* label, uint32_t m) {
+static int32_t stage_labelled(ilcc_handle* h, hipStream_t s, const float* yz, const uint8_t* label, uint32_t m) {
   if (!h || (m > 0 && (!yz || !label))) return ILCC_BAD_ARGUMENT;
   if (m > h->max_points) {
     h->err = "more points than the handle holds";
@@ -1520,7 +1577,6 @@ static int32_t stage_labelled(ilcc_handle* h, const float* yz, const uint8_t* la
     return ILCC_BAD_ARGUMENT;
   }
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = sl.stream;
   const uint64_t off[2] = {0, m};
   ilcc_result r;
   std::memset(&r, 0, sizeof(r));
@@ -1534,17 +1590,21 @@ static int32_t stage_labelled(ilcc_handle* h, const float* yz, const uint8_t* la
     HIP_TRY(h, hipMemcpyAsync(sl.d_yz, yz, sizeof(float2) * m, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(sl.d_lab, label, m, hipMemcpyHostToDevice, s));
   }
-  HIP_TRY(h, hipStreamSynchronize(s));
+  {
+    const int32_t sst = sync_own(h, s);
+    if (sst != ILCC_OK) return sst;
+  }
   sl.n_frames = 0;   // the stage buffers no longer describe a batch
   return ILCC_OK;
 }
 
 int32_t ilcc_grid_cost(ilcc_handle* h, const float* yz, const uint8_t* label, uint32_t m, int32_t use_oob,
                        float* cost_out, int32_t* best_index, float* best_cost) {
-  int32_t st = stage_labelled(h, yz, label, m);
+  if (!h) return ILCC_BAD_ARGUMENT;
+  const hipStream_t s = h->stream[take_stream(h)];
+  int32_t st = stage_labelled(h, s, yz, label, m);
   if (st != ILCC_OK) return st;
   Slot& sl = h->slots[0];
-  hipStream_t s = sl.stream;
   const size_t vol = (size_t)h->p.n_th * h->p.n_ty * h->p.n_tz * 2;
   float* d_vol = nullptr;
   if (cost_out) HIP_TRY(h, hipMalloc((void**)&d_vol, sizeof(float) * vol));
@@ -1567,7 +1627,8 @@ int32_t ilcc_grid_cost(ilcc_handle* h, const float* yz, const uint8_t* label, ui
   hipError_t e = hipGetLastError();   // a launch that asked for more LDS than the device grants fails HERE, not at the copy
   if (e == hipSuccess) e = hipMemcpyAsync(part.data(), sl.d_partial, sizeof(GridPartial) * c.grid_blocks, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && cost_out) e = hipMemcpyAsync(cost_out, d_vol, sizeof(float) * vol, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipEventRecord(h->entry_done, s);
+  if (e == hipSuccess) e = hipEventSynchronize(h->entry_done);
   if (e != hipSuccess) {
     h->err = std::string("ilcc_grid_cost: ") + hipGetErrorString(e);
     return ILCC_HIP_ERROR;
@@ -1589,10 +1650,10 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
     if (h) h->err = "ilcc_grid_solve needs ILCC_SOLVER_GRID";
     return ILCC_BAD_ARGUMENT;
   }
-  int32_t st = stage_labelled(h, yz, label, m);
+  const hipStream_t s = h->stream[take_stream(h)];
+  int32_t st = stage_labelled(h, s, yz, label, m);
   if (st != ILCC_OK) return st;
   Slot& sl = h->slots[0];
-  hipStream_t s = sl.stream;
   uint32_t lds = 1024;
   while (lds < m && lds < (uint32_t)kGridLdsPointsMax) lds <<= 1;
   const uint32_t saved = h->grid_lds_points;
@@ -1605,7 +1666,7 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
   HIP_TRY(h, hipMemcpyAsync(sl.d_bound_sub, &inf_bits, sizeof(inf_bits), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(sl.d_tie_count, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemsetAsync(sl.d_iters, 0, sizeof(unsigned long long) * kBatchWords, s));
-  st = enqueue_grid_search(h, sl, 0, c, s, 1, /*chain=*/false);
+  st = enqueue_grid_search(h, sl, c, s, 1, /*chain=*/false);
   if (st != ILCC_OK) return st;
   Ctx c7 = c;
   c7.tie_count = sl.d_tie_count;
@@ -1615,7 +1676,10 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
   ilcc_result r;
   HIP_TRY(h, hipMemcpyAsync(&rec, sl.d_solverec, sizeof(rec), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipMemcpyAsync(&r, sl.d_res, offsetof(ilcc_result, corners), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
+  {
+    const int32_t sst = sync_own(h, s);
+    if (sst != ILCC_OK) return sst;
+  }
   if (!rec.valid) {
     h->err = "ilcc_grid_solve: the grid search produced no candidate";
     return ILCC_TOO_FEW_POINTS;
@@ -1640,18 +1704,21 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
 
 int32_t ilcc_get_theta_t(ilcc_handle* h, const float* yz, const uint8_t* label, uint32_t m, int32_t topleft_white,
                          int32_t use_oob, double theta_t[3], double* cost, int32_t* iterations) {
-  if (!theta_t) return ILCC_BAD_ARGUMENT;
-  int32_t st = stage_labelled(h, yz, label, m);
+  if (!h || !theta_t) return ILCC_BAD_ARGUMENT;
+  const hipStream_t s = h->stream[take_stream(h)];
+  int32_t st = stage_labelled(h, s, yz, label, m);
   if (st != ILCC_OK) return st;
   Slot& sl = h->slots[0];
-  hipStream_t s = sl.stream;
   HIP_TRY(h, hipMemcpyAsync(h->d_solve, theta_t, sizeof(double) * 3, hipMemcpyHostToDevice, s));
   const Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
   launch_local_solve(c, s, topleft_white, use_oob, h->d_solve, h->d_solve + 3);
   HIP_TRY(h, hipGetLastError());
   double back[5];
   HIP_TRY(h, hipMemcpyAsync(back, h->d_solve, sizeof(back), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
+  {
+    const int32_t sst = sync_own(h, s);
+    if (sst != ILCC_OK) return sst;
+  }
   theta_t[0] = back[0];
   theta_t[1] = back[1];
   theta_t[2] = back[2];
@@ -1668,10 +1735,10 @@ int32_t ilcc_pattern_refine(ilcc_handle* h, const float* yz, const uint8_t* labe
     h->err = "ilcc_pattern_refine: theta lattice coordinate outside [th_min - refine_th_margin, th_max + refine_th_margin] steps";
     return ILCC_BAD_ARGUMENT;
   }
-  int32_t st = stage_labelled(h, yz, label, m);
+  const hipStream_t s = h->stream[take_stream(h)];
+  int32_t st = stage_labelled(h, s, yz, label, m);
   if (st != ILCC_OK) return st;
   Slot& sl = h->slots[0];
-  hipStream_t s = sl.stream;
   RefineOut io{};
   io.lat[0] = lat[0];
   io.lat[1] = lat[1];
@@ -1682,7 +1749,10 @@ int32_t ilcc_pattern_refine(ilcc_handle* h, const float* yz, const uint8_t* labe
   launch_pattern_refine_test(c, s, h->d_refine_io);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(&io, h->d_refine_io, sizeof(io), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
+  {
+    const int32_t sst = sync_own(h, s);
+    if (sst != ILCC_OK) return sst;
+  }
   lat[0] = io.lat[0];
   lat[1] = io.lat[1];
   lat[2] = io.lat[2];
@@ -1701,7 +1771,7 @@ int32_t ilcc_debug_timeline_enable(ilcc_handle* h, int32_t on) {
   h->tl_on = on != 0;
   if (h->tl_on) {
     if (!h->tl_ref) HIP_TRY(h, hipEventCreate(&h->tl_ref));
-    HIP_TRY(h, hipEventRecord(h->tl_ref, h->slots[0].stream));
+    HIP_TRY(h, hipEventRecord(h->tl_ref, h->stream[0]));
     HIP_TRY(h, hipEventSynchronize(h->tl_ref));
   }
   return ILCC_OK;
