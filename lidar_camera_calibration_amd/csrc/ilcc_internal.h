@@ -70,10 +70,6 @@ constexpr float kTieEps = 2e-5f;       // relative cost window of a near-tie (fp
 constexpr int kCoverageCellsMax = 1024;   // K7b: board squares tracked by the coverage mask (board_w x board_h)
 constexpr int kIterSlots = 64;         // K6 executed-iteration counters (spread to avoid one hot atomic); [0,64): all points, [64,128): interior-class points, [128,192): (point, tile) evaluations of the box pre-pass
 constexpr int kBatchWords = 3 * kIterSlots + 2;   // Ctx::grid_iters: the K6 counters, then K2's: [192] most occupied cells a frame's LDS cell grid needed ([193] spare)
-#ifndef ILCC_K2_ALLPAIRS_MAX
-#define ILCC_K2_ALLPAIRS_MAX 256
-#endif
-constexpr int kClusterAllPairsMax = ILCC_K2_ALLPAIRS_MAX;   // K2: above this many points the spatial hash finds neighbours
 constexpr int kClusterHashSize = 1 << 17;    // K2: hash buckets per frame (global memory)
 constexpr int kClusterLdsPointsMax = 4096;   // K2: largest LDS capacity for the cell-sorted points (ROI points per frame); larger frames keep them in HBM/L2
 constexpr int kClusterLdsPointsMin = 1024;   // K2: smallest (the handle grows it in steps of 512 with the ROI sizes it sees)

@@ -21,20 +21,17 @@
 //
 //   Frames the LDS grid cannot hold (bounding grid above kFineBits cells: the un-cropped clouds of the online caller
 //   get_chessboard_by_point, LidarCornersEst.cpp:72-115; or more occupied cells than the handle's capacity) run the same
-//   cell-level algorithm with the cells in a hash table in global memory (hashed_cluster_frame, round 5); only frames beyond
-//   THAT path's limits (> 65 536 ROI points) take the point-level spatial hash of rounds 1-3, one workgroup.
+//   cell-level algorithm with the cells in a hash table in global memory, in the phases hash_setup ... hash_tail: one workgroup
+//   per frame (hashed_cluster_frame, round 5), or the k2h_* chain of kernels over the whole chip for the online caller's second
+//   tier.  Only frames beyond THAT path's limits (> 65 536 ROI points) take the point-level spatial hash of rounds 1-3, one
+//   workgroup (point_level_cluster_frame).
 // Cluster choice follows the reference: components with
 // cluster_min <= size <= cluster_max, sorted by size (largest = index 0); the one containing
-// the exact 1-NN of the click wins, otherwise index 0.  Members are emitted in index order.
+// the exact 1-NN of the click wins, otherwise index 0.  Members are emitted in index order.  Every path ends in the same
+// choice and compaction (choose_cluster, compact_cluster).
 #include "ilcc_internal.h"
 
 namespace ilcc {
-
-#ifdef ILCC_K2_TIMING
-#define K2_MARK(k) do { __syncthreads(); if (f == 0 && threadIdx.x == 0) tmark[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define K2_MARK(k) do {} while (0)
-#endif
 
 // find with path halving.  Parents only ever point to smaller indices (the larger root is hooked
 // under the smaller), so replacing parent[x] by its grandparent keeps it an ancestor: safe against
@@ -67,18 +64,6 @@ __device__ __forceinline__ void uf_unite(P* parent, uint32_t a, uint32_t b) {
   }
 }
 
-// unite, then point both endpoints straight at the common root (only non-roots are rewritten: a root's parent
-// word belongs to the hooks).  Makes the cheap "parents equal?" test of the batched search effective.
-template <typename P>
-__device__ __forceinline__ void uf_unite_compress(P* parent, uint32_t a, uint32_t b) {
-  uf_unite(parent, a, b);
-  const uint32_t r = uf_find(parent, a);
-  if (__hip_atomic_load(&parent[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a)
-    __hip_atomic_store(&parent[a], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (__hip_atomic_load(&parent[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != b)
-    __hip_atomic_store(&parent[b], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // bucket of an integer cell; different cells may share a bucket (a far cell's points then simply
 // fail the distance test)
 __device__ __forceinline__ uint32_t cell_hash(int cx, int cy, int cz) {
@@ -94,58 +79,56 @@ __device__ __forceinline__ bool nn_less(const NnKey& x, const NnKey& y) {
   return x.d2 < y.d2 || (x.d2 == y.d2 && x.idx < y.idx);
 }
 
-// Labels, component sizes, exact 1-NN of the click, the reference's choice rule, compaction: shared by the LDS path
-// (parent = the workgroup's LDS parents) and the multi-workgroup path (parent = the frame's global parents).
-template <bool LDS_PARENT>
-__device__ void cluster_finish(const Ctx& c, uint32_t f, uint32_t* parent, uint32_t* sc) {
-  ilcc_result* r = &c.res[f];
-  const uint32_t M = (uint32_t)r->n_roi;
-  const uint64_t beg = c.off[f];
-  const float4* __restrict__ P = c.roi + beg;
-  uint32_t* gparent = c.uf_parent + beg;
-  uint32_t* count = c.uf_count + beg;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t kT = blockDim.x;   // 256 or 1024 threads
-#ifdef ILCC_K2_TIMING
-  __shared__ unsigned long long tmark[12];
-#endif
-  // ---- flatten: label = root (smallest member index)
-  for (uint32_t base = 0; base < M; base += kT) {
-    const uint32_t i = base + tid;
-    uint32_t root = 0;
-    if (i < M) root = uf_find(parent, i);
-    __syncthreads();
-    if (i < M) {
-      parent[i] = root;
-      if (LDS_PARENT) gparent[i] = root;   // labels kept in global for the fetch/debug path
-    }
-    __syncthreads();
+// ------------------------------------------------------------------ shared by every path
+// bounding box of P[0, M) over the workgroup, returned to every thread.  scratch: 112 floats (reusable on return)
+__device__ __forceinline__ void block_bbox(const float4* __restrict__ P, uint32_t M, float* scf, float3& lo, float3& hi) {
+  const uint32_t tid = threadIdx.x, kT = blockDim.x;
+  lo = make_float3(3.0e38f, 3.0e38f, 3.0e38f);
+  hi = make_float3(-3.0e38f, -3.0e38f, -3.0e38f);
+  for (uint32_t i = tid; i < M; i += kT) {
+    const float4 q = P[i];
+    lo.x = fminf(lo.x, q.x); lo.y = fminf(lo.y, q.y); lo.z = fminf(lo.z, q.z);
+    hi.x = fmaxf(hi.x, q.x); hi.y = fmaxf(hi.y, q.y); hi.z = fmaxf(hi.z, q.z);
   }
-
-  K2_MARK(3);
-  // ---- component sizes (wave-aggregated atomics on the root's counter)
-  for (uint32_t base = 0; base < M; base += kT) {
-    const uint32_t i = base + tid;
-    const bool v = i < M;
-    const uint32_t lab = v ? parent[i] : 0xFFFFFFFFu;
-    unsigned long long todo = __ballot(v);
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const uint32_t ll = __shfl(lab, leader, ILCC_WAVE);
-      const unsigned long long same = __ballot(v && lab == ll);
-      if (lane_id() == leader) atomicAdd(&count[ll], (uint32_t)__popcll(same));
-      todo &= ~same;
-    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo.x = fminf(lo.x, __shfl_xor(lo.x, o, ILCC_WAVE)); lo.y = fminf(lo.y, __shfl_xor(lo.y, o, ILCC_WAVE));
+    lo.z = fminf(lo.z, __shfl_xor(lo.z, o, ILCC_WAVE));
+    hi.x = fmaxf(hi.x, __shfl_xor(hi.x, o, ILCC_WAVE)); hi.y = fmaxf(hi.y, __shfl_xor(hi.y, o, ILCC_WAVE));
+    hi.z = fmaxf(hi.z, __shfl_xor(hi.z, o, ILCC_WAVE));
   }
   __syncthreads();
+  if (lane_id() == 0) {
+    scf[wave_id()] = lo.x; scf[16 + wave_id()] = lo.y; scf[32 + wave_id()] = lo.z;
+    scf[64 + wave_id()] = hi.x; scf[80 + wave_id()] = hi.y; scf[96 + wave_id()] = hi.z;
+  }
+  __syncthreads();
+  for (int w = 0; w < (int)(kT / ILCC_WAVE); ++w) {
+    lo.x = fminf(lo.x, scf[w]); lo.y = fminf(lo.y, scf[16 + w]); lo.z = fminf(lo.z, scf[32 + w]);
+    hi.x = fmaxf(hi.x, scf[64 + w]); hi.y = fmaxf(hi.y, scf[80 + w]); hi.z = fmaxf(hi.z, scf[96 + w]);
+  }
+  __syncthreads();
+}
 
-  K2_MARK(4);
-  // ---- exact 1-NN of the click (float squared distance, ties -> lowest index)
-  const float cx = c.clicks[3 * f], cy = c.clicks[3 * f + 1], cz = c.clicks[3 * f + 2];
+// The tail of every path, on the components k < n_comp of a frame's points P[0, M): comp(k, size, min_index) is true when k is
+// a component (a root) and then gives its size and smallest member index; label(i, q) is the component of point i (q = P[i]).
+// choose_cluster: the exact 1-NN of the click (float squared distance, ties -> lowest index); the largest admissible component
+// (ties -> smallest member index), i.e. sorted index 0; the one holding the 1-NN wins when it is admissible.  Writes
+// found_board.  Scratch: sc[0, 80) and sc[120, 124).
+struct ClusterChoice {
+  uint32_t chosen;   // the component to emit
+  bool any;          // some component is admissible (else the frame has no cluster)
+  bool found;        // the click's 1-NN lies in an admissible component
+  float nn_d2;       // squared distance from the click to its 1-NN
+};
+template <typename Comp, typename Label>
+__device__ __forceinline__ ClusterChoice choose_cluster(const Ctx& c, uint32_t f, float3 click, const float4* __restrict__ P,
+                                                        uint32_t M, uint32_t n_comp, Comp comp, Label label, uint32_t* sc) {
+  const uint32_t tid = threadIdx.x, kT = blockDim.x;
   NnKey best{3.402823466e38f, 0xFFFFFFFFu};
   for (uint32_t i = tid; i < M; i += kT) {
     const float4 q = P[i];
-    const float dx = q.x - cx, dy = q.y - cy, dz = q.z - cz;
+    const float dx = q.x - click.x, dy = q.y - click.y, dz = q.z - click.z;
     float d2 = dx * dx;
     d2 = d2 + dy * dy;
     d2 = d2 + dz * dz;
@@ -159,96 +142,99 @@ __device__ void cluster_finish(const Ctx& c, uint32_t f, uint32_t* parent, uint3
     t.idx = __shfl_down(best.idx, o, ILCC_WAVE);
     if (nn_less(t, best)) best = t;
   }
-  float* scf = reinterpret_cast<float*>(sc);
-  if (lane_id() == 0) {
-    scf[wave_id()] = best.d2;
-    sc[16 + wave_id()] = best.idx;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    NnKey b{scf[0], sc[16]};
-    for (int w = 1; w < (int)(kT / ILCC_WAVE); ++w) {
-      const NnKey k{scf[w], sc[16 + w]};
-      if (nn_less(k, b)) b = k;
-    }
-    sc[32] = b.idx;
-  }
-  __syncthreads();
-  const uint32_t nn = sc[32];
-  const uint32_t nn_label = parent[nn];
-
-  K2_MARK(5);
-  // ---- largest valid component (ties -> smallest root), i.e. sorted index 0
-  const uint32_t cmin = (uint32_t)c.p.cluster_min, cmax = (uint32_t)c.p.cluster_max;
-  uint32_t bsz = 0, broot = 0xFFFFFFFFu;
-  for (uint32_t i = tid; i < M; i += kT) {
-    if (parent[i] != i) continue;
-    const uint32_t sz = __hip_atomic_load(&count[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (sz < cmin || sz > cmax) continue;
-    if (sz > bsz || (sz == bsz && i < broot)) {
+  const uint32_t cmin_sz = (uint32_t)c.p.cluster_min, cmax_sz = (uint32_t)c.p.cluster_max;
+  uint32_t bsz = 0, bidx = 0xFFFFFFFFu, broot = 0xFFFFFFFFu;
+  for (uint32_t k = tid; k < n_comp; k += kT) {
+    uint32_t sz, mi;
+    if (!comp(k, sz, mi)) continue;
+    if (sz < cmin_sz || sz > cmax_sz) continue;
+    if (sz > bsz || (sz == bsz && mi < bidx)) {
       bsz = sz;
-      broot = i;
+      bidx = mi;
+      broot = k;
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t s2 = __shfl_down(bsz, o, ILCC_WAVE);
-    const uint32_t r2 = __shfl_down(broot, o, ILCC_WAVE);
-    if (s2 > bsz || (s2 == bsz && r2 < broot)) {
+    const uint32_t s2 = __shfl_down(bsz, o, ILCC_WAVE), i2 = __shfl_down(bidx, o, ILCC_WAVE), r2 = __shfl_down(broot, o, ILCC_WAVE);
+    if (s2 > bsz || (s2 == bsz && i2 < bidx)) {
       bsz = s2;
+      bidx = i2;
       broot = r2;
     }
   }
+  float* scf = reinterpret_cast<float*>(sc);
   __syncthreads();
   if (lane_id() == 0) {
-    sc[wave_id()] = bsz;
-    sc[16 + wave_id()] = broot;
+    scf[wave_id()] = best.d2;
+    sc[16 + wave_id()] = best.idx;
+    sc[32 + wave_id()] = bsz;
+    sc[48 + wave_id()] = bidx;
+    sc[64 + wave_id()] = broot;
   }
   __syncthreads();
   if (tid == 0) {
-    uint32_t s0 = sc[0], r0 = sc[16];
+    NnKey nb{scf[0], sc[16]};
+    uint32_t s0 = sc[32], i0 = sc[48], r0 = sc[64];
     for (int w = 1; w < (int)(kT / ILCC_WAVE); ++w) {
-      const uint32_t s2 = sc[w], r2 = sc[16 + w];
-      if (s2 > s0 || (s2 == s0 && r2 < r0)) {
+      const NnKey k{scf[w], sc[16 + w]};
+      if (nn_less(k, nb)) nb = k;
+      const uint32_t s2 = sc[32 + w], i2 = sc[48 + w], r2 = sc[64 + w];
+      if (s2 > s0 || (s2 == s0 && i2 < i0)) {
         s0 = s2;
+        i0 = i2;
         r0 = r2;
       }
     }
-    const uint32_t nsz = __hip_atomic_load(&count[nn_label], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t chosen = r0;                                   // plane_index = 0
-    const bool found = nsz >= cmin && nsz <= cmax;          // find_board of get_chessboard_by_point (:91-102)
-    if (found) chosen = nn_label;                           // cluster containing the click's NN
-    r->found_board = found ? 1 : 0;
-    sc[33] = chosen;
-    sc[34] = (s0 == 0) ? 0u : 1u;
+    const uint32_t nn_root = label(nb.idx, P[nb.idx]);
+    uint32_t nsz = 0, nmi;
+    comp(nn_root, nsz, nmi);
+    const bool found = nsz >= cmin_sz && nsz <= cmax_sz;   // find_board of get_chessboard_by_point (:91-102)
+    c.res[f].found_board = found ? 1 : 0;
+    sc[120] = found ? nn_root : r0;                         // cluster containing the click's NN, else plane_index = 0
+    sc[121] = (s0 == 0) ? 0u : 1u;
+    sc[122] = found ? 1u : 0u;
+    scf[123] = nb.d2;
   }
   __syncthreads();
-  const uint32_t chosen = sc[33];
-  const bool any = sc[34] != 0;
-  if (!any) {
-    if (tid == 0) r->status = ILCC_NO_CLUSTER;
-    return;
-  }
+  return ClusterChoice{sc[120], sc[121] != 0u, sc[122] != 0u, scf[123]};
+}
 
-  K2_MARK(6);
-  // ---- stable compaction of the chosen component
-  float4* __restrict__ dst = c.cluster + beg;
+// stable compaction of the chosen component (index order) into dst; kept(q) sees every point emitted.  Returns their number.
+// Scratch: sc[128, 144).
+template <typename Label, typename Kept>
+__device__ __forceinline__ uint32_t compact_cluster(const float4* __restrict__ P, uint32_t M, uint32_t chosen, Label label,
+                                                    float4* __restrict__ dst, uint32_t* sc, Kept kept) {
   uint32_t running = 0;
-  for (uint32_t base = 0; base < M; base += kT) {
-    const uint32_t i = base + tid;
-    const bool keep = (i < M) && parent[i] == chosen;
+  for (uint32_t base = 0; base < M; base += blockDim.x) {
+    const uint32_t i = base + threadIdx.x;
+    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool keep = false;
+    if (i < M) {
+      q = P[i];
+      keep = label(i, q) == chosen;
+    }
+    if (keep) kept(q);
     uint32_t tot;
-    const uint32_t rank = block_rank(keep, sc + 40, tot);
-    if (keep) dst[running + rank] = P[i];
+    const uint32_t rank = block_rank(keep, sc + 128, tot);
+    if (keep) dst[running + rank] = q;
     running += tot;
   }
-  if (tid == 0) r->n_cluster = (int32_t)running;
-  K2_MARK(7);
-#ifdef ILCC_K2_TIMING
-  if (f == 0 && tid == 0)
-    printf("K2 f0 M=%u cycles: flatten %llu count %llu nn %llu largest %llu compact %llu\n", M, tmark[3] - tmark[2],
-           tmark[4] - tmark[3], tmark[5] - tmark[4], tmark[6] - tmark[5], tmark[7] - tmark[6]);
-#endif
+  return running;
+}
+
+// choice and compaction for the paths without a caller-specific check: the frame's result (status or n_cluster)
+template <typename Comp, typename Label>
+__device__ __forceinline__ void cluster_tail(const Ctx& c, uint32_t f, const float4* __restrict__ P, uint32_t M, uint32_t n_comp,
+                                             Comp comp, Label label, uint32_t* sc) {
+  const float3 click = make_float3(c.clicks[3 * f], c.clicks[3 * f + 1], c.clicks[3 * f + 2]);
+  const ClusterChoice ch = choose_cluster(c, f, click, P, M, n_comp, comp, label, sc);
+  if (!ch.any) {
+    if (threadIdx.x == 0) c.res[f].status = ILCC_NO_CLUSTER;
+    return;
+  }
+  const uint32_t n = compact_cluster(P, M, ch.chosen, label, c.cluster + c.off[f], sc, [](const float4&) {});
+  if (threadIdx.x == 0) c.res[f].n_cluster = (int32_t)n;
 }
 
 // ------------------------------------------------------------------ point-level spatial hash (frames beyond the limits of the cell paths)
@@ -302,6 +288,62 @@ __device__ __forceinline__ void big_search_point(const Ctx& c, uint32_t f, uint3
         }
       }
   }
+}
+
+// the point-level spatial hash of rounds 1-3 by ONE workgroup: the last resort for frames beyond the limits of the cell paths.
+// Components are the points that are roots (the smallest member index), their sizes counted on the root.
+__device__ void point_level_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc) {
+  const uint64_t beg = c.off[f];
+  const uint32_t M = (uint32_t)c.res[f].n_roi, tid = threadIdx.x, kT = blockDim.x;
+  uint32_t* parent = c.uf_parent + beg;
+  uint32_t* count = c.uf_count + beg;
+  uint32_t* head = c.uf_hash_head + (uint64_t)f * kClusterHashSize;
+  for (uint32_t i = tid; i < M; i += kT) {
+    parent[i] = i;
+    count[i] = 0u;
+  }
+  for (uint32_t k = tid; k < (uint32_t)kClusterHashSize; k += kT) head[k] = 0xFFFFFFFFu;
+  __threadfence_block();
+  __syncthreads();
+  for (uint32_t i = tid; i < M; i += kT) big_insert_point(c, f, i);
+  __threadfence_block();
+  __syncthreads();
+  const float tol2 = (float)(c.p.cluster_tol * c.p.cluster_tol);
+  for (uint32_t i = tid; i < M; i += kT) big_search_point(c, f, i, tol2);
+  __threadfence_block();
+  __syncthreads();
+  // ---- flatten: label = root (smallest member index)
+  for (uint32_t base = 0; base < M; base += kT) {
+    const uint32_t i = base + tid;
+    uint32_t root = 0;
+    if (i < M) root = uf_find(parent, i);
+    __syncthreads();
+    if (i < M) parent[i] = root;
+    __syncthreads();
+  }
+  // ---- component sizes (wave-aggregated atomics on the root's counter)
+  for (uint32_t base = 0; base < M; base += kT) {
+    const uint32_t i = base + tid;
+    const bool v = i < M;
+    const uint32_t lab = v ? parent[i] : 0xFFFFFFFFu;
+    unsigned long long todo = __ballot(v);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const uint32_t ll = __shfl(lab, leader, ILCC_WAVE);
+      const unsigned long long same = __ballot(v && lab == ll);
+      if (lane_id() == leader) atomicAdd(&count[ll], (uint32_t)__popcll(same));
+      todo &= ~same;
+    }
+  }
+  __syncthreads();
+  cluster_tail(c, f, c.roi + beg, M, M,
+               [&](uint32_t k, uint32_t& sz, uint32_t& mi) {
+                 if (parent[k] != k) return false;
+                 sz = __hip_atomic_load(&count[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                 mi = k;
+                 return true;
+               },
+               [&](uint32_t i, const float4&) { return parent[i]; }, sc);
 }
 
 // ------------------------------------------------------------------ components on cells (the ROI case)
@@ -371,37 +413,13 @@ __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
   const float4* __restrict__ P = c.roi + beg;
   float4* gpts = c.cluster + beg;   // PTS_LDS = false: the sorted points live here until the compaction overwrites it
   const uint32_t tid = threadIdx.x, kT = blockDim.x;
-  const int nwv = (int)(kT / ILCC_WAVE);
   const float tol2 = (float)(c.p.cluster_tol * c.p.cluster_tol);
   uint32_t* sc = L.sc;
-  float* scf = reinterpret_cast<float*>(sc);
   unsigned long long* stats = c.grid_iters + 3 * kIterSlots;   // [0] most occupied cells a frame needed
 
   // ---- bounding box
-  float3 lo = make_float3(3.0e38f, 3.0e38f, 3.0e38f), hi = make_float3(-3.0e38f, -3.0e38f, -3.0e38f);
-  for (uint32_t i = tid; i < M; i += kT) {
-    const float4 q = P[i];
-    lo.x = fminf(lo.x, q.x); lo.y = fminf(lo.y, q.y); lo.z = fminf(lo.z, q.z);
-    hi.x = fmaxf(hi.x, q.x); hi.y = fmaxf(hi.y, q.y); hi.z = fmaxf(hi.z, q.z);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo.x = fminf(lo.x, __shfl_xor(lo.x, o, ILCC_WAVE)); lo.y = fminf(lo.y, __shfl_xor(lo.y, o, ILCC_WAVE));
-    lo.z = fminf(lo.z, __shfl_xor(lo.z, o, ILCC_WAVE));
-    hi.x = fmaxf(hi.x, __shfl_xor(hi.x, o, ILCC_WAVE)); hi.y = fmaxf(hi.y, __shfl_xor(hi.y, o, ILCC_WAVE));
-    hi.z = fmaxf(hi.z, __shfl_xor(hi.z, o, ILCC_WAVE));
-  }
-  __syncthreads();
-  if (lane_id() == 0) {
-    scf[wave_id()] = lo.x; scf[16 + wave_id()] = lo.y; scf[32 + wave_id()] = lo.z;
-    scf[64 + wave_id()] = hi.x; scf[80 + wave_id()] = hi.y; scf[96 + wave_id()] = hi.z;
-  }
-  __syncthreads();
-  for (int w = 0; w < nwv; ++w) {
-    lo.x = fminf(lo.x, scf[w]); lo.y = fminf(lo.y, scf[16 + w]); lo.z = fminf(lo.z, scf[32 + w]);
-    hi.x = fmaxf(hi.x, scf[64 + w]); hi.y = fmaxf(hi.y, scf[80 + w]); hi.z = fmaxf(hi.z, scf[96 + w]);
-  }
-  __syncthreads();
+  float3 lo, hi;
+  block_bbox(P, M, reinterpret_cast<float*>(sc), lo, hi);
   FineGrid g;
   g.lo = lo;
   g.inv = 1.0f / ((float)c.p.cluster_tol * kFineCellOverTol);
@@ -545,115 +563,39 @@ __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
   }
   __syncthreads();
 
-  // ---- exact 1-NN of the click (float squared distance, ties -> lowest index)
-  const float kx = c.clicks[3 * f], ky = c.clicks[3 * f + 1], kz = c.clicks[3 * f + 2];
-  NnKey best{3.402823466e38f, 0xFFFFFFFFu};
-  for (uint32_t i = tid; i < M; i += kT) {
-    const float4 q = P[i];
-    const float dx = q.x - kx, dy = q.y - ky, dz = q.z - kz;
-    float d2 = dx * dx;
-    d2 = d2 + dy * dy;
-    d2 = d2 + dz * dz;
-    const NnKey k{d2, i};
-    if (nn_less(k, best)) best = k;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    NnKey t;
-    t.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-    t.idx = __shfl_down(best.idx, o, ILCC_WAVE);
-    if (nn_less(t, best)) best = t;
-  }
-  // ---- largest admissible component (ties -> smallest member index), i.e. sorted index 0
-  const uint32_t cmin_sz = (uint32_t)c.p.cluster_min, cmax_sz = (uint32_t)c.p.cluster_max;
-  uint32_t bsz = 0, bidx = 0xFFFFFFFFu, broot = 0xFFFFFFFFu;
-  for (uint32_t k = tid; k < C; k += kT) {
-    if (L.cpar[k] != k) continue;
-    const uint32_t sz = L.ccnt[k], mi = L.ckey[k];
-    if (sz < cmin_sz || sz > cmax_sz) continue;
-    if (sz > bsz || (sz == bsz && mi < bidx)) {
-      bsz = sz;
-      bidx = mi;
-      broot = k;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t s2 = __shfl_down(bsz, o, ILCC_WAVE), i2 = __shfl_down(bidx, o, ILCC_WAVE), r2 = __shfl_down(broot, o, ILCC_WAVE);
-    if (s2 > bsz || (s2 == bsz && i2 < bidx)) {
-      bsz = s2;
-      bidx = i2;
-      broot = r2;
-    }
-  }
-  __syncthreads();
-  if (lane_id() == 0) {
-    scf[wave_id()] = best.d2;
-    sc[16 + wave_id()] = best.idx;
-    sc[32 + wave_id()] = bsz;
-    sc[48 + wave_id()] = bidx;
-    sc[64 + wave_id()] = broot;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    NnKey nb{scf[0], sc[16]};
-    uint32_t s0 = sc[32], i0 = sc[48], r0 = sc[64];
-    for (int w = 1; w < nwv; ++w) {
-      const NnKey k{scf[w], sc[16 + w]};
-      if (nn_less(k, nb)) nb = k;
-      const uint32_t s2 = sc[32 + w], i2 = sc[48 + w], r2 = sc[64 + w];
-      if (s2 > s0 || (s2 == s0 && i2 < i0)) {
-        s0 = s2;
-        i0 = i2;
-        r0 = r2;
-      }
-    }
-    const uint32_t nn_root = L.cpar[fine_rank(L.bm, L.pre, fine_key(g, P[nb.idx]))];
-    const uint32_t nsz = L.ccnt[nn_root];
-    const bool found = nsz >= cmin_sz && nsz <= cmax_sz;   // find_board of get_chessboard_by_point (:91-102)
-    r->found_board = found ? 1 : 0;
-    sc[120] = found ? nn_root : r0;                         // cluster containing the click's NN, else plane_index = 0
-    sc[121] = (s0 == 0) ? 0u : 1u;
-    // First tier of the online caller: the points are a WINDOW of +-w around the click, the answer must be the whole cloud's.
-    // It is, when (1) the window's nearest point is the cloud's -- nothing outside the window is nearer than w; (2) that point's
-    // component is admissible -- otherwise the reference falls back to the LARGEST component of the cloud, which a window cannot
-    // know; (3) the component is complete -- checked below: no member within tol (+ 1 mm) of the window's faces, so no point
-    // outside the window is within tol of it.  Anything else: the second tier clusters the whole cloud.
-    if (c.online_tier == 1u) {
-      const float w = c.online_window - 1e-3f;   // (the window's faces are float-rounded: a point outside is farther than this)
-      sc[122] = (found && nb.d2 <= w * w) ? 1u : 0u;
-    }
-  }
-  __syncthreads();
-  const uint32_t chosen = sc[120];
-  if (c.online_tier == 1u && sc[122] == 0u) {
-    if (tid == 0) c.frame_flags[f] = 1u;
+  // ---- exact 1-NN of the click, the choice (components: root cells; a point's: its cell's root)
+  const auto comp = [&](uint32_t k, uint32_t& sz, uint32_t& mi) {
+    if (L.cpar[k] != k) return false;
+    sz = L.ccnt[k];
+    mi = L.ckey[k];
     return true;
+  };
+  const auto label = [&](uint32_t, const float4& q) { return L.cpar[fine_rank(L.bm, L.pre, fine_key(g, q))]; };
+  const float kx = c.clicks[3 * f], ky = c.clicks[3 * f + 1], kz = c.clicks[3 * f + 2];
+  const ClusterChoice ch = choose_cluster(c, f, make_float3(kx, ky, kz), P, M, C, comp, label, sc);
+  // First tier of the online caller: the points are a WINDOW of +-w around the click, the answer must be the whole cloud's.
+  // It is, when (1) the window's nearest point is the cloud's -- nothing outside the window is nearer than w; (2) that point's
+  // component is admissible -- otherwise the reference falls back to the LARGEST component of the cloud, which a window cannot
+  // know; (3) the component is complete -- checked below: no member within tol (+ 1 mm) of the window's faces, so no point
+  // outside the window is within tol of it.  Anything else: the second tier clusters the whole cloud.
+  if (c.online_tier == 1u) {
+    const float w = c.online_window - 1e-3f;   // (the window's faces are float-rounded: a point outside is farther than this)
+    if (!(ch.found && ch.nn_d2 <= w * w)) {
+      if (tid == 0) c.frame_flags[f] = 1u;
+      return true;
+    }
   }
-  if (sc[121] == 0u) {
+  if (!ch.any) {
     if (tid == 0) r->status = ILCC_NO_CLUSTER;
     return true;
   }
 
   // ---- stable compaction of the chosen component (index order)
-  float4* __restrict__ dst = c.cluster + beg;
-  uint32_t running = 0;
   const float safe = c.online_window - ((float)c.p.cluster_tol + 1e-3f);   // (first tier of the online caller: completeness)
   bool near_face = false;
-  for (uint32_t base = 0; base < M; base += kT) {
-    const uint32_t i = base + tid;
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool keep = false;
-    if (i < M) {
-      q = P[i];
-      keep = L.cpar[fine_rank(L.bm, L.pre, fine_key(g, q))] == chosen;
-    }
-    if (keep) near_face |= !(fabsf(q.x - kx) <= safe && fabsf(q.y - ky) <= safe && fabsf(q.z - kz) <= safe);
-    uint32_t tot;
-    const uint32_t rank = block_rank(keep, sc + 128, tot);
-    if (keep) dst[running + rank] = q;
-    running += tot;
-  }
+  const uint32_t n = compact_cluster(P, M, ch.chosen, label, c.cluster + beg, sc, [&](const float4& q) {
+    near_face |= !(fabsf(q.x - kx) <= safe && fabsf(q.y - ky) <= safe && fabsf(q.z - kz) <= safe);
+  });
   if (c.online_tier == 1u) {
     uint32_t tot;
     (void)block_rank(near_face, sc + 128, tot);
@@ -662,7 +604,7 @@ __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
       return true;
     }
   }
-  if (tid == 0) r->n_cluster = (int32_t)running;
+  if (tid == 0) r->n_cluster = (int32_t)n;
   return true;
 }
 
@@ -675,14 +617,18 @@ __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
 // pair of points within tol -- with the dense bitmap replaced by an open-addressing hash table in global memory keyed by BLOCKS
 // of 4 x 4 x 4 cells: an entry holds the block's 64-bit occupancy mask and the dense id of its first cell, so the 124-cell
 // neighbourhood of a cell is read with at most 7 table lookups (the 2 x 2 x 2 blocks its 5-cell windows overlap, minus its own).
-// ONE workgroup per frame, and every atomic at WORKGROUP scope: on this part a device-scope atomic or load is executed beyond
-// the XCD's L2 (the L2s of the eight XCDs are not coherent with each other inside a kernel) at several microseconds a piece --
-// measured here: 8 400 cycles per table lookup with device-scope loads, and a chain of kernels over (frame, chunk) items with
-// device-scope atomics took 2.7 ms for the same 128 clouds.  A frame's data is touched by its own workgroup only, whose
-// read-modify-writes then execute in the L2 of its XCD.  Plain loads may hit stale lines of the CU's L1: every phase boundary
-// invalidates it (acquire fence), and inside a phase staleness is benign by construction -- a table word goes from empty to a key
-// once (a stale "empty" only costs a compare-and-swap that returns the key), union-find parents only ever move to smaller
-// indices (a stale parent is still an ancestor) and a failed hook continues from the value the compare-and-swap returned.
+// The phases (hash_setup ... hash_tail) are written once and run by two callers, which differ in how they spread the work, what
+// separates the phases, and the memory-scope policy they instantiate the phases with:
+//   hashed_cluster_frame (WgScope): ONE workgroup per frame, and every atomic at WORKGROUP scope: on this part a device-scope
+//     atomic or load is executed beyond the XCD's L2 (the L2s of the eight XCDs are not coherent with each other inside a kernel)
+//     at several microseconds a piece -- measured here: 8 400 cycles per table lookup with device-scope loads, and a chain of
+//     kernels over (frame, chunk) items with device-scope atomics took 2.7 ms for the same 128 clouds.  A frame's data is touched
+//     by its own workgroup only, whose read-modify-writes then execute in the L2 of its XCD.  Plain loads may hit stale lines of
+//     the CU's L1: every phase boundary (wg_phase) invalidates it (acquire fence), and inside a phase staleness is benign by
+//     construction -- a table word goes from empty to a key once (a stale "empty" only costs a compare-and-swap that returns the
+//     key), union-find parents only ever move to smaller indices (a stale parent is still an ancestor) and a failed hook
+//     continues from the value the compare-and-swap returned.
+//   the k2h_* chain (AgentScope, below): several workgroups share a frame, so atomics and the loads that race them are agent-scope.
 // Scratch per frame (all dead at K2 time, rewritten by K3 / K4 / K5 / K5w / K7b afterwards): table keys = the frame's slice of
 // uf_hash_head; base ids = board; masks = pca (low words) + optim (high words); per point / per cell words = uf_hash_next
 // (cell of a point), uf_count (count, later component size), uf_parent (cell union-find), yz (smallest index | block-and-bit,
@@ -735,8 +681,10 @@ __device__ __forceinline__ void hb_cell(const HashFrame& g, const float4& q, uin
 __device__ __forceinline__ uint32_t hb_rank(uint32_t lo, uint32_t hi, uint32_t bit) {   // set bits below `bit`
   return bit < 32u ? (uint32_t)__popc(lo & ((1u << bit) - 1u)) : (uint32_t)__popc(lo) + (uint32_t)__popc(hi & ((1u << (bit - 32u)) - 1u));
 }
-// workgroup-scope read-modify-writes on global memory: executed in the XCD's L2
-#define WG_ATOMIC(op, ptr, val) __hip_atomic_##op((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+__device__ __forceinline__ uint32_t hb_axis_mask(int a, int o) {   // cells x of block (own + o) with |x + 4 o - a| <= 2, as a 4-bit mask
+  const int l = max(a - 2 - 4 * o, 0), u = min(a + 2 - 4 * o, 3);
+  return l > u ? 0u : ((1u << (u + 1)) - 1u) & ~((1u << l) - 1u);
+}
 __device__ __forceinline__ uint32_t wg_cas(uint32_t* p, uint32_t expect, uint32_t desired) {
   __hip_atomic_compare_exchange_strong(p, &expect, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   return expect;   // the value found (== the `expect` passed in iff the exchange happened)
@@ -747,15 +695,35 @@ __device__ __forceinline__ void wg_phase() {
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (buffer_inv: invalidates the CU's L1)
 }
-// union-find on global parents owned by ONE workgroup: plain loads (a stale parent is still an ancestor: parents only move to
-// smaller indices), hooks by workgroup-scope compare-and-swap; a failed hook continues from the parent the CAS returned
+// -DILCC_K2_TIMING: counters of the one-workgroup path's edge search (union-find hops, cell pairs tested, thread-cycles per part)
+struct NoClock {
+  __device__ void lap(int) {}
+  __device__ void pair() {}
+  __device__ void hit() {}
+  __device__ void flush() {}
+};
 #ifdef ILCC_K2_TIMING
 __device__ unsigned long long g_k2_hops, g_k2_finds, g_k2_pairs, g_k2_hits, g_k2_t[6];
-#define K2_T(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[k] += now_ - tlast; tlast = now_; } while (0)
 #define K2_COUNT(v, n) atomicAdd(&(v), (unsigned long long)(n))
+struct EdgeClock {
+  unsigned long long t[6] = {0, 0, 0, 0, 0, 0}, last = __builtin_readcyclecounter();
+  __device__ void lap(int k) {
+    const unsigned long long now = __builtin_readcyclecounter();
+    t[k] += now - last;
+    last = now;
+  }
+  __device__ void pair() { K2_COUNT(g_k2_pairs, 1); }
+  __device__ void hit() { K2_COUNT(g_k2_hits, 1); }
+  __device__ void flush() {
+    for (int k = 0; k < 6; ++k) atomicAdd(&g_k2_t[k], t[k]);
+  }
+};
 #else
 #define K2_COUNT(v, n) do {} while (0)
+using EdgeClock = NoClock;
 #endif
+// union-find on global parents owned by ONE workgroup: plain loads (a stale parent is still an ancestor: parents only move to
+// smaller indices), hooks by workgroup-scope compare-and-swap; a failed hook continues from the parent the CAS returned
 __device__ __forceinline__ uint32_t wg_find(uint32_t* parent, uint32_t x) {
   K2_COUNT(g_k2_finds, 1);
   for (;;) {
@@ -783,19 +751,263 @@ __device__ __forceinline__ void wg_unite(uint32_t* parent, uint32_t a, uint32_t 
   }
 }
 
-// Returns false (uniformly) when the frame is outside this path's limits: the caller takes the point-level path.
-__device__ bool hashed_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc) {
-  ilcc_result* r = &c.res[f];
-  const HashViews v = hash_views(c, f);
+// The memory-scope policies the hashed phases are instantiated with: the scope of the read-modify-writes, the flavour of the
+// loads that race them, the union-find, and the edge search's timing counters.
+struct WgScope {   // hashed_cluster_frame: one workgroup owns the frame
+  static constexpr int kScope = __HIP_MEMORY_SCOPE_WORKGROUP;
+  using Clock = EdgeClock;
+  static __device__ __forceinline__ uint32_t load(const uint32_t* p) { return *p; }
+  static __device__ __forceinline__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t desired) { return wg_cas(p, expect, desired); }
+  static __device__ __forceinline__ uint32_t find(uint32_t* parent, uint32_t x) { return wg_find(parent, x); }
+  static __device__ __forceinline__ void unite(uint32_t* parent, uint32_t a, uint32_t b) { wg_unite(parent, a, b); }
+};
+struct AgentScope {   // the k2h_* chain: several workgroups share a frame
+  static constexpr int kScope = __HIP_MEMORY_SCOPE_AGENT;
+  using Clock = NoClock;
+  static __device__ __forceinline__ uint32_t load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static __device__ __forceinline__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t desired) { return atomicCAS(p, expect, desired); }
+  static __device__ __forceinline__ uint32_t find(uint32_t* parent, uint32_t x) { return uf_find(parent, x); }
+  static __device__ __forceinline__ void unite(uint32_t* parent, uint32_t a, uint32_t b) { uf_unite(parent, a, b); }
+};
+// a read-modify-write at the policy S's scope
+#define HB_ATOMIC(op, ptr, val) __hip_atomic_##op((ptr), (val), __ATOMIC_RELAXED, S::kScope)
+// ---- the phases.  Per frame: every thread of one workgroup calls them; per point / per cell: one thread per item.
+
+// setup (per frame): bounding box -> block grid -> table size.  False (uniformly) when the frame is outside the hashed path's
+// limits: its caller takes the point-level path.  scf: 112 floats.
+__device__ __forceinline__ bool hash_setup(const Ctx& c, uint32_t f, const HashViews& v, float* scf, HashFrame& g) {
   const uint32_t M = v.M;
-  if (M == 0u || M > kHashPointsMax) return false;
   // the block arrays (tbase / tlo / thi: at least 1024 words each) live in the frame's OWN slices of board / pca / optim, four
   // words per INPUT point: a frame of fewer than 256 input points cannot hold them (it wrote into its neighbour's)
-  if (c.off[f + 1] - c.off[f] < (uint64_t)kHashMinFramePoints) return false;
-  const uint32_t tid = threadIdx.x, kT = blockDim.x;
-  const int nwv = (int)(kT / ILCC_WAVE);
-  const float tol2 = (float)(c.p.cluster_tol * c.p.cluster_tol);
-  float* scf = reinterpret_cast<float*>(sc);
+  if (M == 0u || M > kHashPointsMax || c.off[f + 1] - c.off[f] < (uint64_t)kHashMinFramePoints) return false;
+  float3 lo, hi;
+  block_bbox(v.P, M, scf, lo, hi);
+  g.lox = lo.x; g.loy = lo.y; g.loz = lo.z;
+  g.inv = 1.0f / ((float)c.p.cluster_tol * kFineCellOverTol);
+  const float ex = (hi.x - lo.x) * g.inv, ey = (hi.y - lo.y) * g.inv, ez = (hi.z - lo.z) * g.inv;
+  if (!(ex < 8192.f && ey < 8192.f && ez < 8192.f)) return false;   // (also a NaN extent)
+  const int nx = (int)floorf(ex) + 5, ny = (int)floorf(ey) + 5, nz = (int)floorf(ez) + 5;
+  g.nbx = (nx + 3) >> 2;
+  g.nby = (ny + 3) >> 2;
+  // 32-bit keys, 0xFFFFFFFF = empty
+  if ((unsigned long long)g.nbx * (unsigned long long)g.nby * (unsigned long long)((nz + 3) >> 2) >= 0xFFFFFFFFull) return false;
+  uint32_t size = 1024u;
+  while (size < 2u * M) size <<= 1;             // <= 2^17: blocks <= cells <= points, the table at most half full
+  g.mask = size - 1u;
+  g.shift = 32u - (uint32_t)__builtin_ctz(size);
+  return true;
+}
+
+// reset (per frame): empty table, no cells; every cell its own union-find root
+__device__ __forceinline__ void hash_reset(const HashViews& v, const HashFrame& g) {
+  for (uint32_t k = threadIdx.x; k <= g.mask; k += blockDim.x) {
+    v.tkey[k] = kHashEmpty;
+    v.tlo[k] = 0u;
+    v.thi[k] = 0u;
+  }
+  for (uint32_t i = threadIdx.x; i < v.M; i += blockDim.x) {
+    v.ccnt[i] = 0u;
+    v.cmin[i] = 0xFFFFFFFFu;
+    v.cpar[i] = i;
+  }
+}
+
+// insert (per point): its block's entry (claimed with a compare-and-swap on the key), its cell's bit
+template <class S>
+__device__ __forceinline__ void hash_insert(const HashViews& v, const HashFrame& g, uint32_t i) {
+  uint32_t key, bit;
+  hb_cell(g, v.P[i], key, bit);
+  uint32_t h = hb_slot(g, key);
+  for (;;) {
+    uint32_t e = S::load(&v.tkey[h]);
+    if (e == kHashEmpty) e = S::cas(&v.tkey[h], kHashEmpty, key);   // (a stale "empty" costs this CAS, which returns the key)
+    if (e == kHashEmpty || e == key) break;
+    h = (h + 1u) & g.mask;
+  }
+  HB_ATOMIC(fetch_or, bit < 32u ? &v.tlo[h] : &v.thi[h], 1u << (bit & 31u));
+  v.cell_of[i] = (h << 6) | bit;
+}
+
+// block bases (per frame): first dense cell id of every block, an exclusive scan of the masks' popcounts (whole tiles of 4 slots
+// per thread: the table size is a power of two >= 1024, 16-byte accesses).  Returns the number of cells.
+__device__ __forceinline__ uint32_t hash_blocks(const HashViews& v, const HashFrame& g, uint32_t* sc) {
+  const uint32_t size = g.mask + 1u;
+  const uint4* lo4 = reinterpret_cast<const uint4*>(v.tlo);
+  const uint4* hi4 = reinterpret_cast<const uint4*>(v.thi);
+  uint4* base4 = reinterpret_cast<uint4*>(v.tbase);
+  uint32_t C = 0;
+  for (uint32_t t0 = 0; t0 < size / 4u; t0 += blockDim.x) {
+    const uint32_t q = t0 + threadIdx.x;
+    uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+    if (q < size / 4u) {
+      const uint4 a = lo4[q], b = hi4[q];
+      n0 = (uint32_t)(__popc(a.x) + __popc(b.x));
+      n1 = (uint32_t)(__popc(a.y) + __popc(b.y));
+      n2 = (uint32_t)(__popc(a.z) + __popc(b.z));
+      n3 = (uint32_t)(__popc(a.w) + __popc(b.w));
+    }
+    uint32_t tot;
+    const uint32_t run = C + block_excl_scan(n0 + n1 + n2 + n3, sc, tot);
+    if (q < size / 4u) base4[q] = make_uint4(run, run + n0, run + n0 + n1, run + n0 + n1 + n2);
+    C += tot;
+  }
+  return C;
+}
+
+// cells (per point): dense cell id (block's base + rank of the bit), cell count, smallest member index
+template <class S>
+__device__ __forceinline__ void hash_cell(const HashViews& v, uint32_t i) {
+  const uint32_t hb = v.cell_of[i], h = hb >> 6, bit = hb & 63u;
+  const uint32_t cell = v.tbase[h] + hb_rank(v.tlo[h], v.thi[h], bit);
+  v.cell_of[i] = cell;
+  HB_ATOMIC(fetch_add, &v.ccnt[cell], 1u);
+  HB_ATOMIC(fetch_min, &v.cmin[cell], i);
+  v.ckey[cell] = hb;   // (every point of the cell writes the same word)
+}
+
+// starts (per frame): first sorted position of every cell, an exclusive scan of the counts (tiles of one cell per thread: coalesced)
+__device__ __forceinline__ void hash_starts(const HashViews& v, uint32_t C, uint32_t* sc) {
+  uint32_t run0 = 0;
+  for (uint32_t t0 = 0; t0 < C; t0 += blockDim.x) {
+    const uint32_t k = t0 + threadIdx.x;
+    const uint32_t n = k < C ? v.ccnt[k] : 0u;
+    uint32_t tot;
+    const uint32_t run = run0 + block_excl_scan(n, sc, tot);
+    if (k < C) v.cstart[k] = run;
+    run0 += tot;
+  }
+  if (threadIdx.x == 0) v.cstart[C] = v.M;
+}
+
+// place (per point): the points sorted by cell, in the frame's slice of the cluster buffer until the compaction (leaves the
+// counts all zero)
+template <class S>
+__device__ __forceinline__ void hash_place(const HashViews& v, uint32_t i) {
+  const uint32_t cell = v.cell_of[i];
+  v.sorted[v.cstart[cell] + (HB_ATOMIC(fetch_sub, &v.ccnt[cell], 1u) - 1u)] = v.P[i];
+}
+
+// edges (per cell A): the occupied neighbour cells with a larger id; same root -> nothing; else the pair's points are tested
+// until the first hit (the reference's float arithmetic) and the cells united (hooks to the smaller id)
+template <class S>
+__device__ __forceinline__ void hash_edges(const HashViews& v, const HashFrame& g, uint32_t A, float tol2, typename S::Clock& clk) {
+  clk.lap(5);
+  const uint32_t hb = v.ckey[A], hA = hb >> 6, bitA = hb & 63u;
+  const uint32_t keyA = v.tkey[hA];
+  const int ax = (int)(bitA & 3u), ay = (int)((bitA >> 2) & 3u), az = (int)(bitA >> 4);
+  const uint32_t a0 = v.cstart[A], a1 = v.cstart[A + 1];
+  // the 5-cell window of an axis overlaps the cell's own block and ONE neighbour: the lower one when the cell sits in the
+  // block's lower half, the upper one otherwise
+  const int sx = ax < 2 ? -1 : 1, sy = ay < 2 ? -1 : 1, sz = az < 2 ? -1 : 1;
+  // slots first, then ALL first probes in flight at once, then all masks: no chain of dependent loads per neighbour
+  uint32_t hs[8], want[8], got[8];
+  hs[0] = hA;
+#pragma unroll
+  for (int nb = 1; nb < 8; ++nb) {
+    const int ox = (nb & 1) ? sx : 0, oy = (nb & 2) ? sy : 0, oz = (nb & 4) ? sz : 0;
+    want[nb] = (uint32_t)((int)keyA + ox + g.nbx * (oy + g.nby * oz));
+    hs[nb] = hb_slot(g, want[nb]);
+  }
+#pragma unroll
+  for (int nb = 1; nb < 8; ++nb) got[nb] = v.tkey[hs[nb]];
+#pragma unroll
+  for (int nb = 1; nb < 8; ++nb) {
+    uint32_t h = hs[nb], e = got[nb];
+    while (e != want[nb] && e != kHashEmpty) {   // (a collision: rare at <= 50 % load)
+      h = (h + 1u) & g.mask;
+      e = v.tkey[h];
+    }
+    hs[nb] = e == kHashEmpty ? kHashEmpty : h;
+  }
+  clk.lap(0);
+  uint32_t mlo[8], mhi[8], base[8];
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) {
+    const uint32_t h = hs[nb] == kHashEmpty ? hA : hs[nb];   // (a harmless load for an absent block)
+    mlo[nb] = v.tlo[h];
+    mhi[nb] = v.thi[h];
+    base[nb] = v.tbase[h];
+  }
+  uint32_t ra = S::find(v.cpar, A);
+  clk.lap(1);
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) {
+    if (hs[nb] == kHashEmpty) continue;
+    const int ox = (nb & 1) ? sx : 0, oy = (nb & 2) ? sy : 0, oz = (nb & 4) ? sz : 0;
+    const uint32_t mx = hb_axis_mask(ax, ox), my = hb_axis_mask(ay, oy), mz = hb_axis_mask(az, oz);
+    // window = { x + 4 y + 16 z : x in mx, y in my, z in mz }: products of disjoint bit patterns
+    const uint32_t plane = mx * ((my & 1u) | ((my & 2u) << 3) | ((my & 4u) << 6) | ((my & 8u) << 9));   // 16 bits
+    const unsigned long long win = (unsigned long long)plane *
+                                   ((unsigned long long)(mz & 1u) | ((unsigned long long)(mz & 2u) << 15) | ((unsigned long long)(mz & 4u) << 30) | ((unsigned long long)(mz & 8u) << 45));
+    unsigned long long occ = (((unsigned long long)mhi[nb] << 32) | mlo[nb]) & win;
+    if (nb == 0) occ &= ~(1ull << bitA);
+    while (occ) {
+      const uint32_t b = (uint32_t)__builtin_ctzll(occ);
+      occ &= occ - 1ull;
+      const uint32_t B = base[nb] + hb_rank(mlo[nb], mhi[nb], b);
+      if (B <= A) continue;   // every pair of cells once: from the smaller id
+      clk.lap(2);
+      const uint32_t rb = S::find(v.cpar, B);
+      clk.lap(3);
+      if (ra == rb) continue;   // (a stale ra only costs a redundant test: unite finds the roots itself)
+      clk.pair();
+      const uint32_t b0 = v.cstart[B], b1 = v.cstart[B + 1];
+      // B's points four at a time (independent loads: one memory round trip per four), A's points inside (re-read for every
+      // neighbour: L1 hits).  A serial walk over B's points for every point of A -- dense cells near the sensor hold dozens, and
+      // two rings a cell apart never touch -- was most of this phase: one round trip per TEST, in the slowest lane of the wavefront
+      bool hit = false;
+      for (uint32_t ib = b0; ib < b1 && !hit; ib += 4u) {
+        float4 q[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) q[k] = v.sorted[min(ib + k, b1 - 1u)];   // (the last point again past the end: harmless)
+        for (uint32_t ia = a0; ia < a1 && !hit; ++ia) {
+          const float4 pa = v.sorted[ia];
+#pragma unroll
+          for (uint32_t k = 0; k < 4u; ++k) {
+            const float ex2 = q[k].x - pa.x, ey2 = q[k].y - pa.y, ez2 = q[k].z - pa.z;
+            float d2 = ex2 * ex2;
+            d2 = d2 + ey2 * ey2;
+            d2 = d2 + ez2 * ez2;
+            hit |= d2 < tol2;
+          }
+        }
+      }
+      clk.lap(4);
+      if (hit) {
+        clk.hit();
+        S::unite(v.cpar, ra, rb);
+        ra = S::find(v.cpar, A);
+      }
+      clk.lap(3);
+    }
+  }
+}
+
+// root (per cell A, its root found by the caller): kept in ckey (block-and-bit is no longer needed); size and smallest member
+// index accumulated on the root (the counts are zero since the placement; a non-root's word is final since the cells phase)
+template <class S>
+__device__ __forceinline__ void hash_root(const HashViews& v, uint32_t A, uint32_t root) {
+  v.ckey[A] = root;
+  HB_ATOMIC(fetch_add, &v.ccnt[root], v.cstart[A + 1] - v.cstart[A]);
+  if (root != A) HB_ATOMIC(fetch_min, &v.cmin[root], S::load(&v.cmin[A]));
+}
+
+// tail (per frame): components = the root cells, a point's = its cell's root
+__device__ __forceinline__ void hash_tail(const Ctx& c, uint32_t f, const HashViews& v, uint32_t C, uint32_t* sc) {
+  cluster_tail(c, f, v.P, v.M, C,
+               [&](uint32_t k, uint32_t& sz, uint32_t& mi) {
+                 if (v.ckey[k] != k) return false;
+                 sz = v.ccnt[k];
+                 mi = v.cmin[k];
+                 return true;
+               },
+               [&](uint32_t i, const float4&) { return v.ckey[v.cell_of[i]]; }, sc);
+}
+// The phases by the frame's own workgroup.  Returns false (uniformly) when the frame is outside this path's limits: the caller
+// takes the point-level path.
+__device__ bool hashed_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc) {
+  const HashViews v = hash_views(c, f);
+  const uint32_t M = v.M, tid = threadIdx.x, kT = blockDim.x;
 #ifdef ILCC_K2_TIMING
   __shared__ unsigned long long hmark[12];
 #define HC_MARK(k) do { __syncthreads(); if (threadIdx.x == 0) hmark[k] = __builtin_readcyclecounter(); } while (0)
@@ -803,388 +1015,54 @@ __device__ bool hashed_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc) {
 #define HC_MARK(k) do {} while (0)
 #endif
   HC_MARK(0);
-
-  // ---- bounding box -> block grid (as in fine_cluster_frame)
-  float3 lo = make_float3(3.0e38f, 3.0e38f, 3.0e38f), hi = make_float3(-3.0e38f, -3.0e38f, -3.0e38f);
-  for (uint32_t i = tid; i < M; i += kT) {
-    const float4 q = v.P[i];
-    lo.x = fminf(lo.x, q.x); lo.y = fminf(lo.y, q.y); lo.z = fminf(lo.z, q.z);
-    hi.x = fmaxf(hi.x, q.x); hi.y = fmaxf(hi.y, q.y); hi.z = fmaxf(hi.z, q.z);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo.x = fminf(lo.x, __shfl_xor(lo.x, o, ILCC_WAVE)); lo.y = fminf(lo.y, __shfl_xor(lo.y, o, ILCC_WAVE));
-    lo.z = fminf(lo.z, __shfl_xor(lo.z, o, ILCC_WAVE));
-    hi.x = fmaxf(hi.x, __shfl_xor(hi.x, o, ILCC_WAVE)); hi.y = fmaxf(hi.y, __shfl_xor(hi.y, o, ILCC_WAVE));
-    hi.z = fmaxf(hi.z, __shfl_xor(hi.z, o, ILCC_WAVE));
-  }
-  __syncthreads();
-  if (lane_id() == 0) {
-    scf[wave_id()] = lo.x; scf[16 + wave_id()] = lo.y; scf[32 + wave_id()] = lo.z;
-    scf[64 + wave_id()] = hi.x; scf[80 + wave_id()] = hi.y; scf[96 + wave_id()] = hi.z;
-  }
-  __syncthreads();
-  for (int w = 0; w < nwv; ++w) {
-    lo.x = fminf(lo.x, scf[w]); lo.y = fminf(lo.y, scf[16 + w]); lo.z = fminf(lo.z, scf[32 + w]);
-    hi.x = fmaxf(hi.x, scf[64 + w]); hi.y = fmaxf(hi.y, scf[80 + w]); hi.z = fmaxf(hi.z, scf[96 + w]);
-  }
-  __syncthreads();
   HashFrame g;
-  g.lox = lo.x; g.loy = lo.y; g.loz = lo.z;
-  g.inv = 1.0f / ((float)c.p.cluster_tol * kFineCellOverTol);
-  const float ex = (hi.x - lo.x) * g.inv, ey = (hi.y - lo.y) * g.inv, ez = (hi.z - lo.z) * g.inv;
-  if (!(ex < 8192.f && ey < 8192.f && ez < 8192.f)) return false;   // (also a NaN extent)
-  {
-    const int nx = (int)floorf(ex) + 5, ny = (int)floorf(ey) + 5, nz = (int)floorf(ez) + 5;
-    g.nbx = (nx + 3) >> 2;
-    g.nby = (ny + 3) >> 2;
-    // 32-bit keys, 0xFFFFFFFF = empty
-    if ((unsigned long long)g.nbx * (unsigned long long)g.nby * (unsigned long long)((nz + 3) >> 2) >= 0xFFFFFFFFull) return false;
-  }
-  uint32_t size = 1024u;
-  while (size < 2u * M) size <<= 1;             // <= 2^17: blocks <= cells <= points, the table at most half full
-  g.mask = size - 1u;
-  g.shift = 32u - (uint32_t)__builtin_ctz(size);
+  if (!hash_setup(c, f, v, reinterpret_cast<float*>(sc), g)) return false;
   HC_MARK(1);
-
-  // ---- reset
-  for (uint32_t k = tid; k < size; k += kT) {
-    v.tkey[k] = kHashEmpty;
-    v.tlo[k] = 0u;
-    v.thi[k] = 0u;
-  }
-  for (uint32_t i = tid; i < M; i += kT) {
-    v.ccnt[i] = 0u;
-    v.cmin[i] = 0xFFFFFFFFu;
-    v.cpar[i] = i;
-  }
+  hash_reset(v, g);
   wg_phase();
   HC_MARK(2);
-  // ---- every point: its block's entry (claimed with a compare-and-swap on the key), its cell's bit
-  for (uint32_t i = tid; i < M; i += kT) {
-    uint32_t key, bit;
-    hb_cell(g, v.P[i], key, bit);
-    uint32_t h = hb_slot(g, key);
-    for (;;) {
-      uint32_t e = v.tkey[h];
-      if (e == kHashEmpty) e = wg_cas(&v.tkey[h], kHashEmpty, key);   // (a stale "empty" costs this CAS, which returns the key)
-      if (e == kHashEmpty || e == key) break;
-      h = (h + 1u) & g.mask;
-    }
-    WG_ATOMIC(fetch_or, bit < 32u ? &v.tlo[h] : &v.thi[h], 1u << (bit & 31u));
-    v.cell_of[i] = (h << 6) | bit;
-  }
+  for (uint32_t i = tid; i < M; i += kT) hash_insert<WgScope>(v, g, i);
   wg_phase();
   HC_MARK(3);
-  // ---- first dense cell id of every block: exclusive scan of the masks' popcounts (whole tiles of 4 slots per thread)
-  uint32_t C = 0;
-  {
-    const uint4* lo4 = reinterpret_cast<const uint4*>(v.tlo);
-    const uint4* hi4 = reinterpret_cast<const uint4*>(v.thi);
-    uint4* base4 = reinterpret_cast<uint4*>(v.tbase);
-    for (uint32_t t0 = 0; t0 < size / 4u; t0 += kT) {
-      const uint32_t q = t0 + tid;
-      uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
-      if (q < size / 4u) {
-        const uint4 a = lo4[q], b = hi4[q];
-        n0 = (uint32_t)(__popc(a.x) + __popc(b.x));
-        n1 = (uint32_t)(__popc(a.y) + __popc(b.y));
-        n2 = (uint32_t)(__popc(a.z) + __popc(b.z));
-        n3 = (uint32_t)(__popc(a.w) + __popc(b.w));
-      }
-      uint32_t tot;
-      const uint32_t run = C + block_excl_scan(n0 + n1 + n2 + n3, sc, tot);
-      if (q < size / 4u) base4[q] = make_uint4(run, run + n0, run + n0 + n1, run + n0 + n1 + n2);
-      C += tot;
-    }
-  }
+  const uint32_t C = hash_blocks(v, g, sc);
   wg_phase();
   HC_MARK(4);
-  // ---- every point: dense cell id (block's base + rank of the bit), cell count, smallest member index
-  for (uint32_t i = tid; i < M; i += kT) {
-    const uint32_t hb = v.cell_of[i], h = hb >> 6, bit = hb & 63u;
-    const uint32_t cell = v.tbase[h] + hb_rank(v.tlo[h], v.thi[h], bit);
-    v.cell_of[i] = cell;
-    WG_ATOMIC(fetch_add, &v.ccnt[cell], 1u);
-    WG_ATOMIC(fetch_min, &v.cmin[cell], i);
-    v.ckey[cell] = hb;   // (every point of the cell writes the same word)
-  }
+  for (uint32_t i = tid; i < M; i += kT) hash_cell<WgScope>(v, i);
   wg_phase();
   HC_MARK(5);
-  // ---- first sorted position of every cell: exclusive scan of the counts (tiles of one cell per thread: coalesced)
-  {
-    uint32_t run0 = 0;
-    for (uint32_t t0 = 0; t0 < C; t0 += kT) {
-      const uint32_t k = t0 + tid;
-      const uint32_t n = k < C ? v.ccnt[k] : 0u;
-      uint32_t tot;
-      const uint32_t run = run0 + block_excl_scan(n, sc, tot);
-      if (k < C) v.cstart[k] = run;
-      run0 += tot;
-    }
-    if (tid == 0) v.cstart[C] = M;
-  }
+  hash_starts(v, C, sc);
   wg_phase();
-  // ---- the points sorted by cell (leaves the counts all zero)
-  for (uint32_t i = tid; i < M; i += kT) {
-    const uint32_t cell = v.cell_of[i];
-    v.sorted[v.cstart[cell] + (WG_ATOMIC(fetch_sub, &v.ccnt[cell], 1u) - 1u)] = v.P[i];
-  }
+  for (uint32_t i = tid; i < M; i += kT) hash_place<WgScope>(v, i);
   wg_phase();
   HC_MARK(6);
-
-  // ---- edges: per cell, the occupied neighbour cells with a larger id; same root -> nothing; else the pair's points are tested
-  // until the first hit (the reference's float arithmetic) and the cells united
-  auto axis_mask = [](int a, int o) -> uint32_t {   // cells x of block (own + o) with |x + 4 o - a| <= 2, as a 4-bit mask
-    const int l = max(a - 2 - 4 * o, 0), u = min(a + 2 - 4 * o, 3);
-    return l > u ? 0u : ((1u << (u + 1)) - 1u) & ~((1u << l) - 1u);
-  };
-#ifdef ILCC_K2_TIMING
-  unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#else
-#define K2_T(k) do {} while (0)
-#endif
-  for (uint32_t A = tid; A < C; A += kT) {
-    K2_T(5);
-    const uint32_t hb = v.ckey[A], hA = hb >> 6, bitA = hb & 63u;
-    const uint32_t keyA = v.tkey[hA];
-    const int ax = (int)(bitA & 3u), ay = (int)((bitA >> 2) & 3u), az = (int)(bitA >> 4);
-    const uint32_t a0 = v.cstart[A], a1 = v.cstart[A + 1];
-    // the 5-cell window of an axis overlaps the cell's own block and ONE neighbour: the lower one when the cell sits in the
-    // block's lower half, the upper one otherwise
-    const int sx = ax < 2 ? -1 : 1, sy = ay < 2 ? -1 : 1, sz = az < 2 ? -1 : 1;
-    // slots first, then ALL first probes in flight at once, then all masks: no chain of dependent loads per neighbour
-    uint32_t hs[8], want[8], got[8];
-    hs[0] = hA;
-#pragma unroll
-    for (int nb = 1; nb < 8; ++nb) {
-      const int ox = (nb & 1) ? sx : 0, oy = (nb & 2) ? sy : 0, oz = (nb & 4) ? sz : 0;
-      want[nb] = (uint32_t)((int)keyA + ox + g.nbx * (oy + g.nby * oz));
-      hs[nb] = hb_slot(g, want[nb]);
-    }
-#pragma unroll
-    for (int nb = 1; nb < 8; ++nb) got[nb] = v.tkey[hs[nb]];
-#pragma unroll
-    for (int nb = 1; nb < 8; ++nb) {
-      uint32_t h = hs[nb], e = got[nb];
-      while (e != want[nb] && e != kHashEmpty) {   // (a collision: rare at <= 50 % load)
-        h = (h + 1u) & g.mask;
-        e = v.tkey[h];
-      }
-      hs[nb] = e == kHashEmpty ? kHashEmpty : h;
-    }
-    K2_T(0);
-    uint32_t mlo[8], mhi[8], base[8];
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) {
-      const uint32_t h = hs[nb] == kHashEmpty ? hA : hs[nb];   // (a harmless load for an absent block)
-      mlo[nb] = v.tlo[h];
-      mhi[nb] = v.thi[h];
-      base[nb] = v.tbase[h];
-    }
-    uint32_t ra = wg_find(v.cpar, A);
-    K2_T(1);
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) {
-      if (hs[nb] == kHashEmpty) continue;
-      const int ox = (nb & 1) ? sx : 0, oy = (nb & 2) ? sy : 0, oz = (nb & 4) ? sz : 0;
-      const uint32_t mx = axis_mask(ax, ox), my = axis_mask(ay, oy), mz = axis_mask(az, oz);
-      // window = { x + 4 y + 16 z : x in mx, y in my, z in mz }: products of disjoint bit patterns
-      const uint32_t plane = mx * ((my & 1u) | ((my & 2u) << 3) | ((my & 4u) << 6) | ((my & 8u) << 9));   // 16 bits
-      const unsigned long long win = (unsigned long long)plane *
-                                     ((unsigned long long)(mz & 1u) | ((unsigned long long)(mz & 2u) << 15) | ((unsigned long long)(mz & 4u) << 30) | ((unsigned long long)(mz & 8u) << 45));
-      unsigned long long occ = (((unsigned long long)mhi[nb] << 32) | mlo[nb]) & win;
-      if (nb == 0) occ &= ~(1ull << bitA);
-      while (occ) {
-        const uint32_t b = (uint32_t)__builtin_ctzll(occ);
-        occ &= occ - 1ull;
-        const uint32_t B = base[nb] + hb_rank(mlo[nb], mhi[nb], b);
-        if (B <= A) continue;   // every pair of cells once: from the smaller id
-        K2_T(2);
-        const uint32_t rb = wg_find(v.cpar, B);
-        K2_T(3);
-        if (ra == rb) continue;   // (a stale ra only costs a redundant test: wg_unite finds the roots itself)
-        K2_COUNT(g_k2_pairs, 1);
-        const uint32_t b0 = v.cstart[B], b1 = v.cstart[B + 1];
-        // B's points four at a time (independent loads: one memory round trip per four), A's points inside (re-read for every
-        // neighbour: L1 hits).  A serial walk over B's points for every point of A -- dense cells near the sensor hold dozens, and
-        // two rings a cell apart never touch -- was most of this phase: one round trip per TEST, in the slowest lane of the wavefront
-        bool hit = false;
-        for (uint32_t ib = b0; ib < b1 && !hit; ib += 4u) {
-          float4 q[4];
-#pragma unroll
-          for (uint32_t k = 0; k < 4u; ++k) q[k] = v.sorted[min(ib + k, b1 - 1u)];   // (the last point again past the end: harmless)
-          for (uint32_t ia = a0; ia < a1 && !hit; ++ia) {
-            const float4 pa = v.sorted[ia];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) {
-              const float ex2 = q[k].x - pa.x, ey2 = q[k].y - pa.y, ez2 = q[k].z - pa.z;
-              float d2 = ex2 * ex2;
-              d2 = d2 + ey2 * ey2;
-              d2 = d2 + ez2 * ez2;
-              hit |= d2 < tol2;
-            }
-          }
-        }
-        K2_T(4);
-        if (hit) {
-          K2_COUNT(g_k2_hits, 1);
-          wg_unite(v.cpar, ra, rb);
-          ra = wg_find(v.cpar, A);
-        }
-        K2_T(3);
-      }
-    }
+  {
+    const float tol2 = (float)(c.p.cluster_tol * c.p.cluster_tol);
+    WgScope::Clock clk;
+    for (uint32_t A = tid; A < C; A += kT) hash_edges<WgScope>(v, g, A, tol2, clk);
+    clk.flush();
   }
-#ifdef ILCC_K2_TIMING
-  for (int k = 0; k < 6; ++k) atomicAdd(&g_k2_t[k], tacc[k]);
-#endif
   wg_phase();
   HC_MARK(7);
-
-  // ---- components: the root of every cell (kept in ckey: block-and-bit is no longer needed); size and smallest member index on the root
   for (uint32_t t0 = 0; t0 < C; t0 += kT) {
     const uint32_t A = t0 + tid;
     uint32_t root = 0;
     if (A < C) root = wg_find(v.cpar, A);
     wg_phase();   // (path halving rewrites parents: finish every find of the tile before the roots are stored)
-    if (A < C) {
-      v.ckey[A] = root;
-      WG_ATOMIC(fetch_add, &v.ccnt[root], v.cstart[A + 1] - v.cstart[A]);   // the counts are zero since the placement
-      if (root != A) WG_ATOMIC(fetch_min, &v.cmin[root], v.cmin[A]);        // (a non-root's word is final since the cells phase)
-    }
+    if (A < C) hash_root<WgScope>(v, A, root);
   }
   wg_phase();
   HC_MARK(8);
-
-  // ---- exact 1-NN of the click (float squared distance, ties -> lowest index)
-  const float kx = c.clicks[3 * f], ky = c.clicks[3 * f + 1], kz = c.clicks[3 * f + 2];
-  NnKey best{3.402823466e38f, 0xFFFFFFFFu};
-  for (uint32_t i = tid; i < M; i += kT) {
-    const float4 q = v.P[i];
-    const float dx = q.x - kx, dy = q.y - ky, dz = q.z - kz;
-    float d2 = dx * dx;
-    d2 = d2 + dy * dy;
-    d2 = d2 + dz * dz;
-    const NnKey k{d2, i};
-    if (nn_less(k, best)) best = k;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    NnKey t;
-    t.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-    t.idx = __shfl_down(best.idx, o, ILCC_WAVE);
-    if (nn_less(t, best)) best = t;
-  }
-  // ---- largest admissible component (ties -> smallest member index), i.e. sorted index 0
-  const uint32_t cmin_sz = (uint32_t)c.p.cluster_min, cmax_sz = (uint32_t)c.p.cluster_max;
-  uint32_t bsz = 0, bidx = 0xFFFFFFFFu, broot = 0xFFFFFFFFu;
-  for (uint32_t k = tid; k < C; k += kT) {
-    if (v.ckey[k] != k) continue;
-    const uint32_t sz = v.ccnt[k], mi = v.cmin[k];
-    if (sz < cmin_sz || sz > cmax_sz) continue;
-    if (sz > bsz || (sz == bsz && mi < bidx)) {
-      bsz = sz;
-      bidx = mi;
-      broot = k;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t s2 = __shfl_down(bsz, o, ILCC_WAVE), i2 = __shfl_down(bidx, o, ILCC_WAVE), r2 = __shfl_down(broot, o, ILCC_WAVE);
-    if (s2 > bsz || (s2 == bsz && i2 < bidx)) {
-      bsz = s2;
-      bidx = i2;
-      broot = r2;
-    }
-  }
-  __syncthreads();
-  if (lane_id() == 0) {
-    scf[wave_id()] = best.d2;
-    sc[16 + wave_id()] = best.idx;
-    sc[32 + wave_id()] = bsz;
-    sc[48 + wave_id()] = bidx;
-    sc[64 + wave_id()] = broot;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    NnKey nb{scf[0], sc[16]};
-    uint32_t s0 = sc[32], i0 = sc[48], r0 = sc[64];
-    for (int w = 1; w < nwv; ++w) {
-      const NnKey k{scf[w], sc[16 + w]};
-      if (nn_less(k, nb)) nb = k;
-      const uint32_t s2 = sc[32 + w], i2 = sc[48 + w], r2 = sc[64 + w];
-      if (s2 > s0 || (s2 == s0 && i2 < i0)) {
-        s0 = s2;
-        i0 = i2;
-        r0 = r2;
-      }
-    }
-    const uint32_t nn_root = v.ckey[v.cell_of[nb.idx]];
-    const uint32_t nsz = v.ccnt[nn_root];
-    const bool found = nsz >= cmin_sz && nsz <= cmax_sz;   // find_board of get_chessboard_by_point (:91-102)
-    r->found_board = found ? 1 : 0;
-    sc[120] = found ? nn_root : r0;                         // cluster containing the click's NN, else plane_index = 0
-    sc[121] = (s0 == 0) ? 0u : 1u;
-  }
-  __syncthreads();
-  const uint32_t chosen = sc[120];
-  if (sc[121] == 0u) {
-    if (tid == 0) r->status = ILCC_NO_CLUSTER;
-    return true;
-  }
-
-  // ---- stable compaction of the chosen component (index order); the sorted points (same buffer) are dead from here on
-  float4* __restrict__ dst = c.cluster + c.off[f];
-  uint32_t running = 0;
-  for (uint32_t base0 = 0; base0 < M; base0 += kT) {
-    const uint32_t i = base0 + tid;
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool keep = false;
-    if (i < M) {
-      q = v.P[i];
-      keep = v.ckey[v.cell_of[i]] == chosen;
-    }
-    uint32_t tot;
-    const uint32_t rank = block_rank(keep, sc + 128, tot);
-    if (keep) dst[running + rank] = q;
-    running += tot;
-  }
-  if (tid == 0) r->n_cluster = (int32_t)running;
+  hash_tail(c, f, v, C, sc);
   HC_MARK(9);
 #ifdef ILCC_K2_TIMING
   if (tid == 0)
     printf("K2 counters (all frames so far): finds %llu hops %llu cell pairs tested %llu hits %llu; thread-cycles lookups %llu masks+findA %llu window %llu find/unite %llu tests %llu loop %llu\n", g_k2_finds, g_k2_hops, g_k2_pairs, g_k2_hits, g_k2_t[0], g_k2_t[1], g_k2_t[2], g_k2_t[3], g_k2_t[4], g_k2_t[5]);
   if (tid == 0)
     printf("K2 hashed M=%u C=%u table %u cycles: bbox %llu reset %llu insert %llu blocks %llu cells %llu sort %llu edges %llu comps %llu nn+compact %llu\n",
-           M, C, size, hmark[1] - hmark[0], hmark[2] - hmark[1], hmark[3] - hmark[2], hmark[4] - hmark[3], hmark[5] - hmark[4], hmark[6] - hmark[5],
+           M, C, g.mask + 1u, hmark[1] - hmark[0], hmark[2] - hmark[1], hmark[3] - hmark[2], hmark[4] - hmark[3], hmark[5] - hmark[4], hmark[6] - hmark[5],
            hmark[7] - hmark[6], hmark[8] - hmark[7], hmark[9] - hmark[8]);
 #endif
   return true;
-}
-
-// the point-level spatial hash of rounds 1-3 by ONE workgroup: the last resort for frames beyond the limits of the cell paths
-__device__ void point_level_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc) {
-  const uint32_t M = (uint32_t)c.res[f].n_roi, kT = blockDim.x;
-  const uint64_t beg = c.off[f];
-  uint32_t* gparent = c.uf_parent + beg;
-  uint32_t* count = c.uf_count + beg;
-  uint32_t* head = c.uf_hash_head + (uint64_t)f * kClusterHashSize;
-  for (uint32_t i = threadIdx.x; i < M; i += kT) {
-    gparent[i] = i;
-    count[i] = 0u;
-  }
-  for (uint32_t k = threadIdx.x; k < (uint32_t)kClusterHashSize; k += kT) head[k] = 0xFFFFFFFFu;
-  __threadfence_block();
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i < M; i += kT) big_insert_point(c, f, i);
-  __threadfence_block();
-  __syncthreads();
-  const float tol2 = (float)(c.p.cluster_tol * c.p.cluster_tol);
-  for (uint32_t i = threadIdx.x; i < M; i += kT) big_search_point(c, f, i, tol2);
-  __threadfence_block();
-  __syncthreads();
-  cluster_finish<false>(c, f, gparent, sc);
 }
 
 // ------------------------------------------------------------------ the same components, the whole chip on a few frames
@@ -1192,19 +1070,15 @@ __device__ void point_level_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc
 // first tier answers most frames from a window; the few it cannot vouch for -- listed in Ctx::list -- need the WHOLE cloud
 // clustered, ~29 k points and ~20 k cells each.  One workgroup per frame (hashed_cluster_frame) is latency-bound there: every
 // phase is a few dozen dependent memory round trips per thread, 2.1 ms per frame however few frames there are.  This chain of
-// kernels spreads every phase of the same algorithm over (listed frame, 256-item chunk) work items on the whole chip; its
-// atomics are device-scope (several workgroups share a frame) and therefore slow one by one -- 2.7 ms when all 128 clouds of a
-// call are listed -- but with a tenth of the frames listed the chain is a tenth as long.
-//   k2h_setup   per frame: bounding box -> block grid, table reset
-//   k2h_insert  per point: its block's entry (claimed with a CAS on the key), its cell's bit
-//   k2h_blocks  per frame: exclusive scan of the masks' popcounts -> first dense cell id of every block, number of cells
-//   k2h_cells   per point: dense cell id (block's base + rank of the bit), cell count, smallest member index
-//   k2h_starts  per frame: exclusive scan of the counts -> first sorted position of every cell
-//   k2h_place   per point: the points sorted by cell (the frame's slice of the cluster buffer, until the compaction)
-//   k2h_edges   per cell: occupied neighbour cells with a larger id; same root -> nothing; else the pair's points are tested
-//               until the first hit (the reference's float arithmetic) and the cells united (hooks to the smaller id)
-//   k2h_roots   per cell: its root; size and smallest member index accumulated on the root
-//   k2h_finish  per frame: exact 1-NN of the click, the reference's choice rule, index-ordered compaction
+// kernels runs the same phases, one kernel each, with the per-point and per-cell ones spread over (listed frame, 256-item chunk)
+// work items on the whole chip; its atomics are agent-scope (AgentScope: several workgroups share a frame) and therefore slow
+// one by one -- 2.7 ms when all 128 clouds of a call are listed -- but with a tenth of the frames listed the chain is a tenth
+// as long.
+//   k2h_setup   per frame: hash_setup, hash_reset        k2h_starts  per frame: hash_starts
+//   k2h_insert  per point: hash_insert                   k2h_place   per point: hash_place
+//   k2h_blocks  per frame: hash_blocks                   k2h_edges   per cell:  hash_edges
+//   k2h_cells   per point: hash_cell                     k2h_roots   per cell:  its root, hash_root
+//   k2h_finish  per frame: hash_tail (point_level_cluster_frame for a frame outside the hashed path's limits)
 // Same scratch as hashed_cluster_frame (hash_views).
 constexpr int kListChunk = 256;       // items per work item
 constexpr int kListBlock = 1024;      // listed frames whose chunk prefix sums a workgroup keeps in LDS at a time
@@ -1257,68 +1131,27 @@ __device__ __forceinline__ void for_each_listed_chunk(const Ctx& c, uint32_t* s_
   }
 }
 
+// the listed frame of this workgroup, for the per-frame kernels (one workgroup per listed frame)
+__device__ __forceinline__ bool listed_frame(const Ctx& c, uint32_t& f) {
+  if (blockIdx.x >= __hip_atomic_load(c.list_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
+  f = c.list[blockIdx.x];
+  return true;
+}
+
 __global__ __launch_bounds__(1024) void k2h_setup(Ctx c, ListedFrame* frames) {
   __shared__ float scf[128];
-  const uint32_t nl = __hip_atomic_load(c.list_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (blockIdx.x >= nl) return;
-  const uint32_t f = c.list[blockIdx.x];
+  uint32_t f;
+  if (!listed_frame(c, f)) return;
   const HashViews v = hash_views(c, f);
-  const uint32_t M = v.M, tid = threadIdx.x, kT = blockDim.x;
-  float3 lo = make_float3(3.0e38f, 3.0e38f, 3.0e38f), hi = make_float3(-3.0e38f, -3.0e38f, -3.0e38f);
-  for (uint32_t i = tid; i < M; i += kT) {
-    const float4 q = v.P[i];
-    lo.x = fminf(lo.x, q.x); lo.y = fminf(lo.y, q.y); lo.z = fminf(lo.z, q.z);
-    hi.x = fmaxf(hi.x, q.x); hi.y = fmaxf(hi.y, q.y); hi.z = fmaxf(hi.z, q.z);
+  HashFrame g{};
+  const bool ok = hash_setup(c, f, v, scf, g);
+  if (threadIdx.x == 0) {
+    ListedFrame L{};   // (valid = 0: n_cells = 0)
+    L.g = g;
+    L.valid = ok ? 1u : 0u;
+    frames[f] = L;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo.x = fminf(lo.x, __shfl_xor(lo.x, o, ILCC_WAVE)); lo.y = fminf(lo.y, __shfl_xor(lo.y, o, ILCC_WAVE));
-    lo.z = fminf(lo.z, __shfl_xor(lo.z, o, ILCC_WAVE));
-    hi.x = fmaxf(hi.x, __shfl_xor(hi.x, o, ILCC_WAVE)); hi.y = fmaxf(hi.y, __shfl_xor(hi.y, o, ILCC_WAVE));
-    hi.z = fmaxf(hi.z, __shfl_xor(hi.z, o, ILCC_WAVE));
-  }
-  if (lane_id() == 0) {
-    scf[wave_id()] = lo.x; scf[16 + wave_id()] = lo.y; scf[32 + wave_id()] = lo.z;
-    scf[64 + wave_id()] = hi.x; scf[80 + wave_id()] = hi.y; scf[96 + wave_id()] = hi.z;
-  }
-  __syncthreads();
-  for (int w = 0; w < (int)(kT / ILCC_WAVE); ++w) {
-    lo.x = fminf(lo.x, scf[w]); lo.y = fminf(lo.y, scf[16 + w]); lo.z = fminf(lo.z, scf[32 + w]);
-    hi.x = fmaxf(hi.x, scf[64 + w]); hi.y = fmaxf(hi.y, scf[80 + w]); hi.z = fmaxf(hi.z, scf[96 + w]);
-  }
-  ListedFrame L{};
-  HashFrame& g = L.g;
-  g.lox = lo.x; g.loy = lo.y; g.loz = lo.z;
-  g.inv = 1.0f / ((float)c.p.cluster_tol * kFineCellOverTol);
-  const float ex = (hi.x - lo.x) * g.inv, ey = (hi.y - lo.y) * g.inv, ez = (hi.z - lo.z) * g.inv;
-  bool ok = M > 0u && M <= kHashPointsMax && ex < 8192.f && ey < 8192.f && ez < 8192.f &&   // (a NaN extent fails the comparisons)
-            c.off[f + 1] - c.off[f] >= (uint64_t)kHashMinFramePoints;   // (the 1024-word block arrays fit the frame's slices)
-  if (ok) {
-    const int nx = (int)floorf(ex) + 5, ny = (int)floorf(ey) + 5, nz = (int)floorf(ez) + 5;
-    g.nbx = (nx + 3) >> 2;
-    g.nby = (ny + 3) >> 2;
-    ok = (unsigned long long)g.nbx * (unsigned long long)g.nby * (unsigned long long)((nz + 3) >> 2) < 0xFFFFFFFFull;   // 32-bit keys, 0xFFFFFFFF = empty
-  }
-  if (!ok) {
-    if (tid == 0) frames[f] = L;   // valid = 0, n_cells = 0
-    return;
-  }
-  uint32_t size = 1024u;
-  while (size < 2u * M) size <<= 1;
-  g.mask = size - 1u;
-  g.shift = 32u - (uint32_t)__builtin_ctz(size);
-  L.valid = 1u;
-  if (tid == 0) frames[f] = L;
-  for (uint32_t k = tid; k < size; k += kT) {
-    v.tkey[k] = kHashEmpty;
-    v.tlo[k] = 0u;
-    v.thi[k] = 0u;
-  }
-  for (uint32_t i = tid; i < M; i += kT) {
-    v.ccnt[i] = 0u;
-    v.cmin[i] = 0xFFFFFFFFu;
-    v.cpar[i] = i;
-  }
+  if (ok) hash_reset(v, g);
 }
 
 __global__ __launch_bounds__(kListChunk) void k2h_insert(Ctx c, const ListedFrame* frames) {
@@ -1326,49 +1159,15 @@ __global__ __launch_bounds__(kListChunk) void k2h_insert(Ctx c, const ListedFram
   for_each_listed_chunk(c, s_pref, [&](uint32_t f) { return frames[f].valid ? (uint32_t)c.res[f].n_roi : 0u; }, [&](uint32_t f, uint32_t first) {
     const HashViews v = hash_views(c, f);
     const uint32_t i = first + threadIdx.x;
-    if (i >= v.M) return;
-    const HashFrame g = frames[f].g;
-    uint32_t key, bit;
-    hb_cell(g, v.P[i], key, bit);
-    uint32_t h = hb_slot(g, key);
-    for (;;) {
-      uint32_t e = __hip_atomic_load(&v.tkey[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (e == kHashEmpty) e = atomicCAS(&v.tkey[h], kHashEmpty, key);
-      if (e == kHashEmpty || e == key) break;
-      h = (h + 1u) & g.mask;
-    }
-    atomicOr(bit < 32u ? &v.tlo[h] : &v.thi[h], 1u << (bit & 31u));
-    v.cell_of[i] = (h << 6) | bit;
+    if (i < v.M) hash_insert<AgentScope>(v, frames[f].g, i);
   });
 }
 
 __global__ __launch_bounds__(1024) void k2h_blocks(Ctx c, ListedFrame* frames) {
   __shared__ uint32_t sc[32];
-  const uint32_t nl = __hip_atomic_load(c.list_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (blockIdx.x >= nl) return;
-  const uint32_t f = c.list[blockIdx.x];
-  if (!frames[f].valid) return;
-  const HashViews v = hash_views(c, f);
-  const uint32_t size = frames[f].g.mask + 1u;   // a power of two >= 1024: whole tiles of 4 slots per thread, 16-byte accesses
-  const uint4* lo4 = reinterpret_cast<const uint4*>(v.tlo);
-  const uint4* hi4 = reinterpret_cast<const uint4*>(v.thi);
-  uint4* base4 = reinterpret_cast<uint4*>(v.tbase);
-  uint32_t C = 0;
-  for (uint32_t t0 = 0; t0 < size / 4u; t0 += blockDim.x) {
-    const uint32_t q = t0 + threadIdx.x;
-    uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
-    if (q < size / 4u) {
-      const uint4 a = lo4[q], b = hi4[q];
-      n0 = (uint32_t)(__popc(a.x) + __popc(b.x));
-      n1 = (uint32_t)(__popc(a.y) + __popc(b.y));
-      n2 = (uint32_t)(__popc(a.z) + __popc(b.z));
-      n3 = (uint32_t)(__popc(a.w) + __popc(b.w));
-    }
-    uint32_t tot;
-    const uint32_t run = C + block_excl_scan(n0 + n1 + n2 + n3, sc, tot);
-    if (q < size / 4u) base4[q] = make_uint4(run, run + n0, run + n0 + n1, run + n0 + n1 + n2);
-    C += tot;
-  }
+  uint32_t f;
+  if (!listed_frame(c, f) || !frames[f].valid) return;
+  const uint32_t C = hash_blocks(hash_views(c, f), frames[f].g, sc);
   if (threadIdx.x == 0) frames[f].n_cells = C;
 }
 
@@ -1377,34 +1176,15 @@ __global__ __launch_bounds__(kListChunk) void k2h_cells(Ctx c, const ListedFrame
   for_each_listed_chunk(c, s_pref, [&](uint32_t f) { return frames[f].valid ? (uint32_t)c.res[f].n_roi : 0u; }, [&](uint32_t f, uint32_t first) {
     const HashViews v = hash_views(c, f);
     const uint32_t i = first + threadIdx.x;
-    if (i >= v.M) return;
-    const uint32_t hb = v.cell_of[i], h = hb >> 6, bit = hb & 63u;
-    const uint32_t cell = v.tbase[h] + hb_rank(v.tlo[h], v.thi[h], bit);
-    v.cell_of[i] = cell;
-    atomicAdd(&v.ccnt[cell], 1u);
-    atomicMin(&v.cmin[cell], i);
-    v.ckey[cell] = hb;   // (every point of the cell writes the same word)
+    if (i < v.M) hash_cell<AgentScope>(v, i);
   });
 }
 
 __global__ __launch_bounds__(1024) void k2h_starts(Ctx c, const ListedFrame* frames) {
   __shared__ uint32_t sc[32];
-  const uint32_t nl = __hip_atomic_load(c.list_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (blockIdx.x >= nl) return;
-  const uint32_t f = c.list[blockIdx.x];
-  if (!frames[f].valid) return;
-  const HashViews v = hash_views(c, f);
-  const uint32_t C = frames[f].n_cells;
-  uint32_t run0 = 0;
-  for (uint32_t t0 = 0; t0 < C; t0 += blockDim.x) {
-    const uint32_t k = t0 + threadIdx.x;
-    const uint32_t n = k < C ? v.ccnt[k] : 0u;
-    uint32_t tot;
-    const uint32_t run = run0 + block_excl_scan(n, sc, tot);
-    if (k < C) v.cstart[k] = run;
-    run0 += tot;
-  }
-  if (threadIdx.x == 0) v.cstart[C] = v.M;
+  uint32_t f;
+  if (!listed_frame(c, f) || !frames[f].valid) return;
+  hash_starts(hash_views(c, f), frames[f].n_cells, sc);
 }
 
 __global__ __launch_bounds__(kListChunk) void k2h_place(Ctx c, const ListedFrame* frames) {
@@ -1412,9 +1192,7 @@ __global__ __launch_bounds__(kListChunk) void k2h_place(Ctx c, const ListedFrame
   for_each_listed_chunk(c, s_pref, [&](uint32_t f) { return frames[f].valid ? (uint32_t)c.res[f].n_roi : 0u; }, [&](uint32_t f, uint32_t first) {
     const HashViews v = hash_views(c, f);
     const uint32_t i = first + threadIdx.x;
-    if (i >= v.M) return;
-    const uint32_t cell = v.cell_of[i];
-    v.sorted[v.cstart[cell] + (atomicSub(&v.ccnt[cell], 1u) - 1u)] = v.P[i];   // leaves the counts all zero
+    if (i < v.M) hash_place<AgentScope>(v, i);
   });
 }
 
@@ -1424,86 +1202,8 @@ __global__ __launch_bounds__(kListChunk) void k2h_edges(Ctx c, const ListedFrame
   for_each_listed_chunk(c, s_pref, [&](uint32_t f) { return frames[f].n_cells; }, [&](uint32_t f, uint32_t first) {
     const uint32_t A = first + threadIdx.x;
     if (A >= frames[f].n_cells) return;
-    const HashFrame g = frames[f].g;
-    const HashViews v = hash_views(c, f);
-    const uint32_t hb = v.ckey[A], hA = hb >> 6, bitA = hb & 63u;
-    const uint32_t keyA = v.tkey[hA];
-    const int ax = (int)(bitA & 3u), ay = (int)((bitA >> 2) & 3u), az = (int)(bitA >> 4);
-    const uint32_t a0 = v.cstart[A], a1 = v.cstart[A + 1];
-    const int sx = ax < 2 ? -1 : 1, sy = ay < 2 ? -1 : 1, sz = az < 2 ? -1 : 1;
-    auto axis_mask = [](int a, int o) -> uint32_t {   // cells x of block (own + o) with |x + 4 o - a| <= 2, as a 4-bit mask
-      const int l = max(a - 2 - 4 * o, 0), u = min(a + 2 - 4 * o, 3);
-      return l > u ? 0u : ((1u << (u + 1)) - 1u) & ~((1u << l) - 1u);
-    };
-    uint32_t hs[8], want[8], got[8];
-    hs[0] = hA;
-#pragma unroll
-    for (int nb = 1; nb < 8; ++nb) {
-      const int ox = (nb & 1) ? sx : 0, oy = (nb & 2) ? sy : 0, oz = (nb & 4) ? sz : 0;
-      want[nb] = (uint32_t)((int)keyA + ox + g.nbx * (oy + g.nby * oz));
-      hs[nb] = hb_slot(g, want[nb]);
-    }
-#pragma unroll
-    for (int nb = 1; nb < 8; ++nb) got[nb] = v.tkey[hs[nb]];
-#pragma unroll
-    for (int nb = 1; nb < 8; ++nb) {
-      uint32_t h = hs[nb], e = got[nb];
-      while (e != want[nb] && e != kHashEmpty) {
-        h = (h + 1u) & g.mask;
-        e = v.tkey[h];
-      }
-      hs[nb] = e == kHashEmpty ? kHashEmpty : h;
-    }
-    uint32_t mlo[8], mhi[8], base[8];
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) {
-      const uint32_t h = hs[nb] == kHashEmpty ? hA : hs[nb];
-      mlo[nb] = v.tlo[h];
-      mhi[nb] = v.thi[h];
-      base[nb] = v.tbase[h];
-    }
-    uint32_t ra = uf_find(v.cpar, A);
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) {
-      if (hs[nb] == kHashEmpty) continue;
-      const int ox = (nb & 1) ? sx : 0, oy = (nb & 2) ? sy : 0, oz = (nb & 4) ? sz : 0;
-      const uint32_t mx = axis_mask(ax, ox), my = axis_mask(ay, oy), mz = axis_mask(az, oz);
-      const uint32_t plane = mx * ((my & 1u) | ((my & 2u) << 3) | ((my & 4u) << 6) | ((my & 8u) << 9));
-      const unsigned long long win = (unsigned long long)plane *
-                                     ((unsigned long long)(mz & 1u) | ((unsigned long long)(mz & 2u) << 15) | ((unsigned long long)(mz & 4u) << 30) | ((unsigned long long)(mz & 8u) << 45));
-      unsigned long long occ = (((unsigned long long)mhi[nb] << 32) | mlo[nb]) & win;
-      if (nb == 0) occ &= ~(1ull << bitA);
-      while (occ) {
-        const uint32_t b = (uint32_t)__builtin_ctzll(occ);
-        occ &= occ - 1ull;
-        const uint32_t B = base[nb] + hb_rank(mlo[nb], mhi[nb], b);
-        if (B <= A) continue;   // every pair of cells once: from the smaller id
-        const uint32_t rb = uf_find(v.cpar, B);
-        if (ra == rb) continue;
-        const uint32_t b0 = v.cstart[B], b1 = v.cstart[B + 1];
-        bool hit = false;
-        for (uint32_t ib = b0; ib < b1 && !hit; ib += 4u) {
-          float4 q[4];
-#pragma unroll
-          for (uint32_t k = 0; k < 4u; ++k) q[k] = v.sorted[min(ib + k, b1 - 1u)];
-          for (uint32_t ia = a0; ia < a1 && !hit; ++ia) {
-            const float4 pa = v.sorted[ia];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) {
-              const float ex2 = q[k].x - pa.x, ey2 = q[k].y - pa.y, ez2 = q[k].z - pa.z;
-              float d2 = ex2 * ex2;
-              d2 = d2 + ey2 * ey2;
-              d2 = d2 + ez2 * ez2;
-              hit |= d2 < tol2;
-            }
-          }
-        }
-        if (hit) {
-          uf_unite(v.cpar, ra, rb);
-          ra = uf_find(v.cpar, A);
-        }
-      }
-    }
+    AgentScope::Clock clk;
+    hash_edges<AgentScope>(hash_views(c, f), frames[f].g, A, tol2, clk);
   });
 }
 
@@ -1513,117 +1213,20 @@ __global__ __launch_bounds__(kListChunk) void k2h_roots(Ctx c, const ListedFrame
     const uint32_t A = first + threadIdx.x;
     if (A >= frames[f].n_cells) return;
     const HashViews v = hash_views(c, f);
-    const uint32_t root = uf_find(v.cpar, A);
-    v.ckey[A] = root;   // (block-and-bit is no longer needed: the word now holds the cell's component)
-    atomicAdd(&v.ccnt[root], v.cstart[A + 1] - v.cstart[A]);   // the counts are zero since the placement
-    // smallest member index of the component, accumulated in place: a root's word only ever falls towards its component's minimum
-    atomicMin(&v.cmin[root], __hip_atomic_load(&v.cmin[A], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    hash_root<AgentScope>(v, A, uf_find(v.cpar, A));
   });
 }
 
 __global__ __launch_bounds__(1024) void k2h_finish(Ctx c, const ListedFrame* frames) {
   __shared__ uint32_t sc[160];
-  const uint32_t nl = __hip_atomic_load(c.list_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (blockIdx.x >= nl) return;
-  const uint32_t f = c.list[blockIdx.x];
+  uint32_t f;
+  if (!listed_frame(c, f)) return;
+  const HashViews v = hash_views(c, f);
   if (!frames[f].valid) {   // beyond the hashed path's limits (> 65 536 points, a bounding grid of > 2^32 blocks): point-level search
     point_level_cluster_frame(c, f, sc);
     return;
   }
-  ilcc_result* r = &c.res[f];
-  const HashViews v = hash_views(c, f);
-  const uint32_t M = v.M, C = frames[f].n_cells, tid = threadIdx.x, kT = blockDim.x;
-  const int nwv = (int)(kT / ILCC_WAVE);
-  float* scf = reinterpret_cast<float*>(sc);
-  const float kx = c.clicks[3 * f], ky = c.clicks[3 * f + 1], kz = c.clicks[3 * f + 2];
-  NnKey best{3.402823466e38f, 0xFFFFFFFFu};
-  for (uint32_t i = tid; i < M; i += kT) {
-    const float4 q = v.P[i];
-    const float dx = q.x - kx, dy = q.y - ky, dz = q.z - kz;
-    float d2 = dx * dx;
-    d2 = d2 + dy * dy;
-    d2 = d2 + dz * dz;
-    const NnKey k{d2, i};
-    if (nn_less(k, best)) best = k;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    NnKey t;
-    t.d2 = __shfl_down(best.d2, o, ILCC_WAVE);
-    t.idx = __shfl_down(best.idx, o, ILCC_WAVE);
-    if (nn_less(t, best)) best = t;
-  }
-  const uint32_t cmin_sz = (uint32_t)c.p.cluster_min, cmax_sz = (uint32_t)c.p.cluster_max;
-  uint32_t bsz = 0, bidx = 0xFFFFFFFFu, broot = 0xFFFFFFFFu;
-  for (uint32_t k = tid; k < C; k += kT) {
-    if (v.ckey[k] != k) continue;
-    const uint32_t sz = v.ccnt[k], mi = v.cmin[k];
-    if (sz < cmin_sz || sz > cmax_sz) continue;
-    if (sz > bsz || (sz == bsz && mi < bidx)) {
-      bsz = sz;
-      bidx = mi;
-      broot = k;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t s2 = __shfl_down(bsz, o, ILCC_WAVE), i2 = __shfl_down(bidx, o, ILCC_WAVE), r2 = __shfl_down(broot, o, ILCC_WAVE);
-    if (s2 > bsz || (s2 == bsz && i2 < bidx)) {
-      bsz = s2;
-      bidx = i2;
-      broot = r2;
-    }
-  }
-  if (lane_id() == 0) {
-    scf[wave_id()] = best.d2;
-    sc[16 + wave_id()] = best.idx;
-    sc[32 + wave_id()] = bsz;
-    sc[48 + wave_id()] = bidx;
-    sc[64 + wave_id()] = broot;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    NnKey nb{scf[0], sc[16]};
-    uint32_t s0 = sc[32], i0 = sc[48], r0 = sc[64];
-    for (int w = 1; w < nwv; ++w) {
-      const NnKey k{scf[w], sc[16 + w]};
-      if (nn_less(k, nb)) nb = k;
-      const uint32_t s2 = sc[32 + w], i2 = sc[48 + w], r2 = sc[64 + w];
-      if (s2 > s0 || (s2 == s0 && i2 < i0)) {
-        s0 = s2;
-        i0 = i2;
-        r0 = r2;
-      }
-    }
-    const uint32_t nn_root = v.ckey[v.cell_of[nb.idx]];
-    const uint32_t nsz = v.ccnt[nn_root];
-    const bool found = nsz >= cmin_sz && nsz <= cmax_sz;   // find_board of get_chessboard_by_point (:91-102)
-    r->found_board = found ? 1 : 0;
-    sc[120] = found ? nn_root : r0;                         // cluster containing the click's NN, else plane_index = 0
-    sc[121] = (s0 == 0) ? 0u : 1u;
-  }
-  __syncthreads();
-  const uint32_t chosen = sc[120];
-  if (sc[121] == 0u) {
-    if (tid == 0) r->status = ILCC_NO_CLUSTER;
-    return;
-  }
-  float4* __restrict__ dst = c.cluster + c.off[f];
-  uint32_t running = 0;
-  for (uint32_t base0 = 0; base0 < M; base0 += kT) {
-    const uint32_t i = base0 + tid;
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool keep = false;
-    if (i < M) {
-      q = v.P[i];
-      keep = v.ckey[v.cell_of[i]] == chosen;
-    }
-    uint32_t tot;
-    const uint32_t rank = block_rank(keep, sc + 128, tot);
-    if (keep) dst[running + rank] = q;
-    running += tot;
-  }
-  if (tid == 0) r->n_cluster = (int32_t)running;
+  hash_tail(c, f, v, frames[f].n_cells, sc);
 }
 
 // second tier of the online caller: the flagged frames, listed (one thread per frame: a few dozen frames at most matter)
