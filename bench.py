@@ -8,7 +8,7 @@ configs[3]'s 1024 synthetic frames PER GPU, fed as ONE batch of 1024 frames (con
 library's submit/wait pipeline (up to 4 batches = 4 steps in flight).  The batch is 472 MB of input per GPU --
 more than the 256 MB Infinity Cache -- so K1 reads HBM, not cache.  (Rounds 3 and 4 until the common pre-pass: 2 batches of
 512; since K6's share fell, larger batches pay: 855 k frames/s at 2 x 512, 925 k at 1 x 1024.)  Inputs are resident in HBM when the timed region
-starts (the bench contract: `value` is never a PCIe-inclusive rate); the same pipeline with every batch starting in
+starts (the bench contract: `value` is never a PCIe-inclusive rate); with `--full`, the same pipeline with every batch starting in
 pinned HOST memory is timed right after, on every rank, and reported at top level as `value_h2d_inclusive` with the
 link's own rate beside it (`link_GBps_achieved`, `link_bound_frames_per_s`, `link_frac`) -- SURVEY.md 8(d)'s metric as
 written counts that copy, and at one GPU config 2 is PCIe-bound by it.  Per-frame result records come back to the host
@@ -21,22 +21,30 @@ Launch: `python bench.py` (N=1) or
 Warm-up: W steps, then blocks of 5 steps until the median step time of a block is within 2 % of the previous block's and
 0.3 s have passed (clock ramp and pipeline fill are not steady state); exactly K steps are then timed between barriers.
 
+A plain run does only what the headline needs: it generates the inputs, sets up, warms up, times the K steps, writes
+`--dump-outputs` and prints the line, with the accuracy of the last timed step and the roofline figures that the timed
+region's own counters give.  Every other leg -- the in-flight-1 leg behind the timed region, the H2D-inclusive, reference-mode,
+config-5, latency, half-grid, online-caller and noise-floor legs, the CPU baseline -- runs only with `--full` (the `--no-*`
+options then leave parts of it out).
+
 Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
   roofline     -- the dominant kernel (k6_grid_cost: five launches per batch -- seed, refinement, anchor, common pre-pass,
                   full pass -- each bracketed by HIP events on the batch's own stream).  VALU-bound (points live in LDS,
                   no MFMA): `bound: "valu"`, achieved = (executed point-candidate evaluations x VALU instructions each)
                   / k6_ms_alone, the launches' summed duration with ONE batch in flight (a short leg right after the timed
-                  region: the only exclusive durations; a rocprofv3 trace of `--in-flight 1` adds up to the same).  The
-                  timed region's own event spans (four batches sharing the chip) are `k6_ms_pipelined` / `frac_pipelined`;
+                  region, `--full`: the only exclusive durations; a rocprofv3 trace of `--in-flight 1` adds up to the same;
+                  without that leg, `frac` is priced on the timed region's event spans, the *_alone figures are null and
+                  `alone_leg` is false).  The timed region's own event spans (four batches sharing the chip) are
+                  `k6_ms_pipelined` / `frac_pipelined`;
                   `frac_rocprof_*` price the same work on the committed rocprofv3 kernel stats.  All scalars: the
                   algorithmic HBM figure BASELINE.json asks for (`hbm_frac`: 16 N + 12 corners + 64 bytes per frame over
                   the whole step; `k1_hbm_frac`: K1's count pass alone), SURVEY.md 8(d)'s H2D-inclusive rate and the
                   link's (`h2d_inclusive_frames_per_s`, `link_frac`).
-  cpu_baseline -- the CPU oracle's reference-faithful path (crop, cluster, RANSAC, PCA, histogram, two-pass
+  cpu_baseline -- (--full) the CPU oracle's reference-faithful path (crop, cluster, RANSAC, PCA, histogram, two-pass
                   Ceres-style local solve for both colour phases), one host thread, median of 5 runs on a bounded
                   sample of the same frames.  A port (the reference cannot be built here: PCL/Eigen/Ceres/ROS
                   absent) and only a reported baseline.
-  grid_vs_reference_path_mm -- how far the headline mode's corners (ILCC_SOLVER_GRID) are from the
+  grid_vs_reference_path_mm -- (--full) how far the headline mode's corners (ILCC_SOLVER_GRID) are from the
                   reference-trajectory mode's (ILCC_SOLVER_REFERENCE_LOCAL, which matches the CPU port to < 1e-6 m)
                   on the same frames, and that mode's own pipelined frames/s.
 `--config 5` runs BASELINE config 5 instead (64-ring 131 072-point clouds, 11x8 board @0.10 m, 129^3 x 2 grid).
@@ -222,17 +230,23 @@ def main():
     ap.add_argument("--distinct-batches", type=int, default=0,
                     help="distinct batches resident per GPU that the steps rotate through (default 4: step s submits batch s mod 4, "
                          "no step repeats its predecessor's data); at least --batches-per-step")
-    ap.add_argument("--no-config5-leg", action="store_true", help="skip the short config-5 leg of the default run (config5_value / config5_frac)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the H2D-inclusive / reference-mode legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: the in-flight-1 leg (roofline.k6_ms_alone / frac), the H2D-inclusive "
+                         "and reference-mode legs, and at N=1 the config-5, latency, half-grid, online-caller and noise-floor legs and "
+                         "the CPU baseline; the --no-* options leave parts of it out.  A plain run times the headline only")
+    ap.add_argument("--no-config5-leg", action="store_true", help="--full: skip the short config-5 leg (config5_value / config5_frac)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (--full, rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="--full: skip every leg but the in-flight-1 one (the H2D-inclusive, reference-mode, config-5, latency, half-grid, "
+                         "online-caller and noise-floor legs and the CPU baseline)")
     ap.add_argument("--in-flight", type=int, default=4, help="batches in flight per GPU (1 = fully synchronous)")
     ap.add_argument("--no-alone-leg", action="store_true",
-                    help="skip the in-flight-1 leg behind the timed region (profiling runs: a kernel trace then holds the pipelined "
-                         "launches only); roofline.frac is then priced on the timed region's own event spans")
+                    help="--full: skip the in-flight-1 leg behind the timed region (a kernel trace then holds the pipelined launches "
+                         "only); roofline.frac is then priced on the timed region's own event spans, as in a plain run")
     ap.add_argument("--ref-n1", type=float, default=0.0,
                     help="frames/s of the N=1 run: rank 0 then prints weak_scaling_efficiency = value / (N x ref)")
-    ap.add_argument("--no-noise-floor", action="store_true", help="skip the sensor-noise sweep (noise_floor_mm)")
+    ap.add_argument("--no-noise-floor", action="store_true", help="--full: skip the sensor-noise sweep (noise_floor_mm)")
     ap.add_argument("--solver", choices=("grid", "reference"), default="grid",
                     help="reference: the TIMED region runs ILCC_SOLVER_REFERENCE_LOCAL (K7a instead of K6 + K7r) -- profiling runs of "
                          "that mode (tools/gpu_profile_reference.sh); the headline and the driver's run are `grid`")
@@ -243,6 +257,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:     # a plain run: inputs, set-up, warm-up, the timed steps, --dump-outputs, the line -- no leg of its own
+        args.no_alone_leg = args.no_extra_legs = True
     ensure_world(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -279,7 +295,7 @@ def main():
     workers = int(os.environ.get("ILCC_BENCH_GEN_WORKERS", "0")) or max(2 if cores >= 2 * local_world else 1, min(16, cores // local_world))
     clouds, clicks, gts = generate(args.config, NB * F, 0xC0FFEE + rank * NB * F, workers)
     t_gen = time.perf_counter() - t_gen
-    # the short config-5 leg of the default run (BASELINE's roofline run made driver-visible: roofline.config5_value / config5_frac)
+    # the short config-5 leg of the --full run (BASELINE's roofline run made driver-visible: roofline.config5_value / config5_frac)
     c5_inputs = None
     if world == 1 and args.config == 2 and not (args.no_extra_legs or args.no_config5_leg):
         c5_inputs = generate(5, 256, 0xC0FFEE, workers)
@@ -519,11 +535,14 @@ def main():
         fps = total_frames / elapsed
         launches = max(1, tm.grid_cost_launches)
         la = max(1, tm_alone.grid_cost_launches)
+        # exclusive durations exist only when the in-flight-1 leg ran (--full) or the timed region itself had one batch in flight;
+        # otherwise the *_alone figures are null and `frac` is priced on the timed region's event spans
+        alone = tm_alone is not tm or depth == 1
         # The K6 stage of one batch, launch by launch (HIP events on the batch's own stream: seed, refinement, anchor, common
         # pre-pass, full pass).  k6_ms_alone: one batch in flight, nothing else on the chip -- exclusive durations, what a
         # rocprofv3 kernel trace of `--in-flight 1` adds up to.  k6_ms_pipelined: the same event spans inside the timed region,
         # where up to four batches share the chip (a span then also holds what a launch waited for a CU).
-        k6_ms_alone = tm_alone.grid_cost_kernel_ms_sum / la
+        k6_ms_alone = tm_alone.grid_cost_kernel_ms_sum / la if alone else None
         k6_ms = tm.grid_cost_kernel_ms_sum / launches
         k6_span_ms = tm.grid_cost_ms_sum / launches
         k6_bytes = bytes_per_frame * F
@@ -534,16 +553,16 @@ def main():
             / max(1.0, evals_per_launch)
         box_evals = tm.grid_cost_box_evals_sum / launches               # (point, tile) evaluations of the box pre-passes
         credited_lane_instr = evals_per_launch * valu_ops_per_eval + box_evals * K6_VALU_OPS_BOX
-        valu_rate = credited_lane_instr / (max(k6_ms_alone, 1e-9) * 1e-3) / 1e12
+        valu_rate = credited_lane_instr / (max(k6_ms_alone if alone else k6_ms, 1e-9) * 1e-3) / 1e12
         valu_rate_pipe = credited_lane_instr / (max(k6_ms, 1e-9) * 1e-3) / 1e12
         pmc = k6_pmc(args.config, F)
         credited_wave_instr = credited_lane_instr / 64.0
         rocprof = k6_rocprof(args.config, credited_lane_instr)
         mix = k6_mix_ceiling(evals_per_launch - evals_interior, evals_interior, box_evals)
         # K1's count pass: the path's HBM-bound kernel (reads every input point exactly once)
-        k1_ms_alone = tm_alone.roi_count_ms_sum / max(1, tm_alone.batches)
-        k1_GBps = 16.0 * n_points * F / (k1_ms_alone * 1e-3) / 1e9 if k1_ms_alone > 0 else None
-        step_ms_alone = tm_alone.stage_ms_sum[6] / max(1, tm_alone.batches)
+        k1_ms_alone = tm_alone.roi_count_ms_sum / max(1, tm_alone.batches) if alone else None
+        k1_GBps = 16.0 * n_points * F / (k1_ms_alone * 1e-3) / 1e9 if k1_ms_alone else None
+        step_ms_alone = tm_alone.stage_ms_sum[6] / max(1, tm_alone.batches) if alone else None
         low = [bool(res[f].flags & N.FLAG_LOW_COVERAGE) for f in range(FS)]
         acc = [f for f in ok if not low[f]]
         err_acc = np.array([synth.corner_error(res[f].corners_array(), gts[f], board) for f in acc])
@@ -622,8 +641,9 @@ def main():
                 "unit": "T lane-instr/s",
                 "frac": valu_rate / VALU_ISSUE_PEAK_T,
                 "frac_what": "credited lane-instr of one batch's K6 launches / k6_ms_alone (HIP events, ONE batch in flight) / peak"
-                             if tm_alone is not tm or depth == 1 else
-                             "credited lane-instr of one batch's K6 launches / the timed region's event spans (--no-alone-leg) / peak",
+                             if alone else
+                             "credited lane-instr of one batch's K6 launches / the timed region's event spans (no in-flight-1 leg: "
+                             "--full without --no-alone-leg runs it) / peak",
                 "k6_ms_alone": k6_ms_alone,
                 "frac_rocprof_alone": rocprof["in_flight_1"]["frac_this_run"] if rocprof and "in_flight_1" in rocprof else None,
                 "frac_whole_step": credited_lane_instr * B / (elapsed / args.steps) / 1e12 / VALU_ISSUE_PEAK_T,
@@ -646,14 +666,14 @@ def main():
                 "config5_frames_per_s": None,
                 "config5_frac": None,
                 # ---- everything below is beyond the 24 scalars the driver keeps
-                "alone_leg": tm_alone is not tm or depth == 1,
+                "alone_leg": alone,
                 "mix_ceiling_at_measured_rates": mix[1] if mix else None,
                 "frac_of_mix_ceiling_at_measured_rates": valu_rate / mix[1] if mix else None,
                 "mix_ceiling_file": mix[2] if mix else None,
                 "k6_ms_pipelined": k6_ms,
-                "k6_locate_ms_alone": tm_alone.grid_cost_locate_ms_sum / la,
-                "k6_prepass_ms_alone": tm_alone.grid_cost_prepass_ms_sum / la,
-                "k6_full_pass_ms_alone": tm_alone.grid_cost_full_ms_sum / la,
+                "k6_locate_ms_alone": tm_alone.grid_cost_locate_ms_sum / la if alone else None,
+                "k6_prepass_ms_alone": tm_alone.grid_cost_prepass_ms_sum / la if alone else None,
+                "k6_full_pass_ms_alone": tm_alone.grid_cost_full_ms_sum / la if alone else None,
                 "k6_locate_ms_pipelined": tm.grid_cost_locate_ms_sum / launches,
                 "k6_prepass_ms_pipelined": tm.grid_cost_prepass_ms_sum / launches,
                 "k6_full_pass_ms_pipelined": tm.grid_cost_full_ms_sum / launches,
@@ -677,7 +697,7 @@ def main():
                 "box_evals_per_batch": box_evals,
                 "valu_instr_per_box_eval": K6_VALU_OPS_BOX,
                 "batches_timed": int(tm.grid_cost_launches),
-                "batches_timed_alone": int(tm_alone.grid_cost_launches),
+                "batches_timed_alone": int(tm_alone.grid_cost_launches) if alone else None,
                 "stage_span_ms": k6_span_ms,
                 "walk_order_k5w_ms": tm.walk_order_ms_sum / launches,
                 "step_ms_alone": step_ms_alone,
@@ -851,9 +871,9 @@ def k6_credit(tm):
 
 def config5_leg(N, synth, inputs, device, steps=10):
     """BASELINE's roofline run (configs[4]: 64-ring 131 072-point clouds, 11 x 8 board @0.10 m, 129^3 x 2 grid) as a SHORT leg of the
-    default run, so that the driver's record carries it (roofline.config5_frames_per_s / config5_frac): two distinct 128-frame batches
+    --full run, so that its line carries it (roofline.config5_frames_per_s / config5_frac): two distinct 128-frame batches
     resident, four in flight, `steps` steps timed after a warm-up; then one batch at a time for the K6 launches' exclusive durations.
-    `python bench.py --config 5` is the full version (H2D-inclusive leg, reference mode, rocprof cross-checks)."""
+    `python bench.py --config 5 --full` is the full version (H2D-inclusive leg, reference mode, rocprof cross-checks)."""
     import torch
     from lidar_camera_calibration_amd import LidarCornersBatch
     clouds, clicks, gts = inputs

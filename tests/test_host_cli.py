@@ -245,15 +245,36 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     assert (rec[:, 0] == N.OK).sum() >= 48 and out["frames_ok"] == "%d/64" % (rec[:, 0] == N.OK).sum()
 
 
+FULL_ONLY_KEYS = ("pcie_inclusive", "grid_vs_reference_path_mm", "reference_local_mode", "single_frame_latency_ms",
+                  "half_resolution_grid_variant", "online_caller", "noise_floor_mm", "config5", "cpu_baseline")
+
+
+def test_bench_plain_run_times_the_headline_only_and_full_runs_the_legs(tmp_path):
+    """A plain run sets up, warms up, times its steps, dumps and prints the line: no leg of its own (no in-flight-1 leg, no
+    H2D-inclusive, reference-mode, latency, half-grid, online-caller, noise-floor, config-5 or CPU leg).  --full runs them,
+    the --no-* options leaving parts out; the timed path and what it dumps are the same either way."""
+    args = ["--steps", "2", "--warmup", "1", "--frames-per-batch", "64"]
+    plain = _bench({}, args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert not any(k in plain for k in FULL_ONLY_KEYS), sorted(plain)
+    assert plain["value_h2d_inclusive"] is None and plain["roofline"]["alone_leg"] is False and plain["roofline"]["k6_ms_alone"] is None
+    full = _bench({}, args + ["--full", "--no-config5-leg", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert full["value_h2d_inclusive"] > 0 and full["roofline"]["alone_leg"] is True and full["roofline"]["k6_ms_alone"] > 0
+    assert full["roofline"]["reference_mode_frames_per_s"] > 0
+    assert all(k in full for k in FULL_ONLY_KEYS if k not in ("config5", "cpu_baseline")), sorted(full)
+    assert "config5" not in full and "cpu_baseline" not in full
+    assert np.array_equal(np.load(tmp_path / "plain" / "records.npy"), np.load(tmp_path / "full" / "records.npy"))
+
+
 def test_bench_two_ranks_on_one_device_over_gloo():
     """Two ranks (both on device 0, records gathered over gloo): shard seeds, per-rank tags and the gathered block's
-    verification on rank 0 with world_size 2."""
+    verification on rank 0 with world_size 2; with --full, the H2D-inclusive leg's barriers and reductions across ranks."""
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", "29613"]
     out = _bench({"ILCC_BENCH_BACKEND": "gloo", "ILCC_BENCH_SINGLE_DEVICE": "1", "ILCC_BENCH_MAX_DEPTH": "2"},
-                 ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batches-per-step", "2", "--frames-per-batch", "64"],
+                 ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batches-per-step", "2", "--frames-per-batch", "64", "--full"],
                  launcher=launcher)
-    assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 500
+    assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 500 and out["value_h2d_inclusive"] > 0
 
 
 def test_bench_plain_invocation_with_gpus_2_launches_two_ranks():
