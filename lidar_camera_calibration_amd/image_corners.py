@@ -73,12 +73,16 @@ def _check(st):
 
 
 def _device_image(image):
-    """(device tensor, width, height, stride): a contiguous 2-D uint8 tensor on the current HIP device."""
+    """(device tensor, width, height, stride): a 2-D uint8 tensor on the current HIP device.  A tensor
+    already there whose rows are contiguous (stride(1) == 1, stride(0) >= width), such as a crop view of a
+    larger frame, is passed as it is, with stride(0) as the row pitch; anything else is copied."""
     import torch
     t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
     if t.dtype != torch.uint8 or t.dim() != 2:
         raise ValueError("expected a 2-D uint8 grayscale image, got %s %s" % (tuple(t.shape), t.dtype))
-    t = t.to("cuda").contiguous()
+    on_device = t.is_cuda and t.device.index == torch.cuda.current_device()
+    if not (on_device and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+        t = t.to("cuda").contiguous()
     return t, int(t.shape[1]), int(t.shape[0]), int(t.stride(0))
 
 

@@ -3,6 +3,7 @@
 in tests/golden/pointgrey<i>_crop.npz, and the six corner files its detector wrote from them), the end
 to end calibration from detected files, synthetic boards, and the host structure recovery."""
 import ctypes as C
+import functools
 import math
 import os
 import re
@@ -251,7 +252,377 @@ def _excused(L, c, tol=1e-5):
     return int((np.abs(win - val) < tol).sum()) > 1
 
 
+# ------------------------------------------------------------------------------------------ restatement stages
+
+def _refine_and_score(img, grad, cand):
+    """refineCorners + scoreCorners of the restatement on the given 1-based candidates: P (1-based), V1,
+    V2 and the best score of every candidate with edges (0 for the others), as the stage records hold."""
+    du, dv, ang, wt = grad
+    P, V1, V2 = R.refine(du, dv, ang, wt, cand)
+    valid = ~((V1[:, 0] == 0) & (V1[:, 1] == 0))
+    S = np.zeros(len(P))
+    if valid.any():
+        S[valid] = R.score(R.normalised(img), wt, P[valid], V1[valid], V2[valid])
+    return P, V1, V2, S
+
+
+def _final_list(P, V1, V2, S):
+    """findCorners.m:97-125 on per-candidate records: (indices of the kept candidates, CORNER_DTYPE list)."""
+    k = np.flatnonzero(~((V1[:, 0] == 0) & (V1[:, 1] == 0)) & ~(S < R.SCORE_TAU))
+    v1, v2 = V1[k].copy(), V2[k].copy()
+    neg = v1[:, 0] + v1[:, 1] < 0
+    v1[neg] = -v1[neg]
+    flip = -np.sign(v1[:, 1] * v2[:, 0] - v1[:, 0] * v2[:, 1])
+    out = np.zeros(len(k), IC.CORNER_DTYPE)
+    out["u"], out["v"] = P[k, 0] - 1, P[k, 1] - 1
+    out["v1"], out["v2"], out["score"] = v1, v2 * flip[:, None], S[k]
+    return k, out
+
+
+def _restate(img):
+    """Every stage of the restatement, each run once: L, candidates, the records of every candidate, the
+    final list (what R.find_corners returns, test_restated_final_list_is_find_corners)."""
+    grad = R.angle_weight(*R.gradients(img))
+    L = R.likelihood(img)
+    cand, _ = R.nms(L)
+    rec = _refine_and_score(img, grad, cand)
+    kept, final = _final_list(*rec)
+    return dict(L=L, cand=cand, grad=grad, records=rec, kept=kept, final=final)
+
+
+# ------------------------------------------------------------------------------------------ edge fixtures
+# Images chosen for where image kernels go wrong: odd sizes, pitched rows, borders, low contrast, ties and
+# many candidates.  Each is built, and run through the restatement, once per session; the CPU guards
+# check that each still exercises its edge, the GPU tests compare K10 with the restatement on it.
+
+SHAPES = [(34, 34), (35, 41), (36, 97), (37, 301), (49, 63), (63, 48), (301, 36), (129, 113)]   # (w, h)
+SQUARE_SEEDS = {(34, 34): 280, (49, 63): 236}    # else 200 + index: seeds that give candidates and no near-ties
+
+
+def _noise(w, h, seed):
+    return np.random.default_rng(seed).integers(0, 256, (h, w), dtype=np.uint8)
+
+
+def _squares(w, h, seed, lo=40, hi=200):
+    """6-8 px squares of random grey on a mid-grey base, light noise, held in [lo, hi]."""
+    rng = np.random.default_rng(seed)
+    img = np.full((h, w), 128.0)
+    for _ in range(w * h // 40):
+        s, x, y = int(rng.integers(6, 9)), int(rng.integers(0, w)), int(rng.integers(0, h))
+        img[y:y + s, x:x + s] = rng.integers(lo, hi + 1)
+    return np.clip(np.rint(img + rng.normal(0, 3.0, img.shape)), lo, hi).astype(np.uint8)
+
+
+def _pitched_large():
+    """640 x 480 (> 1024 x 256 px: k10_minmax strides over it) in [40, 200]; its only 40 and only 200
+    sit in the last column, in the first and the last row."""
+    img, _ = render_board((640, 480), square=48.0, theta=0.25, seed=21)
+    img = np.clip(np.rint(41 + img * (158 / 255.0)), 41, 199).astype(np.uint8)
+    img[0, -1], img[-1, -1] = 40, 200
+    return img
+
+
+def _board_in(lo, hi, size=(160, 128), seed=5, noise=2.0):
+    """A board rescaled into [lo, hi]; without render_board's planted 0 / 255."""
+    img, _ = render_board(size, theta=0.3, square=24.0, seed=seed, noise=noise)
+    img[0, 0], img[-1, -1] = img[0, 1], img[-1, -2]
+    return np.clip(np.rint(lo + (img.astype(np.float64) - 30) * ((hi - lo) / 190.0)), lo, hi).astype(np.uint8)
+
+
+def _contrast_60_190():
+    """[60, 190]: its only 60 and only 190 inside two squares, away from the image's and the board's corners."""
+    img = np.clip(_board_in(60, 190), 61, 189)
+    img[64, 20], img[20, 140] = 60, 190
+    return img
+
+
+def _tie_heavy_two_level():
+    """Two levels (30 / 220), 16 px squares on whole pixels, no blur or noise: every corner sits between
+    four pixels of equal likelihood, so NMS ties everywhere (the one fixture allowed to be tie-heavy)."""
+    yy, xx = np.mgrid[0:128, 0:160]
+    return np.where(((xx - 16) // 16 + (yy - 16) // 16) % 2 == 0, 30, 220).astype(np.uint8)
+
+
+EDGE_FIXTURES = {}
+for _k, (_w, _h) in enumerate(SHAPES):
+    EDGE_FIXTURES["noise_%dx%d" % (_w, _h)] = lambda w=_w, h=_h, k=_k: _noise(w, h, 100 + k)
+    EDGE_FIXTURES["squares_%dx%d" % (_w, _h)] = lambda w=_w, h=_h, k=_k: _squares(w, h, SQUARE_SEEDS.get((w, h), 200 + k))
+EDGE_FIXTURES.update({
+    "pitched_97x61": lambda: _squares(97, 61, 31),
+    "pitched_640x480": _pitched_large,
+    # inner corners at 0-based (8 + 20 i, 8 + 20 j): 1-based 9 on the left / top, w - 4 and h - 4 on the
+    # right / bottom; the board runs off all four sides
+    "border_193x153": lambda: render_board((193, 153), board=(10, 8), square=20.0, centre=(98, 78), seed=4)[0],
+    "border_rotated_150x130": lambda: render_board((150, 130), board=(9, 7), square=22.0, theta=0.45, centre=(70, 70),
+                                                   seed=12)[0],
+    "contrast_60_190": _contrast_60_190,
+    "contrast_range_1": lambda: _board_in(127, 128, seed=6, noise=0.0),
+    "contrast_range_3": lambda: _board_in(127, 130, seed=6, noise=0.0),
+    "tie_heavy_two_level": _tie_heavy_two_level,
+    "noise_240x200": lambda: _noise(240, 200, 1),
+    "dense_640x480": lambda: render_board((640, 480), board=(40, 30), square=8.0, theta=0.1, seed=9)[0],
+})
+SHAPE_FIXTURES = [n for n in EDGE_FIXTURES if n.startswith(("noise_", "squares_")) and n != "noise_240x200"]
+PITCHED_FIXTURES = ["pitched_97x61", "pitched_640x480"]
+BORDER_FIXTURES = ["border_193x153", "border_rotated_150x130"]
+CONTRAST_FIXTURES = ["contrast_60_190", "contrast_range_1", "contrast_range_3"]
+TIE_HEAVY = "tie_heavy_two_level"
+
+
+@functools.lru_cache(maxsize=None)
+def fixture(name):
+    return EDGE_FIXTURES[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name):
+    return _restate(fixture(name))
+
+
+def _nms_bound_decides(L):
+    """Scan blocks of nonMaximumSuppression.m that only the last column of the neighbourhood check
+    (1-based w - margin) rejects: they would pass with the bound one column short."""
+    h, w = L.shape
+    n, m = R.NMS_N, R.NMS_MARGIN
+    hits = 0
+    for i in range(n + 1 + m, w - n - m + 1, n + 1):
+        for j in range(n + 1 + m, h - n - m + 1, n + 1):
+            blk = L[j - 1:j + n, i - 1:i + n]
+            di, dj = divmod(int(np.argmax(blk.T)), n + 1)      # first maximum in scan order (u outer)
+            maxi, maxj, maxval = i + di, j + dj, blk[dj, di]
+            if maxval < R.NMS_TAU:
+                continue
+
+            def fails(ie):
+                jj = np.arange(maxj - n, min(maxj + n, h - m) + 1)[:, None]
+                ii = np.arange(maxi - n, ie + 1)[None, :]
+                out = (ii < i) | (ii > i + n) | (jj < j) | (jj > j + n)
+                return bool(((L[jj - 1, ii - 1] > maxval) & out).any())
+            hits += fails(min(maxi + n, w - m)) and not fails(min(maxi + n, w - m - 1))
+    return hits
+
+
+def _radius_scores(img, grad, p, v1, v2):
+    """scoreCorners.m per radius at 1-based p: {r: score}, None where the window leaves the image."""
+    h, w = img.shape
+    u, v = R.mround(p[0]), R.mround(p[1])
+    out = {}
+    for r in R.RADII:
+        out[r] = None
+        if u > r and u <= w - r and v > r and v <= h - r:
+            sl = (slice(v - r - 1, v + r), slice(u - r - 1, u + r))
+            out[r] = R.correlation_score(R.normalised(img)[sl], grad[3][sl], v1, v2)
+    return out
+
+
+def _border_reach(img, grad, cand, records, kept):
+    """What a border image reaches: candidates with a clipped refinement window per side, kept corners
+    scored at radius 4 with radius 12 skipped, and the radii r that give a kept corner its best score with
+    its rounded u == w - r (v == h - r): the last column (row) scoreCorners.m scores."""
+    h, w = img.shape
+    r = R.REFINE_R
+    cand = np.array(cand).reshape(-1, 2)
+    clipped = dict(left=int((cand[:, 0] - r < 1).sum()), right=int((cand[:, 0] + r > w).sum()),
+                   top=int((cand[:, 1] - r < 1).sum()), bottom=int((cand[:, 1] + r > h).sum()))
+    P, V1, V2, S = records
+    r12_skipped, last_u, last_v = 0, [], []
+    for k in kept:
+        rs = _radius_scores(img, grad, P[k], V1[k], V2[k])
+        top = max(s for s in rs.values() if s is not None)
+        assert abs(top - S[k]) < 1e-9 + 1e-7 * abs(top)
+        r12_skipped += rs[12] is None and rs[4] is not None
+        best = [rr for rr, s in rs.items() if s is not None and s == top and s > 0]
+        u, v = R.mround(P[k, 0]), R.mround(P[k, 1])
+        last_u += [rr for rr in best if u == w - rr]
+        last_v += [rr for rr in best if v == h - rr]
+    return clipped, r12_skipped, last_u, last_v
+
+
+def _assert_border_reach(reach):
+    """Summed over the border fixtures: each side clips refinement windows, radius 12 is skipped where radius 4
+    scores, and a corner's best radius r sits at u == w - r and one at v == h - r."""
+    clipped, r12, last_u, last_v = {}, 0, [], []
+    for c, s, lu, lv in reach:
+        clipped = {k: clipped.get(k, 0) + x for k, x in c.items()}
+        r12, last_u, last_v = r12 + s, last_u + lu, last_v + lv
+    assert min(clipped.values()) >= 1, clipped
+    assert r12 >= 1
+    assert last_u and last_v, (last_u, last_v)
+    return clipped, r12, last_u, last_v
+
+
+def _ties(name):
+    ref = restated(name)
+    return sum(_excused(ref["L"], c) for c in ref["cand"])
+
+
+# ------------------------------------------------------------------------------------------ CPU guards
+
+def test_restated_final_list_is_find_corners():
+    for name in ("border_193x153", "squares_37x301"):
+        want, got = R.find_corners(fixture(name)), restated(name)["final"]
+        assert len(got) == len(want["p"]) > 0
+        assert np.array_equal(np.stack([got["u"], got["v"]], 1), want["p"])
+        for f in ("v1", "v2", "score"):
+            assert np.array_equal(got[f], want[f]), f
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_FIXTURES))
+def test_edge_fixture_has_candidates_without_ties(name):
+    img, ref = fixture(name), restated(name)
+    assert img.dtype == np.uint8 and min(img.shape) >= IC.MIN_SIDE
+    n = len(ref["cand"])
+    assert n >= 5, n
+    if name == TIE_HEAVY:
+        assert _ties(name) >= 0.9 * n             # built to tie
+    else:
+        assert _ties(name) <= 0.02 * n, _ties(name)
+
+
+def test_shape_matrix_covers_the_residues():
+    ws = {int(n.split("_")[1].split("x")[0]) for n in SHAPE_FIXTURES}
+    hs = {int(n.split("x")[1]) for n in SHAPE_FIXTURES}
+    for s in (ws, hs):
+        assert 34 in s                                       # the smallest side K10 takes
+        assert {1, 15} <= {x % 16 for x in s}                # the 16 x 16 likelihood tile: one past, one short
+        assert {(x - 17) % 4 for x in s} == {0, 1, 2, 3}     # where the last NMS scan block ends
+    assert any(w <= 40 and h >= 290 for w, h in SHAPES) and any(h <= 40 and w >= 290 for w, h in SHAPES)
+    for name in SHAPE_FIXTURES:
+        assert len(restated(name)["cand"]) >= 2, name
+    # the right-hand bound of the NMS neighbourhood check decides some block on a width with (w - 17) % 4 != 0
+    decided = {n: _nms_bound_decides(restated(n)["L"]) for n in SHAPE_FIXTURES + ["noise_240x200"]
+               if (fixture(n).shape[1] - 17) % 4}
+    assert sum(decided.values()) >= 1, decided
+
+
+def test_pitched_fixtures():
+    for name in PITCHED_FIXTURES:
+        img = fixture(name)
+        assert 40 <= img.min() and img.max() <= 200, name
+        assert len(restated(name)["cand"]) >= 20
+    big = fixture("pitched_640x480")
+    assert big.size > 1024 * 256
+    assert (big == 40).sum() == 1 and (big == 200).sum() == 1
+    assert big[0, -1] == 40 and big[-1, -1] == 200
+    assert len(restated("pitched_640x480")["final"]) >= 20
+
+
+def test_border_fixtures_reach_the_edges():
+    reach = []
+    for name in BORDER_FIXTURES:
+        ref = restated(name)
+        reach.append(_border_reach(fixture(name), ref["grad"], ref["cand"], ref["records"], ref["kept"]))
+    _assert_border_reach(reach)
+
+
+def test_contrast_fixtures():
+    img = fixture("contrast_60_190")
+    assert img.min() == 60 and img.max() == 190 and (img == 60).sum() == 1 and (img == 190).sum() == 1
+    final = restated("contrast_60_190")["final"]
+    assert len(final) >= 20
+    for y, x in zip(*np.nonzero((img == 60) | (img == 190))):
+        assert 10 <= x < img.shape[1] - 10 and 10 <= y < img.shape[0] - 10
+        assert np.hypot(final["u"] - x, final["v"] - y).min() > 8       # away from every corner
+    for name, rng in (("contrast_range_1", 1), ("contrast_range_3", 3)):
+        img = fixture(name)
+        assert int(img.max()) - int(img.min()) == rng and img.min() > 0
+        assert len(restated(name)["cand"]) >= 20
+    assert len(restated("contrast_range_3")["final"]) == 0     # gradients under refineCorners' 0.1 gate
+
+
+def test_many_candidates_fixtures():
+    assert len(restated("noise_240x200")["cand"]) >= 800
+    assert len(restated("dense_640x480")["cand"]) >= 1200
+    assert len(restated("dense_640x480")["final"]) >= 1100
+    assert len(restated(TIE_HEAVY)["final"]) >= 200
+
+
 # ------------------------------------------------------------------------------------------ GPU
+
+def _records(refined):
+    """GPU stage records as the restatement's (P 1-based, V1, V2, S)."""
+    return (np.stack([refined["u"], refined["v"]], 1), refined["v1"], refined["v2"], refined["score"])
+
+
+def _assert_records_match(g, r, cand, what):
+    """Refined records, candidate by candidate: same validity; for valid ones position within 1e-3 px,
+    directions | |dot| - 1 | < 1e-9, score within 1e-9 + 1e-7 x the largest; zero score without edges."""
+    (Pg, V1g, V2g, Sg), (Pr, V1r, V2r, Sr) = g, r
+    smax = np.abs(Sr).max() if len(Sr) else 0.0
+    for k, c in enumerate(cand):
+        gvalid, rvalid = bool(V1g[k].any()), bool(V1r[k].any())
+        assert gvalid == rvalid, (what, c)
+        if not rvalid:
+            assert Sg[k] == 0, (what, c, Sg[k])
+            continue
+        assert abs(Pg[k, 0] - Pr[k, 0]) < 1e-3 and abs(Pg[k, 1] - Pr[k, 1]) < 1e-3, (what, c, Pg[k], Pr[k])
+        for gv, rv in ((V1g[k], V1r[k]), (V2g[k], V2r[k])):
+            assert abs(abs(float(gv @ rv)) - 1) < 1e-9, (what, c, gv, rv)
+        assert abs(Sg[k] - Sr[k]) < 1e-9 + 1e-7 * smax, (what, c, Sg[k], Sr[k])
+
+
+def _assert_stages_match(img, name, ref=None, image=None, tie_heavy=False):
+    """K10 through the C-ABI against the restatement, stage by stage, on uint8 `img` (passed to the GPU as
+    `image` when given: a pitched device view of it).  Candidates may differ only by near-ties (_excused),
+    at most 2 % of them unless the fixture is built to tie.  Every GPU record is checked against the
+    restatement run on the GPU's own candidates, the final list against those records by the host's rules,
+    and the end to end result against the restatement's own candidates.  Returns (corners, stages)."""
+    ref = ref if ref is not None else _restate(img)
+    corners, st = IC.find_corners(img if image is None else image, stages=True)
+    h, w = img.shape
+    Lg = st["likelihood"].cpu().numpy().astype(np.float64)
+    assert Lg.shape == (h, w)
+    dL = np.abs(Lg - ref["L"]).max()
+    assert dL < 1e-5, (name, dL)
+    gc = [(int(u), int(v)) for u, v in st["candidates"]]
+    rc = list(ref["cand"])
+    assert st["n_candidates"] == len(gc)
+    only_g, only_r = set(gc) - set(rc), set(rc) - set(gc)
+    excused = sorted(c for c in only_g | only_r if _excused(ref["L"], c))
+    assert not (only_g | only_r) - set(excused), (name, sorted((only_g | only_r) - set(excused)))
+    common_g = [c for c in gc if c not in excused]
+    common_r = [c for c in rc if c not in excused]
+    assert common_g == common_r, name
+    stride = image.stride(0) if image is not None else w
+    print("%s: %d x %d, stride %d, %d candidates, excused %d, |dL| %.2e" % (name, w, h, stride, len(gc), len(excused), dL))
+    if not tie_heavy:
+        assert len(excused) <= 0.02 * len(gc), (name, excused)
+    # every GPU record against the restatement's refine + score on the GPU's own candidates
+    g = _records(st["refined"])
+    on_gpu_cand = ref["records"] if gc == rc else _refine_and_score(img, ref["grad"], gc)
+    _assert_records_match(g, on_gpu_cand, gc, name + " (GPU candidates)")
+    # the final list is the GPU records' under findCorners.m:97-125, value for value
+    kept_g, want = _final_list(*g)
+    assert len(corners) == len(want), (name, len(corners), len(want))
+    for f in ("u", "v", "v1", "v2", "score"):
+        assert np.array_equal(corners[f], want[f]), (name, f)
+    # end to end: refinement of every common candidate, then the final list through the candidates
+    ri = {c: k for k, c in enumerate(rc)}
+    gi = {c: k for k, c in enumerate(gc)}
+    sel = lambda rec, idx: tuple(x[idx] for x in rec)
+    _assert_records_match(sel(g, [gi[c] for c in common_r]), sel(ref["records"], [ri[c] for c in common_r]), common_r,
+                          name + " (restatement candidates)")
+    final = ref["final"]
+    fg = {gc[k]: j for j, k in enumerate(kept_g)}
+    fr = {rc[k]: j for j, k in enumerate(ref["kept"])}
+    for c in common_r:
+        assert (c in fg) == (c in fr), (name, c)
+        if c in fr:
+            a, b = corners[fg[c]], final[fr[c]]
+            assert abs(a["u"] - b["u"]) < 1e-3 and abs(a["v"] - b["v"]) < 1e-3, (name, c)
+            assert np.abs(a["v1"] - b["v1"]).max() < 1e-6 and np.abs(a["v2"] - b["v2"]).max() < 1e-6, (name, c)
+            assert abs(a["score"] - b["score"]) < 1e-9 + 1e-7 * np.abs(final["score"]).max(), (name, c)
+    if not excused:
+        # final list: same corners, same order, same directions and scores
+        assert len(corners) == len(final), (len(corners), len(final))
+        p = np.stack([final["u"], final["v"]], 1)
+        dp = np.abs(np.stack([corners["u"], corners["v"]], 1) - p).max() if len(corners) else 0.0
+        assert dp < 1e-3, dp
+        if len(corners):
+            assert np.abs(corners["v1"] - final["v1"]).max() < 1e-6 and np.abs(corners["v2"] - final["v2"]).max() < 1e-6
+            assert np.abs(corners["score"] - final["score"]).max() < 1e-9 + 1e-7 * np.abs(final["score"]).max()
+    return corners, st
+
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("which", ["crop2", "crop6", "synthetic"])
@@ -260,40 +631,150 @@ def test_stage_parity_with_restatement(which):
         img, _ = render_board((320, 256), theta=0.35, square=24.0, persp=(2e-4, -1e-4), seed=7)
     else:
         img, _ = _crop(int(which[-1]))
-    corners, st = IC.find_corners(img, stages=True)
-    ref = R.find_corners(img, stages=True)
-    Lg = st["likelihood"].cpu().numpy().astype(np.float64)
-    dL = np.abs(Lg - ref["L"]).max()
-    assert dL < 1e-5, dL
-    gc = [tuple(x) for x in st["candidates"]]
-    rc = list(ref["cand"])
-    assert st["n_candidates"] == len(gc)
-    only_g, only_r = set(gc) - set(rc), set(rc) - set(gc)
-    excused = sorted(c for c in only_g | only_r if _excused(ref["L"], c))
-    assert not (only_g | only_r) - set(excused), sorted((only_g | only_r) - set(excused))
-    common_g = [c for c in gc if c not in excused]
-    common_r = [c for c in rc if c not in excused]
-    assert common_g == common_r
-    print("%s: %d candidates, |dL| %.2e, excused %s" % (which, len(gc), dL, excused))
-    # refinement of every common candidate
-    Pr, V1r, V2r = ref["refined_all"]
-    ri = {c: k for k, c in enumerate(rc)}
-    gi = {c: k for k, c in enumerate(gc)}
-    for c in common_r:
-        g, r = st["refined"][gi[c]], ri[c]
-        gvalid, rvalid = bool(g["v1"].any()), bool(V1r[r].any())
-        assert gvalid == rvalid, c
-        if not rvalid:
-            continue
-        assert abs(g["u"] - Pr[r, 0]) < 1e-3 and abs(g["v"] - Pr[r, 1]) < 1e-3, (c, g["u"], g["v"], Pr[r])
-        for gv, rv in ((g["v1"], V1r[r]), (g["v2"], V2r[r])):
-            assert abs(abs(float(gv @ rv)) - 1) < 1e-9, (c, gv, rv)
-    # final list: same corners, same order, same directions and scores
-    assert len(corners) == len(ref["p"]), (len(corners), len(ref["p"]))
-    dp = np.abs(np.stack([corners["u"], corners["v"]], 1) - ref["p"]).max() if len(corners) else 0.0
-    assert dp < 1e-3, dp
-    assert np.abs(corners["v1"] - ref["v1"]).max() < 1e-6 and np.abs(corners["v2"] - ref["v2"]).max() < 1e-6
-    assert np.abs(corners["score"] - ref["score"]).max() < 1e-9 + 1e-7 * np.abs(ref["score"]).max()
+    _assert_stages_match(img, which)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SHAPE_FIXTURES)
+def test_stage_parity_shapes(name):
+    _assert_stages_match(fixture(name), name, restated(name))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", CONTRAST_FIXTURES + ["noise_240x200", "dense_640x480"])
+def test_stage_parity_contrast_and_many_candidates(name):
+    corners, _ = _assert_stages_match(fixture(name), name, restated(name))
+    assert len(corners) == len(restated(name)["final"])
+
+
+@pytest.mark.gpu
+def test_stage_parity_tie_heavy_board():
+    """Ties everywhere: the GPU's fp32 map breaks them its own way; every difference must be a tie, and every
+    GPU record still matches the restatement on the GPU's own candidates."""
+    _, st = _assert_stages_match(fixture(TIE_HEAVY), TIE_HEAVY, restated(TIE_HEAVY), tie_heavy=True)
+    assert bool(st["refined"]["v1"].any(axis=1).any())
+
+
+@pytest.mark.gpu
+def test_stage_parity_borders():
+    reach = []
+    for name in BORDER_FIXTURES:
+        img, ref = fixture(name), restated(name)
+        corners, st = _assert_stages_match(img, name, ref)
+        assert len(corners) == len(ref["final"])
+        g = _records(st["refined"])
+        reach.append(_border_reach(img, ref["grad"], st["candidates"], g, _final_list(*g)[0]))
+    clipped, r12, last_u, last_v = _assert_border_reach(reach)     # what the GPU's own corners reached
+    print("borders: clipped windows %s, radius 12 skipped for %d, best radius at w - r %s, at h - r %s"
+          % (clipped, r12, sorted(set(last_u)), sorted(set(last_v))))
+
+
+def _pitched_view(img, stride, offset):
+    """A (h, w) device view of `img`, rows `stride` bytes apart, `offset` bytes into a buffer whose other
+    bytes alternate 0 and 255, outside the image's range."""
+    import torch
+    h, w = img.shape
+    flat = (torch.arange(offset + h * stride, device="cuda") % 2 * 255).to(torch.uint8)
+    view = flat.as_strided((h, w), (stride, 1), offset)
+    view.copy_(torch.from_numpy(np.ascontiguousarray(img)).cuda())
+    return view
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", PITCHED_FIXTURES)
+def test_pitched_rows_equal_contiguous(name):
+    import torch
+    img = fixture(name)
+    h, w = img.shape
+    corners, st = _assert_stages_match(img, name, restated(name))
+    for stride in (w + 1, w + 13, 256 * -(-(w + 3) // 256)):
+        for offset in (0, 1, 3):
+            view = _pitched_view(img, stride, offset)
+            t, tw, th, ts = IC._device_image(view)
+            assert t.data_ptr() == view.data_ptr() and (tw, th, ts) == (w, h, stride)   # passed as it is, no copy
+            c2, st2 = IC.find_corners(view, stages=True)
+            what = (name, stride, offset)
+            assert torch.equal(st2["likelihood"], st["likelihood"]), what
+            assert np.array_equal(st2["candidates"], st["candidates"]), what
+            assert st2["refined"].tobytes() == st["refined"].tobytes(), what
+            assert c2.tobytes() == corners.tobytes(), what
+    print("%s: pitched == contiguous at strides w + 1, w + 13, %d; offsets 0, 1, 3" % (name, 256 * -(-(w + 3) // 256)))
+
+
+def _call(img_t, capacity, corners=True, stages=None):
+    """ilcc_image_corners_device through ctypes: (status, n_corners, output array of capacity + 4 records,
+    pre-filled with 0xA5 bytes)."""
+    out = np.frombuffer(bytes([0xA5]) * (IC.CORNER_DTYPE.itemsize * (capacity + 4)), IC.CORNER_DTYPE).copy()
+    n = C.c_int32(-1)
+    h, w = img_t.shape
+    rc = IC.lib().ilcc_image_corners_device(C.c_void_p(img_t.data_ptr()), w, h, img_t.stride(0),
+                                            out.ctypes.data_as(C.c_void_p) if corners else None, capacity, C.byref(n),
+                                            C.byref(stages) if stages is not None else None, IC._stream_of(img_t))
+    return rc, n.value, out
+
+
+@pytest.mark.gpu
+def test_capacity_contract():
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(fixture("dense_640x480"))).cuda()
+    torch.cuda.synchronize()
+    rc, n_full, full = _call(t, 4096)
+    assert rc == N.OK and n_full >= 1100, (rc, n_full)
+    pad = full[n_full:].tobytes()
+    # corners: capacity below the count writes the first `capacity`, reports the full count
+    for cap in (1, n_full // 2, n_full - 1):
+        rc, n, out = _call(t, cap)
+        assert rc == N.CAPACITY and n == n_full, (cap, rc, n)
+        assert out[:cap].tobytes() == full[:cap].tobytes(), cap
+        assert out[cap:].tobytes() == pad[:4 * IC.CORNER_DTYPE.itemsize], cap    # nothing past capacity
+    rc, n, _ = _call(t, n_full)
+    assert rc == N.OK and n == n_full
+    # capacity 0 and no output: the count alone
+    rc, n, _ = _call(t, 0, corners=False)
+    assert rc == N.CAPACITY and n == n_full
+    none = torch.from_numpy(np.ascontiguousarray(fixture("contrast_range_3"))).cuda()
+    torch.cuda.synchronize()
+    rc, n, _ = _call(none, 0, corners=False)
+    assert rc == N.OK and n == 0
+    # stage outputs: capacity below n_candidates fills the first `capacity`, reports the full count
+    def stage_call(cap):
+        cand = np.full((cap + 4, 2), -7, np.int32)
+        ref = np.frombuffer(bytes([0x5A]) * (IC.CORNER_DTYPE.itemsize * (cap + 4)), IC.CORNER_DTYPE).copy()
+        s = IC.ImageCornerStages()
+        s.candidates = cand.ctypes.data_as(C.POINTER(C.c_int32))
+        s.refined = ref.ctypes.data_as(C.POINTER(IC.ImageCorner))
+        s.capacity = cap
+        rc, n, out = _call(t, 4096, stages=s)
+        return rc, n, out, s.n_candidates, cand, ref
+    rc, n, out, nc, cand_full, ref_full = stage_call(2048)
+    assert rc == N.OK and n == n_full and 1200 <= nc < 2048
+    assert out.tobytes() == full.tobytes()
+    for cap in (1, nc // 3, nc - 1):
+        rc, n, out, nc2, cand, ref = stage_call(cap)
+        assert rc == N.OK and n == n_full and nc2 == nc, (cap, rc, nc2)
+        assert np.array_equal(cand[:cap], cand_full[:cap]) and (cand[cap:] == -7).all(), cap
+        assert ref[:cap].tobytes() == ref_full[:cap].tobytes(), cap
+        assert ref[cap:].tobytes() == bytes([0x5A]) * (4 * IC.CORNER_DTYPE.itemsize), cap
+        assert out.tobytes() == full.tobytes(), cap              # the corners do not depend on it
+
+
+@pytest.mark.gpu
+def test_same_answer_by_every_route():
+    import torch
+    for name in ("dense_640x480", "border_193x153", "noise_35x41"):
+        img = fixture(name)
+        a = IC.find_corners(img)                      # the library's own likelihood buffer
+        b, _ = IC.find_corners(img, stages=True)      # the caller's
+        assert len(a) > 0 or name == "noise_35x41"
+        assert a.tobytes() == b.tobytes(), name
+        # on a side stream, with the image made by a torch op on that stream just before the call
+        src = torch.from_numpy(np.ascontiguousarray(img)).cuda()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            t = (src.to(torch.int16) * 3 - src.to(torch.int16) * 2).to(torch.uint8)
+            c = IC.find_corners(t)
+        assert c.tobytes() == a.tobytes(), name
 
 
 def _detected_file(i, path):
