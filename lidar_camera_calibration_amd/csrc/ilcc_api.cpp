@@ -25,10 +25,29 @@ constexpr int kSlots = ILCC_SLOTS;   // batches in flight per handle (submit/wai
                             // streams, so the hardware queues a handle needs do not grow with the batches in flight
 constexpr int kStreams = 3;   // the handle's streams: batch seq runs whole on S[seq mod 3]
 
+// A batch's timing events, in the order the pipeline records them (= the columns of the debug timeline behind the slot number)
+enum BatchEvent {
+  kEvStart,         // in front of K1
+  kEvCropCounted,   // between K1's count pass and its scatter
+  kEvCropped,       // behind K1
+  kEvClustered,     // behind K2
+  kEvPlane,         // behind K3
+  kEvLabelled,      // behind K4/K5: the grid search starts here
+  kEvWalkOrdered,   // behind K5w
+  kEvSeeded,        // behind the seed launch (or the whole of k6_locate)
+  kEvRefined,       // behind the refinement launch
+  kEvAnchored,      // behind the anchor rounds
+  kEvPrepassed,     // behind the common pre-pass: here the full pass may have to wait for the previous batch's
+  kEvFullStart,     // in front of the full pass
+  kEvSearched,      // behind the full pass (GRID mode; else = kEvLabelled's successor)
+  kEvEnd,           // behind K7
+  kEvCount
+};
+static_assert(kEvCount == ILCC_TIMELINE_COLS - 1, "a timeline row is the slot and one time per event");
+
 // One in-flight batch: its events, stage buffers and pinned result staging.
 struct Slot {
-  hipEvent_t ev[10]{};   // 0..6 stage boundaries; 7, 8: end of K6's seed + refinement passes / start of its full pass; 9: behind K1's count pass
-  hipEvent_t k6ev[4]{};  // inside the K6 stage: after K5w, after the seed launch, after the refinement launch, after the anchor launch (launch-by-launch event spans)
+  hipEvent_t ev[kEvCount]{};   // by BatchEvent (kEvWalkOrdered ... kEvFullStart: GRID batches only)
   hipEvent_t done = nullptr;   // the batch's last command (what a wait synchronises on: never a whole shared stream)
   hipEvent_t late = nullptr;   // behind what a wait enqueues itself (K9 into d_records, the late compact pack, ensure_full's copy)
   hipEvent_t k6_done = nullptr;   // no timing: behind the full pass (the next batch's full pass waits for it)
@@ -94,7 +113,9 @@ struct ilcc_handle {
   float *d_cth = nullptr, *d_sth = nullptr, *d_ay = nullptr, *d_az = nullptr;
   // decimated subset of the same tables: seeding pass of K6's branch and bound
   float *d_cth2 = nullptr, *d_sth2 = nullptr, *d_ay2 = nullptr, *d_az2 = nullptr;
-  int32_t n_th2 = 0, n_ty2 = 0, n_tz2 = 0, seed_stride_th = 12, seed_stride_t = 2;
+  // what the kernels are given of them (upload_tables): the full grid, the seed grid, and where the seed's entries sit in the full one
+  GridTables grid{}, seed_grid{};
+  SeedMap seed_map{2, 12, 6};
   // K7r: cos/sin of the theta lattice (grid step / refine_div, refine_th_margin grid steps beyond the grid on both sides)
   double2* d_th_lattice = nullptr;
   size_t th_lattice_cap = 0;
@@ -221,19 +242,27 @@ int32_t upload_tables(ilcc_handle* h) {
 #ifndef ILCC_REFINE_RADIUS_DIV
 #define ILCC_REFINE_RADIUS_DIV 3   // refinement pass: theta radius = seed stride / 3 (measured in the pipelined bench: /2: 245.3 k, /3: 248.9 k, /4: 245.6 k frames/s)
 #endif
-  h->seed_stride_th = std::max(2, p.n_th / ILCC_SEED_THETAS);
-  h->seed_stride_t = std::max(1, std::min(p.n_ty, p.n_tz) / 8);
+  SeedMap& map = h->seed_map;
+  map.stride_th = std::max(2, p.n_th / ILCC_SEED_THETAS);
+  map.stride_t = std::max(1, std::min(p.n_ty, p.n_tz) / 8);
+  map.off_th = map.stride_th / 2;
   std::vector<float> cth2, sth2, ay2, az2;
-  for (int k = h->seed_stride_th / 2; k < p.n_th; k += h->seed_stride_th) {
+  for (int k = map.off_th; k < p.n_th; k += map.stride_th) {
     cth2.push_back(cth[k]);
     sth2.push_back(sth[k]);
   }
-  for (int a = 0; a < p.n_ty; a += h->seed_stride_t) ay2.push_back(ay[a]);
-  for (int b = 0; b < p.n_tz; b += h->seed_stride_t) az2.push_back(az[b]);
-  h->n_th2 = (int32_t)cth2.size();
-  h->n_ty2 = (int32_t)ay2.size();
-  h->n_tz2 = (int32_t)az2.size();
-  if (h->n_th2 > 0) {
+  for (int a = 0; a < p.n_ty; a += map.stride_t) ay2.push_back(ay[a]);
+  for (int b = 0; b < p.n_tz; b += map.stride_t) az2.push_back(az[b]);
+  // the "nearest to zero" indices: each grid's own (a kernel reads ay[c_ty] / az[c_tz] and uses all three for the tie-break distance)
+  GridTables& full = h->grid;
+  full = GridTables{h->d_cth, h->d_sth, h->d_ay, h->d_az, p.n_th, p.n_ty, p.n_tz, near_zero_index(p.th_min, p.th_step, p.n_th),
+                    near_zero_index(p.ty_min, p.ty_step, p.n_ty), near_zero_index(p.tz_min, p.tz_step, p.n_tz)};
+  GridTables& seed = h->seed_grid;
+  seed = GridTables{h->d_cth2, h->d_sth2, h->d_ay2, h->d_az2, (int32_t)cth2.size(), (int32_t)ay2.size(), (int32_t)az2.size(), 0, 0, 0};
+  seed.c_th = std::min(std::max(full.c_th / map.stride_th, 0), seed.n_th - 1);
+  seed.c_ty = std::min(full.c_ty / map.stride_t, seed.n_ty - 1);
+  seed.c_tz = std::min(full.c_tz / map.stride_t, seed.n_tz - 1);
+  if (seed.n_th > 0) {
     HIP_TRY(h, hipMemcpyAsync(h->d_cth2, cth2.data(), sizeof(float) * cth2.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(h->d_sth2, sth2.data(), sizeof(float) * sth2.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipMemcpyAsync(h->d_ay2, ay2.data(), sizeof(float) * ay2.size(), hipMemcpyHostToDevice, st));
@@ -279,8 +308,6 @@ void free_slot(Slot& sl) {
   if (sl.h_off) (void)hipHostFree(sl.h_off);
   if (sl.h_online) (void)hipHostFree(sl.h_online);
   for (auto& ev : sl.ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : sl.k6ev)
     if (ev) (void)hipEventDestroy(ev);
   if (sl.done) (void)hipEventDestroy(sl.done);
   if (sl.late) (void)hipEventDestroy(sl.late);
@@ -354,7 +381,6 @@ int32_t alloc_slot(ilcc_handle* h, Slot& sl) {
   const uint64_t np = h->max_points;
   const uint32_t mf = h->max_frames;
   for (auto& ev : sl.ev) HIP_TRY(h, hipEventCreate(&ev));
-  for (auto& ev : sl.k6ev) HIP_TRY(h, hipEventCreate(&ev));
   HIP_TRY(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
   HIP_TRY(h, hipEventCreateWithFlags(&sl.late, hipEventDisableTiming));
   HIP_TRY(h, hipEventCreateWithFlags(&sl.k6_done, hipEventDisableTiming));
@@ -463,33 +489,16 @@ Ctx make_ctx(ilcc_handle* h, Slot& sl, const float4* d_xyzi, const float* d_clic
   c.grid_lds_points = h->grid_lds_points;
   c.grid_bound = sl.d_bound;
   c.grid_bound_sub = sl.d_bound_sub;
-  c.walk_limit = 0;
-  c.tie_count = nullptr;   // only the full pass of K6 collects; K7a gets the pointers below
-  c.tie_count_all = sl.d_tie_count;
+  c.tie_count = sl.d_tie_count;
   c.tie_list = sl.d_tie_list;
   c.grid_iters = sl.d_iters;
-  c.seed_partial = nullptr;
-  c.seed_blocks = 0;
-  c.seed_n_ty = c.seed_n_tz = 1;
-  c.seed_stride_t = 1;
-  c.seed_stride_th = 1;
-  c.seed_off_th = 0;
-  c.refine_radius_th = 0;
-  c.refine_step_th = 1;
-  c.refine_window = 0;
-  c.cth = h->d_cth;
-  c.sth = h->d_sth;
-  c.ay = h->d_ay;
-  c.az = h->d_az;
+  c.grid = h->grid;
   c.th_lattice = h->d_th_lattice;
   c.th_lat_lo = h->th_lat_lo;
   c.th_lat_hi = h->th_lat_hi;
   c.refine_hop_y = h->hop_y;
   c.refine_hop_z = h->hop_z;
   c.p = h->p;
-  c.c_th = near_zero_index(h->p.th_min, h->p.th_step, h->p.n_th);
-  c.c_ty = near_zero_index(h->p.ty_min, h->p.ty_step, h->p.n_ty);
-  c.c_tz = near_zero_index(h->p.tz_min, h->p.tz_step, h->p.n_tz);
   return c;
 }
 
@@ -590,73 +599,93 @@ constexpr int kAnchorRadius = 1;   // the anchor scores 2 * 1 + 1 thetas around 
 #endif
 constexpr int kAnchorRounds = ILCC_ANCHOR_ROUNDS;   // k6_anchor rounds, each re-centred on the previous one's argmin (config 5: 62.5 -> 70.6 k frames/s)
 
-// where the full pass (and the common pre-pass) find the records of the launch that published the frame's bound: `blocks` records
-// per frame from a launch over the FULL tables
-void seeded_by_full_table_records(Ctx& full, const ilcc_handle* h, GridPartial* records, uint32_t blocks) {
-  full.seed_partial = records;
-  full.seed_blocks = blocks;
-  full.seed_n_ty = h->p.n_ty;
-  full.seed_n_tz = h->p.n_tz;
-  full.seed_stride_t = 1;
-  full.seed_stride_th = 1;
-  full.seed_off_th = 0;
+// ---- The launches of the grid search, one GridPass each.  whole_grid_pass is the plain evaluation; every other constructor starts
+// from it and names only what its launch differs in.
+
+// every candidate of `t` on every labelled point, one workgroup per theta, following no other launch, against the frame's bound:
+// what ilcc_grid_cost runs
+GridPass whole_grid_pass(const Ctx& c, const GridTables& t, GridPartial* out) {
+  GridPass g{};
+  g.t = t;
+  g.out = out;
+  g.blocks = (uint32_t)t.n_th;
+  g.bound = c.grid_bound;
+  return g;
+}
+
+// `blocks` records per frame from a launch over the FULL tables
+GridSeed full_table_records(const GridPartial* records, uint32_t blocks) { return GridSeed{records, blocks, SeedMap{1, 1, 0}}; }
+
+// seed: the decimated tables on a prefix of the walk.  Sums over a prefix are not costs of complete candidates: a bound word of their own
+GridPass seed_pass(const ilcc_handle* h, const Slot& sl, const Ctx& c) {
+  GridPass g = whole_grid_pass(c, h->seed_grid, sl.d_partial2);
+  g.walk_limit = (uint32_t)ILCC_SEED_POINTS;
+  g.bound = c.grid_bound_sub;
+  return g;
+}
+
+// refinement: every kRefineThetaStride-th theta within refine_radius steps of the seed's argmin, a window of translations that
+// spans the seed's stride around it; the same prefix of the walk and bound word as the seed
+GridPass refine_pass(const ilcc_handle* h, const Slot& sl, const Ctx& c, int32_t refine_radius) {
+  GridPass g = whole_grid_pass(c, h->grid, sl.d_partial3);
+  g.seed = GridSeed{sl.d_partial2, (uint32_t)h->seed_grid.n_th, h->seed_map};
+  g.window_tiles = h->seed_map.stride_t > 2 * kTileA ? 4 : 2;
+  g.radius_th = (refine_radius / kRefineThetaStride) * kRefineThetaStride;
+  g.step_th = kRefineThetaStride;
+  g.blocks = std::min((uint32_t)(2 * (g.radius_th / kRefineThetaStride) + 1), h->max_theta);
+  g.walk_limit = (uint32_t)ILCC_SEED_POINTS;
+  g.bound = c.grid_bound_sub;
+  return g;
+}
+
+// one anchor round (k6_anchor): 2 kAnchorRadius + 1 thetas x one tile around the argmin of `seed`, on ALL points -- complete costs,
+// which publish the frame's real bound
+GridPass anchor_pass(const ilcc_handle* h, const Ctx& c, const GridSeed& seed, GridPartial* out) {
+  GridPass g = whole_grid_pass(c, h->grid, out);
+  g.seed = seed;
+  g.radius_th = kAnchorRadius;
+  g.blocks = 2 * kAnchorRadius + 1;
+  return g;
+}
+
+// full pass: the whole grid behind the bound the launches before it published (seed: their records, its starting tile; none on a
+// grid too small to locate on), collecting the near ties for K7r.  The box pre-passes are set by enqueue_grid_search
+GridPass full_pass(const ilcc_handle* h, const Ctx& c, const GridSeed& seed) {
+  GridPass g = whole_grid_pass(c, h->grid, c.partial);
+  g.seed = seed;
+  g.collect_ties = 1u;
+  return g;
+}
+
+// k6_locate's plan: the handle's two grids, the sample, one record per frame
+LocatePlan locate_plan(const ilcc_handle* h, const Slot& sl, const Ctx& c) {
+  LocatePlan lp{};
+  lp.seed = h->seed_grid;
+  lp.map = h->seed_map;
+  lp.refine_radius = std::max(1, h->seed_map.stride_th / ILCC_REFINE_RADIUS_DIV);
+  lp.sample_min = (uint32_t)ILCC_SEED_POINTS;
+  lp.sample_cap = std::max((uint32_t)ILCC_SEED_POINTS, ((c.grid_lds_points >> 3) + 63u) & ~63u);
+  lp.out = sl.d_partial4;
+  return lp;
 }
 
 // Locating the minimum with three kinds of launches (batches too small for k6_locate's one workgroup per frame): seed over the
-// decimated tables, refinement around its argmin (both on the walk's prefix, with a bound word of their own: their sums are not
-// costs of complete candidates), then kAnchorRounds anchor rounds on every point, which publish the frame's real bound.
-int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, const LocatePlan& lp, Ctx& full) {
-  Ctx seed = c;
-  seed.cth = h->d_cth2;
-  seed.sth = h->d_sth2;
-  seed.ay = h->d_ay2;
-  seed.az = h->d_az2;
-  seed.p.n_th = h->n_th2;
-  seed.p.n_ty = h->n_ty2;
-  seed.p.n_tz = h->n_tz2;
-  seed.grid_blocks = (uint32_t)h->n_th2;
-  seed.partial = sl.d_partial2;
-  // the "nearest to zero" indices of the decimated tables (the kernel reads ay[c_ty] / az[c_tz] for its rim test and
-  // uses all three for the tie-break distance: they must index THIS launch's tables, not the full ones)
-  seed.c_th = lp.c_th2;
-  seed.c_ty = lp.c_ty2;
-  seed.c_tz = lp.c_tz2;
-  seed.walk_limit = (uint32_t)ILCC_SEED_POINTS;
-  seed.grid_bound = sl.d_bound_sub;
-  launch_grid_cost(seed, s, /*use_oob=*/1, nullptr, true);
-  HIP_TRY(h, hipEventRecord(sl.k6ev[1], s));
-  // refinement: every kRefineThetaStride-th theta within a third of a seed stride of the seed's argmin, 8 x 8 translations
-  Ctx refine = c;
-  refine.seed_partial = sl.d_partial2;
-  refine.seed_blocks = (uint32_t)h->n_th2;
-  refine.seed_n_ty = h->n_ty2;
-  refine.seed_n_tz = h->n_tz2;
-  refine.seed_stride_t = h->seed_stride_t;
-  refine.seed_stride_th = h->seed_stride_th;
-  refine.seed_off_th = h->seed_stride_th / 2;
-  refine.refine_window = h->seed_stride_t > 2 * kTileA ? 4 : 2;   // tiles per axis: the window spans the seed's stride
-  refine.refine_radius_th = (lp.refine_radius / kRefineThetaStride) * kRefineThetaStride;
-  refine.refine_step_th = kRefineThetaStride;
-  refine.grid_blocks = std::min((uint32_t)(2 * (refine.refine_radius_th / kRefineThetaStride) + 1), h->max_theta);
-  refine.partial = sl.d_partial3;
-  refine.walk_limit = (uint32_t)ILCC_SEED_POINTS;
-  refine.grid_bound = sl.d_bound_sub;
-  launch_grid_cost(refine, s, /*use_oob=*/1, nullptr, true);
-  HIP_TRY(h, hipEventRecord(sl.k6ev[2], s));
-  // anchor rounds (k6_anchor): 3 thetas x one tile on ALL points; every further round re-centres the tile on the previous
-  // round's argmin -- a greedy descent on complete costs towards the grid minimum, for a tighter bound in front of the full pass
-  Ctx anchor = c;
-  seeded_by_full_table_records(anchor, h, sl.d_partial3, refine.grid_blocks);
-  anchor.refine_radius_th = kAnchorRadius;
-  anchor.grid_blocks = 2 * kAnchorRadius + 1;
+// decimated tables, refinement around its argmin, then kAnchorRounds anchor rounds, each re-centred on the previous round's argmin
+// -- a greedy descent on complete costs towards the grid minimum, for a tighter bound in front of the full pass.  Returns where
+// the full pass finds the last round's records.
+int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, int32_t refine_radius, GridSeed& located) {
+  launch_grid_cost(c, seed_pass(h, sl, c), s, /*use_oob=*/1, nullptr, true);
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));
+  const GridPass refine = refine_pass(h, sl, c, refine_radius);
+  launch_grid_cost(c, refine, s, /*use_oob=*/1, nullptr, true);
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvRefined], s));
+  located = full_table_records(refine.out, refine.blocks);
   GridPartial* const ping[2] = {sl.d_partial4, sl.d_partial2};
   for (int round = 0; round < kAnchorRounds; ++round) {
-    anchor.partial = ping[round & 1];
-    launch_anchor(anchor, s);
-    anchor.seed_partial = ping[round & 1];
-    anchor.seed_blocks = 2 * kAnchorRadius + 1;
+    const GridPass anchor = anchor_pass(h, c, located, ping[round & 1]);
+    launch_anchor(c, anchor, s);
+    located = full_table_records(anchor.out, anchor.blocks);
   }
-  seeded_by_full_table_records(full, h, ping[(kAnchorRounds - 1) & 1], 2 * kAnchorRadius + 1);
   return ILCC_OK;
 }
 
@@ -667,75 +696,58 @@ int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStrea
 int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, uint32_t n_frames, bool chain) {
   const bool prune = h->p.grid_prune != 0;
   launch_walk_order(c, s);   // K5w: the labelled points in K6's walk layout, once per frame
-  HIP_TRY(h, hipEventRecord(sl.k6ev[0], s));
-  Ctx full = c;
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvWalkOrdered], s));
+  GridSeed located{};   // (records == nullptr: nothing located)
   // (grid_prune = 0 keeps the locate launches: they only initialise the frame's bound, which the cut-free full
   // pass still needs to recognise near ties; it never cuts a tile)
-  if (h->n_th2 > 0 && h->p.n_th >= 8 && h->p.n_ty >= 8 && h->p.n_tz >= 8) {
+  if (h->seed_grid.n_th > 0 && h->p.n_th >= 8 && h->p.n_ty >= 8 && h->p.n_tz >= 8) {
     // These launches only have to LOCATE the minimum.  Seed and refinement therefore look at a prefix of the point walk (an
     // eighth of the frame's labelled points, at least ILCC_SEED_POINTS positions: a uniform sample of the board) and keep their
     // own bound word; the anchor evaluates what they found on EVERY point and publishes the frame's real bound.  (Round 2 ran
     // seed and refinement on all points: 16 % of the path's VALU instructions.)
-    LocatePlan lp{};
-    lp.cth2 = h->d_cth2;
-    lp.sth2 = h->d_sth2;
-    lp.ay2 = h->d_ay2;
-    lp.az2 = h->d_az2;
-    lp.n_th2 = h->n_th2;
-    lp.n_ty2 = h->n_ty2;
-    lp.n_tz2 = h->n_tz2;
-    lp.c_th2 = std::min(std::max(c.c_th / std::max(1, h->seed_stride_th), 0), h->n_th2 - 1);
-    lp.c_ty2 = std::min(c.c_ty / std::max(1, h->seed_stride_t), h->n_ty2 - 1);
-    lp.c_tz2 = std::min(c.c_tz / std::max(1, h->seed_stride_t), h->n_tz2 - 1);
-    lp.stride_th = h->seed_stride_th;
-    lp.off_th = h->seed_stride_th / 2;
-    lp.stride_t = h->seed_stride_t;
-    lp.refine_radius = std::max(1, h->seed_stride_th / ILCC_REFINE_RADIUS_DIV);
-    lp.sample_min = (uint32_t)ILCC_SEED_POINTS;
-    lp.sample_cap = std::max((uint32_t)ILCC_SEED_POINTS, ((c.grid_lds_points >> 3) + 63u) & ~63u);
-    lp.out = sl.d_partial4;
+    const LocatePlan lp = locate_plan(h, sl, c);
     // one launch, one workgroup per frame (k6_locate) when the batch has the frames to fill the chip that way
-    const bool fused = n_frames >= (uint32_t)kLocateMinFrames && h->n_th2 <= 16 &&
-                       locate_lds_bytes(lp.sample_cap, h->p.n_ty, h->p.n_tz, h->n_ty2, h->n_tz2) <= 60u * 1024u;
+    const bool fused = n_frames >= (uint32_t)kLocateMinFrames && lp.seed.n_th <= 16 &&
+                       locate_lds_bytes(lp.sample_cap, h->grid.n_ty, h->grid.n_tz, lp.seed.n_ty, lp.seed.n_tz) <= 60u * 1024u;
     if (fused) {
       launch_locate(c, s, lp);
-      HIP_TRY(h, hipEventRecord(sl.k6ev[1], s));   // (the whole locate launch is accounted as the "seed" span)
-      HIP_TRY(h, hipEventRecord(sl.k6ev[2], s));
-      seeded_by_full_table_records(full, h, sl.d_partial4, 1);
+      HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));   // (the whole locate launch is accounted as the "seed" span)
+      HIP_TRY(h, hipEventRecord(sl.ev[kEvRefined], s));
+      located = full_table_records(lp.out, 1);
     } else {
-      const int32_t st = enqueue_locate_launches(h, sl, c, s, lp, full);
+      const int32_t st = enqueue_locate_launches(h, sl, c, s, lp.refine_radius, located);
       if (st != ILCC_OK) return st;
     }
   } else {
-    HIP_TRY(h, hipEventRecord(sl.k6ev[1], s));
-    HIP_TRY(h, hipEventRecord(sl.k6ev[2], s));
+    HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));
+    HIP_TRY(h, hipEventRecord(sl.ev[kEvRefined], s));
   }
-  HIP_TRY(h, hipEventRecord(sl.k6ev[3], s));   // behind the anchor: the common pre-pass gets an event span of its own
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvAnchored], s));   // behind the anchor: the common pre-pass gets an event span of its own
+  GridPass full = full_pass(h, c, located);
   const GroupPrepassPlan gp = group_prepass_plan(h->p);
   full.box_points = gp.box ? (uint32_t)ILCC_BOX_POINTS : 0u;   // (eligibility: group_prepass_plan, which also sized the buffers)
   // k6_group_prepass: one box pre-pass for kThetaGroup consecutive thetas, launched HERE -- behind the anchor (it needs the
   // frame's bound), in front of the full pass.  Its buffers were sized for (max_frames, this grid) by alloc_slot / ilcc_set_params.
   if (full.box_points != 0u && gp.on && (size_t)n_frames * gp.groups <= sl.grp_alive_cap &&
       (size_t)n_frames * gp.groups * gp.words <= sl.grp_mask_cap) {
-    full.grp_count = gp.groups;
-    full.grp_words = gp.words;
-    launch_group_prepass(full, s, sl.d_grp_alive, sl.d_grp_mask);
     full.grp_alive = sl.d_grp_alive;
     full.grp_mask = sl.d_grp_mask;
+    full.grp_count = gp.groups;
+    full.grp_words = gp.words;
+    launch_group_prepass(c, full, s);
   } else if (full.box_points != 0u && gp.on) {
     // eligible grid, buffers too small for this batch (never expected: size_group_prepass sized them): slower, not wrong -- say so once
     if (h->group_prepass_skipped++ == 0) h->err = "note: k6_group_prepass skipped (mask buffers smaller than this batch needs): slower, results unaffected";
   }
-  HIP_TRY(h, hipEventRecord(sl.ev[7], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvPrepassed], s));
   // The FULL passes of consecutive batches are chained so that they never share the chip (two passes side by side both run at
   // half speed and every batch's front end waits longer for wave slots); the launches above are small and are left free to
   // overlap with another batch's full pass, like K2 / K3 / K7.
   const int si = (int)(&sl - h->slots);
   if (chain && h->k6_last >= 0 && h->k6_last != si && h->slots[h->k6_last].busy)
     HIP_TRY(h, hipStreamWaitEvent(s, h->slots[h->k6_last].k6_done, 0));
-  HIP_TRY(h, hipEventRecord(sl.ev[8], s));
-  full.tie_count = sl.d_tie_count;
-  launch_grid_cost(full, s, /*use_oob=*/1, nullptr, prune);
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvFullStart], s));
+  launch_grid_cost(c, full, s, /*use_oob=*/1, nullptr, prune);
   if (chain) {
     HIP_TRY(h, hipEventRecord(sl.k6_done, s));
     h->k6_last = si;
@@ -760,10 +772,10 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
   HIP_TRY(h, hipMemcpyAsync(sl.d_off, sl.h_off, sizeof(uint64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
   // (result records, component counters, K6 counters and near-tie counters are reset inside K1 / K2)
   Ctx c = make_ctx(h, sl, d_xyzi, d_clicks, n_frames, chunks);
-  HIP_TRY(h, hipEventRecord(sl.ev[0], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvStart], s));
   if (!no_crop) {
-    launch_roi_crop(c, s, sl.ev[9]);   // ev[9]: between the count pass and the scatter
-    HIP_TRY(h, hipEventRecord(sl.ev[1], s));
+    launch_roi_crop(c, s, sl.ev[kEvCropCounted]);
+    HIP_TRY(h, hipEventRecord(sl.ev[kEvCropped], s));
     launch_cluster(c, s);
   } else {
     // get_chessboard_by_point clusters the WHOLE cloud (no ROI; setClusterTolerance(0.1), LidarCornersEst.cpp:80 -- EuclideanCluster()
@@ -778,8 +790,8 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     t1.online_window = 1.25f;
     t1.p.roi_half[0] = t1.p.roi_half[1] = t1.p.roi_half[2] = (double)t1.online_window;
     t1.cluster_bits = cluster_bits_online();
-    launch_roi_crop(t1, s, sl.ev[9]);
-    HIP_TRY(h, hipEventRecord(sl.ev[1], s));
+    launch_roi_crop(t1, s, sl.ev[kEvCropCounted]);
+    HIP_TRY(h, hipEventRecord(sl.ev[kEvCropped], s));
     launch_cluster(t1, s);
     Ctx t2 = c;
     t2.online_tier = 2u;
@@ -789,27 +801,25 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     HIP_TRY(h, hipMemcpyAsync(sl.h_online, sl.d_flags, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(sl.h_online + h->max_frames, sl.d_nfinite, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
   }
-  HIP_TRY(h, hipEventRecord(sl.ev[2], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvClustered], s));
   launch_ransac_plane(c, s);
-  HIP_TRY(h, hipEventRecord(sl.ev[3], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvPlane], s));
   launch_plane_frame_hist(c, s);
   sl.grid = !front_only && h->p.solver == ILCC_SOLVER_GRID;
-  HIP_TRY(h, hipEventRecord(sl.ev[4], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvLabelled], s));
   if (sl.grid) {
     const int32_t st = enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/true);
     if (st != ILCC_OK) return st;
   }
-  HIP_TRY(h, hipEventRecord(sl.ev[5], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvSearched], s));
   if (!front_only) {
     if (sl.grid) {
-      Ctx c7 = c;
-      c7.tie_count = sl.d_tie_count;   // near ties of the full pass, re-ordered on fixed-point sums by K7r
-      launch_pattern_refine_corners(c7, s);
+      launch_pattern_refine_corners(c, s);   // (with the near ties of the full pass, re-ordered on fixed-point sums by K7r)
     } else {
       launch_refine_corners(c, s);
     }
   }
-  HIP_TRY(h, hipEventRecord(sl.ev[6], s));
+  HIP_TRY(h, hipEventRecord(sl.ev[kEvEnd], s));
   HIP_TRY(h, hipGetLastError());
   // the copy back: what the result mode asks for rides on the batch's stream (include/ilcc_hip.h, "Result traffic")
   sl.compact = h->result_mode == ILCC_RESULTS_COMPACT;
@@ -872,28 +882,31 @@ int32_t finish(ilcc_handle* h, int si, ilcc_result* out, float* out_compact = nu
     for (uint32_t f = 0; f < n_frames; ++f) std::memcpy(&out[f], &sl.h_res[f], row);
   }
   if (out_compact) std::memcpy(out_compact, sl.h_rec, sizeof(float) * n_frames * rec_w);
-  float ms[6];
-  for (int k = 0; k < 6; ++k) HIP_TRY(h, hipEventElapsedTime(&ms[k], sl.ev[k], sl.ev[k + 1]));
+  auto span = [&](BatchEvent from, BatchEvent to, float& ms_out) { return hipEventElapsedTime(&ms_out, sl.ev[from], sl.ev[to]); };
+  float ms[6];   // K1, K2, K3, K4/K5, K6, K7
+  HIP_TRY(h, span(kEvStart, kEvCropped, ms[0]));
+  HIP_TRY(h, span(kEvCropped, kEvClustered, ms[1]));
+  HIP_TRY(h, span(kEvClustered, kEvPlane, ms[2]));
+  HIP_TRY(h, span(kEvPlane, kEvLabelled, ms[3]));
+  HIP_TRY(h, span(kEvLabelled, kEvSearched, ms[4]));
+  HIP_TRY(h, span(kEvSearched, kEvEnd, ms[5]));
   float k6k[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // K5w, seed, refinement, anchor, common pre-pass, full pass
-  if (sl.grid) {   // K6 = (seed + refinement passes) + (full pass); the wait for the previous batch's full pass in between is not K6 time
-    float pre = 0.f, fullp = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&pre, sl.ev[4], sl.ev[7]));
-    HIP_TRY(h, hipEventElapsedTime(&fullp, sl.ev[8], sl.ev[5]));
-    ms[4] = pre + fullp;
-    HIP_TRY(h, hipEventElapsedTime(&k6k[0], sl.ev[4], sl.k6ev[0]));
-    HIP_TRY(h, hipEventElapsedTime(&k6k[1], sl.k6ev[0], sl.k6ev[1]));
-    HIP_TRY(h, hipEventElapsedTime(&k6k[2], sl.k6ev[1], sl.k6ev[2]));
-    HIP_TRY(h, hipEventElapsedTime(&k6k[3], sl.k6ev[2], sl.k6ev[3]));
-    HIP_TRY(h, hipEventElapsedTime(&k6k[4], sl.k6ev[3], sl.ev[7]));
-    k6k[5] = fullp;
+  if (sl.grid) {   // K6 = (what locates the minimum + the common pre-pass) + (full pass); the wait for the previous batch's full pass in between is not K6 time
+    float pre = 0.f;
+    HIP_TRY(h, span(kEvLabelled, kEvPrepassed, pre));
+    HIP_TRY(h, span(kEvLabelled, kEvWalkOrdered, k6k[0]));
+    HIP_TRY(h, span(kEvWalkOrdered, kEvSeeded, k6k[1]));
+    HIP_TRY(h, span(kEvSeeded, kEvRefined, k6k[2]));
+    HIP_TRY(h, span(kEvRefined, kEvAnchored, k6k[3]));
+    HIP_TRY(h, span(kEvAnchored, kEvPrepassed, k6k[4]));
+    HIP_TRY(h, span(kEvFullStart, kEvSearched, k6k[5]));
+    ms[4] = pre + k6k[5];
   }
   float tot = 0;
-  HIP_TRY(h, hipEventElapsedTime(&tot, sl.ev[0], sl.ev[6]));
+  HIP_TRY(h, span(kEvStart, kEvEnd, tot));
   if (h->tl_on && h->tl_ref && sl.grid) {
-    const hipEvent_t evs[ILCC_TIMELINE_COLS - 1] = {sl.ev[0], sl.ev[9], sl.ev[1], sl.ev[2], sl.ev[3], sl.ev[4], sl.k6ev[0], sl.k6ev[1],
-                                                    sl.k6ev[2], sl.k6ev[3], sl.ev[7], sl.ev[8], sl.ev[5], sl.ev[6]};
     h->tl_rows.push_back((double)si);
-    for (hipEvent_t e : evs) {
+    for (hipEvent_t e : sl.ev) {   // (BatchEvent order = the timeline's columns)
       float t = 0.f;
       HIP_TRY(h, hipEventElapsedTime(&t, h->tl_ref, e));
       h->tl_rows.push_back((double)t);
@@ -912,7 +925,7 @@ int32_t finish(ilcc_handle* h, int si, ilcc_result* out, float* out_compact = nu
   t.stage_ms_sum[6] += tot;
   {
     float cnt = 0.f;
-    HIP_TRY(h, hipEventElapsedTime(&cnt, sl.ev[0], sl.ev[9]));
+    HIP_TRY(h, span(kEvStart, kEvCropCounted, cnt));
     t.roi_count_ms_sum += cnt;
   }
   uint32_t max_lab = 0, max_roi = 0;
@@ -1622,7 +1635,7 @@ int32_t ilcc_grid_cost(ilcc_handle* h, const float* yz, const uint8_t* label, ui
   HIP_TRY(h, hipMemcpyAsync(sl.d_bound, &inf_bits, sizeof(inf_bits), hipMemcpyHostToDevice, s));
   launch_walk_order(c, s);
   // full evaluation when the volume is wanted, the pipeline's branch-and-bound variant otherwise
-  launch_grid_cost(c, s, use_oob, d_vol, /*prune=*/d_vol == nullptr && h->p.grid_prune != 0);
+  launch_grid_cost(c, whole_grid_pass(c, c.grid, c.partial), s, use_oob, d_vol, /*prune=*/d_vol == nullptr && h->p.grid_prune != 0);
   std::vector<GridPartial> part(c.grid_blocks);
   hipError_t e = hipGetLastError();   // a launch that asked for more LDS than the device grants fails HERE, not at the copy
   if (e == hipSuccess) e = hipMemcpyAsync(part.data(), sl.d_partial, sizeof(GridPartial) * c.grid_blocks, hipMemcpyDeviceToHost, s);
@@ -1658,7 +1671,7 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
   while (lds < m && lds < (uint32_t)kGridLdsPointsMax) lds <<= 1;
   const uint32_t saved = h->grid_lds_points;
   h->grid_lds_points = std::max(saved, lds);
-  Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
+  const Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
   h->grid_lds_points = saved;
   // what K1 resets per frame and per batch
   const uint32_t inf_bits = 0x7f800000u, zero = 0u;
@@ -1668,9 +1681,7 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
   HIP_TRY(h, hipMemsetAsync(sl.d_iters, 0, sizeof(unsigned long long) * kBatchWords, s));
   st = enqueue_grid_search(h, sl, c, s, 1, /*chain=*/false);
   if (st != ILCC_OK) return st;
-  Ctx c7 = c;
-  c7.tie_count = sl.d_tie_count;
-  launch_pattern_refine_corners(c7, s);
+  launch_pattern_refine_corners(c, s);
   HIP_TRY(h, hipGetLastError());
   SolveRec rec{};
   ilcc_result r;

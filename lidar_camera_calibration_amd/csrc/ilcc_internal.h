@@ -97,7 +97,53 @@ struct RefineOut {     // K7r diagnostic entry (ilcc_pattern_refine)
   int32_t phase, rounds, hops;
 };
 
-// everything a kernel needs, passed by value
+// one candidate grid as a K6 kernel sees it.  The handle owns two -- the full grid and the decimated seed grid (a subset of the
+// same float values) -- both filled where the tables are uploaded
+struct GridTables {
+  const float* cth;          // cos(theta_k)/g
+  const float* sth;          // sin(theta_k)/g
+  const float* ay;           // (ty_a + W g/2)/g
+  const float* az;           // (tz_b + H g/2)/g
+  int32_t n_th, n_ty, n_tz;
+  int32_t c_th, c_ty, c_tz;  // index of the candidate nearest zero on each axis OF THESE TABLES (tie-break distance, K5w's rim test)
+};
+
+// candidate (k2, a2, b2) of the tables a launch's records index -> (off_th + k2 stride_th, a2 stride_t, b2 stride_t) of the full tables
+struct SeedMap {
+  int32_t stride_t, stride_th, off_th;
+};
+
+// where a K6 launch finds the records of the launch before it, and how they map to its own tables
+struct GridSeed {
+  const GridPartial* records;   // n_frames x blocks (nullptr: this launch follows no other)
+  uint32_t blocks;
+  SeedMap map;
+};
+
+// everything that distinguishes one K6 launch from another (k6_grid_cost, k6_anchor, k6_group_prepass); ilcc_api.cpp builds one per launch
+struct GridPass {
+  GridTables t;              // the tables it scores: the full ones for every launch but the seed
+  GridPartial* out;          // n_frames x blocks records
+  uint32_t blocks;           // workgroups (= records) per frame
+  uint32_t walk_limit;       // 0 = every labelled point; else a prefix of the walk (a uniform sample of the board): M >> kSeedShift positions, at least walk_limit
+  uint32_t* bound;           // per frame, the word it prunes against and publishes to: Ctx::grid_bound, or Ctx::grid_bound_sub for a launch on a prefix of the walk
+  GridSeed seed;
+  // refinement: workgroup j scores the window of window_tiles x window_tiles tiles (2: 8 x 8 translations; 4: 16 x 16) around the seed's
+  // argmin at theta (seed's theta) + j step_th - radius_th.  window_tiles = 0: the whole tables, workgroup j = theta j.
+  // (k6_anchor: workgroup j scores ONE tile at theta (seed's theta) + j - radius_th)
+  int32_t window_tiles, radius_th, step_th;
+  // near ties: candidates whose fp32 cost is within kTieEps of the bound at the time they complete go to Ctx::tie_list (the full pass);
+  // K7r recounts them on the oracle's fixed-point cost so that the argmin is the oracle's even when fp32 cannot order them
+  uint32_t collect_ties;
+  uint32_t box_points;       // border-class walk positions the box pre-pass looks at per tile, at least (0: no pre-pass)
+  // the full pass behind k6_group_prepass, which writes them (nullptr: no common pre-pass): per (frame, group of kThetaGroup thetas) a
+  // state word and a bit mask
+  uint32_t* grp_alive;
+  uint32_t* grp_mask;
+  uint32_t grp_count, grp_words;   // theta groups per frame = ceil(n_th / kThetaGroup); mask words per group = ceil(tiles / 32)
+};
+
+// what is true for a whole batch, passed by value to every kernel
 struct Ctx {
   // inputs
   const float4* xyzi;        // all frames, packed
@@ -145,46 +191,22 @@ struct Ctx {
   uint32_t* list;            // ... and their indices
   void* list_frames;         // tier 2: one 64-byte ListedFrame (k2_cluster.hip) per frame
   uint32_t list_grid;        // tier 2: workgroups of the kernels over (listed frame, chunk) items
-  GridPartial* partial;      // n_frames x grid_blocks
+  GridPartial* partial;      // n_frames x grid_blocks: the records of K6's full pass (K7r takes their argmin)
   SolveRec* solve_rec;       // n_frames x 2
-  uint32_t grid_blocks;      // K6 workgroups per frame
+  uint32_t grid_blocks;      // records per frame of the full pass (one per theta)
   uint32_t grid_lds_points;  // K6 points staged in LDS per workgroup (multiple of 64)
-  uint32_t* grid_bound;      // per frame: float bits of the best complete candidate cost so far (K6 pruning)
-  uint32_t* grid_bound_sub;  // the same for the subsampled seed / refinement launches (costs over a prefix of the walk: never a valid bound for complete costs)
-  uint32_t walk_limit;       // K6: 0 = every labelled point; else only the first walk_limit positions of the walk (a uniform sample of the board)
-  // near ties: candidates of the full pass whose fp32 cost is within kTieEps of the bound at the time they
-  // complete; K7r recounts them on the oracle's fixed-point cost so that the argmin is the oracle's even when fp32 cannot order them
-  uint32_t* tie_count;       // per frame (nullptr: this launch does not collect)
-  uint32_t* tie_count_all;   // the same array, always set: K1 resets it
-  GridPartial* tie_list;     // n_frames x kTieCap: cost (fp32), d2, flat
+  // K1 resets these per frame, the launches of K6 write them (GridPass), K7r reads the near ties
+  uint32_t* grid_bound;      // float bits of the best complete candidate cost so far (K6 pruning)
+  uint32_t* grid_bound_sub;  // the same for the launches on a prefix of the walk (never a valid bound for complete costs)
+  uint32_t* tie_count;       // near ties listed by the full pass (GridPass::collect_ties) ...
+  GridPartial* tie_list;     // ... n_frames x kTieCap: cost (fp32), d2, flat
   unsigned long long* grid_iters;  // executed K6 work in counts of grid_cost_evals_per_count() evaluations, for the VALU rate
-  uint32_t box_points;             // K6 full pass: border-class walk positions the box pre-pass looks at per tile (0: no pre-pass)
-  // K6 full pass behind k6_group_prepass (nullptr: no common pre-pass): per (frame, group of kThetaGroup thetas) a state word and a bit mask
-  const uint32_t* grp_alive;
-  const uint32_t* grp_mask;
-  uint32_t grp_count, grp_words;   // theta groups per frame = ceil(n_th / kThetaGroup); mask words per group = ceil(tiles / 32)
-  // seeding pass of the branch-and-bound (a decimated subset of the same grid, evaluated first)
-  const GridPartial* seed_partial; // n_frames x seed_blocks, nullptr when this launch is the seed pass / unused
-  uint32_t seed_blocks;
-  int32_t seed_n_ty, seed_n_tz, seed_stride_t;   // seed (a2,b2) -> grid (a2*stride, b2*stride)
-  int32_t seed_stride_th, seed_off_th;           // seed k2 -> grid theta index seed_off_th + k2*seed_stride_th
-  // refinement pass (between seed and full pass): workgroup j evaluates the 16 x 16 (ty, tz) window around
-  // the seed argmin at theta index (seed theta) + j - refine_radius_th; 0 = this launch is not a refinement
-  int32_t refine_window;     // != 0: this launch (the refinement) evaluates only a window of refine_window x refine_window tiles (2: 8 x 8 translations; 4: 16 x 16) around the seed argmin, every refine_step_th-th theta within +-refine_radius_th
-  int32_t refine_radius_th;
-  int32_t refine_step_th;    // theta step between the workgroups of a refinement / anchor launch (kRefineThetaStride / 1)
-  // candidate tables (device)
-  const float* cth;          // cos(theta_k)/g
-  const float* sth;          // sin(theta_k)/g
-  const float* ay;           // (ty_a + W g/2)/g
-  const float* az;           // (tz_b + H g/2)/g
+  GridTables grid;           // the handle's FULL candidate tables (K5w, k6_locate, K7r; a K6 launch scores GridPass::t)
   // K7r: cos/sin of every theta lattice point, index (lattice theta) - th_lat_lo
   const double2* th_lattice;
   int32_t th_lat_lo, th_lat_hi;
   int32_t refine_hop_y, refine_hop_z;   // one board square along y / z in lattice units
-  // parameters
-  ilcc_params p;
-  int32_t c_th, c_ty, c_tz;  // index of the candidate nearest zero on each axis
+  ilcc_params p;             // the handle's parameters, never edited for a launch
 };
 
 // K6 walks a frame's M labelled points in the order slot s <- point (s * S) mod M with S ~ 0.618 M coprime to M (a
@@ -278,10 +300,8 @@ __device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* scratch, uin
 
 // k6_locate (k6_grid_cost.hip): seed + refinement + anchor of the grid search in one launch, one workgroup per frame
 struct LocatePlan {
-  const float *cth2, *sth2, *ay2, *az2;   // the seed's decimated tables (subsets of the full ones)
-  int32_t n_th2, n_ty2, n_tz2;
-  int32_t c_th2, c_ty2, c_tz2;            // their entries nearest zero (tie-break distance)
-  int32_t stride_th, off_th, stride_t;    // seed (k2, a2, b2) -> full tables (off_th + k2 stride_th, a2 stride_t, b2 stride_t)
+  GridTables seed;                        // the seed's decimated tables ...
+  SeedMap map;                            // ... and where their entries sit in the full ones (Ctx::grid)
   int32_t refine_radius;                  // refinement: theta within +- this many steps of the seed's
   uint32_t sample_min, sample_cap;        // the sample: max(sample_min, M >> kSeedShift) walk positions, at most sample_cap (LDS)
   GridPartial* out;                       // one record per frame: the anchor's best candidate (full-table flat index, (a << 16) | b)
@@ -289,7 +309,7 @@ struct LocatePlan {
 
 size_t locate_lds_bytes(uint32_t sample_cap, int n_ty, int n_tz, int n_ty2, int n_tz2);
 void launch_locate(const Ctx& c, hipStream_t s, const LocatePlan& lp);
-void launch_anchor(const Ctx& c, hipStream_t s);   // one anchor round of the separate locate launches (c.seed_partial -> c.partial, c.grid_blocks thetas)
+void launch_anchor(const Ctx& c, const GridPass& pass, hipStream_t s);   // one anchor round of the separate locate launches (pass.seed -> pass.out, pass.blocks thetas)
 constexpr int kRefineThetaStride = 2;  // the refinement scores every other theta of its range (the anchor covers the ones in between)
 constexpr int kLocateMinFrames = 512;   // smaller batches keep the three launches: a frame's workgroups per theta are what fills the chip there (128 frames alone: 0.27 ms in three launches, 0.30 ms in one)
 
@@ -299,9 +319,8 @@ void launch_cluster(const Ctx& c, hipStream_t s);
 void launch_ransac_plane(const Ctx& c, hipStream_t s);
 void launch_plane_frame_hist(const Ctx& c, hipStream_t s);
 void launch_walk_order(const Ctx& c, hipStream_t s);   // K5w (k6_grid_cost.hip): before any launch_grid_cost on the frames
-void launch_grid_cost(const Ctx& c, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/,
-                      bool prune);
-void launch_group_prepass(const Ctx& c, hipStream_t s, uint32_t* grp_alive, uint32_t* grp_mask);   // in front of the full pass (c.grp_count, c.grp_words set)
+void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/, bool prune);
+void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // in front of the full pass it is given: writes full.grp_alive / grp_mask
 uint32_t grid_cost_evals_per_count();   // (point, candidate) evaluations behind one count of Ctx::grid_iters
 void launch_refine_corners(const Ctx& c, hipStream_t s);
 void launch_pack_records(const ilcc_result* d_res, uint32_t n_frames, uint32_t n_corners, uint32_t tag_base, float* d_out,

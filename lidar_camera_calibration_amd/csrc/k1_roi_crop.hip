@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kCropThreads) void k1_roi_count(Ctx c) {
   }
   if (s == 0 && threadIdx.x == 0) {
     // fresh per-frame record
-    if (c.tie_count_all) c.tie_count_all[f] = 0u;
+    if (c.tie_count) c.tie_count[f] = 0u;
     ilcc_result* r = &c.res[f];
     r->status = ILCC_OK;
     r->n_points = (int32_t)n;

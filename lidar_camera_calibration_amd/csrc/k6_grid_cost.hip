@@ -62,12 +62,12 @@ __device__ unsigned long long k6_prof[kProfWaves * kProfWords];   // one record 
 #ifndef ILCC_SEED_SHIFT
 #define ILCC_SEED_SHIFT 4   // round 3: an eighth (1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s); round 6, with the bound anchored on all points anyway: 1/4: 1 247 k, 1/8: 1 282 k (locate 0.187 ms alone), 1/16 = the 128-point floor on VLP-16 frames: 1 288 k (0.166 ms), 1/32: the same; config 5 unchanged (90-91 k)
 #endif
-constexpr int kSeedShift = ILCC_SEED_SHIFT;     // subsampled (locate) launches walk M >> kSeedShift positions, at least Ctx::walk_limit
+constexpr int kSeedShift = ILCC_SEED_SHIFT;     // subsampled (locate) launches walk M >> kSeedShift positions, at least GridPass::walk_limit
 constexpr int kTile = 4;          // 4 x 4 candidates per wavefront; lane = ((a << 2) | b) << 2 | slice
 constexpr int kSlices = 4;        // lanes (one quad) sharing a candidate, each on every 4th point of the walk
 constexpr int kUnroll = 2;        // points per lane and block of the generic walk
 constexpr int kStep = kSlices * kUnroll;
-constexpr int kBoxShiftSmall = 3;   // box pre-pass: at least 1/8 of the frame's labelled points per tile (and at least Ctx::box_points) ...
+constexpr int kBoxShiftSmall = 3;   // box pre-pass: at least 1/8 of the frame's labelled points per tile (and at least GridPass::box_points) ...
 constexpr int kBoxShiftLarge = 2;   // ... 1/4 in the 512-thread instance (frames of several thousand labelled points)
 // the common pre-pass (k6_group_prepass) looks at M >> kGroupShift points of the rim-first walk: a quarter in the 256-thread instance, half in
 // the 512-thread one (twice what each theta's own pre-pass looks at)
@@ -182,8 +182,8 @@ __device__ __forceinline__ void no_candidate(GridPartial* out) { *out = GridPart
 
 // Ctx::grid_iters: kIterSlots words per counter, frame f adds to word f mod kIterSlots of each (spread: fewer colliding atomics)
 enum EvalCounter { kEvalsAll = 0, kEvalsInterior = 1, kEvalsBox = 2 };
-__device__ __forceinline__ void count_evals(const Ctx& c, uint32_t f, EvalCounter which, unsigned long long n) {
-  atomicAdd(c.grid_iters + (int)which * kIterSlots + (f & (kIterSlots - 1)), n);
+__device__ __forceinline__ void count_evals(unsigned long long* grid_iters, uint32_t f, EvalCounter which, unsigned long long n) {
+  atomicAdd(grid_iters + (int)which * kIterSlots + (f & (kIterSlots - 1)), n);
 }
 
 // first candidate of a window of `width` candidates that starts `before` candidates ahead of `centre`, kept inside an axis of n
@@ -306,14 +306,14 @@ __device__ __forceinline__ void box_term(float pi_lo, float pi_hi, float pj_lo, 
   lb = (out_all && count) ? fmaf(T, 0.5f, lb) : lb;   // (count = false: a lane past the end of the sample, evaluated branch-free)
 }
 
-// the seed pass's best candidate of frame f and the seed workgroup (= seed theta index) that found it; wave-uniform.
+// the best candidate of frame f among the records of the launch before, and the workgroup (seed launch: = seed theta index) that found it; wave-uniform.
 // A handful of records: every lane reads them all (uniform addresses, scalar-cache loads) -- no cross-lane reduction.
-__device__ __forceinline__ Best seed_argmin(const Ctx& c, uint32_t f, uint32_t& k2, uint32_t& ab) {
-  const GridPartial* sp = c.seed_partial + (uint64_t)f * c.seed_blocks;
+__device__ __forceinline__ Best seed_argmin(const GridSeed& seed, uint32_t f, uint32_t& k2, uint32_t& ab) {
+  const GridPartial* sp = seed.records + (uint64_t)f * seed.blocks;
   Best sb{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
   k2 = 0;
   ab = 0;
-  for (uint32_t q = 0; q < c.seed_blocks; ++q) {
+  for (uint32_t q = 0; q < seed.blocks; ++q) {
     const GridPartial g = sp[q];
     if (better(g.cost, g.d2, g.flat, sb)) {
       sb = Best{g.cost, g.d2, g.flat};
@@ -434,12 +434,12 @@ __device__ __forceinline__ uint32_t box_prepass_rounds(int n_tiles, int ntb, int
 // there.  Same points, same order, same sums.  (Before: such a frame took the LDS-free body, which has no box pre-pass: a handful of
 // frames with 6 682 labelled points made config 5's full pass 5.6 ms instead of 0.74 ms per 128 frames.)
 template <bool OOB, bool VOLUME, bool LDS_POINTS, bool PRUNE, int THREADS, bool OVERFLOW = false>
-__device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, float2* s_ij, float* s_hw, Best* s_best,
+__device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pass, float* volume, float2* s_ij, float* s_hw, Best* s_best,
                                                uint32_t* s_iters, uint32_t* s_cnt, float* s_ay, float* s_az, uint32_t* s_dead, uint16_t* s_live,
                                                uint32_t* s_next, const uint32_t kblk) {
   // kblk: this workgroup's index within the frame (= blockIdx.x)
   const uint32_t f = blockIdx.y;
-  uint32_t k = kblk;   // theta index (refinement pass: set from the seed below)
+  uint32_t k = kblk;   // theta index (a launch with a window: set from the seed below)
   [[maybe_unused]] const unsigned long long t_entry = K6_NOW();
   [[maybe_unused]] unsigned long long t_rej = 0, t_surv = 0, n_rej = 0, n_surv = 0, n_done = 0, p_surv = 0;
   [[maybe_unused]] unsigned long long n_tests = 0, alive_sum = 0, alive_le4 = 0, alive_le2 = 0;   // bound tests after the first one
@@ -447,17 +447,17 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
   const int lane = lane_id();
   const int wid = __builtin_amdgcn_readfirstlane(wave_id());
   constexpr int kBoxShift = (THREADS == kGridThreadsLarge && kGridThreadsLarge != kGridThreads) ? kBoxShiftLarge : kBoxShiftSmall;
-  GridPartial* out = &c.partial[(uint64_t)f * c.grid_blocks + kblk];
+  GridPartial* out = &pass.out[(uint64_t)f * pass.blocks + kblk];
   // full pass behind k6_group_prepass: tiles the pre-pass common to this theta's group has already rejected (a bit mask in
   // global memory), or nothing at all to do when it rejected them all
   const uint32_t* s_dead0 = nullptr;
   bool group_dead = false;
   if constexpr (PRUNE && OOB && LDS_POINTS && !VOLUME) {
-    if (c.grp_alive != nullptr) {
-      const uint32_t tr = (uint32_t)f * c.grp_count + kblk / (uint32_t)kThetaGroup;
-      const uint32_t st = c.grp_alive[tr];   // 0: every tile dead, 1: mask valid, 2: no common pre-pass ran for this group
+    if (pass.grp_alive != nullptr) {
+      const uint32_t tr = (uint32_t)f * pass.grp_count + kblk / (uint32_t)kThetaGroup;
+      const uint32_t st = pass.grp_alive[tr];   // 0: every tile dead, 1: mask valid, 2: no common pre-pass ran for this group
       group_dead = st == 0u;
-      if (st == 1u) s_dead0 = c.grp_mask + (uint64_t)tr * c.grp_words;
+      if (st == 1u) s_dead0 = pass.grp_mask + (uint64_t)tr * pass.grp_words;
     }
   }
   if (r->status != ILCC_OK || group_dead) {
@@ -469,31 +469,31 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
   // a bound word of their own.  The anchor launch then evaluates the found neighbourhood on every point: that is the bound.
   // (the LDS-free body walks the frame's own arrays in golden-ratio order, layout or not)
   const uint32_t Mfull = c.n_lab[f];
-  const uint32_t M = c.walk_limit ? walk_sample(Mfull, c.walk_limit) : Mfull;   // an eighth of the points (measured: 1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s), at least walk_limit
+  const uint32_t M = pass.walk_limit ? walk_sample(Mfull, pass.walk_limit) : Mfull;   // an eighth of the points (measured: 1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s), at least walk_limit
   const uint64_t beg = c.off[f];
   const float2* __restrict__ gyz = c.yz + beg;
   const uint8_t* __restrict__ glab = c.lab + beg;   // an eighth of the points (measured: 1/2: 323 k, 1/4: 331 k, 1/8: 335 k, 1/16: 329 k frames/s), at least walk_limit
-  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
+  const int n_ty = pass.t.n_ty, n_tz = pass.t.n_tz;
   int nta = (n_ty + kTile - 1) / kTile, ntb = (n_tz + kTile - 1) / kTile;
   int a_org = 0, b_org = 0;   // first candidate of tile (0, 0)
   int t0 = 0;
-  if (PRUNE && c.seed_partial != nullptr) {
+  if (PRUNE && pass.seed.records != nullptr) {
     uint32_t k2u, ab;
-    const Best sb = seed_argmin(c, f, k2u, ab);
+    const Best sb = seed_argmin(pass.seed, f, k2u, ab);
     if (sb.flat != 0xFFFFFFFFu) {
       const int a2 = __builtin_amdgcn_readfirstlane((int)(ab >> 16)), b2 = __builtin_amdgcn_readfirstlane((int)(ab & 0xFFFFu));
       const int k2 = __builtin_amdgcn_readfirstlane((int)k2u);
-      const int sa = min(a2 * c.seed_stride_t, n_ty - 1), sbb = min(b2 * c.seed_stride_t, n_tz - 1);
-      if (c.refine_window) {
+      const int sa = min(a2 * pass.seed.map.stride_t, n_ty - 1), sbb = min(b2 * pass.seed.map.stride_t, n_tz - 1);
+      if (pass.window_tiles) {
         // refinement pass: every candidate within +-radius theta steps and the 8 x 8 (ty, tz) window
         // around the seed argmin -> the frame's bound is (nearly always) the true minimum before the
         // full pass starts, which is what lets the full pass cut almost every tile after 8 points
-        // (it scores every kRefineThetaStride-th theta of its range: refine_step_th; the anchor rounds -- k6_anchor, or the tail of k6_locate -- cover the ones in between)
-        const int kc = c.seed_off_th + k2 * c.seed_stride_th + (int)kblk * c.refine_step_th - c.refine_radius_th;
-        k = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(kc, 0), c.p.n_th - 1));
-        // refine_window = tiles per axis of the window: 2 (8 x 8 translations around the seed's argmin) or, on grids whose seed stride
+        // (it scores every kRefineThetaStride-th theta of its range: step_th; the anchor rounds -- k6_anchor, or the tail of k6_locate -- cover the ones in between)
+        const int kc = pass.seed.map.off_th + k2 * pass.seed.map.stride_th + (int)kblk * pass.step_th - pass.radius_th;
+        k = (uint32_t)__builtin_amdgcn_readfirstlane(min(max(kc, 0), pass.t.n_th - 1));
+        // window_tiles = tiles per axis of the window: 2 (8 x 8 translations around the seed's argmin) or, on grids whose seed stride
         // is wider than that window (config 5: every 16th translation), 4 -- the seed's best can be half a stride from the minimum
-        const int wt = max(2, c.refine_window);
+        const int wt = max(2, pass.window_tiles);
         a_org = __builtin_amdgcn_readfirstlane(window_origin(sa, (wt * kTile) / 2, n_ty, wt * kTile));
         b_org = __builtin_amdgcn_readfirstlane(window_origin(sbb, (wt * kTile) / 2, n_tz, wt * kTile));
         nta = min(wt, nta);
@@ -504,7 +504,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       }
     }
   }
-  const float cth = c.cth[k], sth = c.sth[k];
+  const float cth = pass.t.cth[k], sth = pass.t.sth[k];
 
   // Point order: k5w_walk_order (below) has written the frame's labelled points in WALK layout (FrameWalk), once per frame instead
   // of once per workgroup.  Golden-ratio order makes every prefix of a part a sample spread over the whole board: the bound test
@@ -530,15 +530,15 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     Mi = n_in;
     // The full pass stages the points its box pre-pass looks at first: a workgroup the pre-pass leaves no tile (half of
     // them: every theta more than a few steps from the minimum) never stages, or reads, the rest.
-    const bool box_first = PRUNE && OOB && c.box_points != 0u && nta * ntb <= kBoxTilesMax && M > Mi;   // (= use_box below)
+    const bool box_first = PRUNE && OOB && pass.box_points != 0u && nta * ntb <= kBoxTilesMax && M > Mi;   // (= use_box below)
     stage_lo = box_first ? Mi : 0u;
-    stage_hi = box_first ? Mi + min(max(c.box_points, Mfull >> kBoxShift), M - Mi) : lds_n;   // (OVERFLOW: the caller made sure the sample fits)
+    stage_hi = box_first ? Mi + min(max(pass.box_points, Mfull >> kBoxShift), M - Mi) : lds_n;   // (OVERFLOW: the caller made sure the sample fits)
     for (uint32_t sl = stage_lo + threadIdx.x; sl < stage_hi; sl += THREADS) stage_point(sl);
   }
   // (ty, tz) tables in LDS: a cut-short tile lasts about as long as one L2 round trip, so its
   // prologue must not wait for global loads
-  for (int i = threadIdx.x; i < c.p.n_ty; i += THREADS) s_ay[i] = c.ay[i];
-  for (int i = threadIdx.x; i < c.p.n_tz; i += THREADS) s_az[i] = c.az[i];
+  for (int i = threadIdx.x; i < n_ty; i += THREADS) s_ay[i] = pass.t.ay[i];
+  for (int i = threadIdx.x; i < n_tz; i += THREADS) s_az[i] = pass.t.az[i];
   if (threadIdx.x == 0) *s_next = 0u;   // the workgroup's tile-chunk counter (see the tile loop)
   __syncthreads();
   [[maybe_unused]] const unsigned long long t_staged = K6_NOW();
@@ -546,10 +546,10 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
   const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h;
   const float delta2 = (float)c.p.huber_delta;   // (the terms carry plain r and q: a lane's sums are cost / 2)
   const int n_tiles = nta * ntb;
-  const uint32_t dk = (uint32_t)((int)k - c.c_th) * (uint32_t)((int)k - c.c_th);
+  const uint32_t dk = (uint32_t)((int)k - pass.t.c_th) * (uint32_t)((int)k - pass.t.c_th);
 
   Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-  uint32_t* bound = c.grid_bound + f;
+  uint32_t* bound = pass.bound + f;
   float shared_bound = __builtin_inff();   // what this wavefront last published
   uint32_t gb_bits = PRUNE ? __hip_atomic_load(bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0x7f800000u;
   uint32_t pts_done = 0, pts_in = 0;   // walk positions executed by this wavefront (all / interior class)
@@ -567,11 +567,11 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
   bool use_box = false;
   unsigned long long box_evals = 0;   // (point, tile) evaluations of this workgroup's pre-pass
   if constexpr (PRUNE && LDS_POINTS && OOB) {
-    use_box = c.box_points != 0u && n_tiles <= kBoxTilesMax && M > Mi;
+    use_box = pass.box_points != 0u && n_tiles <= kBoxTilesMax && M > Mi;
     if (use_box) {
       for (int w = threadIdx.x; w < (n_tiles + 31) / 32; w += THREADS) s_dead[w] = s_dead0 ? s_dead0[w] : 0u;
       if (threadIdx.x == 0) s_cnt[0] = 0u;   // "a tile of this workgroup is still alive" (s_cnt is free until the epilogue)
-      const uint32_t n_pre = min(max(c.box_points, Mfull >> kBoxShift), M - Mi);   // the frame's bound grows with its point count: so must the sample that has to exceed it
+      const uint32_t n_pre = min(max(pass.box_points, Mfull >> kBoxShift), M - Mi);   // the frame's bound grows with its point count: so must the sample that has to exceed it
       const float lim_box = 0.5f * (1.f + kTieEps) * __uint_as_float(gb_bits);
       // (tiles the group's common pre-pass has rejected are not looked at again)
       // Round 6: behind a VALID common mask (k6_group_prepass, state 1) the workgroup walks what the mask leaves, without a pre-pass of
@@ -598,7 +598,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       if (!any_alive) {   // nothing to walk at this theta: the rest of the frame's points is never staged
         if (threadIdx.x == 0) {
           no_candidate(out);
-          count_evals(c, f, kEvalsBox, box_evals);
+          count_evals(c.grid_iters, f, kEvalsBox, box_evals);
         }
         return;
       }
@@ -607,7 +607,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       __syncthreads();
     }
   }
-  float* vol = VOLUME ? volume + (uint64_t)f * (uint64_t)c.p.n_th * n_ty * n_tz * 2u : nullptr;
+  float* vol = VOLUME ? volume + (uint64_t)f * (uint64_t)pass.t.n_th * n_ty * n_tz * 2u : nullptr;
   const int my_s = lane & (kSlices - 1), my_c = lane >> 2;
   const int my_a = my_c >> 2, my_b = my_c & 3;
 
@@ -844,9 +844,9 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     const float t0s = quad_sum(A0), t1s = quad_sum(A1);   // the four slices of each candidate
     if (owner) {
       const uint32_t cell = ((uint32_t)k * (uint32_t)n_ty + (uint32_t)ia) * (uint32_t)n_tz + (uint32_t)ib;
-      const uint32_t d2 = dk + (uint32_t)((ia - c.c_ty) * (ia - c.c_ty)) + (uint32_t)((ib - c.c_tz) * (ib - c.c_tz));
+      const uint32_t d2 = dk + (uint32_t)((ia - pass.t.c_ty) * (ia - pass.t.c_ty)) + (uint32_t)((ib - pass.t.c_tz) * (ib - pass.t.c_tz));
       const float c0 = 2.f * t0s, c1 = 2.f * t1s;
-      if (c.tie_count != nullptr && my_s == 0 && fminf(c0, c1) <= 2.f * lim2) {   // full pass: near ties of the bound
+      if (pass.collect_ties && my_s == 0 && fminf(c0, c1) <= 2.f * lim2) {   // full pass: near ties of the bound
         // completions are rare: afford a fresh look at the frame's bound so that little junk is listed while it is loose
         const float fresh = __uint_as_float(__hip_atomic_load(bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         const float thr = (1.f + kTieEps) * fminf(fresh, fminf(best.cost, fminf(c0, c1)));
@@ -984,9 +984,9 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
       it_sum += s_iters[w];
       in_sum += s_cnt[w];
     }
-    count_evals(c, f, kEvalsAll, it_sum);
-    count_evals(c, f, kEvalsInterior, in_sum);
-    if (use_box) count_evals(c, f, kEvalsBox, box_evals);
+    count_evals(c.grid_iters, f, kEvalsAll, it_sum);
+    count_evals(c.grid_iters, f, kEvalsInterior, in_sum);
+    if (use_box) count_evals(c.grid_iters, f, kEvalsBox, box_evals);
     uint32_t none = 0;
     const Best b = block_argmin<THREADS / ILCC_WAVE>(s_best, nullptr, none);
     out->cost = b.cost;
@@ -1001,9 +1001,9 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
     out->pad = ab;
   }
 #ifdef ILCC_K6_TIMING
-  if (lane == 0 && c.tie_count != nullptr) {   // the full pass only
+  if (lane == 0 && pass.collect_ties) {   // the full pass only
     const unsigned long long t_end = K6_NOW();
-    const uint32_t w = ((f * c.grid_blocks + kblk) * (THREADS / ILCC_WAVE) + (uint32_t)wid) & (kProfWaves - 1);
+    const uint32_t w = ((f * pass.blocks + kblk) * (THREADS / ILCC_WAVE) + (uint32_t)wid) & (kProfWaves - 1);
     unsigned long long* o = k6_prof + (size_t)w * kProfWords;
     o[0] = 1ull;
     o[1] = t_end - t_entry;
@@ -1031,7 +1031,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, float* volume, floa
 // (BASELINE config 5: 4 198) stage 50+ KB per workgroup, three workgroups fit a CU, and 512 threads then double the
 // resident wavefronts per SIMD (3 -> 6).  Same sums either way: a candidate's points are added by its quad in walk order.
 template <bool OOB, bool VOLUME, bool PRUNE, int THREADS>
-__global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, float* volume) {
+__global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, GridPass pass, float* volume) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ Best s_best[THREADS / ILCC_WAVE];
   __shared__ uint32_t s_iters[THREADS / ILCC_WAVE];
@@ -1042,30 +1042,31 @@ __global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, float* volume) {
   float2* s_ij = reinterpret_cast<float2*>(smem);
   float* s_hw = reinterpret_cast<float*>(smem + sizeof(float2) * (size_t)c.grid_lds_points);
   float* s_ay = s_hw + c.grid_lds_points;   // n_ty floats
-  float* s_az = s_ay + c.p.n_ty;            // n_tz floats
+  float* s_az = s_ay + pass.t.n_ty;         // n_tz floats
   const uint32_t Mall = c.n_lab[blockIdx.y];
-  // (unused, and kept: without it the full pass compiles to another register allocation and schedule -- 1.6 k of the 9.4 k lines
-  // of its gfx950 assembly differ)
-  const uint32_t M = c.walk_limit ? walk_sample(Mall, c.walk_limit) : Mall;
+  // (unused, and kept on measurement: without it the full pass compiles to another schedule, same registers -- 6.2 k of the 10 k lines
+  // of its gfx950 assembly differ -- and is slower: alone on the chip 0.350 against 0.342 ms per 1024 frames, five alternating
+  // benchmark runs each 1 222 k against 1 241 k frames/s (medians; config 5: 96.9 against 96.3 k, inside its spread))
+  const uint32_t M = pass.walk_limit ? walk_sample(Mall, pass.walk_limit) : Mall;
   (void)M;
   if (Mall <= c.grid_lds_points) {   // (k5w_walk_order has laid out every frame of at most kGridLdsPointsMax points)
-    grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS>(c, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
+    grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
     return;
   }
   if constexpr (OOB && !VOLUME && PRUNE) {
     // the pipeline's full pass on a frame above the staging capacity: the staged prefix + the rest through L2, as long as the
     // interior class and the box pre-pass's sample (what every workgroup reads) are inside the prefix
     constexpr int kBoxShift = (THREADS == kGridThreadsLarge && kGridThreadsLarge != kGridThreads) ? kBoxShiftLarge : kBoxShiftSmall;
-    if (c.walk_limit == 0u && c.box_points != 0u && Mall <= (uint32_t)kGridLdsPointsMax) {
+    if (pass.walk_limit == 0u && pass.box_points != 0u && Mall <= (uint32_t)kGridLdsPointsMax) {
       const uint32_t Mi = c.walk_mi[blockIdx.y];
-      if (Mall > Mi && Mi + min(max(c.box_points, Mall >> kBoxShift), Mall - Mi) <= c.grid_lds_points) {
-        grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS, true>(c, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next,
+      if (Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShift), Mall - Mi) <= c.grid_lds_points) {
+        grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS, true>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next,
                                                                 blockIdx.x);
         return;
       }
     }
   }
-  grid_cost_body<OOB, VOLUME, false, PRUNE, THREADS>(c, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
+  grid_cost_body<OOB, VOLUME, false, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
 }
 
 // k6_group_prepass: ONE box pre-pass for a GROUP of kThetaGroup consecutive thetas, in front of the full pass.  71 % of the (frame,
@@ -1079,7 +1080,7 @@ __global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, float* volume) {
 // group's full-pass workgroups exit on their first instructions), 1: a bit mask of the rejected tiles follows (their own
 // pre-pass starts from it and only looks at the rest), 2: no common pre-pass (conditions not met) -- and the mask.
 template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, uint32_t* grp_alive, uint32_t* grp_mask) {
+__global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, GridPass pass) {
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ uint32_t s_iters[THREADS / ILCC_WAVE];
   __shared__ uint32_t s_dead3[kBoxTilesMax / 32];
@@ -1087,26 +1088,26 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, uint32_t* grp
   __shared__ uint32_t s_cnt2[2];
   __shared__ uint32_t s_any;
   const uint32_t f = blockIdx.y;
-  const int k0 = kThetaGroup * (int)blockIdx.x, nk = min(kThetaGroup, c.p.n_th - k0);
-  const uint32_t tr = f * c.grp_count + blockIdx.x;
+  const int k0 = kThetaGroup * (int)blockIdx.x, nk = min(kThetaGroup, pass.t.n_th - k0);
+  const uint32_t tr = f * pass.grp_count + blockIdx.x;
   const uint32_t Mall = c.n_lab[f];
   // (frames above the full pass's staging capacity have a walk layout too -- k5w lays out every frame of at most kGridLdsPointsMax
   // points -- and their full pass reads this mask in its OVERFLOW form)
   const bool lds = Mall <= (uint32_t)kGridLdsPointsMax;
-  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
+  const int n_ty = pass.t.n_ty, n_tz = pass.t.n_tz;
   const int nta = (n_ty + kTile - 1) / kTile, ntb = (n_tz + kTile - 1) / kTile, n_tiles = nta * ntb;
   const uint32_t Mi = lds ? c.walk_mi[f] : 0u;
   // (every condition is uniform over the workgroup)
-  if (!(c.res[f].status == ILCC_OK && lds && nk > 1 && c.box_points != 0u && n_tiles <= kBoxTilesMax && Mall > Mi)) {
-    if (threadIdx.x == 0) grp_alive[tr] = 2u;
+  if (!(c.res[f].status == ILCC_OK && lds && nk > 1 && pass.box_points != 0u && n_tiles <= kBoxTilesMax && Mall > Mi)) {
+    if (threadIdx.x == 0) pass.grp_alive[tr] = 2u;
     return;
   }
   const int lane = lane_id();
   const int wid = __builtin_amdgcn_readfirstlane(wave_id());
   // (the sample never exceeds what launch_group_prepass sized the LDS for: any prefix of the rim-first walk gives a valid bound)
   constexpr int kGroupShift = (THREADS == kGridThreadsLarge && kGridThreadsLarge != kGridThreads) ? kGroupShiftLarge : kGroupShiftSmall;
-  const uint32_t n_pre = min(min(max(c.box_points, Mall >> kGroupShift), Mall - Mi),
-                             max(c.grid_lds_points / 2u + 64u, c.box_points));
+  const uint32_t n_pre = min(min(max(pass.box_points, Mall >> kGroupShift), Mall - Mi),
+                             max(c.grid_lds_points / 2u + 64u, pass.box_points));
   float4* s_w4 = reinterpret_cast<float4*>(smem);   // n_pre x (pi_lo, pi_hi, pj_lo, pj_hi)
   float* s_ay = reinterpret_cast<float*>(s_w4 + n_pre);
   float* s_az = s_ay + n_ty;
@@ -1114,8 +1115,8 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, uint32_t* grp
   float cth[kThetaGroup], sth[kThetaGroup];
 #pragma unroll
   for (int t = 0; t < kThetaGroup; ++t) {
-    cth[t] = c.cth[k0 + min(t, nk - 1)];
-    sth[t] = c.sth[k0 + min(t, nk - 1)];
+    cth[t] = pass.t.cth[k0 + min(t, nk - 1)];
+    sth[t] = pass.t.sth[k0 + min(t, nk - 1)];
   }
   for (uint32_t sl = threadIdx.x; sl < n_pre; sl += THREADS) {
     const float2 v = wyz[Mi + sl];   // the rim-first border-class part of the walk layout: what each theta's own pre-pass looks at
@@ -1133,49 +1134,49 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, uint32_t* grp
     const bool wide = !(ihi - ilo <= 0.5f && jhi - jlo <= 0.5f);
     s_w4[sl] = wide ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(ilo, ihi, jlo, jhi);
   }
-  for (int i = threadIdx.x; i < n_ty; i += THREADS) s_ay[i] = c.ay[i];
-  for (int i = threadIdx.x; i < n_tz; i += THREADS) s_az[i] = c.az[i];
+  for (int i = threadIdx.x; i < n_ty; i += THREADS) s_ay[i] = pass.t.ay[i];
+  for (int i = threadIdx.x; i < n_tz; i += THREADS) s_az[i] = pass.t.az[i];
   for (int w = threadIdx.x; w < (n_tiles + 31) / 32; w += THREADS) s_dead3[w] = 0u;
   if (threadIdx.x == 0) s_any = 0u;
   __syncthreads();
   const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h, delta2 = (float)c.p.huber_delta;
-  const float lim_box = 0.5f * (1.f + kTieEps) * __uint_as_float(__hip_atomic_load(c.grid_bound + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const float lim_box = 0.5f * (1.f + kTieEps) * __uint_as_float(__hip_atomic_load(pass.bound + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   const uint32_t wave_evals = box_prepass_rounds<THREADS>(n_tiles, ntb, 0, 0, n_ty, n_tz, s_ay, s_az, s_dead3, s_live, s_cnt2, &s_any, n_pre, lim_box, Wh, Hh,
                                                           delta2, [&](uint32_t u) { return s_w4[u]; });
   if (lane == 0) s_iters[wid] = wave_evals;
   __syncthreads();
   const bool any_alive = s_any != 0u;
   if (any_alive)
-    for (int w = threadIdx.x; w < (n_tiles + 31) / 32; w += THREADS) grp_mask[(uint64_t)tr * c.grp_words + w] = s_dead3[w];
+    for (int w = threadIdx.x; w < (n_tiles + 31) / 32; w += THREADS) pass.grp_mask[(uint64_t)tr * pass.grp_words + w] = s_dead3[w];
   if (threadIdx.x == 0) {
     unsigned long long box_evals = 0;
     for (int w = 0; w < THREADS / ILCC_WAVE; ++w) box_evals += s_iters[w];
-    count_evals(c, f, kEvalsBox, box_evals);
-    grp_alive[tr] = any_alive ? 1u : 0u;
+    count_evals(c.grid_iters, f, kEvalsBox, box_evals);
+    pass.grp_alive[tr] = any_alive ? 1u : 0u;
   }
 }
 
-void launch_group_prepass(const Ctx& c, hipStream_t s, uint32_t* grp_alive, uint32_t* grp_mask) {
-  const dim3 grid(c.grp_count, c.n_frames);
+void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s) {
+  const dim3 grid(full.grp_count, c.n_frames);
   // LDS: the widened pre-pass points (16 B each: at most M >> 1 of the frame's M <= grid_lds_points labelled points, or box_points of
   // them when that is more -- the static_assert next to kGroupShiftSmall) and the (ty, tz) tables
-  const size_t lds = sizeof(float4) * std::max<size_t>((size_t)c.grid_lds_points / 2 + 64, (size_t)c.box_points) + sizeof(float) * (size_t)(c.p.n_ty + c.p.n_tz);
+  const size_t lds = sizeof(float4) * std::max<size_t>((size_t)c.grid_lds_points / 2 + 64, (size_t)full.box_points) + sizeof(float) * (size_t)(full.t.n_ty + full.t.n_tz);
   if (c.grid_lds_points > (uint32_t)kGridLargeFrom)
-    hipLaunchKernelGGL((k6_group_prepass<kGridThreadsLarge>), grid, dim3(kGridThreadsLarge), lds, s, c, grp_alive, grp_mask);
+    hipLaunchKernelGGL((k6_group_prepass<kGridThreadsLarge>), grid, dim3(kGridThreadsLarge), lds, s, c, full);
   else
-    hipLaunchKernelGGL((k6_group_prepass<kGridThreads>), grid, dim3(kGridThreads), lds, s, c, grp_alive, grp_mask);
+    hipLaunchKernelGGL((k6_group_prepass<kGridThreads>), grid, dim3(kGridThreads), lds, s, c, full);
 }
 
-// ANCHOR (k6_anchor, and the last stage of k6_locate): the 4 x 4 tile at (a_org, b_org) of the full tables at theta k on EVERY
+// ANCHOR (k6_anchor, and the last stage of k6_locate): the 4 x 4 tile at (a_org, b_org) of the full tables t at theta k on EVERY
 // labelled point of the frame, by the n_parts wavefronts of that theta -- blocks of four walk positions go round them, this one takes
 // blocks part, part + n_parts, ...  Writes the quad sums of its 16 candidates (cost / 2 per phase) to s_part[candidate][phase].
 // ty / tz: the translation tables (in LDS or in global memory).
-__device__ __forceinline__ void anchor_walk(const Ctx& c, const FrameWalk& fw, int k, int a_org, int b_org, const float* ty, const float* tz,
+__device__ __forceinline__ void anchor_walk(const ilcc_params& p, const GridTables& t, const FrameWalk& fw, int k, int a_org, int b_org, const float* ty, const float* tz,
                                             uint32_t part, uint32_t n_parts, float (*s_part)[2], uint32_t& pts_done, uint32_t& pts_in) {
   const int my_s = lane_id() & (kSlices - 1), my_c = lane_id() >> 2;
-  const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h, delta2 = (float)c.p.huber_delta;
-  const float cth = c.cth[k], sth = c.sth[k];
-  const float ay = ty[min(a_org + (my_c >> 2), c.p.n_ty - 1)], az = tz[min(b_org + (my_c & 3), c.p.n_tz - 1)];
+  const float Wh = 0.5f * (float)p.board_w, Hh = 0.5f * (float)p.board_h, delta2 = (float)p.huber_delta;
+  const float cth = t.cth[k], sth = t.sth[k];
+  const float ay = ty[min(a_org + (my_c >> 2), t.n_ty - 1)], az = tz[min(b_org + (my_c & 3), t.n_tz - 1)];
   float A0 = 0.f, A1 = 0.f;
   uint32_t pos = 0, pin = 0;
   for (uint32_t at0 = part * kSlices; at0 < fw.M; at0 += n_parts * kSlices) {
@@ -1203,32 +1204,32 @@ __device__ __forceinline__ void anchor_walk(const Ctx& c, const FrameWalk& fw, i
 
 // The anchor's result, by one wavefront behind the barrier that follows the walks: candidate (t, cand) costs the sum of its PARTS
 // partial sums s_part[t * PARTS + part][cand], in part order (the published bound is compared bit for bit downstream); the argmin over
-// (theta k0 + t, candidate) carries (a << 16) | b.  Lane 0 writes the record and lowers the frame's bound: a complete candidate on
+// (theta k0 + th, candidate) of the tables t carries (a << 16) | b.  Lane 0 writes the record and lowers the frame's bound word: a complete candidate on
 // every point is a valid bound.
 template <int THETAS, int PARTS>
-__device__ __forceinline__ void anchor_publish(const Ctx& c, uint32_t f, const float (*s_part)[16][2], int k0, int a_org, int b_org,
+__device__ __forceinline__ void anchor_publish(const GridTables& t, uint32_t* bound, const float (*s_part)[16][2], int k0, int a_org, int b_org,
                                                GridPartial* out) {
   const int lane = lane_id();
-  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
+  const int n_ty = t.n_ty, n_tz = t.n_tz;
   Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
   uint32_t ab = 0;
   if (lane < 16 * THETAS) {
-    const int t = lane >> 4, cand = lane & 15;
-    const int k = min(max(k0 + t, 0), c.p.n_th - 1), ja = a_org + (cand >> 2), jb = b_org + (cand & 3);
+    const int th = lane >> 4, cand = lane & 15;
+    const int k = min(max(k0 + th, 0), t.n_th - 1), ja = a_org + (cand >> 2), jb = b_org + (cand & 3);
     if (ja < n_ty && jb < n_tz) {
       float h0 = 0.f, h1 = 0.f;
 #pragma unroll
       for (int q = 0; q < PARTS; ++q) {
-        h0 += s_part[t * PARTS + q][cand][0];
-        h1 += s_part[t * PARTS + q][cand][1];
+        h0 += s_part[th * PARTS + q][cand][0];
+        h1 += s_part[th * PARTS + q][cand][1];
       }
-      score(2.f * h0, 2.f * h1, k, ja, jb, n_ty, n_tz, c.c_th, c.c_ty, c.c_tz, best, ab);
+      score(2.f * h0, 2.f * h1, k, ja, jb, n_ty, n_tz, t.c_th, t.c_ty, t.c_tz, best, ab);
     }
   }
   best = wave_argmin<true>(best, ab);
   if (lane == 0) {
     *out = GridPartial{best.cost, best.d2, best.flat, ab};
-    if (best.flat != 0xFFFFFFFFu) atomicMin(c.grid_bound + f, __float_as_uint(best.cost));
+    if (best.flat != 0xFFFFFFFFu) atomicMin(bound, __float_as_uint(best.cost));
   }
 }
 
@@ -1258,7 +1259,7 @@ constexpr int kAnchorParts = (kLocateThreads / 64) / kAnchorThetas;  // wavefron
 constexpr int kLocateWaves = kLocateThreads / ILCC_WAVE;
 constexpr int kLocateThetasMax = 16;      // rotations of the sample kept in LDS at a time (seed: 5, refinement: 2 r + 1 = 9)
 // k6_locate's refinement window, in tiles per axis: 2 (8 x 8 translations around the seed's argmin) on EVERY grid.  The separate
-// launches widen theirs to 4 tiles (16 x 16) on grids whose seed stride is wider than 8 translations (Ctx::refine_window); whether
+// launches widen theirs to 4 tiles (16 x 16) on grids whose seed stride is wider than 8 translations (GridPass::window_tiles); whether
 // this path should too is a change of its own, to be measured.
 constexpr int kLocateWindowTiles = 2;
 __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp) {
@@ -1281,7 +1282,9 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   const uint32_t Ms = min(fw.sample(lp.sample_min), lp.sample_cap);
   uint32_t n_in, n_rm;
   fw.prefix(Ms, n_in, n_rm);
-  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz, n_th = c.p.n_th;
+  const GridTables& full = c.grid;   // (the seed scores lp.seed, refinement and anchor the full tables)
+  const int n_ty = full.n_ty, n_tz = full.n_tz, n_th = full.n_th;
+  const int n_ty2 = lp.seed.n_ty, n_tz2 = lp.seed.n_tz;
   // dynamic LDS: the raw sample, its rotations, the (ty, tz) tables (full, then the seed's)
   float2* s_raw = reinterpret_cast<float2*>(smem);
   float* s_hw = reinterpret_cast<float*>(s_raw + lp.sample_cap);
@@ -1289,16 +1292,16 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   float* s_ay = reinterpret_cast<float*>(s_rot + (size_t)kLocateThetasMax * lp.sample_cap);
   float* s_az = s_ay + n_ty;
   float* s_ay2 = s_az + n_tz;
-  float* s_az2 = s_ay2 + lp.n_ty2;
+  float* s_az2 = s_ay2 + n_ty2;
   for (uint32_t sl = threadIdx.x; sl < Ms; sl += kLocateThreads) {
     const uint32_t src = fw.source(sl, n_in, n_rm);
     s_raw[sl] = fw.yz[src];
     s_hw[sl] = fw.lab[src] ? 0.5f : 0.f;
   }
-  for (int i = threadIdx.x; i < n_ty; i += kLocateThreads) s_ay[i] = c.ay[i];
-  for (int i = threadIdx.x; i < n_tz; i += kLocateThreads) s_az[i] = c.az[i];
-  for (int i = threadIdx.x; i < lp.n_ty2; i += kLocateThreads) s_ay2[i] = lp.ay2[i];
-  for (int i = threadIdx.x; i < lp.n_tz2; i += kLocateThreads) s_az2[i] = lp.az2[i];
+  for (int i = threadIdx.x; i < n_ty; i += kLocateThreads) s_ay[i] = full.ay[i];
+  for (int i = threadIdx.x; i < n_tz; i += kLocateThreads) s_az[i] = full.az[i];
+  for (int i = threadIdx.x; i < n_ty2; i += kLocateThreads) s_ay2[i] = lp.seed.ay[i];
+  for (int i = threadIdx.x; i < n_tz2; i += kLocateThreads) s_az2[i] = lp.seed.az[i];
   if (threadIdx.x == 0) s_bound = 0x7f800000u;
   const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h, delta2 = (float)c.p.huber_delta;
   const int my_s = lane & (kSlices - 1), my_c = lane >> 2, my_a = my_c >> 2, my_b = my_c & 3;
@@ -1388,11 +1391,11 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
   __syncthreads();
 
   // ---- 1. seed: n_th2 thetas x (n_ty2 x n_tz2 decimated translations) on the sample
-  const int n_th2 = min(lp.n_th2, kLocateThetasMax);
-  rotate_sample(n_th2, [&](int r) { return r; }, lp.cth2, lp.sth2);
+  const int n_th2 = min(lp.seed.n_th, kLocateThetasMax);
+  rotate_sample(n_th2, [&](int r) { return r; }, lp.seed.cth, lp.seed.sth);
   __syncthreads();
   {
-    const int nta = (lp.n_ty2 + kTile - 1) / kTile, ntb = (lp.n_tz2 + kTile - 1) / kTile, per = nta * ntb, n_tiles = n_th2 * per;
+    const int nta = (n_ty2 + kTile - 1) / kTile, ntb = (n_tz2 + kTile - 1) / kTile, per = nta * ntb, n_tiles = n_th2 * per;
     Best best{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
     uint32_t best_ab = 0;
     // The order of the tiles never changes the result (only provably losing candidates are cut, ties never), but it decides how
@@ -1406,7 +1409,7 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
         const int k2 = t / per, q = t - k2 * per, ta = q / ntb, tb = q - ta * ntb;
         const int ia = ta * kTile + my_a, ib = tb * kTile + my_b;
         const float2* rot = s_rot + (size_t)k2 * lp.sample_cap;
-        const float ay = s_ay2[min(ia, lp.n_ty2 - 1)], az = s_az2[min(ib, lp.n_tz2 - 1)];
+        const float ay = s_ay2[min(ia, n_ty2 - 1)], az = s_az2[min(ib, n_tz2 - 1)];
         float A0 = 0.f, A1 = 0.f;
         for (uint32_t at0 = n_in; at0 < min(Ms, n_in + (uint32_t)kSeedPeek); at0 += kSlices) {
           const uint32_t at = at0 + (uint32_t)my_s;
@@ -1416,7 +1419,7 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
           }
         }
         pts_done += min(Ms - n_in, (uint32_t)kSeedPeek);
-        const float pm = wave_min((ia < lp.n_ty2 && ib < lp.n_tz2) ? fminf(quad_sum(A0), quad_sum(A1)) : __builtin_inff());
+        const float pm = wave_min((ia < n_ty2 && ib < n_tz2) ? fminf(quad_sum(A0), quad_sum(A1)) : __builtin_inff());
         if (pm < peek_best) {   // (wave-uniform)
           peek_best = pm;
           t_first = t;
@@ -1429,10 +1432,10 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
       if (it >= 0 && t == t_first) continue;
       const int k2 = t / per, q = t - k2 * per, ta = q / ntb, tb = q - ta * ntb;
       const int ia = ta * kTile + my_a, ib = tb * kTile + my_b;
-      const bool owner = ia < lp.n_ty2 && ib < lp.n_tz2;
+      const bool owner = ia < n_ty2 && ib < n_tz2;
       float c0, c1;
-      if (!sample_tile(s_rot + (size_t)k2 * lp.sample_cap, s_ay2[min(ia, lp.n_ty2 - 1)], s_az2[min(ib, lp.n_tz2 - 1)], c0, c1)) continue;
-      if (owner) score(c0, c1, k2, ia, ib, lp.n_ty2, lp.n_tz2, lp.c_th2, lp.c_ty2, lp.c_tz2, best, best_ab);
+      if (!sample_tile(s_rot + (size_t)k2 * lp.sample_cap, s_ay2[min(ia, n_ty2 - 1)], s_az2[min(ib, n_tz2 - 1)], c0, c1)) continue;
+      if (owner) score(c0, c1, k2, ia, ib, n_ty2, n_tz2, lp.seed.c_th, lp.seed.c_ty, lp.seed.c_tz, best, best_ab);
       lower_sample_bound(owner ? fminf(c0, c1) : __builtin_inff());
     }
     reduce_best(best, best_ab);
@@ -1442,15 +1445,15 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
     return;
   }
   // ---- 2. refinement: theta within +- refine_radius steps of the seed's, the window of full-table translations around its argmin
-  const int k2s = (int)((s_pick[0] >> 1) / (uint32_t)(lp.n_ty2 * lp.n_tz2));
-  const int sa = min((int)(s_pick[1] >> 16) * lp.stride_t, n_ty - 1), sbb = min((int)(s_pick[1] & 0xFFFFu) * lp.stride_t, n_tz - 1);
+  const int k2s = (int)((s_pick[0] >> 1) / (uint32_t)(n_ty2 * n_tz2));
+  const int sa = min((int)(s_pick[1] >> 16) * lp.map.stride_t, n_ty - 1), sbb = min((int)(s_pick[1] & 0xFFFFu) * lp.map.stride_t, n_tz - 1);
   // every OTHER theta of the refinement's range: the anchor scores theta - 1, theta, theta + 1 around its argmin on every point, so
   // the thetas in between are still looked at -- measured: locate 0.265 -> 0.229 ms alone, the full pass's time and executed work
   // unchanged (the bound is as tight), bench 1085 -> 1112 k frames/s; every fourth theta, or every other translation: no further gain
   constexpr int kRefStride = kRefineThetaStride;
   const int n_ref = min(2 * (lp.refine_radius / kRefStride) + 1, kLocateThetasMax);
-  const int k_ref0 = lp.off_th + k2s * lp.stride_th - (lp.refine_radius / kRefStride) * kRefStride;
-  rotate_sample(n_ref, [&](int r) { return min(max(k_ref0 + kRefStride * r, 0), n_th - 1); }, c.cth, c.sth);
+  const int k_ref0 = lp.map.off_th + k2s * lp.map.stride_th - (lp.refine_radius / kRefStride) * kRefStride;
+  rotate_sample(n_ref, [&](int r) { return min(max(k_ref0 + kRefStride * r, 0), n_th - 1); }, full.cth, full.sth);
   __syncthreads();
   {
     constexpr int kWindow = kLocateWindowTiles * kTile;
@@ -1466,7 +1469,7 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
       const bool owner = ia < n_ty && ib < n_tz;
       float c0, c1;
       if (!sample_tile(s_rot + (size_t)r * lp.sample_cap, s_ay[min(ia, n_ty - 1)], s_az[min(ib, n_tz - 1)], c0, c1)) continue;
-      if (owner) score(c0, c1, k, ia, ib, n_ty, n_tz, c.c_th, c.c_ty, c.c_tz, best, best_ab);
+      if (owner) score(c0, c1, k, ia, ib, n_ty, n_tz, full.c_th, full.c_ty, full.c_tz, best, best_ab);
       lower_sample_bound(owner ? fminf(c0, c1) : __builtin_inff());
     }
     reduce_best(best, best_ab);
@@ -1480,11 +1483,11 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
     const int k0 = kr - kAnchorThetas / 2;
     if (wid < kAnchorThetas * kAnchorParts) {
       const int t = wid % kAnchorThetas, part = wid / kAnchorThetas;
-      anchor_walk(c, fw, min(max(k0 + t, 0), n_th - 1), a_org, b_org, s_ay, s_az, (uint32_t)part, kAnchorParts, s_part[t * kAnchorParts + part],
+      anchor_walk(c.p, full, fw, min(max(k0 + t, 0), n_th - 1), a_org, b_org, s_ay, s_az, (uint32_t)part, kAnchorParts, s_part[t * kAnchorParts + part],
                   pts_done, pts_in);
     }
     __syncthreads();
-    if (wid == 0) anchor_publish<kAnchorThetas, kAnchorParts>(c, f, s_part, k0, a_org, b_org, out);
+    if (wid == 0) anchor_publish<kAnchorThetas, kAnchorParts>(full, c.grid_bound + f, s_part, k0, a_org, b_org, out);
   }
   if (lane == 0) {
     s_iters[wid] = pts_done;
@@ -1497,8 +1500,8 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
       it_sum += s_iters[w];
       in_sum += s_iters_in[w];
     }
-    count_evals(c, f, kEvalsAll, it_sum);
-    count_evals(c, f, kEvalsInterior, in_sum);
+    count_evals(c.grid_iters, f, kEvalsAll, it_sum);
+    count_evals(c.grid_iters, f, kEvalsInterior, in_sum);
   }
 }
 
@@ -1513,47 +1516,47 @@ __global__ __launch_bounds__(kLocateThreads) void k6_locate(Ctx c, LocatePlan lp
 // point-candidate evaluations per 64 frames in the full pass, 224 -> 189 M in the pre-passes).
 constexpr int kAnchorThreads = 512;
 constexpr int kAnchorWaves = kAnchorThreads / ILCC_WAVE;
-__global__ __launch_bounds__(kAnchorThreads) void k6_anchor(Ctx c) {
+__global__ __launch_bounds__(kAnchorThreads) void k6_anchor(Ctx c, GridPass pass) {
   __shared__ float s_part[kAnchorWaves][16][2];
   __shared__ uint32_t s_iters[kAnchorWaves], s_iters_in[kAnchorWaves];
   const uint32_t f = blockIdx.y, kblk = blockIdx.x;
-  GridPartial* out = &c.partial[(uint64_t)f * c.grid_blocks + kblk];
+  GridPartial* out = &pass.out[(uint64_t)f * pass.blocks + kblk];
   const int lane = lane_id();
   const int wid = __builtin_amdgcn_readfirstlane(wave_id());
   uint32_t k2u = 0, ab = 0;
   Best sb{__builtin_inff(), 0xFFFFFFFFu, 0xFFFFFFFFu};
-  if (c.res[f].status == ILCC_OK) sb = seed_argmin(c, f, k2u, ab);
+  if (c.res[f].status == ILCC_OK) sb = seed_argmin(pass.seed, f, k2u, ab);
   if (sb.flat == 0xFFFFFFFFu) {
     if (threadIdx.x == 0) no_candidate(out);
     return;
   }
-  const int n_ty = c.p.n_ty, n_tz = c.p.n_tz;
+  const int n_ty = pass.t.n_ty, n_tz = pass.t.n_tz;
   const int kr = (int)((sb.flat >> 1) / (uint32_t)(n_ty * n_tz));   // (the records come from launches over the full tables)
-  const int k0 = kr + (int)kblk - c.refine_radius_th;                 // this workgroup's theta, before the clamp to the table
+  const int k0 = kr + (int)kblk - pass.radius_th;                      // this workgroup's theta, before the clamp to the table
   const int ra = min((int)(ab >> 16), n_ty - 1), rb = min((int)(ab & 0xFFFFu), n_tz - 1);
   const int a_org = window_origin(ra, 1, n_ty, kTile), b_org = window_origin(rb, 1, n_tz, kTile);
   uint32_t pts_done = 0, pts_in = 0;
-  anchor_walk(c, FrameWalk(c, f), min(max(k0, 0), c.p.n_th - 1), a_org, b_org, c.ay, c.az, (uint32_t)wid, kAnchorWaves, s_part[wid], pts_done,
+  anchor_walk(c.p, pass.t, FrameWalk(c, f), min(max(k0, 0), pass.t.n_th - 1), a_org, b_org, pass.t.ay, pass.t.az, (uint32_t)wid, kAnchorWaves, s_part[wid], pts_done,
               pts_in);
   if (lane == 0) {
     s_iters[wid] = pts_done;
     s_iters_in[wid] = pts_in;
   }
   __syncthreads();
-  if (wid == 0) anchor_publish<1, kAnchorWaves>(c, f, s_part, k0, a_org, b_org, out);
+  if (wid == 0) anchor_publish<1, kAnchorWaves>(pass.t, pass.bound + f, s_part, k0, a_org, b_org, out);
   if (threadIdx.x == 0) {
     uint32_t it_sum = 0, in_sum = 0;
     for (int w = 0; w < kAnchorWaves; ++w) {
       it_sum += s_iters[w];
       in_sum += s_iters_in[w];
     }
-    count_evals(c, f, kEvalsAll, it_sum);
-    count_evals(c, f, kEvalsInterior, in_sum);
+    count_evals(c.grid_iters, f, kEvalsAll, it_sum);
+    count_evals(c.grid_iters, f, kEvalsInterior, in_sum);
   }
 }
 
-void launch_anchor(const Ctx& c, hipStream_t s) {
-  hipLaunchKernelGGL(k6_anchor, dim3(c.grid_blocks, c.n_frames), dim3(kAnchorThreads), 0, s, c);
+void launch_anchor(const Ctx& c, const GridPass& pass, hipStream_t s) {
+  hipLaunchKernelGGL(k6_anchor, dim3(pass.blocks, c.n_frames), dim3(kAnchorThreads), 0, s, c, pass);
 }
 
 size_t locate_lds_bytes(uint32_t sample_cap, int n_ty, int n_tz, int n_ty2, int n_tz2) {
@@ -1562,7 +1565,7 @@ size_t locate_lds_bytes(uint32_t sample_cap, int n_ty, int n_tz, int n_ty2, int 
 }
 
 void launch_locate(const Ctx& c, hipStream_t s, const LocatePlan& lp) {
-  const size_t lds = locate_lds_bytes(lp.sample_cap, c.p.n_ty, c.p.n_tz, lp.n_ty2, lp.n_tz2);
+  const size_t lds = locate_lds_bytes(lp.sample_cap, c.grid.n_ty, c.grid.n_tz, lp.seed.n_ty, lp.seed.n_tz);
   hipLaunchKernelGGL(k6_locate, dim3(c.n_frames), dim3(kLocateThreads), lds, s, c, lp);
 }
 
@@ -1601,14 +1604,15 @@ __global__ __launch_bounds__(kWalkThreads) void k5w_walk_order(Ctx c) {
   const uint8_t* __restrict__ glab = c.lab + beg;
   const uint32_t S = c.walk_stride[f];
   const float Wh = 0.5f * (float)c.p.board_w, Hh = 0.5f * (float)c.p.board_h;
-  const float ay_lo = c.ay[0], ay_hi = c.ay[c.p.n_ty - 1], az_lo = c.az[0], az_hi = c.az[c.p.n_tz - 1];
-  const float ay_c = c.ay[c.c_ty], az_c = c.az[c.c_tz];
+  const GridTables& t = c.grid;
+  const float ay_lo = t.ay[0], ay_hi = t.ay[t.n_ty - 1], az_lo = t.az[0], az_hi = t.az[t.n_tz - 1];
+  const float ay_c = t.ay[t.c_ty], az_c = t.az[t.c_tz];
   const float rim_thr = -(float)kRimMilli * 1e-3f;
-  const int n_th = c.p.n_th;
+  const int n_th = t.n_th;
   float cmax = 0.f, smax = 0.f;   // (uniform: the tables are a few dozen values)
   for (int k = 0; k < n_th; ++k) {
-    cmax = fmaxf(cmax, fabsf(c.cth[k]));
-    smax = fmaxf(smax, fabsf(c.sth[k]));
+    cmax = fmaxf(cmax, fabsf(t.cth[k]));
+    smax = fmaxf(smax, fabsf(t.sth[k]));
   }
   const float room_i = fminf(fminf(ay_lo, ay_hi), 2.f * Wh - fmaxf(ay_lo, ay_hi)), room_j = fminf(fminf(az_lo, az_hi), 2.f * Hh - fmaxf(az_lo, az_hi));
   // class of every walk slot: 0 interior, 1 other border, 2 rim
@@ -1622,7 +1626,7 @@ __global__ __launch_bounds__(kWalkThreads) void k5w_walk_order(Ctx c) {
     const bool inside_always = bi + 1e-4f < room_i && bj + 1e-4f < room_j;
     int cl = 0;
     if (!inside_always) {
-      const float2 p = rotate(v, c.cth[c.c_th], c.sth[c.c_th]);
+      const float2 p = rotate(v, t.cth[t.c_th], t.sth[t.c_th]);
       const float uc = fabsf((p.x + ay_c) - Wh) - Wh, wc = fabsf((p.y + az_c) - Hh) - Hh;
       cl = (fmaxf(uc, wc) > rim_thr) ? 2 : 1;
     }
@@ -1764,27 +1768,27 @@ hipError_t set_kernel_attributes_k6() {
   return hipSuccess;
 }
 
-void launch_grid_cost(const Ctx& c, hipStream_t s, int32_t use_oob, float* cost_volume, bool prune) {
-  const dim3 grid(c.grid_blocks, c.n_frames), block(kGridThreads);
-  const size_t lds = (sizeof(float2) + sizeof(float)) * (size_t)c.grid_lds_points + sizeof(float) * (size_t)(c.p.n_ty + c.p.n_tz);
+void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume, bool prune) {
+  const dim3 grid(pass.blocks, c.n_frames), block(kGridThreads);
+  const size_t lds = (sizeof(float2) + sizeof(float)) * (size_t)c.grid_lds_points + sizeof(float) * (size_t)(pass.t.n_ty + pass.t.n_tz);
   // the diagnostic volume is always a complete evaluation (no pruning)
   if (cost_volume) {
     if (use_oob)
-      hipLaunchKernelGGL((k6_grid_cost<true, true, false, kGridThreads>), grid, block, lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<true, true, false, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
     else
-      hipLaunchKernelGGL((k6_grid_cost<false, true, false, kGridThreads>), grid, block, lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<false, true, false, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
   } else if (prune) {
     if (use_oob && c.grid_lds_points > (uint32_t)kGridLargeFrom)   // the pipeline's launches on large frames
-      hipLaunchKernelGGL((k6_grid_cost<true, false, true, kGridThreadsLarge>), grid, dim3(kGridThreadsLarge), lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<true, false, true, kGridThreadsLarge>), grid, dim3(kGridThreadsLarge), lds, s, c, pass, cost_volume);
     else if (use_oob)
-      hipLaunchKernelGGL((k6_grid_cost<true, false, true, kGridThreads>), grid, block, lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<true, false, true, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
     else
-      hipLaunchKernelGGL((k6_grid_cost<false, false, true, kGridThreads>), grid, block, lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<false, false, true, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
   } else {
     if (use_oob)
-      hipLaunchKernelGGL((k6_grid_cost<true, false, false, kGridThreads>), grid, block, lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<true, false, false, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
     else
-      hipLaunchKernelGGL((k6_grid_cost<false, false, false, kGridThreads>), grid, block, lds, s, c, cost_volume);
+      hipLaunchKernelGGL((k6_grid_cost<false, false, false, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
   }
 }
 

@@ -1235,17 +1235,17 @@ __device__ void refine_frame(const Ctx& c, SolveRec* rec, float2* s_yz, uint8_t*
       for (int dk = -1; dk <= 1; ++dk) {
         const int k = gk + dk;
         if (k < 0 || k >= c.p.n_th) continue;
-        const float cth = c.cth[k], sth = c.sth[k];
+        const float cth = c.grid.cth[k], sth = c.grid.sth[k];
         const float pi = fmaf(-sth, v.y, cth * v.x), pj = fmaf(cth, v.y, sth * v.x);   // = k6_grid_cost's staging
 #pragma unroll
         for (int d = -1; d <= 1; ++d) {
           const int a = ga + d, b = gb + d;
           if (a >= 0 && a < (int)n_ty) {
-            const float x = pi + c.ay[a];
+            const float x = pi + c.grid.ay[a];
             risk |= fabsf(x - rintf(x)) < kBorderRisk;
           }
           if (b >= 0 && b < (int)n_tz) {
-            const float x = pj + c.az[b];
+            const float x = pj + c.grid.az[b];
             risk |= fabsf(x - rintf(x)) < kBorderRisk;
           }
         }
