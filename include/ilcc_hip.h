@@ -206,13 +206,15 @@ typedef struct ilcc_timing {
    * (nothing else on the chip) they are what a rocprofv3 kernel trace of the same run adds up to. */
   double grid_cost_kernel_ms_sum;   /* sum over batches of the event spans of seed + refinement + anchor + common pre-pass + full pass, ms */
   double grid_cost_full_ms_sum;     /* the full pass alone */
-  double walk_order_ms_sum;         /* K5w (once per frame, in front of the K6 launches) */
+  double walk_order_ms_sum;         /* K5w (once per frame, in front of the K6 launches); 0 for batches whose front end ran as one launch (below) */
   double grid_cost_prepass_ms_sum;  /* ABI 5: the common pre-pass (k6_group_prepass) alone; it is part of grid_cost_kernel_ms_sum */
   double grid_cost_locate_ms_sum;   /* ABI 5: seed + refinement + anchor (the launches that only locate the minimum and publish the bound) */
   /* ABI 5: every stage accumulated over the batches since ilcc_reset_timing (the float fields above are the LAST batch only) */
   uint64_t batches;                 /* batches accounted */
   double stage_ms_sum[7];           /* roi_crop, cluster, ransac_plane, plane_frame_hist, grid_cost, refine_corners, total */
-  double roi_count_ms_sum;          /* K1's count pass alone -- the kernel that reads every input point once (the HBM-bound one) */
+  double roi_count_ms_sum;          /* K1's count pass alone -- the kernel that reads every input point once (the HBM-bound one).  Batches of 512
+                                       frames and more crop in ONE pass (k1_roi_crop_frame), which is then what this times: it still reads
+                                       every input point exactly once */
   uint64_t online_second_tier_frames; /* ilcc_chessboard_by_point_batch: frames whose answer needed the whole cloud clustered (the first
                                          tier answers from a window around the predicted point and verifies it) */
 } ilcc_timing;
@@ -381,8 +383,17 @@ int32_t ilcc_get_theta_t(ilcc_handle* h, const float* yz, const uint8_t* label, 
  * common pre-pass (= ready for the full pass), full pass start (behind the wait for the previous batch's full pass), full pass
  * end, end of K7.  ilcc_debug_timeline_fetch copies up to cap_rows rows (oldest first) and clears the log; returns the rows. */
 #define ILCC_TIMELINE_COLS 15
+/* Batches of more than 64 frames (outside the online calls) run K3, K4/K5 and -- GRID solver -- K5w as ONE launch (k345_front_end).
+ * The events behind K3, K4/K5 and K5w are then recorded back to back behind it: the whole launch is accounted as `ransac_plane`
+ * (stage_ms_sum[2]), and `plane_frame_hist` (stage_ms_sum[3]) and walk_order_ms_sum read 0 for such a batch (the few microseconds
+ * between two event records) -- as `seed` carries k6_locate. */
 int32_t ilcc_debug_timeline_enable(ilcc_handle* h, int32_t on);
 int32_t ilcc_debug_timeline_fetch(ilcc_handle* h, double* rows, uint32_t cap_rows);
+
+/* Diagnostic: on != 0 makes the handle run K3, K4/K5 and K5w as launches of their own and the ROI crop as its two kernels at any
+ * batch size (what small batches run anyway); 0 restores the default.  Results are identical either way -- the tests and the A/B
+ * measurements compare the two.  No batch may be in flight. */
+int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on);
 
 void ilcc_get_timing(const ilcc_handle* h, ilcc_timing* t);
 void ilcc_reset_timing(ilcc_handle* h);

@@ -33,7 +33,7 @@ EXPORTS = [
     "ilcc_grid_cost", "ilcc_grid_solve", "ilcc_pattern_refine", "ilcc_get_theta_t", "ilcc_get_timing", "ilcc_reset_timing",
     "ilcc_save_corners2txt", "ilcc_read_lidar_corners",
     "ilcc_set_result_mode", "ilcc_wait_compact", "ilcc_record_floats", "ilcc_fetch_results",
-    "ilcc_debug_timeline_enable", "ilcc_debug_timeline_fetch",
+    "ilcc_debug_timeline_enable", "ilcc_debug_timeline_fetch", "ilcc_debug_separate_launches",
 ]
 ABI_VERSION = 5            # the layout of Params / Result / Timing below is ILCC_ABI_VERSION 5 of include/ilcc_hip.h
 RESULTS_FULL, RESULTS_COMPACT = 0, 1
@@ -215,6 +215,9 @@ def lib():
         L.ilcc_debug_timeline_enable.restype = C.c_int32
         L.ilcc_debug_timeline_fetch.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32]
         L.ilcc_debug_timeline_fetch.restype = C.c_int32
+        if hasattr(L, "ilcc_debug_separate_launches"):   # (an ILCC_HIP_LIB build from before the entry existed: A/B runs against it)
+            L.ilcc_debug_separate_launches.argtypes = [vp, C.c_int32]
+            L.ilcc_debug_separate_launches.restype = C.c_int32
         L.ilcc_fetch_results.argtypes = [vp, C.c_uint32, C.c_uint32, rp]
         L.ilcc_fetch_results.restype = C.c_int32
         _lib = L

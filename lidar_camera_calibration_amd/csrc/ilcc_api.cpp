@@ -132,6 +132,7 @@ struct ilcc_handle {
   ilcc_timing timing{};
   hipEvent_t tl_ref = nullptr;       // ilcc_debug_timeline_*: reference event, rows of ILCC_TIMELINE_COLS doubles
   bool tl_on = false;
+  bool separate_launches = false;    // ilcc_debug_separate_launches: K3, K4/K5, K5w and K1's two kernels as launches of their own at any batch size
   std::vector<double> tl_rows;
   std::string err;
 };
@@ -693,9 +694,10 @@ int32_t enqueue_locate_launches(ilcc_handle* h, Slot& sl, const Ctx& c, hipStrea
 // or seed + refinement + anchor rounds), the common pre-pass, the full pass -- with the slot's K6 events recorded in between.
 // chain: the full pass waits for the previous batch's, on whichever stream that one runs (every batch; the diagnostic entry
 // ilcc_grid_solve runs alone).
-int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, uint32_t n_frames, bool chain) {
+// walk_laid_out: the front end's one launch has written the walk layout already.
+int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t s, uint32_t n_frames, bool chain, bool walk_laid_out = false) {
   const bool prune = h->p.grid_prune != 0;
-  launch_walk_order(c, s);   // K5w: the labelled points in K6's walk layout, once per frame
+  if (!walk_laid_out) launch_walk_order(c, s);   // K5w: the labelled points in K6's walk layout, once per frame
   HIP_TRY(h, hipEventRecord(sl.ev[kEvWalkOrdered], s));
   GridSeed located{};   // (records == nullptr: nothing located)
   // (grid_prune = 0 keeps the locate launches: they only initialise the frame's bound, which the cut-free full
@@ -774,7 +776,8 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
   Ctx c = make_ctx(h, sl, d_xyzi, d_clicks, n_frames, chunks);
   HIP_TRY(h, hipEventRecord(sl.ev[kEvStart], s));
   if (!no_crop) {
-    launch_roi_crop(c, s, sl.ev[kEvCropCounted]);
+    // (one pass, one workgroup per frame, when the batch has the frames for it)
+    launch_roi_crop(c, s, sl.ev[kEvCropCounted], !h->separate_launches && n_frames >= (uint32_t)kCropFrameMinFrames);
     HIP_TRY(h, hipEventRecord(sl.ev[kEvCropped], s));
     launch_cluster(c, s);
   } else {
@@ -802,13 +805,21 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     HIP_TRY(h, hipMemcpyAsync(sl.h_online + h->max_frames, sl.d_nfinite, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvClustered], s));
-  launch_ransac_plane(c, s);
-  HIP_TRY(h, hipEventRecord(sl.ev[kEvPlane], s));
-  launch_plane_frame_hist(c, s);
   sl.grid = !front_only && h->p.solver == ILCC_SOLVER_GRID;
+  // K3, K4/K5 and (GRID mode) K5w: one launch when the batch would run them at the same width anyway.  The whole launch is then
+  // accounted as the K3 span, like k6_locate as the seed's
+  const bool one_launch = !h->separate_launches && front_end_fusable(c);
+  if (one_launch) {
+    launch_front_end(c, s, /*walk_layout=*/sl.grid);
+    HIP_TRY(h, hipEventRecord(sl.ev[kEvPlane], s));
+  } else {
+    launch_ransac_plane(c, s);
+    HIP_TRY(h, hipEventRecord(sl.ev[kEvPlane], s));
+    launch_plane_frame_hist(c, s);
+  }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvLabelled], s));
   if (sl.grid) {
-    const int32_t st = enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/true);
+    const int32_t st = enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/true, /*walk_laid_out=*/one_launch);
     if (st != ILCC_OK) return st;
   }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvSearched], s));
@@ -1785,6 +1796,18 @@ int32_t ilcc_debug_timeline_enable(ilcc_handle* h, int32_t on) {
     HIP_TRY(h, hipEventRecord(h->tl_ref, h->stream[0]));
     HIP_TRY(h, hipEventSynchronize(h->tl_ref));
   }
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on) {
+  if (!h) return ILCC_BAD_ARGUMENT;
+  for (const Slot& sl : h->slots) {
+    if (sl.busy) {
+      h->err = "ilcc_debug_separate_launches with a batch in flight: ilcc_wait first";
+      return ILCC_BAD_ARGUMENT;
+    }
+  }
+  h->separate_launches = on != 0;
   return ILCC_OK;
 }
 

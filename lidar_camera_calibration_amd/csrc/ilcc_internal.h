@@ -31,6 +31,10 @@ constexpr int kPlaneThreadsSmallBatch = 1024;     // K3 in batches of <= kSmallB
 #endif
 constexpr int kSmallBatchFrames = ILCC_SMALL_BATCH;   // batches this small cannot fill 256 CUs with one workgroup per frame: the per-frame kernels go wide
 constexpr int kHistThreads = ILCC_K45_THREADS;    // K4/K5: one workgroup per frame
+// K5w.  256 threads: in the pipeline the kernel runs beside another batch's full pass, and a 1024-thread workgroup needs 16 free wave
+// slots on ONE CU while that pass keeps refilling them -- its span on the batch's stream was 0.65 ms against 0.04 ms alone, the
+// largest item of a batch's front end (tools/dev_depth_timeline.py).  1024 -> 256 threads: bench 1105 -> 1157 k frames/s
+constexpr int kWalkThreads = 256;
 #ifndef ILCC_K6_THREADS
 #define ILCC_K6_THREADS 256
 #endif
@@ -314,10 +318,18 @@ constexpr int kRefineThetaStride = 2;  // the refinement scores every other thet
 constexpr int kLocateMinFrames = 512;   // smaller batches keep the three launches: a frame's workgroups per theta are what fills the chip there (128 frames alone: 0.27 ms in three launches, 0.30 ms in one)
 
 // ---------------------------------------------------------------- launchers (one per stage TU)
-void launch_roi_crop(const Ctx& c, hipStream_t s, hipEvent_t after_count = nullptr);   // after_count: recorded between the count pass and the scatter
+// after_count: recorded between the count pass and the scatter; one_pass: k1_roi_crop_frame, one workgroup per frame (behind which after_count is recorded)
+void launch_roi_crop(const Ctx& c, hipStream_t s, hipEvent_t after_count = nullptr, bool one_pass = false);
+constexpr int kCropFrameMinFrames = 512;   // the one-pass crop needs a frame per workgroup slot of the chip (256 CUs x 4); smaller batches keep (chunk, frame) workgroups
 void launch_cluster(const Ctx& c, hipStream_t s);
 void launch_ransac_plane(const Ctx& c, hipStream_t s);
 void launch_plane_frame_hist(const Ctx& c, hipStream_t s);
+// K3 + K4/K5 (+ K5w with walk_layout) in one launch, one workgroup per frame (k345_front_end.hip): batches that would run all of
+// them at the same width (front_end_fusable)
+void launch_front_end(const Ctx& c, hipStream_t s, bool walk_layout);
+inline bool front_end_fusable(const Ctx& c) {
+  return kPlaneThreads == kHistThreads && kHistThreads == kWalkThreads && c.n_frames > (uint32_t)kSmallBatchFrames && !c.wide;
+}
 void launch_walk_order(const Ctx& c, hipStream_t s);   // K5w (k6_grid_cost.hip): before any launch_grid_cost on the frames
 void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/, bool prune);
 void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // in front of the full pass it is given: writes full.grp_alive / grp_mask

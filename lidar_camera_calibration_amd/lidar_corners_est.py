@@ -246,6 +246,13 @@ class LidarCornersBatch:
         if st != N.OK:
             raise IlccError(st, self._err())
 
+    def debug_separate_launches(self, on: bool):
+        """Diagnostic: K3, K4/K5, K5w and the ROI crop's two kernels as launches of their own at any batch size (``on``), or the
+        default -- one front-end launch and a one-pass crop in large batches.  Results are identical either way."""
+        st = self._lib.ilcc_debug_separate_launches(self._h, 1 if on else 0)
+        if st != N.OK:
+            raise IlccError(st, self._err())
+
     def wait_compact(self, ticket) -> np.ndarray:
         """The batch's compact records: [n_frames, RECORD_HEADER + 3 * board corners] float32 (layout:
         ``sharding.pack_records``; tag = frame index within the batch)."""
