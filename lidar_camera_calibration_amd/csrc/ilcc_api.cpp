@@ -1715,8 +1715,8 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
     lat[2] = (int32_t)std::lround((rec.x[2] - h->p.tz_min) / (h->p.tz_step / div));
   }
   if (phase) *phase = rec.phase;
-  if (cost_q) *cost_q = (int64_t)std::llround(rec.sel * 1099511627776.0);      // exact: the record holds cost_q / 2^40 in a double
-  if (alt_cost_q) *alt_cost_q = (int64_t)std::llround(rec.cost_b * 1099511627776.0);
+  if (cost_q) *cost_q = rec.cost_q;   // (not rec.sel x 2^40: a sum of 2^53 or more does not survive the double)
+  if (alt_cost_q) *alt_cost_q = rec.alt_q;
   if (rounds) *rounds = rec.iters_a;
   if (hops) *hops = rec.iters_b;
   if (flags) *flags = rec.flags;

@@ -93,6 +93,7 @@ struct SolveRec {      // K7a / K7r result for one (frame, phase slot)
   double margin;       // K7r: (cheapest neighbouring basin - cost) / cost
   int32_t iters_a, iters_b, phase, valid;
   int32_t flags, ties;
+  long long cost_q, alt_q;   // K7r: the fixed-point costs as summed (cost_a / cost_b hold them / 2^40 in a double: the integer only below 2^53)
 };
 
 struct RefineOut {     // K7r diagnostic entry (ilcc_pattern_refine)

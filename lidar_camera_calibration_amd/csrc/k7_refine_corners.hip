@@ -805,6 +805,7 @@ struct RCand {
   int32_t q0, q1, q2, phase;   // lattice coordinates (theta, ty, tz), topleftWhite
 };
 constexpr int kRefineWavesMax = kRefineThreadsSmallBatch / ILCC_WAVE;
+constexpr double kExactDoubleSum = 9007199254740992.0;   // 2^53: a sum of non-negative integers below it was added exactly in double
 constexpr int kActQueue = 128;                   // per-wavefront queue of active point indices: < 64 left over + <= 64 pushed
 struct RefineShared {
   RCand cand[kRefineList];
@@ -941,77 +942,111 @@ __device__ __forceinline__ int stencil_sweep(const Ctx& c, const Board& bd, cons
       x2[k] = c.p.tz_min + (double)tz[k] * (c.p.tz_step / div);
     }
     const double inv_g = 1.0 / bd.g;
-    double acc[9];   // integer-valued partial sums of a handful of terms: exact in double
-#pragma unroll
-    for (int e = 0; e < 9; ++e) acc[e] = 0.0;
-    auto eval_point = [&](uint32_t p) {
-      const float2 v = yz[p];
-      const bool laser_white = lab[p] != 0;
-      const double y = (double)v.x, z = (double)v.y;
-      const double ry = cs.x * y - cs.y * z;
-      const double rz = cs.y * y + cs.x * z;
-      AxisTerms ai[3], aj[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        ai[k] = axis_terms(((ry + x1[k]) + bd.W * bd.g / 2.0) * inv_g, bd.W);
-        aj[k] = axis_terms(((rz + x2[k]) + bd.H * bd.g / 2.0) * inv_g, bd.H);
-      }
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          const bool tlw = ((phase ^ (parity ? ((a + b) & 1) : 0)) != 0);
-          acc[a * 3 + b] += term_q(ai[a], aj[b], tlw, laser_white, bd.delta);
-        }
-    };
+    // The lane's nine partial sums.  The terms are integers below 2^53, and a double adds integers exactly as long as the SUM
+    // stays below 2^53 -- one fp64 add per term where an int64 sum costs a conversion (no 64-bit one in the ISA) and a carry.
+    // Domain: a lane adds P = ceil(n / n_slices) terms (n_slices = 64 x the theta's wavefronts: 64 in the pattern rounds
+    // of the 192-thread kernel, 192 in its basin check, 256 / 768 in small batches) of at most 2^39 rho(r), where
+    // rho(r) = r^2 for r <= huber_delta, else 2 huber_delta r - huber_delta^2, and r is a point's distance from the board in
+    // squares (the sum over y and z of its distance to the nearer outline, or at most 1 inside).  The doubles are exact when
+    //   P x rho(r_max) < 2^14 = 16384:
+    // the default delta = 0.1 with 28 800 points 2 m off a 0.15 m board gives 450 x 5.3; delta = 5 with 8 000 points
+    // up to 0.9 m off gives 125 x 44.  Outside it (delta = 5, 28 800 points 1-2 m off: 450 x 191) a lane's sum passes 2^53
+    // and an add may round.  That is DETECTED, not assumed away: the terms are >= 0, so the sums only grow and rounding is
+    // monotone -- a lane whose final sum is below 2^53 never rounded.  A wavefront with a lane at or above 2^53 walks
+    // its points again with int64 sums (the oracle's own arithmetic): the totals are the exact ones for every input.
     const uint32_t n_slices = (uint32_t)(waves_per_theta * ILCC_WAVE);
     // the silence test needs ty[0] <= ty[2] and tz[0] <= tz[2] (pattern-search rounds: centre -/+ stride, steps > 0)
     const bool skip_silent = !parity && ty[0] <= ty[1] && ty[1] <= ty[2] && tz[0] <= tz[1] && tz[1] <= tz[2] && c.p.ty_step > 0.0 && c.p.tz_step > 0.0;   // (monotone in BOTH steps: the middle value's cell lies between the outer two's)
-    if (skip_silent) {
-      uint32_t* queue = sh.queue[wid];
-      uint32_t head = 0, tail = 0;   // wave-uniform
-      const bool tlw0 = phase != 0;
-      for (uint32_t base = (uint32_t)(grp * ILCC_WAVE); base < n; base += n_slices) {
-        const uint32_t p = base + (uint32_t)lane;
-        bool active = false;
-        if (p < n) {
-          const float2 v = yz[p];
-          const double y = (double)v.x, z = (double)v.y;
-          const double ry = cs.x * y - cs.y * z;
-          const double rz = cs.y * y + cs.x * z;
-          const double i0 = ((ry + x1[0]) + bd.W * bd.g / 2.0) * inv_g, i2 = ((ry + x1[2]) + bd.W * bd.g / 2.0) * inv_g;
-          const double j0 = ((rz + x2[0]) + bd.H * bd.g / 2.0) * inv_g, j2 = ((rz + x2[2]) + bd.H * bd.g / 2.0) * inv_g;
-          const double fi = floor(i0), fj = floor(j0);
-          const bool one_cell = i0 > 0 && i2 < bd.W && j0 > 0 && j2 < bd.H && fi == floor(i2) && fj == floor(j2);
-          const bool odd_i = (((int)fi) & 1) != 0, odd_j = (((int)fj) & 1) != 0;
-          const bool white = (odd_i == odd_j) ? tlw0 : !tlw0;   // term_q's colour rule (:53-61)
-          active = !(one_cell && (lab[p] != 0) == white);
+    // one walk over this wavefront's points, the nine sums in acc[] (double: the fast form; long long: the exact one)
+    auto walk = [&](auto* acc) {
+      using Acc = std::remove_reference_t<decltype(acc[0])>;
+#pragma unroll
+      for (int e = 0; e < 9; ++e) acc[e] = (Acc)0;
+      auto eval_point = [&](uint32_t p) {
+        const float2 v = yz[p];
+        const bool laser_white = lab[p] != 0;
+        const double y = (double)v.x, z = (double)v.y;
+        const double ry = cs.x * y - cs.y * z;
+        const double rz = cs.y * y + cs.x * z;
+        AxisTerms ai[3], aj[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          ai[k] = axis_terms(((ry + x1[k]) + bd.W * bd.g / 2.0) * inv_g, bd.W);
+          aj[k] = axis_terms(((rz + x2[k]) + bd.H * bd.g / 2.0) * inv_g, bd.H);
         }
-        const unsigned long long m = __ballot(active);
-        if (m != 0ull) {
-          if (active) queue[(tail + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (kActQueue - 1)] = p;
-          tail += (uint32_t)__popcll(m);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // one wavefront: LDS executes its instructions in order; keep the compiler from reordering
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          while (tail - head >= (uint32_t)ILCC_WAVE) {
-            eval_point(queue[(head + (uint32_t)lane) & (kActQueue - 1)]);
-            head += ILCC_WAVE;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) {
+            const bool tlw = ((phase ^ (parity ? ((a + b) & 1) : 0)) != 0);
+            acc[a * 3 + b] += (Acc)term_q(ai[a], aj[b], tlw, laser_white, bd.delta);
           }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the reads above before the next round's writes
-          __builtin_amdgcn_wave_barrier();
+      };
+      if (skip_silent) {
+        uint32_t* queue = sh.queue[wid];
+        uint32_t head = 0, tail = 0;   // wave-uniform
+        const bool tlw0 = phase != 0;
+        for (uint32_t base = (uint32_t)(grp * ILCC_WAVE); base < n; base += n_slices) {
+          const uint32_t p = base + (uint32_t)lane;
+          bool active = false;
+          if (p < n) {
+            const float2 v = yz[p];
+            const double y = (double)v.x, z = (double)v.y;
+            const double ry = cs.x * y - cs.y * z;
+            const double rz = cs.y * y + cs.x * z;
+            const double i0 = ((ry + x1[0]) + bd.W * bd.g / 2.0) * inv_g, i2 = ((ry + x1[2]) + bd.W * bd.g / 2.0) * inv_g;
+            const double j0 = ((rz + x2[0]) + bd.H * bd.g / 2.0) * inv_g, j2 = ((rz + x2[2]) + bd.H * bd.g / 2.0) * inv_g;
+            const double fi = floor(i0), fj = floor(j0);
+            const bool one_cell = i0 > 0 && i2 < bd.W && j0 > 0 && j2 < bd.H && fi == floor(i2) && fj == floor(j2);
+            const bool odd_i = (((int)fi) & 1) != 0, odd_j = (((int)fj) & 1) != 0;
+            const bool white = (odd_i == odd_j) ? tlw0 : !tlw0;   // term_q's colour rule (:53-61)
+            active = !(one_cell && (lab[p] != 0) == white);
+          }
+          const unsigned long long m = __ballot(active);
+          if (m != 0ull) {
+            if (active) queue[(tail + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (kActQueue - 1)] = p;
+            tail += (uint32_t)__popcll(m);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // one wavefront: LDS executes its instructions in order; keep the compiler from reordering
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            while (tail - head >= (uint32_t)ILCC_WAVE) {
+              eval_point(queue[(head + (uint32_t)lane) & (kActQueue - 1)]);
+              head += ILCC_WAVE;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the reads above before the next round's writes
+            __builtin_amdgcn_wave_barrier();
+          }
         }
+        if ((uint32_t)lane < tail - head) eval_point(queue[(head + (uint32_t)lane) & (kActQueue - 1)]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // ... and before a second walk's
+        __builtin_amdgcn_wave_barrier();
+      } else {
+        for (uint32_t p = (uint32_t)(grp * ILCC_WAVE + lane); p < n; p += n_slices) eval_point(p);
       }
-      if ((uint32_t)lane < tail - head) eval_point(queue[(head + (uint32_t)lane) & (kActQueue - 1)]);
-    } else {
-      for (uint32_t p = (uint32_t)(grp * ILCC_WAVE + lane); p < n; p += n_slices) eval_point(p);
+    };
+    unsigned long long tot[9];
+    {
+      double acc[9];
+      walk(acc);
+      bool rounded = false;
+#pragma unroll
+      for (int e = 0; e < 9; ++e) {
+        rounded |= !(acc[e] < kExactDoubleSum);
+        tot[e] = (unsigned long long)(long long)acc[e];
+      }
+      if (__ballot(rounded) != 0ull) {
+        long long iacc[9];
+        walk(iacc);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) tot[e] = (unsigned long long)iacc[e];
+      }
     }
     // integer sums: any reduction order gives the same totals
 #pragma unroll
     for (int e = 0; e < 9; ++e) {
       // within the 16-lane rows only (plain DPP); the four rows then add their totals to the LDS word themselves -- the two
       // cross-row steps (permlane swaps and selects on both halves of a 64-bit value) cost more than three more atomics
-      unsigned long long t = (unsigned long long)(long long)acc[e];
+      unsigned long long t = tot[e];
       t += xor_lane_u64<8>(t);
       t += xor_lane_u64<4>(t);
       t += xor_lane_u64<2>(t);
@@ -1271,6 +1306,8 @@ __device__ void refine_frame(const Ctx& c, SolveRec* rec, float2* s_yz, uint8_t*
     out->valid = 1;
     out->flags = flags | (st.capped ? ILCC_FLAG_REFINE_CAPPED : 0);
     out->ties = (int32_t)n_ties;
+    out->cost_q = st.cost;
+    out->alt_q = st.alt;
   }
 }
 
