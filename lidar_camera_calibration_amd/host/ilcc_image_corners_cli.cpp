@@ -1,0 +1,94 @@
+// ilcc_image_corners -- ROS-free counterpart of get_image_corners_bag plus the MATLAB step, for machines
+// without ROS, OpenCV or MATLAB (the GPU box): the first sensor_msgs/Image of a bag -> mono8 -> undistorted
+// with the yaml's K and d -> chessboard corners -> `<camera><i>.txt` as ilcc_calib_lidar_cam reads it.
+//   ilcc_image_corners --bag 20181101_1.bag --topic /camera/image_raw --yaml pointgrey.yaml --out pointgrey1.txt
+//                      [--pgm undistorted.pgm] [--device N]
+// --pgm writes the undistorted image as a binary PGM (P5): it stands in for the reference's imwrite.
+// Mirrors the per-bag body of /root/reference/ilcc2/test/get_image_corners_bag.cpp:67-112 and
+// libcbdetect's findCorners / chessboardsFromCorners / plotChessboards dump.
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "ilcc_camera_image.h"
+#include "ilcc_hip.h"
+#include "ilcc_image_corners.h"
+
+int main(int argc, char** argv) {
+  std::string bag_path, topic, yaml_path, out_path, pgm_path;
+  int device = 0;
+  for (int i = 1; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--bag" && i + 1 < argc) bag_path = argv[++i];
+    else if (a == "--topic" && i + 1 < argc) topic = argv[++i];
+    else if (a == "--yaml" && i + 1 < argc) yaml_path = argv[++i];
+    else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
+    else if (a == "--pgm" && i + 1 < argc) pgm_path = argv[++i];
+    else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
+    else {
+      std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
+      return 2;
+    }
+  }
+  if (bag_path.empty() || topic.empty() || yaml_path.empty() || out_path.empty()) {
+    std::fprintf(stderr, "usage: ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt "
+                         "[--pgm undistorted.pgm] [--device N]\n");
+    return 2;
+  }
+  ilcc_camera_model cam;
+  if (ilcc_read_camera_yaml(yaml_path.c_str(), &cam) != ILCC_OK) {
+    std::fprintf(stderr, "%s\n", ilcc_last_error(nullptr));   // "can not open ..." as ImageCornersEst.cpp:20-24
+    return 1;
+  }
+  // the board: corner_in_x x corner_in_y of the same yaml (ilcc_set_chessboard_param stores them + 1, smaller first)
+  ilcc_params params;
+  ilcc_default_params(&params);
+  if (ilcc_set_chessboard_param(&params, yaml_path.c_str()) != ILCC_OK) {
+    std::fprintf(stderr, "%s\n", ilcc_last_error(nullptr));
+    return 1;
+  }
+  const int32_t board_w = params.board_h - 1, board_h = params.board_w - 1;
+
+  if (!pgm_path.empty()) {
+    int32_t w = 0, h = 0;
+    int32_t st = ilcc_bag_first_image(device, bag_path.c_str(), topic.c_str(), &cam, nullptr, 0, &w, &h);
+    std::vector<uint8_t> pixels;
+    if (st == ILCC_CAPACITY || st == ILCC_OK) {
+      pixels.resize((size_t)w * (size_t)h);
+      st = ilcc_bag_first_image(device, bag_path.c_str(), topic.c_str(), &cam, pixels.data(), pixels.size(), &w, &h);
+    }
+    if (st != ILCC_OK) {
+      std::fprintf(stderr, "can't read image topic: %s\n", ilcc_last_error(nullptr));
+      return 1;
+    }
+    FILE* f = std::fopen(pgm_path.c_str(), "wb");
+    bool ok = f != nullptr;
+    if (f) {
+      ok = std::fprintf(f, "P5\n%d %d\n255\n", w, h) > 0 && std::fwrite(pixels.data(), 1, pixels.size(), f) == pixels.size();
+      ok = (std::fclose(f) == 0) && ok;
+    }
+    if (!ok) {
+      std::fprintf(stderr, "can not write %s\n", pgm_path.c_str());
+      return 1;
+    }
+  }
+
+  int32_t rows = 0, cols = 0;
+  std::vector<double> xy((size_t)board_w * board_h * 2);
+  const int32_t st = ilcc_bag_find_chessboard(device, bag_path.c_str(), topic.c_str(), &cam, board_w, board_h, &rows, &cols, xy.data());
+  if (st == ILCC_BOARD_NOT_FOUND || st == ILCC_AMBIGUOUS) {
+    std::fprintf(stderr, "no chessboard: %s\n", ilcc_last_error(nullptr));
+    return 4;
+  }
+  if (st != ILCC_OK) {
+    std::fprintf(stderr, "can't read image topic: %s\n", ilcc_last_error(nullptr));
+    return 1;
+  }
+  if (ilcc_save_cam_corners(out_path.c_str(), rows, cols, xy.data()) != ILCC_OK) {
+    std::fprintf(stderr, "can not write %s\n", out_path.c_str());
+    return 1;
+  }
+  std::printf("image %d x %d board %d x %d -> %s\n", cam.width, cam.height, rows, cols, out_path.c_str());
+  return 0;
+}
