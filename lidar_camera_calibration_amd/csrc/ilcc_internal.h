@@ -180,7 +180,7 @@ struct Ctx {
   uint32_t* uf_hash_head;    // K2 spatial hash: n_frames x kClusterHashSize bucket heads
   uint32_t* uf_hash_next;    // K2 spatial hash: chain links, one per point
   uint32_t cluster_lds_points;   // K2: ROI points per frame whose cell-sorted copy fits the workgroup's LDS; larger frames sort into HBM
-  uint32_t cluster_cells_cap;    // K2: occupied cells per frame the workgroup's LDS arrays hold; frames with more take the point-level path
+  uint32_t cluster_cells_cap;    // K2: occupied cells per frame the workgroup's LDS arrays hold; frames with more take the hashed-cell path (hashed_cluster_frame)
   uint32_t wide;             // per-frame kernels at their small-batch (latency) widths whatever the batch size: synchronous calls nothing overlaps with (the online caller)
   uint32_t cluster_bits;     // K2: cells of the padded bounding grid the LDS bitmap holds (a multiple of 64)
   // The online caller (get_chessboard_by_point on un-cropped clouds) in two tiers.  online_tier 1: K1 crops a window of

@@ -186,6 +186,9 @@ __device__ __forceinline__ ClusterChoice choose_cluster(const Ctx& c, uint32_t f
         r0 = r2;
       }
     }
+    // a click with a NaN or infinite component is at no comparable distance from any point: no candidate ever beat the initial
+    // key.  The reference's search then keeps its initial index, point 0 (and P[0xFFFFFFFF] is far outside the frame)
+    if (nb.idx == 0xFFFFFFFFu) nb.idx = 0u;
     const uint32_t nn_root = label(nb.idx, P[nb.idx]);
     uint32_t nsz = 0, nmi;
     comp(nn_root, nsz, nmi);

@@ -895,9 +895,10 @@ def test_large_roi_takes_the_global_memory_paths(ob):
 
 def test_large_roi_one_workgroup_and_multi_workgroup_clustering_agree(ob):
     """K2's three ways through a dense ROI (~12 k points, ~1 300 occupied cells): a fresh handle's cell arrays hold 512 cells,
-    so its first call clusters these frames with the point-level spatial hash (its own workgroup: the multi-workgroup
-    kernels are not armed); its second call, the capacity grown, takes the cell-level path with the sorted points in
-    HBM; a reserved handle takes that path at once -- identical clusters, planes and corners (and the oracle's: previous test)."""
+    so its first call clusters these frames on hashed cells (hashed_cluster_frame: the same cell-level components with the
+    cells in a hash table in global memory, by the frame's own workgroup); its second call, the capacity grown, takes the
+    cell-level path on the LDS grid with the sorted points in HBM; a reserved handle takes that path at once -- identical
+    clusters, planes and corners (and the oracle's: previous test)."""
     board = synth.Board(9, 12, 0.10)
     rng = np.random.default_rng(33)
     clouds, clicks = [], []
@@ -913,7 +914,7 @@ def test_large_roi_one_workgroup_and_multi_workgroup_clustering_agree(ob):
     p.ty_min = p.tz_min = -0.04
     p.ty_step = p.tz_step = 0.01
     cold = LidarCornersBatch(3, 131072, p)
-    r_cold = cold.extract(clouds, clicks)            # more occupied cells than a fresh handle's 512: point-level hash, unarmed
+    r_cold = cold.extract(clouds, clicks)            # more occupied cells than a fresh handle's 512: hashed cells
     r_warm = cold.extract(clouds, clicks)            # capacity grown: components on cells, sorted points in HBM
     res = LidarCornersBatch(3, 131072, p)
     res.reserve(4500, 25000)
