@@ -1,21 +1,25 @@
-// ilcc_api.cpp -- host side of the C-ABI (include/ilcc_hip.h): handle, HBM buffers, the stage
-// pipeline on the handle's three HIP streams, HIP-event timing, and the two file contracts of the path.
+// ilcc_api.cpp -- the handle behind the C-ABI (include/ilcc_hip.h): its HBM buffers and slots, the stage pipeline on the handle's
+// three HIP streams, the one path every batch entry takes (run_batch), the waits, HIP-event timing, and the diagnostic and fetch
+// entries.  What needs no handle (parameters, status texts, the two file contracts of the path) is ilcc_params.cpp.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <mutex>
 #include <new>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "ilcc_internal.h"
 
 using namespace ilcc;
+
+namespace ilcc {
+bool params_ok(const ilcc_params& p, std::string& why);   // ilcc_params.cpp
+}
 
 #ifndef ILCC_SLOTS
 #define ILCC_SLOTS 4
@@ -44,6 +48,11 @@ enum BatchEvent {
   kEvCount
 };
 static_assert(kEvCount == ILCC_TIMELINE_COLS - 1, "a timeline row is the slot and one time per event");
+
+// What a batch runs: the ROI pipeline (crop around the click, cluster, plane, labels, grid search or local solve, corners) or
+// get_chessboard_by_point's front half (no crop: the whole cloud in two tiers, up to the labels).  A ticket carries its batch's
+// kind: only ilcc_wait_chessboard_by_point applies the by-point epilogue
+enum BatchKind { kRoiPipeline, kByPoint };
 
 // One in-flight batch: its events, stage buffers and pinned result staging.
 struct Slot {
@@ -88,7 +97,7 @@ struct Slot {
   std::vector<uint64_t> off;
   uint32_t n_frames = 0;
   bool busy = false, grid = false;
-  bool online = false;   // the batch in flight came from ilcc_submit_chessboard_by_point (no crop, front end only): its wait applies the by-point epilogue
+  BatchKind kind = kRoiPipeline;   // of the batch in flight
   bool h_res_valid = false;  // h_res holds the last completed batch's full (trimmed) records
   bool compact = false;      // what was enqueued with the batch in flight: the K9 records (true) or the trimmed full records
   uint32_t rec_corners = 0;  // corners per K9 record of that batch
@@ -122,7 +131,7 @@ struct ilcc_handle {
   int32_t th_lat_lo = 0, th_lat_hi = 0, hop_y = 0, hop_z = 0;
   double* d_solve = nullptr;   // 3 theta_t + 2 (cost, iterations) for the test entries
   RefineOut* d_refine_io = nullptr;
-  uint32_t grid_lds_points = 1024;   // grows with the frames seen (finish()); frames above it take the global-memory path
+  uint32_t grid_lds_points = 1024;   // grows with the frames seen (grow_capacities); frames above it take the global-memory path
   uint64_t group_prepass_skipped = 0;   // batches whose grid was eligible for k6_group_prepass but whose mask buffers were too small: a sizing bug if ever non-zero -- the first such batch leaves a note in ilcc_last_error (results are unaffected: the full pass runs without the common mask)
   uint32_t cluster_lds_points = 2048;   // K2's LDS capacity for cell-sorted ROI points per frame: grows likewise (<= 4096); larger frames sort into HBM
   uint32_t cluster_cells_cap = kClusterCellsMin;   // K2's LDS capacity in occupied cells per frame: grows with what the batches needed
@@ -150,52 +159,18 @@ thread_local std::string g_err;
     }                                                                                      \
   } while (0)
 
+// ... and a step of the library's own that failed has said why already
+#define ILCC_TRY(expr)                   \
+  do {                                   \
+    const int32_t st_ = (expr);          \
+    if (st_ != ILCC_OK) return st_;      \
+  } while (0)
+
 int32_t near_zero_index(double vmin, double step, int32_t n) {
   long c = std::lround(-vmin / step);
   if (c < 0) c = 0;
   if (c > n - 1) c = n - 1;
   return (int32_t)c;
-}
-
-bool params_ok(const ilcc_params& p, std::string& why) {
-  auto bad = [&](const char* m) {
-    why = m;
-    return false;
-  };
-  if (!(p.grid_length > 0)) return bad("grid_length must be > 0");
-  if (p.board_w < 2 || p.board_h < 2 || p.board_w > p.board_h) return bad("board_w/board_h: need 2 <= w <= h");
-  if ((p.board_w - 1) * (p.board_h - 1) > ILCC_MAX_CORNERS) return bad("too many corners");
-  if (p.hist_bins < 1 || p.hist_bins > 4096) return bad("hist_bins out of range");
-  if (!(p.gray_rate > 0) || !(p.huber_delta > 0)) return bad("gray_rate / huber_delta must be > 0");
-  if (p.ransac_hyp < 1 || p.ransac_hyp > 65536) return bad("ransac_hyp out of range");
-  if (!(p.ransac_probability == p.ransac_probability) || p.ransac_probability >= 1.0) return bad("ransac_probability must be < 1");
-  if (!(p.cluster_tol > 0) || p.cluster_min < 1 || p.cluster_max < p.cluster_min) return bad("cluster params");
-  if (p.solver != ILCC_SOLVER_REFERENCE_LOCAL && p.solver != ILCC_SOLVER_GRID) return bad("solver");
-  if (p.phase_mode < 0 || p.phase_mode > 2) return bad("phase_mode");
-  if (p.grid_prune != 0 && p.grid_prune != 1) return bad("grid_prune must be 0 or 1");
-  if (p.max_iterations < 0 || p.max_iterations > 100000) return bad("max_iterations");
-  if (p.n_th < 1 || p.n_ty < 1 || p.n_tz < 1) return bad("grid sizes must be >= 1");
-  if (p.n_th > 4096 || p.n_ty > 4096 || p.n_tz > 4096) return bad("grid axes are limited to 4096 candidates");
-  // K6 keeps the (ty, tz) tables in LDS behind the staged points: the raised dynamic-LDS limit covers kGridTableMax floats
-  if (p.n_ty + p.n_tz > kGridTableMax) return bad("n_ty + n_tz exceeds the LDS table capacity of the grid kernel");
-  if (p.refine_div < 0 || p.refine_div > 64 || (p.refine_div & (p.refine_div - 1)) != 0)
-    return bad("refine_div must be 0 or a power of two <= 64");
-  if (p.refine_max_rounds < 0 || p.refine_max_rounds > 4096) return bad("refine_max_rounds");
-  if (p.refine_th_margin < 0 || p.refine_th_margin > 4096) return bad("refine_th_margin");
-  if (!(p.online_cluster_tol > 0)) return bad("online_cluster_tol must be > 0");
-  if (!(p.ambiguity_eps == p.ambiguity_eps)) return bad("ambiguity_eps is NaN");
-  if (!(p.min_cell_coverage == p.min_cell_coverage) || p.min_cell_coverage > 1.0) return bad("min_cell_coverage must be <= 1");
-  if (p.board_w * p.board_h > kCoverageCellsMax) return bad("board has more squares than the coverage mask holds");
-  if ((uint64_t)p.n_th * p.n_ty * p.n_tz * 2ull >= 0xFFFFFFFFull) return bad("grid too large");
-  if (!(p.th_step > 0) || !(p.ty_step > 0) || !(p.tz_step > 0)) return bad("grid steps must be > 0");
-  {
-    // K7r's basin check compares with the positions ONE SQUARE away: lround(g / (step / div)) lattice units.  A step so
-    // coarse that this rounds to 0 would compare the centre with itself (margin 0: every frame ILCC_AMBIGUOUS)
-    const double div = (double)(p.refine_div > 0 ? p.refine_div : 1);
-    if (std::lround(p.grid_length / (p.ty_step / div)) < 1 || std::lround(p.grid_length / (p.tz_step / div)) < 1)
-      return bad("ty_step / tz_step too coarse: one board square is less than half a refinement-lattice step");
-  }
-  return true;
 }
 
 // a diagnostic entry or a table upload waits for its own work on an event behind it, never for the whole shared stream
@@ -297,22 +272,100 @@ int32_t upload_tables(ilcc_handle* h) {
   return sync_own(h, st);
 }
 
-void free_slot(Slot& sl) {
-  void* bufs[] = {sl.d_grp_alive, sl.d_grp_mask, sl.d_xyzi, sl.d_clicks, sl.d_off, sl.d_res, sl.d_roi, sl.d_cluster, sl.d_board, sl.d_pca, sl.d_optim,
-                  sl.d_yz, sl.d_walk_yz, sl.d_walk_lab, sl.d_walk_mi, sl.d_walk_nrim, sl.d_lab, sl.d_cls, sl.d_nlab, sl.d_walk, sl.d_counts, sl.d_parent, sl.d_count, sl.d_hash_head, sl.d_hash_next, sl.d_flags, sl.d_nfinite, sl.d_counts_fin, sl.d_list, sl.d_list_frames, sl.d_partial, sl.d_partial2, sl.d_partial3, sl.d_partial4, sl.d_masks,
-                  sl.d_solverec, sl.d_bound, sl.d_bound_sub, sl.d_iters, sl.d_tie_count, sl.d_tie_list};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (sl.h_res) (void)hipHostFree(sl.h_res);
-  if (sl.h_rec) (void)hipHostFree(sl.h_rec);
-  if (sl.h_iters) (void)hipHostFree(sl.h_iters);
-  if (sl.h_off) (void)hipHostFree(sl.h_off);
-  if (sl.h_online) (void)hipHostFree(sl.h_online);
-  for (auto& ev : sl.ev)
-    if (ev) (void)hipEventDestroy(ev);
-  if (sl.done) (void)hipEventDestroy(sl.done);
-  if (sl.late) (void)hipEventDestroy(sl.late);
-  if (sl.k6_done) (void)hipEventDestroy(sl.k6_done);
+// The handle's buffers, and a slot's buffers and events, are each named ONCE: in the lists that both the allocation and the release walk
+struct Buffer {
+  void** ptr;
+  size_t bytes;   // 0: sized elsewhere, released with the rest
+};
+template <class T>
+Buffer buffer(T*& p, size_t count) { return {reinterpret_cast<void**>(&p), sizeof(T) * count}; }
+
+auto handle_buffers(ilcc_handle* h) {
+  const size_t mt = h->max_theta;
+  return std::array{buffer(h->d_cth, mt),  buffer(h->d_sth, mt),  buffer(h->d_ay, mt),  buffer(h->d_az, mt),
+                    buffer(h->d_cth2, mt), buffer(h->d_sth2, mt), buffer(h->d_ay2, mt), buffer(h->d_az2, mt),
+                    buffer(h->d_solve, 8), buffer(h->d_refine_io, 1), buffer(h->d_th_lattice, 0) /* follows the grid: upload_tables */};
+}
+
+auto slot_device_buffers(const ilcc_handle* h, Slot& sl) {
+  const size_t np = h->max_points, mf = h->max_frames, chunks = h->crop_chunks_cap, mt = h->max_theta;
+  return std::array{
+      buffer(sl.d_xyzi, np),
+      buffer(sl.d_clicks, 3 * mf),
+      buffer(sl.d_off, mf + 1),
+      buffer(sl.d_res, mf),
+      buffer(sl.d_roi, np),
+      buffer(sl.d_cluster, np),
+      buffer(sl.d_board, np),
+      buffer(sl.d_pca, np),
+      buffer(sl.d_optim, np),
+      buffer(sl.d_yz, np),
+      buffer(sl.d_walk_yz, np),
+      buffer(sl.d_walk_lab, np),
+      buffer(sl.d_walk_mi, mf),
+      buffer(sl.d_walk_nrim, mf),
+      buffer(sl.d_lab, np),
+      buffer(sl.d_cls, np),
+      buffer(sl.d_nlab, mf),
+      buffer(sl.d_walk, mf),
+      buffer(sl.d_counts, chunks),
+      buffer(sl.d_counts_fin, chunks),
+      buffer(sl.d_flags, mf),
+      buffer(sl.d_nfinite, mf),
+      buffer(sl.d_list, mf + 1),
+      Buffer{&sl.d_list_frames, 64 * mf},
+      buffer(sl.d_masks, chunks * (kCropChunk / 64)),
+      buffer(sl.d_parent, np),
+      buffer(sl.d_count, np),
+      buffer(sl.d_hash_head, mf * kClusterHashSize),
+      buffer(sl.d_hash_next, np),
+      buffer(sl.d_partial, mf * mt),
+      buffer(sl.d_partial2, mf * mt),
+      buffer(sl.d_partial3, mf * mt),
+      buffer(sl.d_partial4, mf * 4),
+      buffer(sl.d_solverec, 2 * mf),
+      buffer(sl.d_bound, mf),
+      buffer(sl.d_bound_sub, mf),
+      buffer(sl.d_tie_count, mf),
+      buffer(sl.d_tie_list, mf * kTieCap),
+      buffer(sl.d_iters, kBatchWords),
+      buffer(sl.d_grp_alive, 0),   // the common pre-pass's two follow the grid: size_group_prepass
+      buffer(sl.d_grp_mask, 0),
+  };
+}
+
+auto slot_pinned_buffers(const ilcc_handle* h, Slot& sl) {
+  const size_t mf = h->max_frames;
+  return std::array{
+      buffer(sl.h_res, mf),
+      buffer(sl.h_rec, mf * (ILCC_RECORD_HEADER + 3 * ILCC_MAX_CORNERS)),
+      buffer(sl.h_iters, kBatchWords),
+      buffer(sl.h_off, mf + 1),
+      buffer(sl.h_online, 2 * mf),
+  };
+}
+
+struct SlotEvent {
+  hipEvent_t* ev;
+  unsigned flags;
+};
+auto slot_events(Slot& sl) {
+  std::array<SlotEvent, kEvCount + 3> evs;
+  for (int k = 0; k < kEvCount; ++k) evs[k] = {&sl.ev[k], hipEventDefault};   // the batch's timing events
+  evs[kEvCount] = {&sl.done, hipEventDisableTiming};
+  evs[kEvCount + 1] = {&sl.late, hipEventDisableTiming};
+  evs[kEvCount + 2] = {&sl.k6_done, hipEventDisableTiming};
+  return evs;
+}
+
+// (also of a slot whose allocation stopped half-way: whatever the lists hold is released, the slot is as new)
+void free_slot(const ilcc_handle* h, Slot& sl) {
+  for (const Buffer& b : slot_device_buffers(h, sl))
+    if (*b.ptr) (void)hipFree(*b.ptr);
+  for (const Buffer& b : slot_pinned_buffers(h, sl))
+    if (*b.ptr) (void)hipHostFree(*b.ptr);
+  for (const SlotEvent& e : slot_events(sl))
+    if (*e.ev) (void)hipEventDestroy(*e.ev);
   sl = Slot{};
 }
 
@@ -377,66 +430,24 @@ int32_t size_group_prepass(ilcc_handle* h, Slot& sl) {
   return ILCC_OK;
 }
 
-int32_t alloc_slot(ilcc_handle* h, Slot& sl) {
-  if (sl.allocated) return ILCC_OK;
-  const uint64_t np = h->max_points;
-  const uint32_t mf = h->max_frames;
-  for (auto& ev : sl.ev) HIP_TRY(h, hipEventCreate(&ev));
-  HIP_TRY(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-  HIP_TRY(h, hipEventCreateWithFlags(&sl.late, hipEventDisableTiming));
-  HIP_TRY(h, hipEventCreateWithFlags(&sl.k6_done, hipEventDisableTiming));
-#define ALLOC(ptr, bytes) HIP_TRY(h, hipMalloc((void**)&(ptr), (size_t)(bytes)))
-  ALLOC(sl.d_xyzi, sizeof(float4) * np);
-  ALLOC(sl.d_clicks, sizeof(float) * 3 * mf);
-  ALLOC(sl.d_off, sizeof(uint64_t) * (mf + 1));
-  ALLOC(sl.d_res, sizeof(ilcc_result) * mf);
-  ALLOC(sl.d_roi, sizeof(float4) * np);
-  ALLOC(sl.d_cluster, sizeof(float4) * np);
-  ALLOC(sl.d_board, sizeof(float4) * np);
-  ALLOC(sl.d_pca, sizeof(float4) * np);
-  ALLOC(sl.d_optim, sizeof(float4) * np);
-  ALLOC(sl.d_yz, sizeof(float2) * np);
-  ALLOC(sl.d_walk_yz, sizeof(float2) * np);
-  ALLOC(sl.d_walk_lab, np);
-  ALLOC(sl.d_walk_mi, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_walk_nrim, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_lab, np);
-  ALLOC(sl.d_cls, np);
-  ALLOC(sl.d_nlab, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_walk, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_counts, sizeof(uint32_t) * h->crop_chunks_cap);
-  ALLOC(sl.d_counts_fin, sizeof(uint32_t) * h->crop_chunks_cap);
-  ALLOC(sl.d_flags, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_nfinite, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_list, sizeof(uint32_t) * ((size_t)mf + 1));
-  ALLOC(sl.d_list_frames, (size_t)64 * mf);
-  ALLOC(sl.d_masks, sizeof(unsigned long long) * (size_t)h->crop_chunks_cap * (kCropChunk / 64));
-  ALLOC(sl.d_parent, sizeof(uint32_t) * np);
-  ALLOC(sl.d_count, sizeof(uint32_t) * np);
-  ALLOC(sl.d_hash_head, sizeof(uint32_t) * (size_t)mf * kClusterHashSize);
-  ALLOC(sl.d_hash_next, sizeof(uint32_t) * np);
-  ALLOC(sl.d_partial, sizeof(GridPartial) * (size_t)mf * h->max_theta);
-  ALLOC(sl.d_partial2, sizeof(GridPartial) * (size_t)mf * h->max_theta);
-  ALLOC(sl.d_partial3, sizeof(GridPartial) * (size_t)mf * h->max_theta);
-  ALLOC(sl.d_partial4, sizeof(GridPartial) * (size_t)mf * 4);
-  ALLOC(sl.d_solverec, sizeof(SolveRec) * 2 * (size_t)mf);
-  ALLOC(sl.d_bound, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_bound_sub, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_tie_count, sizeof(uint32_t) * mf);
-  ALLOC(sl.d_tie_list, sizeof(GridPartial) * (size_t)mf * kTieCap);
-  ALLOC(sl.d_iters, sizeof(unsigned long long) * kBatchWords);
-#undef ALLOC
-  HIP_TRY(h, hipHostMalloc((void**)&sl.h_res, sizeof(ilcc_result) * mf, hipHostMallocDefault));
-  HIP_TRY(h, hipHostMalloc((void**)&sl.h_rec, sizeof(float) * (size_t)mf * (ILCC_RECORD_HEADER + 3 * ILCC_MAX_CORNERS), hipHostMallocDefault));
-  HIP_TRY(h, hipHostMalloc((void**)&sl.h_iters, sizeof(unsigned long long) * kBatchWords, hipHostMallocDefault));
+int32_t alloc_slot_parts(ilcc_handle* h, Slot& sl) {
+  for (const SlotEvent& e : slot_events(sl)) HIP_TRY(h, hipEventCreateWithFlags(e.ev, e.flags));
+  for (const Buffer& b : slot_device_buffers(h, sl))
+    if (b.bytes) HIP_TRY(h, hipMalloc(b.ptr, b.bytes));
+  for (const Buffer& b : slot_pinned_buffers(h, sl)) HIP_TRY(h, hipHostMalloc(b.ptr, b.bytes, hipHostMallocDefault));
   // (the records and counters are written by kernels, not by D2H copies: the device's view of the two pinned buffers)
   HIP_TRY(h, hipHostGetDevicePointer((void**)&sl.h_rec_dev, sl.h_rec, 0));
   HIP_TRY(h, hipHostGetDevicePointer((void**)&sl.h_iters_dev, sl.h_iters, 0));
-  HIP_TRY(h, hipHostMalloc((void**)&sl.h_off, sizeof(uint64_t) * (mf + 1), hipHostMallocDefault));
-  HIP_TRY(h, hipHostMalloc((void**)&sl.h_online, sizeof(uint32_t) * 2 * (size_t)mf, hipHostMallocDefault));
-  {
-    const int32_t st = size_group_prepass(h, sl);
-    if (st != ILCC_OK) return st;
+  return size_group_prepass(h, sl);
+}
+
+// A slot's first use.  A failure half-way releases what the slot had got, so the next use of the slot starts over
+int32_t alloc_slot(ilcc_handle* h, Slot& sl) {
+  if (sl.allocated) return ILCC_OK;
+  const int32_t st = alloc_slot_parts(h, sl);
+  if (st != ILCC_OK) {
+    free_slot(h, sl);
+    return st;
   }
   sl.allocated = true;
   return ILCC_OK;
@@ -546,9 +557,6 @@ hipStream_t late_stream(const ilcc_handle* h) {
   return h->stream[best];
 }
 
-int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
-                     const float* d_clicks, bool front_only, bool no_crop);
-
 // K2's workgroup keeps bitmap + per-cell arrays + (up to cluster_lds_points) sorted points in LDS: when the cell arrays have
 // grown large (dense clouds), give up LDS points first -- frames of that size sort into HBM anyway
 void fit_cluster_lds(ilcc_handle* h) {
@@ -564,26 +572,6 @@ hipError_t copy_results_trimmed(ilcc_result* dst, const ilcc_result* d_src, uint
   if (n_frames == 0) return hipSuccess;
   return hipMemcpy2DAsync(dst, sizeof(ilcc_result), d_src, sizeof(ilcc_result), trimmed_bytes(n_corners), n_frames,
                           hipMemcpyDeviceToHost, s);
-}
-
-// enqueue the whole path for one batch on the stream (no host synchronisation).  On a mid-pipeline failure the kernels already
-// queued may still be running on the slot's buffers: wait for them before handing the error back, so that the next submit can
-// reuse the slot.  (The batch is the newest one: its stream holds nothing behind it.)
-int32_t enqueue(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
-                const float* d_clicks, bool front_only = false, bool no_crop = false) {
-  if (h->poisoned) {
-    h->err = "handle unusable: a failed ilcc_set_params could not restore the device tables";
-    return ILCC_HIP_ERROR;
-  }
-  const int32_t st = enqueue_impl(h, si, s, d_xyzi, offsets, n_frames, d_clicks, front_only, no_crop);
-  if (st != ILCC_OK) {
-    const std::string why = h->err;
-    (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    h->slots[si].busy = false;
-    h->err = why;
-  }
-  return st;
 }
 
 // Host-side constants of the grid search.  (A/B builds override the #defines with -D, tools/build_variant.sh; what each was
@@ -717,8 +705,7 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
       HIP_TRY(h, hipEventRecord(sl.ev[kEvRefined], s));
       located = full_table_records(lp.out, 1);
     } else {
-      const int32_t st = enqueue_locate_launches(h, sl, c, s, lp.refine_radius, located);
-      if (st != ILCC_OK) return st;
+      ILCC_TRY(enqueue_locate_launches(h, sl, c, s, lp.refine_radius, located));
     }
   } else {
     HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));
@@ -758,7 +745,7 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
 }
 
 int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
-                     const float* d_clicks, bool front_only, bool no_crop) {
+                     const float* d_clicks, BatchKind kind) {
   Slot& sl = h->slots[si];
   uint64_t max_n = 0;
   for (uint32_t f = 0; f < n_frames; ++f) max_n = std::max<uint64_t>(max_n, offsets[f + 1] - offsets[f]);
@@ -775,7 +762,7 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
   // (result records, component counters, K6 counters and near-tie counters are reset inside K1 / K2)
   Ctx c = make_ctx(h, sl, d_xyzi, d_clicks, n_frames, chunks);
   HIP_TRY(h, hipEventRecord(sl.ev[kEvStart], s));
-  if (!no_crop) {
+  if (kind == kRoiPipeline) {
     // (one pass, one workgroup per frame, when the batch has the frames for it)
     launch_roi_crop(c, s, sl.ev[kEvCropCounted], !h->separate_launches && n_frames >= (uint32_t)kCropFrameMinFrames);
     HIP_TRY(h, hipEventRecord(sl.ev[kEvCropped], s));
@@ -805,7 +792,7 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     HIP_TRY(h, hipMemcpyAsync(sl.h_online + h->max_frames, sl.d_nfinite, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvClustered], s));
-  sl.grid = !front_only && h->p.solver == ILCC_SOLVER_GRID;
+  sl.grid = kind == kRoiPipeline && h->p.solver == ILCC_SOLVER_GRID;
   // K3, K4/K5 and (GRID mode) K5w: one launch when the batch would run them at the same width anyway.  The whole launch is then
   // accounted as the K3 span, like k6_locate as the seed's
   const bool one_launch = !h->separate_launches && front_end_fusable(c);
@@ -819,11 +806,10 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
   }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvLabelled], s));
   if (sl.grid) {
-    const int32_t st = enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/true, /*walk_laid_out=*/one_launch);
-    if (st != ILCC_OK) return st;
+    ILCC_TRY(enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/true, /*walk_laid_out=*/one_launch));
   }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvSearched], s));
-  if (!front_only) {
+  if (kind == kRoiPipeline) {
     if (sl.grid) {
       launch_pattern_refine_corners(c, s);   // (with the near ties of the full pass, re-ordered on fixed-point sums by K7r)
     } else {
@@ -846,8 +832,28 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(sl.done, s));
   sl.busy = true;
-  sl.online = no_crop;
+  sl.kind = kind;
   return ILCC_OK;
+}
+
+// enqueue the whole path for one batch on the stream (no host synchronisation).  On a mid-pipeline failure the kernels already
+// queued may still be running on the slot's buffers: wait for them before handing the error back, so that the next submit can
+// reuse the slot.  (The batch is the newest one: its stream holds nothing behind it.)
+int32_t enqueue(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
+                const float* d_clicks, BatchKind kind) {
+  if (h->poisoned) {
+    h->err = "handle unusable: a failed ilcc_set_params could not restore the device tables";
+    return ILCC_HIP_ERROR;
+  }
+  const int32_t st = enqueue_impl(h, si, s, d_xyzi, offsets, n_frames, d_clicks, kind);
+  if (st != ILCC_OK) {
+    const std::string why = h->err;
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    h->slots[si].busy = false;
+    h->err = why;
+  }
+  return st;
 }
 
 // What a wait launches for a batch that has completed (on late_stream) is waited for on its own event
@@ -862,61 +868,93 @@ int32_t ensure_full(ilcc_handle* h, Slot& sl) {
   if (sl.h_res_valid) return ILCC_OK;
   const hipStream_t s = late_stream(h);
   HIP_TRY(h, copy_results_trimmed(sl.h_res, sl.d_res, sl.n_frames, sl.rec_corners, s));
-  const int32_t st = run_late(h, sl, s);
-  if (st != ILCC_OK) return st;
+  ILCC_TRY(run_late(h, sl, s));
   sl.h_res_valid = true;
   return ILCC_OK;
 }
 
-// wait for the slot's batch, hand the records over (full and / or compact), account the timing
-int32_t finish(ilcc_handle* h, int si, ilcc_result* out, float* out_compact = nullptr, float* d_records = nullptr,
-               uint32_t n_corners = 0, uint32_t tag_base = 0) {
-  Slot& sl = h->slots[si];
+// ---- A wait in four parts: wait_batch, hand_over, account_timing, grow_capacities (finish runs them in turn)
+
+// wait for the slot's batch, then launch and wait for what this wait wants beyond what was enqueued with the batch: K9 into
+// d_records, the compact records of a batch submitted in ILCC_RESULTS_FULL mode
+int32_t wait_batch(ilcc_handle* h, Slot& sl, bool want_compact, float* d_records, uint32_t n_corners, uint32_t tag_base) {
+  HIP_TRY(h, hipSetDevice(h->device));   // (a wait may come from another thread than the submit)
   HIP_TRY(h, hipEventSynchronize(sl.done));
-  const uint32_t n_frames = sl.n_frames;
-  const size_t rec_w = (size_t)ILCC_RECORD_HEADER + 3 * (size_t)sl.rec_corners;
-  const bool pack_now = out_compact && !sl.compact;   // the compact records were not enqueued with the batch
+  const bool pack_now = want_compact && !sl.compact;   // the compact records were not enqueued with the batch
   const hipStream_t ls = late_stream(h);
-  if (d_records) launch_pack_records(sl.d_res, n_frames, n_corners, tag_base, d_records, ls);
-  if (pack_now) launch_pack_records(sl.d_res, n_frames, sl.rec_corners, 0u, sl.h_rec_dev, ls);
+  if (d_records) launch_pack_records(sl.d_res, sl.n_frames, n_corners, tag_base, d_records, ls);
+  if (pack_now) launch_pack_records(sl.d_res, sl.n_frames, sl.rec_corners, 0u, sl.h_rec_dev, ls);
   if (d_records || pack_now) {
-    const int32_t st = run_late(h, sl, ls);
-    if (st != ILCC_OK) return st;
+    ILCC_TRY(run_late(h, sl, ls));
   }
   sl.busy = false;
   sl.h_res_valid = !sl.compact;
-  h->last_slot = si;
+  h->last_slot = (int)(&sl - h->slots);
+  return ILCC_OK;
+}
+
+size_t record_floats(const Slot& sl) { return (size_t)ILCC_RECORD_HEADER + 3 * (size_t)sl.rec_corners; }
+
+// hand the completed batch's records to the caller: full and / or compact
+int32_t hand_over(ilcc_handle* h, Slot& sl, ilcc_result* out, float* out_compact) {
   if (out) {
-    const int32_t st = ensure_full(h, sl);
-    if (st != ILCC_OK) return st;
+    ILCC_TRY(ensure_full(h, sl));
     const size_t row = trimmed_bytes(sl.rec_corners);
-    for (uint32_t f = 0; f < n_frames; ++f) std::memcpy(&out[f], &sl.h_res[f], row);
+    for (uint32_t f = 0; f < sl.n_frames; ++f) std::memcpy(&out[f], &sl.h_res[f], row);
   }
-  if (out_compact) std::memcpy(out_compact, sl.h_rec, sizeof(float) * n_frames * rec_w);
+  if (out_compact) std::memcpy(out_compact, sl.h_rec, sizeof(float) * sl.n_frames * record_floats(sl));
+  return ILCC_OK;
+}
+
+// what the completed batch's records say about its frames
+struct BatchCounts {
+  uint32_t max_lab = 0, max_roi = 0;   // the most labelled points of a frame that reached the search; the most ROI points K2's LDS path can hold
+  uint64_t evals = 0;                  // (labelled point, candidate) pairs of the whole grid
+};
+BatchCounts count_batch(const ilcc_handle* h, const Slot& sl) {
+  BatchCounts n;
+  for (uint32_t f = 0; f < sl.n_frames; ++f) {
+    // (status, n_roi, labelled points) from whichever record came back with the batch
+    int32_t status, n_roi;
+    uint32_t m;
+    if (sl.h_res_valid) {
+      const ilcc_result& r = sl.h_res[f];
+      status = r.status;
+      n_roi = r.n_roi;
+      m = (uint32_t)(r.n_black + r.n_white);
+    } else {
+      const float* r = sl.h_rec + (size_t)f * record_floats(sl);
+      status = (int32_t)r[0];
+      n_roi = (int32_t)r[19];
+      m = (uint32_t)r[13] + (uint32_t)r[14];
+    }
+    if (n_roi > 0 && (uint32_t)n_roi <= (uint32_t)kClusterLdsPointsMax) n.max_roi = std::max(n.max_roi, (uint32_t)n_roi);
+    if (status != ILCC_OK && status != ILCC_AMBIGUOUS) continue;
+    n.max_lab = std::max(n.max_lab, m);
+    n.evals += (uint64_t)m * (uint64_t)h->p.n_th * h->p.n_ty * h->p.n_tz;
+  }
+  return n;
+}
+
+// the batch's events into ilcc_timing (and the debug timeline)
+int32_t account_timing(ilcc_handle* h, const Slot& sl, uint64_t evals) {
   auto span = [&](BatchEvent from, BatchEvent to, float& ms_out) { return hipEventElapsedTime(&ms_out, sl.ev[from], sl.ev[to]); };
-  float ms[6];   // K1, K2, K3, K4/K5, K6, K7
-  HIP_TRY(h, span(kEvStart, kEvCropped, ms[0]));
-  HIP_TRY(h, span(kEvCropped, kEvClustered, ms[1]));
-  HIP_TRY(h, span(kEvClustered, kEvPlane, ms[2]));
-  HIP_TRY(h, span(kEvPlane, kEvLabelled, ms[3]));
-  HIP_TRY(h, span(kEvLabelled, kEvSearched, ms[4]));
-  HIP_TRY(h, span(kEvSearched, kEvEnd, ms[5]));
-  float k6k[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // K5w, seed, refinement, anchor, common pre-pass, full pass
+  float ms[6];   // K1, K2, K3, K4/K5, K6, K7: from one of these events to the next
+  const BatchEvent stage[7] = {kEvStart, kEvCropped, kEvClustered, kEvPlane, kEvLabelled, kEvSearched, kEvEnd};
+  for (int k = 0; k < 6; ++k) HIP_TRY(h, span(stage[k], stage[k + 1], ms[k]));
+  float k6k[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // K5w, seed, refinement, anchor, common pre-pass; full pass
   if (sl.grid) {   // K6 = (what locates the minimum + the common pre-pass) + (full pass); the wait for the previous batch's full pass in between is not K6 time
+    const BatchEvent part[6] = {kEvLabelled, kEvWalkOrdered, kEvSeeded, kEvRefined, kEvAnchored, kEvPrepassed};
+    for (int k = 0; k < 5; ++k) HIP_TRY(h, span(part[k], part[k + 1], k6k[k]));
+    HIP_TRY(h, span(kEvFullStart, kEvSearched, k6k[5]));
     float pre = 0.f;
     HIP_TRY(h, span(kEvLabelled, kEvPrepassed, pre));
-    HIP_TRY(h, span(kEvLabelled, kEvWalkOrdered, k6k[0]));
-    HIP_TRY(h, span(kEvWalkOrdered, kEvSeeded, k6k[1]));
-    HIP_TRY(h, span(kEvSeeded, kEvRefined, k6k[2]));
-    HIP_TRY(h, span(kEvRefined, kEvAnchored, k6k[3]));
-    HIP_TRY(h, span(kEvAnchored, kEvPrepassed, k6k[4]));
-    HIP_TRY(h, span(kEvFullStart, kEvSearched, k6k[5]));
     ms[4] = pre + k6k[5];
   }
   float tot = 0;
   HIP_TRY(h, span(kEvStart, kEvEnd, tot));
   if (h->tl_on && h->tl_ref && sl.grid) {
-    h->tl_rows.push_back((double)si);
+    h->tl_rows.push_back((double)(&sl - h->slots));
     for (hipEvent_t e : sl.ev) {   // (BatchEvent order = the timeline's columns)
       float t = 0.f;
       HIP_TRY(h, hipEventElapsedTime(&t, h->tl_ref, e));
@@ -939,28 +977,6 @@ int32_t finish(ilcc_handle* h, int si, ilcc_result* out, float* out_compact = nu
     HIP_TRY(h, span(kEvStart, kEvCropCounted, cnt));
     t.roi_count_ms_sum += cnt;
   }
-  uint32_t max_lab = 0, max_roi = 0;
-  uint64_t evals = 0;
-  for (uint32_t f = 0; f < n_frames; ++f) {
-    // (status, n_roi, labelled points) from whichever record came back with the batch
-    int32_t status, n_roi;
-    uint32_t m;
-    if (sl.h_res_valid) {
-      const ilcc_result& r = sl.h_res[f];
-      status = r.status;
-      n_roi = r.n_roi;
-      m = (uint32_t)(r.n_black + r.n_white);
-    } else {
-      const float* r = sl.h_rec + (size_t)f * rec_w;
-      status = (int32_t)r[0];
-      n_roi = (int32_t)r[19];
-      m = (uint32_t)r[13] + (uint32_t)r[14];
-    }
-    if (n_roi > 0 && (uint32_t)n_roi <= (uint32_t)kClusterLdsPointsMax) max_roi = std::max(max_roi, (uint32_t)n_roi);
-    if (status != ILCC_OK && status != ILCC_AMBIGUOUS) continue;
-    max_lab = std::max(max_lab, m);
-    evals += (uint64_t)m * (uint64_t)h->p.n_th * h->p.n_ty * h->p.n_tz;
-  }
   if (sl.grid) {
     t.grid_cost_launches += 1;
     t.grid_cost_ms_sum += ms[4];
@@ -981,31 +997,199 @@ int32_t finish(ilcc_handle* h, int si, ilcc_result* out, float* out_compact = nu
     t.grid_cost_evals_sum += (uint64_t)iters * grid_cost_evals_per_count();
     t.grid_cost_evals_interior_sum += (uint64_t)iters_in * grid_cost_evals_per_count();
   }
-  // adapt the K6 / K7 LDS staging size to the labelled-point counts actually seen (later calls): the largest count so far,
-  // rounded up to 256 points.  (Not to a power of two: 1 781 points -- the largest of the bench frames -- need 21.8 KB per K6
-  // workgroup at 1 792 and 24.9 KB at 2 048: seven instead of six workgroups per CU -- which, the kernel being VALU-bound,
-  // measured no difference: 248.8 k vs 250 k frames/s.)
-  // ... but never, on its own, past the capacity at which TWO workgroups of the K6 full pass still share a CU's 160 KB (12 bytes per
-  // staged point + the (ty, tz) tables + ~3 KB of static LDS: 6 400 points for both BASELINE grids).  Round 6: a stream of 64-ring
-  // frames whose closest boards hold 6 682 labelled points (the first 128 frames: 6 170) grew the staging to 6 912 points, ONE
-  // workgroup per CU, and every frame's full pass took 1.15 ms instead of 0.74 ms per 128 frames.  The few frames above the capacity
-  // walk their points through L2 (grid_cost_body<LDS_POINTS = false>); ilcc_reserve may still ask for more, explicitly.
-  const uint32_t two_per_cu = (uint32_t)(((160u * 1024u / 2u) - 3072u - 4u * (uint32_t)(h->p.n_ty + h->p.n_tz)) / 12u) & ~255u;
-  uint32_t want = std::min<uint32_t>((uint32_t)kGridLdsPointsMax, std::max<uint32_t>(1024u, (max_lab + 255u) & ~255u));
-  want = std::min<uint32_t>(want, std::max<uint32_t>(1024u, two_per_cu));
-  if (want > h->grid_lds_points) h->grid_lds_points = want;
-  // the same for K2's one-workgroup LDS path (ROI points per frame, steps of 512): what it does not hold of a CU's 160 KiB
-  // is room for K6 workgroups of other batches
-  want = std::min<uint32_t>((uint32_t)kClusterLdsPointsMax, (max_roi + 511u) & ~511u);
-  if (want > h->cluster_lds_points) h->cluster_lds_points = want;
-  // ... and for its per-cell arrays: the most occupied cells a frame of this batch needed (+ 1/8), steps of 256.  Frames the LDS
-  // cell grid cannot hold at any capacity (bounding grid too large: un-cropped clouds; more cells than the largest capacity) take
-  // the hashed-cell path of their own workgroup (k2_cluster.hip).
-  const uint64_t cells_needed = sl.h_iters[3 * kIterSlots];
-  want = (uint32_t)std::min<uint64_t>((uint64_t)kClusterCellsMax, (cells_needed + cells_needed / 8 + 255u) & ~255ull);
-  if (want > h->cluster_cells_cap) h->cluster_cells_cap = want;
-  fit_cluster_lds(h);
   return ILCC_OK;
+}
+
+// An LDS capacity for frames that need `need` entries: rounded up to `step` (a power of two), within [lo, hi].  The one rule
+// behind both the growth with the frames seen and ilcc_reserve
+uint32_t lds_capacity(uint32_t need, uint32_t step, uint32_t lo, uint32_t hi) {
+  return std::min(hi, std::max(lo, (need + step - 1u) & ~(step - 1u)));
+}
+uint32_t grid_lds_capacity(uint32_t labelled_points) { return lds_capacity(labelled_points, 256u, 1024u, (uint32_t)kGridLdsPointsMax); }
+uint32_t cluster_lds_capacity(uint32_t roi_points, uint32_t lo) { return lds_capacity(roi_points, 512u, lo, (uint32_t)kClusterLdsPointsMax); }
+uint32_t cluster_cells_capacity(uint64_t cells) {
+  const uint32_t need = (uint32_t)std::min<uint64_t>(cells, (uint64_t)kClusterCellsMax);
+  return lds_capacity(need, 256u, (uint32_t)kClusterCellsMin, (uint32_t)kClusterCellsMax);
+}
+void raise_capacities(ilcc_handle* h, uint32_t grid_points, uint32_t cluster_points, uint32_t cluster_cells) {
+  h->grid_lds_points = std::max(h->grid_lds_points, grid_points);
+  h->cluster_lds_points = std::max(h->cluster_lds_points, cluster_points);
+  h->cluster_cells_cap = std::max(h->cluster_cells_cap, cluster_cells);
+  fit_cluster_lds(h);
+}
+
+// Adapt the three LDS capacities to what the frames of a batch needed (later calls).
+// K6 / K7 staging: the largest labelled-point count so far, rounded up to 256 points.  (Not to a power of two: 1 781 points -- the
+// largest of the bench frames -- need 21.8 KB per K6 workgroup at 1 792 and 24.9 KB at 2 048: seven instead of six workgroups per
+// CU -- which, the kernel being VALU-bound, measured no difference: 248.8 k vs 250 k frames/s.)
+// ... but never, on its own, past the capacity at which TWO workgroups of the K6 full pass still share a CU's 160 KB (12 bytes per
+// staged point + the (ty, tz) tables + ~3 KB of static LDS: 6 400 points for both BASELINE grids).  Round 6: a stream of 64-ring
+// frames whose closest boards hold 6 682 labelled points (the first 128 frames: 6 170) grew the staging to 6 912 points, ONE
+// workgroup per CU, and every frame's full pass took 1.15 ms instead of 0.74 ms per 128 frames.  The few frames above the capacity
+// walk their points through L2 (grid_cost_body<LDS_POINTS = false>); ilcc_reserve may still ask for more, explicitly.
+// K2's one-workgroup LDS path likewise (ROI points per frame, steps of 512): what it does not hold of a CU's 160 KiB is room for K6
+// workgroups of other batches.  Its per-cell arrays: the most occupied cells a frame of the batch needed (+ 1/8), steps of 256.
+// Frames the LDS cell grid cannot hold at any capacity (bounding grid too large: un-cropped clouds; more cells than the largest
+// capacity) take the hashed-cell path of their own workgroup (k2_cluster.hip).
+void grow_capacities(ilcc_handle* h, const BatchCounts& n, uint64_t cells_needed) {
+  const uint32_t two_per_cu = (uint32_t)(((160u * 1024u / 2u) - 3072u - 4u * (uint32_t)(h->p.n_ty + h->p.n_tz)) / 12u) & ~255u;
+  raise_capacities(h, std::min(grid_lds_capacity(n.max_lab), std::max(1024u, two_per_cu)), cluster_lds_capacity(n.max_roi, 0u),
+                   cluster_cells_capacity(cells_needed + cells_needed / 8));
+}
+
+// wait for the slot's batch, hand the records over (full and / or compact), account the timing, grow the capacities
+int32_t finish(ilcc_handle* h, Slot& sl, ilcc_result* out, float* out_compact = nullptr, float* d_records = nullptr,
+               uint32_t n_corners = 0, uint32_t tag_base = 0) {
+  ILCC_TRY(wait_batch(h, sl, out_compact != nullptr, d_records, n_corners, tag_base));
+  ILCC_TRY(hand_over(h, sl, out, out_compact));
+  const BatchCounts n = count_batch(h, sl);
+  ILCC_TRY(account_timing(h, sl, n.evals));
+  grow_capacities(h, n, sl.h_iters[3 * kIterSlots]);
+  return ILCC_OK;
+}
+
+// ---- The one path of the six batch entries.  They differ in the batch's kind, in whether the input is in HBM already, and in
+// whether the caller wants a ticket (the next slot in turn; all of them busy: ILCC_CAPACITY) or the records at once (slot 0, which
+// ilcc_create allocated; busy: ILCC_BAD_ARGUMENT).  No hipMalloc / hipFree runs here except on a slot's first use.
+int32_t run_batch(ilcc_handle* h, BatchKind kind, bool on_device, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
+                  const float* clicks, int32_t* ticket, ilcc_result* out) {
+  HIP_TRY(h, hipSetDevice(h->device));
+  ILCC_TRY(check_offsets(h, offsets, n_frames));
+  const int si = ticket ? h->next_slot : 0;
+  Slot& sl = h->slots[si];
+  if (sl.busy) {
+    h->err = ticket ? "every pipeline slot holds a batch: wait for the oldest ticket first" : "synchronous call while ticket 0 is in flight";
+    return ticket ? ILCC_CAPACITY : ILCC_BAD_ARGUMENT;
+  }
+  if (ticket) ILCC_TRY(alloc_slot(h, sl));
+  const hipStream_t s = h->stream[take_stream(h)];
+  if (!on_device) {
+    // the copy rides on the batch's stream: ordered before this batch's K1, concurrent with the other batches' kernels
+    if (offsets[n_frames] > 0)
+      HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
+    xyzi = reinterpret_cast<const float*>(sl.d_xyzi);
+    clicks = sl.d_clicks;
+  }
+  ILCC_TRY(enqueue(h, si, s, reinterpret_cast<const float4*>(xyzi), offsets, n_frames, clicks, kind));
+  if (!ticket) return finish(h, sl, out);
+  *ticket = si;
+  h->next_slot = (si + 1) % kSlots;
+  return ILCC_OK;
+}
+
+// ---- Tickets
+
+const Slot* busy_slot(const ilcc_handle* h, int32_t ticket) {
+  return h && ticket >= 0 && ticket < kSlots && h->slots[ticket].busy ? &h->slots[ticket] : nullptr;
+}
+
+// The slot a wait of the `kind` call family (`fn`) is to finish, or null with the reason in ilcc_last_error; the batch stays in
+// flight.  A ticket belongs to the call family that issued it: ilcc_submit_chessboard_by_point's batches skip the
+// crop and the search, and only their own wait applies the by-point epilogue (plane >= min_plane_points, whole-cloud n_roi); the
+// other way round that epilogue would read staging no copy of the batch has filled.
+Slot* ticket_slot(ilcc_handle* h, int32_t ticket, const char* fn, BatchKind kind, bool args_ok) {
+  if (!h) return nullptr;
+  Slot* sl = const_cast<Slot*>(busy_slot(h, ticket));
+  if (!args_ok || !sl) {
+    h->err = std::string(fn) + ": bad argument or no batch in flight under this ticket";
+    return nullptr;
+  }
+  if (sl->kind != kind) {
+    h->err = std::string(fn) + (sl->kind == kByPoint ? ": this ticket came from ilcc_submit_chessboard_by_point: wait with ilcc_wait_chessboard_by_point"
+                                                     : ": this ticket came from ilcc_submit_batch[_device]: wait with ilcc_wait / ilcc_wait_compact / ilcc_wait_records_device");
+    return nullptr;
+  }
+  return sl;
+}
+
+// the parameter set, the capacities and the modes belong to the batches in flight
+bool any_batch_in_flight(ilcc_handle* h, const char* fn) {
+  for (const Slot& sl : h->slots)
+    if (sl.busy) {
+      h->err = std::string(fn) + " with a batch in flight: ilcc_wait first";
+      return true;
+    }
+  return false;
+}
+
+// what get_chessboard_by_point reports beyond the front half's record: n_roi of the WHOLE cloud, the second-tier count, and
+// `if(outcloud->size() < 500 || find_board == false) return false;` (LidarCornersEst.cpp:111-112)
+void finish_chessboard_by_point(ilcc_handle* h, Slot& sl, uint32_t n_frames, int32_t min_plane_points, ilcc_result* out) {
+  // frames the first tier answered from a window of the cloud: n_roi is what the clustering of the WHOLE cloud runs on -- its
+  // finite points (K1 counted them on the way); the handle's own copy keeps the window's count, which is what ILCC_CLOUD_ROI holds
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (sl.h_online[f] == 0u && out[f].status != ILCC_NO_ROI_POINTS) out[f].n_roi = (int32_t)sl.h_online[h->max_frames + f];
+  for (uint32_t f = 0; f < n_frames; ++f) h->timing.online_second_tier_frames += sl.h_online[f] != 0u ? 1u : 0u;
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (out[f].status == ILCC_OK && (out[f].n_plane < min_plane_points || !out[f].found_board)) {
+      out[f].status = ILCC_BOARD_NOT_FOUND;
+      sl.h_res[f].status = ILCC_BOARD_NOT_FOUND;
+    }
+}
+
+// ---- Diagnostic and fetch entries
+
+// The slot the fetch entries read -- the last completed batch, of which they want `n` frames from `first` -- on the handle's device
+int32_t fetch_slot(ilcc_handle* h, uint32_t first, uint32_t n, Slot*& slot) {
+  if (!h || h->last_slot < 0) return ILCC_BAD_ARGUMENT;
+  Slot& sl = h->slots[h->last_slot];
+  if (sl.busy || first > sl.n_frames || n > sl.n_frames - first) {
+    h->err = "fetch: no completed batch, or the frames asked for exceed it";
+    return ILCC_BAD_ARGUMENT;
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  slot = &sl;
+  return ILCC_OK;
+}
+
+// what ilcc_fetch_labelled / ilcc_fetch_walk return: the frame's n points, of which the caller's buffers take cap_points at most
+int64_t fetch_labelled_points(const float2* d_yz, const uint8_t* d_lab, uint32_t n, float* out_yz, uint8_t* out_label, uint64_t cap_points) {
+  const uint64_t m = std::min<uint64_t>(n, cap_points);
+  if (m > 0 && ((out_yz && hipMemcpy(out_yz, d_yz, sizeof(float2) * m, hipMemcpyDeviceToHost) != hipSuccess) ||
+                (out_label && hipMemcpy(out_label, d_lab, m, hipMemcpyDeviceToHost) != hipSuccess)))
+    return -(int64_t)ILCC_HIP_ERROR;
+  return (int64_t)n;
+}
+
+// shared setup for the two single-kernel test entries: frame 0 of slot 0 = caller's labelled points
+int32_t stage_labelled(ilcc_handle* h, hipStream_t s, const float* yz, const uint8_t* label, uint32_t m) {
+  if (!h || (m > 0 && (!yz || !label))) return ILCC_BAD_ARGUMENT;
+  if (m > h->max_points) {
+    h->err = "more points than the handle holds";
+    return ILCC_CAPACITY;
+  }
+  Slot& sl = h->slots[0];
+  if (sl.busy) {
+    h->err = "diagnostic entry while ticket 0 is in flight";
+    return ILCC_BAD_ARGUMENT;
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  const uint64_t off[2] = {0, m};
+  ilcc_result r;
+  std::memset(&r, 0, sizeof(r));
+  r.status = ILCC_OK;
+  HIP_TRY(h, hipMemcpyAsync(sl.d_off, off, sizeof(off), hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_res, &r, sizeof(r), hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_nlab, &m, sizeof(m), hipMemcpyHostToDevice, s));
+  const uint32_t stride = walk_stride(m);
+  HIP_TRY(h, hipMemcpyAsync(sl.d_walk, &stride, sizeof(stride), hipMemcpyHostToDevice, s));
+  if (m > 0) {
+    HIP_TRY(h, hipMemcpyAsync(sl.d_yz, yz, sizeof(float2) * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(sl.d_lab, label, m, hipMemcpyHostToDevice, s));
+  }
+  ILCC_TRY(sync_own(h, s));
+  sl.n_frames = 0;   // the stage buffers no longer describe a batch
+  return ILCC_OK;
+}
+
+// The one-frame Ctx of a diagnostic entry on slot 0, its LDS staging sized for m labelled points (m = 0: as the handle has it)
+Ctx diagnostic_ctx(ilcc_handle* h, Slot& sl, uint32_t m) {
+  Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
+  uint32_t lds = 1024;
+  while (lds < m && lds < (uint32_t)kGridLdsPointsMax) lds <<= 1;
+  c.grid_lds_points = std::max(c.grid_lds_points, lds);
+  return c;
 }
 
 }  // namespace
@@ -1017,118 +1201,7 @@ void set_global_error(const std::string& s) { g_err = s; }
 
 extern "C" {
 
-int32_t ilcc_abi_version(void) { return ILCC_ABI_VERSION; }
-
-const char* ilcc_strerror(int32_t status) {
-  switch (status) {
-    case ILCC_OK: return "ok";
-    case ILCC_NO_ROI_POINTS: return "no points inside the ROI box around the click";
-    case ILCC_NO_CLUSTER: return "no Euclidean cluster of admissible size";
-    case ILCC_NO_PLANE: return "could not estimate a planar model";
-    case ILCC_DEGENERATE_HIST: return "intensity histogram is degenerate (no bin on one side of the mean)";
-    case ILCC_TOO_FEW_POINTS: return "too few points";
-    case ILCC_BAD_ARGUMENT: return "bad argument";
-    case ILCC_CAPACITY: return "handle capacity exceeded";
-    case ILCC_HIP_ERROR: return "HIP runtime error";
-    case ILCC_IO_ERROR: return "file I/O error";
-    case ILCC_BOARD_NOT_FOUND: return "no chessboard plane of sufficient size around the given point";
-    case ILCC_AMBIGUOUS: return "board position ambiguous: a basin one square away costs about the same";
-    default: return "unknown status";
-  }
-}
-
 const char* ilcc_last_error(const ilcc_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
-
-void ilcc_default_params(ilcc_params* p) {
-  std::memset(p, 0, sizeof(*p));
-  p->roi_half[0] = 1.0;
-  p->roi_half[1] = 1.5;
-  p->roi_half[2] = 2.0;
-  p->cluster_tol = 0.12;
-  p->cluster_min = 100;
-  p->cluster_max = 25000;
-  p->ransac_thresh = 0.03;
-  p->ransac_hyp = 50;            // SACSegmentation: max_iterations_
-  p->ransac_probability = 0.99;  // SACSegmentation: probability_
-  p->ransac_seed = 12345u;
-  p->hist_bins = 100;
-  p->gray_rate = 2.5;
-  p->huber_delta = 0.1;
-  p->grid_length = 0.15;
-  p->board_w = 6;
-  p->board_h = 8;
-  p->solver = ILCC_SOLVER_GRID;
-  p->phase_mode = 2;
-  p->max_iterations = 50;
-  p->grid_prune = 1;
-  const double kPi = 3.14159265358979323846;
-  p->n_th = 61;
-  p->th_step = 0.5 * kPi / 180.0;
-  p->th_min = -15.0 * kPi / 180.0;
-  p->n_ty = 40;
-  p->ty_step = 0.15 / 20.0;
-  p->ty_min = -0.15;
-  p->n_tz = 40;
-  p->tz_step = 0.15 / 20.0;
-  p->tz_min = -0.15;
-  p->refine_div = 16;
-  p->refine_max_rounds = 64;
-  p->refine_th_margin = 32;
-  p->ambiguity_eps = 1.0;
-  p->online_cluster_tol = 0.10;   // LidarCornersEst.cpp:80
-  p->min_cell_coverage = 0.9;
-}
-
-// Minimal OpenCV-FileStorage YAML reader for the three scalar keys the path uses
-// (cv::FileStorage is not available; /root/reference/ilcc2/config/pointgrey.yaml:17-19).
-int32_t ilcc_set_chessboard_param(ilcc_params* p, const char* cam_yaml) {
-  if (!p || !cam_yaml) return ILCC_BAD_ARGUMENT;
-  std::ifstream in(cam_yaml);
-  if (!in.is_open()) {
-    g_err = std::string("can not open ") + cam_yaml;   // LidarCornersEst.cpp:27
-    return ILCC_IO_ERROR;
-  }
-  double grid_length = -1;
-  long cx = -1, cy = -1;
-  std::string line;
-  while (std::getline(in, line)) {
-    const size_t hash = line.find('#');
-    if (hash != std::string::npos) line.erase(hash);
-    const size_t colon = line.find(':');
-    if (colon == std::string::npos) continue;
-    std::string key = line.substr(0, colon), val = line.substr(colon + 1);
-    auto trim = [](std::string& s) {
-      const size_t a = s.find_first_not_of(" \t\r\n");
-      const size_t b = s.find_last_not_of(" \t\r\n");
-      s = (a == std::string::npos) ? std::string() : s.substr(a, b - a + 1);
-    };
-    trim(key);
-    trim(val);
-    if (val.empty()) continue;
-    char* endp = nullptr;
-    if (key == "grid_length") grid_length = std::strtod(val.c_str(), &endp);
-    else if (key == "corner_in_x") cx = (long)std::strtod(val.c_str(), &endp);
-    else if (key == "corner_in_y") cy = (long)std::strtod(val.c_str(), &endp);
-  }
-  if (!(grid_length > 0) || cx < 1 || cy < 1) {
-    g_err = "grid_length / corner_in_x / corner_in_y missing or invalid";
-    return ILCC_BAD_ARGUMENT;
-  }
-  int32_t w = (int32_t)cx + 1, hh = (int32_t)cy + 1;   // :31-32
-  if (w > hh) std::swap(w, hh);                        // :35-39
-  // keep the default grid's meaning (one cell either way, g/20 steps) when the square size changes
-  const double scale = grid_length / p->grid_length;
-  p->grid_length = grid_length;
-  p->board_w = w;
-  p->board_h = hh;
-  if (scale > 0 && scale != 1.0) {
-    p->ty_min *= scale;
-    p->ty_step *= scale;
-    p->tz_min *= scale;
-    p->tz_step *= scale;
-  }
-  return ILCC_OK;
-}
 
 ilcc_handle* ilcc_create(int32_t device, const ilcc_params* p, uint32_t max_frames, uint64_t max_total_points) {
   g_err.clear();
@@ -1175,13 +1248,8 @@ ilcc_handle* ilcc_create(int32_t device, const ilcc_params* p, uint32_t max_fram
   if ((e = set_kernel_attributes_k2()) != hipSuccess || (e = set_kernel_attributes_k6()) != hipSuccess ||
       (e = set_kernel_attributes_k7()) != hipSuccess)
     return fail(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
-  float** tabs[] = {&h->d_cth, &h->d_sth, &h->d_ay, &h->d_az, &h->d_cth2, &h->d_sth2, &h->d_ay2, &h->d_az2};
-  for (float** t : tabs)
-    if ((e = hipMalloc((void**)t, sizeof(float) * h->max_theta)) != hipSuccess)
-      return fail(std::string("hipMalloc tables: ") + hipGetErrorString(e));
-  if ((e = hipMalloc((void**)&h->d_solve, sizeof(double) * 8)) != hipSuccess ||
-      (e = hipMalloc((void**)&h->d_refine_io, sizeof(RefineOut))) != hipSuccess)
-    return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
+  for (const Buffer& b : handle_buffers(h))
+    if (b.bytes && (e = hipMalloc(b.ptr, b.bytes)) != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
   warn_hw_queues_once();
   for (hipStream_t& s : h->stream)
     if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess)
@@ -1197,13 +1265,11 @@ void ilcc_destroy(ilcc_handle* h) {
   if (!h) return;
   for (hipStream_t s : h->stream)
     if (s) (void)hipStreamSynchronize(s);
-  for (Slot& sl : h->slots) free_slot(sl);
+  for (Slot& sl : h->slots) free_slot(h, sl);
   for (hipStream_t s : h->stream)
     if (s) (void)hipStreamDestroy(s);
-  void* bufs[] = {h->d_cth, h->d_sth, h->d_ay, h->d_az, h->d_cth2, h->d_sth2, h->d_ay2, h->d_az2, h->d_solve, h->d_refine_io,
-                  h->d_th_lattice};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
+  for (const Buffer& b : handle_buffers(h))
+    if (*b.ptr) (void)hipFree(*b.ptr);
   if (h->tl_ref) (void)hipEventDestroy(h->tl_ref);
   if (h->entry_done) (void)hipEventDestroy(h->entry_done);
   delete h;
@@ -1216,16 +1282,11 @@ int32_t ilcc_set_params(ilcc_handle* h, const ilcc_params* p) {
     h->err = why;
     return ILCC_BAD_ARGUMENT;
   }
-  for (const Slot& sl : h->slots)
-    if (sl.busy) {
-      h->err = "ilcc_set_params with a batch in flight: ilcc_wait first";
-      return ILCC_BAD_ARGUMENT;
-    }
-  int32_t st = sync_all(h);
-  if (st != ILCC_OK) return st;
+  if (any_batch_in_flight(h, "ilcc_set_params")) return ILCC_BAD_ARGUMENT;
+  ILCC_TRY(sync_all(h));
   const ilcc_params old = h->p;
   h->p = *p;
-  st = upload_tables(h);
+  int32_t st = upload_tables(h);
   for (Slot& sl : h->slots)   // the common pre-pass's buffers follow the grid (no batch is in flight here)
     if (st == ILCC_OK && sl.allocated) st = size_group_prepass(h, sl);
   if (st != ILCC_OK) {
@@ -1240,186 +1301,44 @@ int32_t ilcc_set_params(ilcc_handle* h, const ilcc_params* p) {
 }
 
 int32_t ilcc_reserve(ilcc_handle* h, uint32_t labelled_points_per_frame, uint32_t roi_points_per_frame) {
-  if (!h) return ILCC_BAD_ARGUMENT;
-  for (const Slot& sl : h->slots)
-    if (sl.busy) {
-      h->err = "ilcc_reserve with a batch in flight: ilcc_wait first";
-      return ILCC_BAD_ARGUMENT;
-    }
-  const uint32_t lab = std::min<uint32_t>((uint32_t)kGridLdsPointsMax, (std::max(labelled_points_per_frame, 1u) + 255u) & ~255u);
-  h->grid_lds_points = std::max(h->grid_lds_points, std::max(1024u, lab));
-  const uint32_t roi = std::min<uint32_t>((uint32_t)kClusterLdsPointsMax, (std::max(roi_points_per_frame, 1u) + 511u) & ~511u);
-  h->cluster_lds_points = std::max(h->cluster_lds_points, std::max((uint32_t)kClusterLdsPointsMin, roi));
+  if (!h || any_batch_in_flight(h, "ilcc_reserve")) return ILCC_BAD_ARGUMENT;
   // occupied cells: a cell of side 0.57 tol holds ~4.5 points of a VLP-16 ROI and ~8 of a 64-ring one; a quarter of the
   // points is a safe capacity (a frame above it takes the slower point-level path once and the handle grows)
-  const uint32_t cells = std::min<uint32_t>((uint32_t)kClusterCellsMax, (roi_points_per_frame / 4u + 255u) & ~255u);
-  h->cluster_cells_cap = std::max(h->cluster_cells_cap, std::max((uint32_t)kClusterCellsMin, cells));
-  fit_cluster_lds(h);
+  raise_capacities(h, grid_lds_capacity(labelled_points_per_frame), cluster_lds_capacity(roi_points_per_frame, (uint32_t)kClusterLdsPointsMin),
+                   cluster_cells_capacity(roi_points_per_frame / 4u));
   return ILCC_OK;
 }
+
+int32_t ilcc_set_result_mode(ilcc_handle* h, int32_t mode) {
+  if (!h || (mode != ILCC_RESULTS_FULL && mode != ILCC_RESULTS_COMPACT) || any_batch_in_flight(h, "ilcc_set_result_mode")) return ILCC_BAD_ARGUMENT;
+  h->result_mode = mode;
+  return ILCC_OK;
+}
+
+// ---- The batch entries: the argument check, then run_batch
 
 int32_t ilcc_submit_batch_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
                                  const float* d_clicks, int32_t* ticket) {
   if (!h || !d_xyzi || !d_clicks || !ticket) return ILCC_BAD_ARGUMENT;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int32_t st = check_offsets(h, offsets, n_frames);
-  if (st != ILCC_OK) return st;
-  const int si = h->next_slot;
-  Slot& sl = h->slots[si];
-  if (sl.busy) {
-    h->err = "every pipeline slot holds a batch: ilcc_wait for the oldest ticket first";
-    return ILCC_CAPACITY;
-  }
-  st = alloc_slot(h, sl);
-  if (st != ILCC_OK) return st;
-  const hipStream_t s = h->stream[take_stream(h)];
-  st = enqueue(h, si, s, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, d_clicks);
-  if (st != ILCC_OK) return st;
-  *ticket = si;
-  h->next_slot = (si + 1) % kSlots;
-  return ILCC_OK;
+  return run_batch(h, kRoiPipeline, /*on_device=*/true, d_xyzi, offsets, n_frames, d_clicks, ticket, nullptr);
 }
 
 int32_t ilcc_submit_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const float* clicks,
                           int32_t* ticket) {
   if (!h || !xyzi || !clicks || !ticket) return ILCC_BAD_ARGUMENT;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int32_t st = check_offsets(h, offsets, n_frames);
-  if (st != ILCC_OK) return st;
-  const int si = h->next_slot;
-  Slot& sl = h->slots[si];
-  if (sl.busy) {
-    h->err = "every pipeline slot holds a batch: ilcc_wait for the oldest ticket first";
-    return ILCC_CAPACITY;
-  }
-  st = alloc_slot(h, sl);
-  if (st != ILCC_OK) return st;
-  const hipStream_t s = h->stream[take_stream(h)];
-  // the copy rides on the batch's front-end stream: ordered before this batch's K1, concurrent with the other batches' kernels
-  if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
-  st = enqueue(h, si, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks);
-  if (st != ILCC_OK) return st;
-  *ticket = si;
-  h->next_slot = (si + 1) % kSlots;
-  return ILCC_OK;
-}
-
-// A ticket belongs to the call family that issued it: ilcc_submit_chessboard_by_point's batches skip the crop and
-// the search, and only their own wait applies the by-point epilogue (plane >= min_plane_points, whole-cloud n_roi); the other way
-// round that epilogue would read staging no copy of the batch has filled.  The batch stays in flight.
-static int32_t wrong_ticket_kind(ilcc_handle* h, const char* fn, bool ticket_is_online) {
-  h->err = std::string(fn) + (ticket_is_online ? ": this ticket came from ilcc_submit_chessboard_by_point: wait with ilcc_wait_chessboard_by_point"
-                                               : ": this ticket came from ilcc_submit_batch[_device]: wait with ilcc_wait / ilcc_wait_compact / ilcc_wait_records_device");
-  return ILCC_BAD_ARGUMENT;
-}
-
-int32_t ilcc_wait(ilcc_handle* h, int32_t ticket, ilcc_result* out) {
-  if (!h || !out || ticket < 0 || ticket >= kSlots || !h->slots[ticket].busy) {
-    if (h) h->err = "ilcc_wait: no batch in flight under this ticket";
-    return ILCC_BAD_ARGUMENT;
-  }
-  if (h->slots[ticket].online) return wrong_ticket_kind(h, "ilcc_wait", true);
-  HIP_TRY(h, hipSetDevice(h->device));
-  return finish(h, ticket, out);
-}
-
-int32_t ilcc_wait_records_device(ilcc_handle* h, int32_t ticket, ilcc_result* out, void* d_records, uint32_t n_corners,
-                                 uint32_t tag_base) {
-  if (!h || !d_records || n_corners > ILCC_MAX_CORNERS || ticket < 0 || ticket >= kSlots || !h->slots[ticket].busy) {   // (out may be NULL: device records only)
-    if (h) h->err = "ilcc_wait_records_device: bad argument or no batch in flight under this ticket";
-    return ILCC_BAD_ARGUMENT;
-  }
-  if (h->slots[ticket].online) return wrong_ticket_kind(h, "ilcc_wait_records_device", true);
-  HIP_TRY(h, hipSetDevice(h->device));
-  return finish(h, ticket, out, nullptr, static_cast<float*>(d_records), n_corners, tag_base);
-}
-
-int32_t ilcc_set_result_mode(ilcc_handle* h, int32_t mode) {
-  if (!h || (mode != ILCC_RESULTS_FULL && mode != ILCC_RESULTS_COMPACT)) return ILCC_BAD_ARGUMENT;
-  for (const Slot& sl : h->slots)
-    if (sl.busy) {
-      h->err = "ilcc_set_result_mode with a batch in flight: ilcc_wait first";
-      return ILCC_BAD_ARGUMENT;
-    }
-  h->result_mode = mode;
-  return ILCC_OK;
-}
-
-uint32_t ilcc_record_floats(const ilcc_handle* h, int32_t ticket) {
-  if (!h || ticket < 0 || ticket >= kSlots || !h->slots[ticket].busy) return 0u;
-  return (uint32_t)ILCC_RECORD_HEADER + 3u * h->slots[ticket].rec_corners;
-}
-
-int32_t ilcc_wait_compact(ilcc_handle* h, int32_t ticket, float* records, uint64_t capacity_floats) {
-  if (!h || !records || ticket < 0 || ticket >= kSlots || !h->slots[ticket].busy) {
-    if (h) h->err = "ilcc_wait_compact: no batch in flight under this ticket";
-    return ILCC_BAD_ARGUMENT;
-  }
-  if (h->slots[ticket].online) return wrong_ticket_kind(h, "ilcc_wait_compact", true);
-  {
-    const Slot& sl = h->slots[ticket];   // the record width was fixed when the batch was submitted
-    const uint64_t need = (uint64_t)sl.n_frames * ((uint64_t)ILCC_RECORD_HEADER + 3ull * sl.rec_corners);
-    if (capacity_floats < need) {
-      h->err = "ilcc_wait_compact: the batch's records need " + std::to_string(need) + " floats, the buffer holds " +
-               std::to_string(capacity_floats) + " (the batch stays in flight)";
-      return ILCC_BAD_ARGUMENT;
-    }
-  }
-  HIP_TRY(h, hipSetDevice(h->device));
-  return finish(h, ticket, nullptr, records);
-}
-
-int32_t ilcc_fetch_results(ilcc_handle* h, uint32_t first, uint32_t n, ilcc_result* out) {
-  if (!h || !out || h->last_slot < 0) return ILCC_BAD_ARGUMENT;
-  Slot& sl = h->slots[h->last_slot];
-  if (sl.busy || first > sl.n_frames || n > sl.n_frames - first) {
-    h->err = "ilcc_fetch_results: no completed batch, or the range exceeds it";
-    return ILCC_BAD_ARGUMENT;
-  }
-  HIP_TRY(h, hipSetDevice(h->device));
-  const int32_t st = ensure_full(h, sl);
-  if (st != ILCC_OK) return st;
-  const size_t row = trimmed_bytes(sl.rec_corners);
-  for (uint32_t f = 0; f < n; ++f) std::memcpy(&out[f], &sl.h_res[first + f], row);
-  return ILCC_OK;
+  return run_batch(h, kRoiPipeline, /*on_device=*/false, xyzi, offsets, n_frames, clicks, ticket, nullptr);
 }
 
 int32_t ilcc_extract_batch_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets,
                                   uint32_t n_frames, const float* d_clicks, ilcc_result* out) {
   if (!h || !d_xyzi || !d_clicks || !out) return ILCC_BAD_ARGUMENT;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int32_t st = check_offsets(h, offsets, n_frames);
-  if (st != ILCC_OK) return st;
-  if (h->slots[0].busy) {
-    h->err = "synchronous call while ticket 0 is in flight";
-    return ILCC_BAD_ARGUMENT;
-  }
-  const hipStream_t s = h->stream[take_stream(h)];
-  st = enqueue(h, 0, s, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, d_clicks);
-  if (st != ILCC_OK) return st;
-  return finish(h, 0, out);
+  return run_batch(h, kRoiPipeline, /*on_device=*/true, d_xyzi, offsets, n_frames, d_clicks, nullptr, out);
 }
 
 int32_t ilcc_extract_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
                            const float* clicks, ilcc_result* out) {
   if (!h || !xyzi || !clicks || !out) return ILCC_BAD_ARGUMENT;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int32_t st = check_offsets(h, offsets, n_frames);
-  if (st != ILCC_OK) return st;
-  Slot& sl = h->slots[0];
-  if (sl.busy) {
-    h->err = "synchronous call while ticket 0 is in flight";
-    return ILCC_BAD_ARGUMENT;
-  }
-  const hipStream_t s = h->stream[take_stream(h)];
-  if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, clicks, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
-  st = enqueue(h, 0, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks);
-  if (st != ILCC_OK) return st;
-  return finish(h, 0, out);
+  return run_batch(h, kRoiPipeline, /*on_device=*/false, xyzi, offsets, n_frames, clicks, nullptr, out);
 }
 
 int32_t ilcc_extract(ilcc_handle* h, const float* xyzi, uint32_t n, const float click[3], ilcc_result* out) {
@@ -1427,93 +1346,80 @@ int32_t ilcc_extract(ilcc_handle* h, const float* xyzi, uint32_t n, const float 
   return ilcc_extract_batch(h, xyzi, off, 1, click, out);
 }
 
-namespace {
-// what get_chessboard_by_point reports beyond the front half's record: n_roi of the WHOLE cloud, the second-tier count, and
-// `if(outcloud->size() < 500 || find_board == false) return false;` (LidarCornersEst.cpp:111-112)
-void finish_chessboard_by_point(ilcc_handle* h, Slot& sl, uint32_t n_frames, int32_t min_plane_points, ilcc_result* out) {
-  // frames the first tier answered from a window of the cloud: n_roi is what the clustering of the WHOLE cloud runs on -- its
-  // finite points (K1 counted them on the way); the handle's own copy keeps the window's count, which is what ILCC_CLOUD_ROI holds
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (sl.h_online[f] == 0u && out[f].status != ILCC_NO_ROI_POINTS) out[f].n_roi = (int32_t)sl.h_online[h->max_frames + f];
-  for (uint32_t f = 0; f < n_frames; ++f) h->timing.online_second_tier_frames += sl.h_online[f] != 0u ? 1u : 0u;
-  for (uint32_t f = 0; f < n_frames; ++f)
-    if (out[f].status == ILCC_OK && (out[f].n_plane < min_plane_points || !out[f].found_board)) {
-      out[f].status = ILCC_BOARD_NOT_FOUND;
-      sl.h_res[f].status = ILCC_BOARD_NOT_FOUND;
-    }
-}
-}  // namespace
-
 int32_t ilcc_chessboard_by_point_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
                                        const float* points, int32_t min_plane_points, ilcc_result* out) {
   if (!h || !xyzi || !points || !out) return ILCC_BAD_ARGUMENT;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int32_t st = check_offsets(h, offsets, n_frames);
-  if (st != ILCC_OK) return st;
-  Slot& sl = h->slots[0];
-  if (sl.busy) {
-    h->err = "synchronous call while ticket 0 is in flight";
-    return ILCC_BAD_ARGUMENT;
-  }
-  const hipStream_t s = h->stream[take_stream(h)];
-  if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, points, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
-  st = enqueue(h, 0, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks, /*front_only=*/true, /*no_crop=*/true);
-  if (st != ILCC_OK) return st;
-  st = finish(h, 0, out);
-  if (st != ILCC_OK) return st;
-  finish_chessboard_by_point(h, sl, n_frames, min_plane_points, out);
+  ILCC_TRY(run_batch(h, kByPoint, /*on_device=*/false, xyzi, offsets, n_frames, points, nullptr, out));
+  finish_chessboard_by_point(h, h->slots[0], n_frames, min_plane_points, out);
   return ILCC_OK;
 }
 
 // The same call in two halves, like ilcc_submit_batch / ilcc_wait: up to four calls in flight per handle, each whole on one of
-// the handle's three streams in turn, the H2D copy of one overlapping the kernels of the others (the two tiers need no host decision in between: the second tier's kernels skip the
-// frames the first has answered).  A tracker that hands over one scan at a time gains nothing; a recorded sequence does.
+// the handle's three streams in turn, the H2D copy of one overlapping the kernels of the others (the two tiers need no host
+// decision in between: the second tier's kernels skip the frames the first has answered).  A tracker that hands over one scan at
+// a time gains nothing; a recorded sequence does.
 int32_t ilcc_submit_chessboard_by_point(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
                                         const float* points, int32_t* ticket) {
   if (!h || !xyzi || !points || !ticket) return ILCC_BAD_ARGUMENT;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int32_t st = check_offsets(h, offsets, n_frames);
-  if (st != ILCC_OK) return st;
-  const int si = h->next_slot;
-  Slot& sl = h->slots[si];
-  if (sl.busy) {
-    h->err = "every pipeline slot holds a batch: wait for the oldest ticket first";
-    return ILCC_CAPACITY;
+  return run_batch(h, kByPoint, /*on_device=*/false, xyzi, offsets, n_frames, points, ticket, nullptr);
+}
+
+// ---- The waits: ticket_slot, then finish
+
+int32_t ilcc_wait(ilcc_handle* h, int32_t ticket, ilcc_result* out) {
+  Slot* sl = ticket_slot(h, ticket, "ilcc_wait", kRoiPipeline, out != nullptr);
+  return sl ? finish(h, *sl, out) : ILCC_BAD_ARGUMENT;
+}
+
+int32_t ilcc_wait_records_device(ilcc_handle* h, int32_t ticket, ilcc_result* out, void* d_records, uint32_t n_corners,
+                                 uint32_t tag_base) {
+  // (out may be NULL: device records only)
+  Slot* sl = ticket_slot(h, ticket, "ilcc_wait_records_device", kRoiPipeline, d_records && n_corners <= ILCC_MAX_CORNERS);
+  return sl ? finish(h, *sl, out, nullptr, static_cast<float*>(d_records), n_corners, tag_base) : ILCC_BAD_ARGUMENT;
+}
+
+uint32_t ilcc_record_floats(const ilcc_handle* h, int32_t ticket) {
+  const Slot* sl = busy_slot(h, ticket);
+  return sl ? (uint32_t)record_floats(*sl) : 0u;
+}
+
+int32_t ilcc_wait_compact(ilcc_handle* h, int32_t ticket, float* records, uint64_t capacity_floats) {
+  Slot* sl = ticket_slot(h, ticket, "ilcc_wait_compact", kRoiPipeline, records != nullptr);
+  if (!sl) return ILCC_BAD_ARGUMENT;
+  const uint64_t need = (uint64_t)sl->n_frames * record_floats(*sl);   // the record width was fixed when the batch was submitted
+  if (capacity_floats < need) {
+    h->err = "ilcc_wait_compact: the batch's records need " + std::to_string(need) + " floats, the buffer holds " +
+             std::to_string(capacity_floats) + " (the batch stays in flight)";
+    return ILCC_BAD_ARGUMENT;
   }
-  st = alloc_slot(h, sl);
-  if (st != ILCC_OK) return st;
-  const hipStream_t s = h->stream[take_stream(h)];
-  if (offsets[n_frames] > 0)
-    HIP_TRY(h, hipMemcpyAsync(sl.d_xyzi, xyzi, sizeof(float4) * offsets[n_frames], hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_clicks, points, sizeof(float) * 3 * n_frames, hipMemcpyHostToDevice, s));
-  st = enqueue(h, si, s, sl.d_xyzi, offsets, n_frames, sl.d_clicks, /*front_only=*/true, /*no_crop=*/true);
-  if (st != ILCC_OK) return st;
-  *ticket = si;
-  h->next_slot = (si + 1) % kSlots;
-  return ILCC_OK;
+  return finish(h, *sl, nullptr, records);
 }
 
 int32_t ilcc_wait_chessboard_by_point(ilcc_handle* h, int32_t ticket, int32_t min_plane_points, ilcc_result* out) {
-  if (!h || !out || ticket < 0 || ticket >= kSlots || !h->slots[ticket].busy) {
-    if (h) h->err = "ilcc_wait_chessboard_by_point: no batch in flight under this ticket";
-    return ILCC_BAD_ARGUMENT;
-  }
-  if (!h->slots[ticket].online) return wrong_ticket_kind(h, "ilcc_wait_chessboard_by_point", false);
-  HIP_TRY(h, hipSetDevice(h->device));
-  Slot& sl = h->slots[ticket];
-  const uint32_t n_frames = sl.n_frames;
-  const int32_t st = finish(h, ticket, out);
-  if (st != ILCC_OK) return st;
-  finish_chessboard_by_point(h, sl, n_frames, min_plane_points, out);
+  Slot* sl = ticket_slot(h, ticket, "ilcc_wait_chessboard_by_point", kByPoint, out != nullptr);
+  if (!sl) return ILCC_BAD_ARGUMENT;
+  ILCC_TRY(finish(h, *sl, out));
+  finish_chessboard_by_point(h, *sl, sl->n_frames, min_plane_points, out);
+  return ILCC_OK;
+}
+
+// ---- The fetch entries: the last completed batch's records and stage buffers
+
+int32_t ilcc_fetch_results(ilcc_handle* h, uint32_t first, uint32_t n, ilcc_result* out) {
+  Slot* slp = nullptr;
+  ILCC_TRY(out ? fetch_slot(h, first, n, slp) : ILCC_BAD_ARGUMENT);
+  Slot& sl = *slp;
+  ILCC_TRY(ensure_full(h, sl));
+  const size_t row = trimmed_bytes(sl.rec_corners);
+  for (uint32_t f = 0; f < n; ++f) std::memcpy(&out[f], &sl.h_res[first + f], row);
   return ILCC_OK;
 }
 
 int64_t ilcc_fetch_classes(ilcc_handle* h, uint32_t frame, uint8_t* out_class, uint64_t cap_points) {
-  if (!h || h->last_slot < 0) return -(int64_t)ILCC_BAD_ARGUMENT;
-  Slot& sl = h->slots[h->last_slot];
-  if (sl.busy || frame >= sl.n_frames) return -(int64_t)ILCC_BAD_ARGUMENT;
+  Slot* slp = nullptr;
+  const int32_t st = fetch_slot(h, frame, 1, slp);
+  if (st != ILCC_OK) return -(int64_t)st;
+  Slot& sl = *slp;
   if (ensure_full(h, sl) != ILCC_OK) return -(int64_t)ILCC_HIP_ERROR;
   const ilcc_result& r = sl.h_res[frame];
   const int64_t n = (r.status == ILCC_OK || r.status == ILCC_AMBIGUOUS || r.status == ILCC_BOARD_NOT_FOUND) ? r.n_plane : 0;
@@ -1525,9 +1431,10 @@ int64_t ilcc_fetch_classes(ilcc_handle* h, uint32_t frame, uint8_t* out_class, u
 }
 
 int64_t ilcc_fetch_cloud(ilcc_handle* h, uint32_t frame, int32_t which, float* out_xyzi, uint64_t cap_points) {
-  if (!h || h->last_slot < 0) return -(int64_t)ILCC_BAD_ARGUMENT;
-  Slot& sl = h->slots[h->last_slot];
-  if (sl.busy || frame >= sl.n_frames) return -(int64_t)ILCC_BAD_ARGUMENT;
+  Slot* slp = nullptr;
+  const int32_t st = fetch_slot(h, frame, 1, slp);
+  if (st != ILCC_OK) return -(int64_t)st;
+  Slot& sl = *slp;
   if (ensure_full(h, sl) != ILCC_OK) return -(int64_t)ILCC_HIP_ERROR;
   const ilcc_result& r = sl.h_res[frame];
   const float4* src = nullptr;
@@ -1551,25 +1458,21 @@ int64_t ilcc_fetch_cloud(ilcc_handle* h, uint32_t frame, int32_t which, float* o
 }
 
 int64_t ilcc_fetch_labelled(ilcc_handle* h, uint32_t frame, float* out_yz, uint8_t* out_label, uint64_t cap_points) {
-  if (!h || h->last_slot < 0) return -(int64_t)ILCC_BAD_ARGUMENT;
-  Slot& sl = h->slots[h->last_slot];
-  if (sl.busy || frame >= sl.n_frames) return -(int64_t)ILCC_BAD_ARGUMENT;
+  Slot* slp = nullptr;
+  const int32_t st = fetch_slot(h, frame, 1, slp);
+  if (st != ILCC_OK) return -(int64_t)st;
+  Slot& sl = *slp;
   uint32_t n = 0;
   if (hipMemcpy(&n, sl.d_nlab + frame, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return -(int64_t)ILCC_HIP_ERROR;
-  const uint64_t m = std::min<uint64_t>(n, cap_points);
-  if (m > 0) {
-    if (out_yz && hipMemcpy(out_yz, sl.d_yz + sl.off[frame], sizeof(float2) * m, hipMemcpyDeviceToHost) != hipSuccess)
-      return -(int64_t)ILCC_HIP_ERROR;
-    if (out_label && hipMemcpy(out_label, sl.d_lab + sl.off[frame], m, hipMemcpyDeviceToHost) != hipSuccess)
-      return -(int64_t)ILCC_HIP_ERROR;
-  }
-  return (int64_t)n;
+  return fetch_labelled_points(sl.d_yz + sl.off[frame], sl.d_lab + sl.off[frame], n, out_yz, out_label, cap_points);
 }
 
 int64_t ilcc_fetch_walk(ilcc_handle* h, uint32_t frame, float* out_yz, uint8_t* out_label, uint64_t cap_points, uint32_t counts[2]) {
-  if (!h || h->last_slot < 0) return -(int64_t)ILCC_BAD_ARGUMENT;
-  Slot& sl = h->slots[h->last_slot];
-  if (sl.busy || frame >= sl.n_frames || !sl.grid) return -(int64_t)ILCC_BAD_ARGUMENT;
+  Slot* slp = nullptr;
+  const int32_t st = fetch_slot(h, frame, 1, slp);
+  if (st != ILCC_OK) return -(int64_t)st;
+  Slot& sl = *slp;
+  if (!sl.grid) return -(int64_t)ILCC_BAD_ARGUMENT;
   uint32_t n = 0;
   if (hipMemcpy(&n, sl.d_nlab + frame, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return -(int64_t)ILCC_HIP_ERROR;
   if (n > (uint32_t)kGridLdsPointsMax) n = 0;   // such a frame is walked through global memory: no layout
@@ -1578,56 +1481,14 @@ int64_t ilcc_fetch_walk(ilcc_handle* h, uint32_t frame, float* out_yz, uint8_t* 
         hipMemcpy(&counts[1], sl.d_walk_nrim + frame, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
       return -(int64_t)ILCC_HIP_ERROR;
   }
-  const uint64_t m = std::min<uint64_t>(n, cap_points);
-  if (m > 0) {
-    if (out_yz && hipMemcpy(out_yz, sl.d_walk_yz + sl.off[frame], sizeof(float2) * m, hipMemcpyDeviceToHost) != hipSuccess)
-      return -(int64_t)ILCC_HIP_ERROR;
-    if (out_label && hipMemcpy(out_label, sl.d_walk_lab + sl.off[frame], m, hipMemcpyDeviceToHost) != hipSuccess)
-      return -(int64_t)ILCC_HIP_ERROR;
-  }
-  return (int64_t)n;
-}
-
-// shared setup for the two single-kernel test entries: frame 0 of slot 0 = caller's labelled points
-static int32_t stage_labelled(ilcc_handle* h, hipStream_t s, const float* yz, const uint8_t* label, uint32_t m) {
-  if (!h || (m > 0 && (!yz || !label))) return ILCC_BAD_ARGUMENT;
-  if (m > h->max_points) {
-    h->err = "more points than the handle holds";
-    return ILCC_CAPACITY;
-  }
-  Slot& sl = h->slots[0];
-  if (sl.busy) {
-    h->err = "diagnostic entry while ticket 0 is in flight";
-    return ILCC_BAD_ARGUMENT;
-  }
-  HIP_TRY(h, hipSetDevice(h->device));
-  const uint64_t off[2] = {0, m};
-  ilcc_result r;
-  std::memset(&r, 0, sizeof(r));
-  r.status = ILCC_OK;
-  HIP_TRY(h, hipMemcpyAsync(sl.d_off, off, sizeof(off), hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_res, &r, sizeof(r), hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(sl.d_nlab, &m, sizeof(m), hipMemcpyHostToDevice, s));
-  const uint32_t stride = walk_stride(m);
-  HIP_TRY(h, hipMemcpyAsync(sl.d_walk, &stride, sizeof(stride), hipMemcpyHostToDevice, s));
-  if (m > 0) {
-    HIP_TRY(h, hipMemcpyAsync(sl.d_yz, yz, sizeof(float2) * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(sl.d_lab, label, m, hipMemcpyHostToDevice, s));
-  }
-  {
-    const int32_t sst = sync_own(h, s);
-    if (sst != ILCC_OK) return sst;
-  }
-  sl.n_frames = 0;   // the stage buffers no longer describe a batch
-  return ILCC_OK;
+  return fetch_labelled_points(sl.d_walk_yz + sl.off[frame], sl.d_walk_lab + sl.off[frame], n, out_yz, out_label, cap_points);
 }
 
 int32_t ilcc_grid_cost(ilcc_handle* h, const float* yz, const uint8_t* label, uint32_t m, int32_t use_oob,
                        float* cost_out, int32_t* best_index, float* best_cost) {
   if (!h) return ILCC_BAD_ARGUMENT;
   const hipStream_t s = h->stream[take_stream(h)];
-  int32_t st = stage_labelled(h, s, yz, label, m);
-  if (st != ILCC_OK) return st;
+  ILCC_TRY(stage_labelled(h, s, yz, label, m));
   Slot& sl = h->slots[0];
   const size_t vol = (size_t)h->p.n_th * h->p.n_ty * h->p.n_tz * 2;
   float* d_vol = nullptr;
@@ -1636,12 +1497,7 @@ int32_t ilcc_grid_cost(ilcc_handle* h, const float* yz, const uint8_t* label, ui
     float* p;
     ~VolGuard() { if (p) (void)hipFree(p); }
   } guard{d_vol};
-  uint32_t lds = 1024;
-  while (lds < m && lds < (uint32_t)kGridLdsPointsMax) lds <<= 1;
-  const uint32_t saved = h->grid_lds_points;
-  h->grid_lds_points = std::max(saved, lds);
-  const Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
-  h->grid_lds_points = saved;
+  const Ctx c = diagnostic_ctx(h, sl, m);
   const uint32_t inf_bits = 0x7f800000u;
   HIP_TRY(h, hipMemcpyAsync(sl.d_bound, &inf_bits, sizeof(inf_bits), hipMemcpyHostToDevice, s));
   launch_walk_order(c, s);
@@ -1675,33 +1531,23 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
     return ILCC_BAD_ARGUMENT;
   }
   const hipStream_t s = h->stream[take_stream(h)];
-  int32_t st = stage_labelled(h, s, yz, label, m);
-  if (st != ILCC_OK) return st;
+  ILCC_TRY(stage_labelled(h, s, yz, label, m));
   Slot& sl = h->slots[0];
-  uint32_t lds = 1024;
-  while (lds < m && lds < (uint32_t)kGridLdsPointsMax) lds <<= 1;
-  const uint32_t saved = h->grid_lds_points;
-  h->grid_lds_points = std::max(saved, lds);
-  const Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
-  h->grid_lds_points = saved;
+  const Ctx c = diagnostic_ctx(h, sl, m);
   // what K1 resets per frame and per batch
   const uint32_t inf_bits = 0x7f800000u, zero = 0u;
   HIP_TRY(h, hipMemcpyAsync(sl.d_bound, &inf_bits, sizeof(inf_bits), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(sl.d_bound_sub, &inf_bits, sizeof(inf_bits), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(sl.d_tie_count, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemsetAsync(sl.d_iters, 0, sizeof(unsigned long long) * kBatchWords, s));
-  st = enqueue_grid_search(h, sl, c, s, 1, /*chain=*/false);
-  if (st != ILCC_OK) return st;
+  ILCC_TRY(enqueue_grid_search(h, sl, c, s, 1, /*chain=*/false));
   launch_pattern_refine_corners(c, s);
   HIP_TRY(h, hipGetLastError());
   SolveRec rec{};
   ilcc_result r;
   HIP_TRY(h, hipMemcpyAsync(&rec, sl.d_solverec, sizeof(rec), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipMemcpyAsync(&r, sl.d_res, offsetof(ilcc_result, corners), hipMemcpyDeviceToHost, s));
-  {
-    const int32_t sst = sync_own(h, s);
-    if (sst != ILCC_OK) return sst;
-  }
+  ILCC_TRY(sync_own(h, s));
   if (!rec.valid) {
     h->err = "ilcc_grid_solve: the grid search produced no candidate";
     return ILCC_TOO_FEW_POINTS;
@@ -1728,19 +1574,15 @@ int32_t ilcc_get_theta_t(ilcc_handle* h, const float* yz, const uint8_t* label, 
                          int32_t use_oob, double theta_t[3], double* cost, int32_t* iterations) {
   if (!h || !theta_t) return ILCC_BAD_ARGUMENT;
   const hipStream_t s = h->stream[take_stream(h)];
-  int32_t st = stage_labelled(h, s, yz, label, m);
-  if (st != ILCC_OK) return st;
+  ILCC_TRY(stage_labelled(h, s, yz, label, m));
   Slot& sl = h->slots[0];
   HIP_TRY(h, hipMemcpyAsync(h->d_solve, theta_t, sizeof(double) * 3, hipMemcpyHostToDevice, s));
-  const Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
+  const Ctx c = diagnostic_ctx(h, sl, 0);
   launch_local_solve(c, s, topleft_white, use_oob, h->d_solve, h->d_solve + 3);
   HIP_TRY(h, hipGetLastError());
   double back[5];
   HIP_TRY(h, hipMemcpyAsync(back, h->d_solve, sizeof(back), hipMemcpyDeviceToHost, s));
-  {
-    const int32_t sst = sync_own(h, s);
-    if (sst != ILCC_OK) return sst;
-  }
+  ILCC_TRY(sync_own(h, s));
   theta_t[0] = back[0];
   theta_t[1] = back[1];
   theta_t[2] = back[2];
@@ -1758,8 +1600,7 @@ int32_t ilcc_pattern_refine(ilcc_handle* h, const float* yz, const uint8_t* labe
     return ILCC_BAD_ARGUMENT;
   }
   const hipStream_t s = h->stream[take_stream(h)];
-  int32_t st = stage_labelled(h, s, yz, label, m);
-  if (st != ILCC_OK) return st;
+  ILCC_TRY(stage_labelled(h, s, yz, label, m));
   Slot& sl = h->slots[0];
   RefineOut io{};
   io.lat[0] = lat[0];
@@ -1767,14 +1608,11 @@ int32_t ilcc_pattern_refine(ilcc_handle* h, const float* yz, const uint8_t* labe
   io.lat[2] = lat[2];
   io.phase = *phase;
   HIP_TRY(h, hipMemcpyAsync(h->d_refine_io, &io, sizeof(io), hipMemcpyHostToDevice, s));
-  const Ctx c = make_ctx(h, sl, nullptr, nullptr, 1, 1);
+  const Ctx c = diagnostic_ctx(h, sl, 0);
   launch_pattern_refine_test(c, s, h->d_refine_io);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(&io, h->d_refine_io, sizeof(io), hipMemcpyDeviceToHost, s));
-  {
-    const int32_t sst = sync_own(h, s);
-    if (sst != ILCC_OK) return sst;
-  }
+  ILCC_TRY(sync_own(h, s));
   lat[0] = io.lat[0];
   lat[1] = io.lat[1];
   lat[2] = io.lat[2];
@@ -1800,13 +1638,7 @@ int32_t ilcc_debug_timeline_enable(ilcc_handle* h, int32_t on) {
 }
 
 int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on) {
-  if (!h) return ILCC_BAD_ARGUMENT;
-  for (const Slot& sl : h->slots) {
-    if (sl.busy) {
-      h->err = "ilcc_debug_separate_launches with a batch in flight: ilcc_wait first";
-      return ILCC_BAD_ARGUMENT;
-    }
-  }
+  if (!h || any_batch_in_flight(h, "ilcc_debug_separate_launches")) return ILCC_BAD_ARGUMENT;
   h->separate_launches = on != 0;
   return ILCC_OK;
 }
@@ -1825,36 +1657,6 @@ void ilcc_get_timing(const ilcc_handle* h, ilcc_timing* t) {
 }
 void ilcc_reset_timing(ilcc_handle* h) {
   if (h) h->timing = ilcc_timing{};
-}
-
-// get_lidar_corners.cpp:27-36 -- ofstream(trunc), `x << " " << y << " " << z << endl` with the
-// stream's default float formatting (precision 6).
-int32_t ilcc_save_corners2txt(const float* corners_xyz, uint32_t n_corners, const char* filename) {
-  if (!corners_xyz || !filename) return ILCC_BAD_ARGUMENT;
-  std::ofstream outfile(filename, std::ios_base::trunc);
-  if (!outfile.is_open()) return ILCC_IO_ERROR;
-  for (uint32_t i = 0; i < n_corners; ++i)
-    outfile << corners_xyz[3 * i] << " " << corners_xyz[3 * i + 1] << " " << corners_xyz[3 * i + 2] << std::endl;
-  outfile.close();
-  return outfile.fail() ? ILCC_IO_ERROR : ILCC_OK;
-}
-
-// ImageCornersEst.cpp:281-299 -- `float x,y,z; infile >> x >> y >> z` until eof or num corners
-int32_t ilcc_read_lidar_corners(const char* filename, uint32_t num, double* out_xyz) {
-  if (!filename || !out_xyz) return -ILCC_BAD_ARGUMENT;
-  std::ifstream infile(filename);
-  if (!infile.is_open()) return -ILCC_IO_ERROR;
-  uint32_t counter = 0;
-  while (!infile.eof() && counter < num) {
-    float x = 0, y = 0, z = 0;
-    infile >> x >> y >> z;
-    if (infile.fail()) break;
-    out_xyz[3 * counter] = x;
-    out_xyz[3 * counter + 1] = y;
-    out_xyz[3 * counter + 2] = z;
-    ++counter;
-  }
-  return (int32_t)counter;
 }
 
 }  // extern "C"
