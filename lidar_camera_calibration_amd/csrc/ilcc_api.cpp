@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ilcc_internal.h"
+#include "k7_common.h"
 
 using namespace ilcc;
 
@@ -811,10 +812,11 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
   HIP_TRY(h, hipEventRecord(sl.ev[kEvSearched], s));
   if (kind == kRoiPipeline) {
     if (sl.grid) {
-      launch_pattern_refine_corners(c, s);   // (with the near ties of the full pass, re-ordered on fixed-point sums by K7r)
+      launch_pattern_refine(c, s);   // (with the near ties of the full pass, re-ordered on fixed-point sums by K7r)
     } else {
-      launch_refine_corners(c, s);
+      launch_reference_solve(c, s);
     }
+    launch_corners(c, s, solve_slots(c.p));
   }
   HIP_TRY(h, hipEventRecord(sl.ev[kEvEnd], s));
   HIP_TRY(h, hipGetLastError());
@@ -1246,7 +1248,7 @@ ilcc_handle* ilcc_create(int32_t device, const ilcc_params* p, uint32_t max_fram
   }
   // dynamic-LDS limits are kept per (function, device): raise them for THIS device, and say so when that fails
   if ((e = set_kernel_attributes_k2()) != hipSuccess || (e = set_kernel_attributes_k6()) != hipSuccess ||
-      (e = set_kernel_attributes_k7()) != hipSuccess)
+      (e = set_kernel_attributes_k7a()) != hipSuccess || (e = set_kernel_attributes_k7r()) != hipSuccess)
     return fail(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
   for (const Buffer& b : handle_buffers(h))
     if (b.bytes && (e = hipMalloc(b.ptr, b.bytes)) != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -1541,7 +1543,8 @@ int32_t ilcc_grid_solve(ilcc_handle* h, const float* yz, const uint8_t* label, u
   HIP_TRY(h, hipMemcpyAsync(sl.d_tie_count, &zero, sizeof(zero), hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemsetAsync(sl.d_iters, 0, sizeof(unsigned long long) * kBatchWords, s));
   ILCC_TRY(enqueue_grid_search(h, sl, c, s, 1, /*chain=*/false));
-  launch_pattern_refine_corners(c, s);
+  launch_pattern_refine(c, s);
+  launch_corners(c, s, 1);
   HIP_TRY(h, hipGetLastError());
   SolveRec rec{};
   ilcc_result r;

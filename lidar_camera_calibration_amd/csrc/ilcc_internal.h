@@ -69,7 +69,7 @@ constexpr int kSolveThreads = ILCC_K7_THREADS;     // K7: wavefronts x 64 per (f
 constexpr int kRefineThreads = ILCC_K7R_THREADS;   // K7r: one workgroup per frame
 constexpr int kRefineThreadsSmallBatch = 768;      // K7r in batches of <= kSmallBatchFrames frames: 4 wavefronts per theta of the stencil
 constexpr int kRefineList = 32;        // K7r: candidates evaluated per sweep over the points
-constexpr int kTieCap = 256;           // K6 -> K7a: near-tie candidates kept per frame for the fp64 recount
+constexpr int kTieCap = 256;           // K6 -> K7r: near-tie candidates kept per frame for the fp64 recount
 constexpr float kTieEps = 2e-5f;       // relative cost window of a near-tie (fp32 sums of ~1e3 terms agree to ~1e-6)
 constexpr int kCoverageCellsMax = 1024;   // K7b: board squares tracked by the coverage mask (board_w x board_h)
 constexpr int kIterSlots = 64;         // K6 executed-iteration counters (spread to avoid one hot atomic); [0,64): all points, [64,128): interior-class points, [128,192): (point, tile) evaluations of the box pre-pass
@@ -335,13 +335,16 @@ void launch_walk_order(const Ctx& c, hipStream_t s);   // K5w (k6_grid_cost.hip)
 void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/, bool prune);
 void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // in front of the full pass it is given: writes full.grp_alive / grp_mask
 uint32_t grid_cost_evals_per_count();   // (point, candidate) evaluations behind one count of Ctx::grid_iters
-void launch_refine_corners(const Ctx& c, hipStream_t s);
+// K7a on every frame of the batch (REFERENCE_LOCAL mode: solve_slots(c.p) solves per frame, k7_common.h)
+void launch_reference_solve(const Ctx& c, hipStream_t s);
+// K7r on every frame of the batch (GRID mode: one solve per frame)
+void launch_pattern_refine(const Ctx& c, hipStream_t s);
+// K7b behind either solver: corners from the better of each frame's n_slots solve records
+void launch_corners(const Ctx& c, hipStream_t s, int n_slots);
 void launch_pack_records(const ilcc_result* d_res, uint32_t n_frames, uint32_t n_corners, uint32_t tag_base, float* d_out,
                          hipStream_t s);
-// device memory -> pinned (mapped) host memory with the GPU's own stores, on stream s: no SDMA command (k7_refine_corners.hip)
+// device memory -> pinned (mapped) host memory with the GPU's own stores, on stream s: no SDMA command (k9_pack_records.hip)
 void launch_store_to_host(const void* d_src, void* h_dst, size_t bytes, hipStream_t s);
-// K7r on every frame of the batch (GRID mode), then K7b
-void launch_pattern_refine_corners(const Ctx& c, hipStream_t s);
 // stand-alone K7r on the labelled points of frame 0 (test entry)
 void launch_pattern_refine_test(const Ctx& c, hipStream_t s, RefineOut* d_io);
 // once per (process, device): raise the dynamic-LDS limits of the kernels that need more than 64 KiB
@@ -350,7 +353,8 @@ size_t cluster_lds_bytes(uint32_t pts_cap, uint32_t cells_cap, uint32_t bits);  
 uint32_t cluster_bits_default();
 uint32_t cluster_bits_online();
 hipError_t set_kernel_attributes_k6();
-hipError_t set_kernel_attributes_k7();
+hipError_t set_kernel_attributes_k7a();
+hipError_t set_kernel_attributes_k7r();
 // stand-alone local solve on the labelled points of frame 0 (test entry)
 void launch_local_solve(const Ctx& c, hipStream_t s, int32_t tlw, int32_t use_oob, double* theta_t,
                         double* cost_iters /*[2]: cost, iterations*/);

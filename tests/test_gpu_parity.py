@@ -1713,6 +1713,36 @@ def test_reference_solver_single_phase_layouts_and_global_memory_fallback(ob, fr
     assert n_ok >= 5
 
 
+@pytest.mark.parametrize("phase_mode", [0, 2])
+def test_reference_solver_partly_filled_workgroup_and_failed_frames(frames272, phase_mode):
+    """K7a's one-wavefront-per-solve layout with a last workgroup that is only partly filled, and with failed frames inside
+    workgroups that share a staging area.  257 frames: with one solve per frame (phase_mode 0) the 65th and last workgroup
+    holds one live wavefront, with two (phase_mode 2) the 129th holds two.  Frames 3, 130 and 256 have their click moved away from everything, so
+    they fail in front of K7a: their wavefronts stage nothing and write an invalid record beside neighbours that solve.
+    Every field of the 72 compared frames, the status included, equals the workgroup layout's (three batches of 24).
+    (The oracle alone leaves 3 of the other 69 frames not OK -- 0, 126 and 141 -- in both phase modes: the cap is 9.)"""
+    clouds, clicks = frames272[0][:257], frames272[1][:257].copy()
+    moved = (3, 130, 256)
+    for f in moved:
+        clicks[f] = (50.0, 50.0, 50.0)          # nothing in the ROI
+    p = N.default_params()
+    p.solver = N.SOLVER_REFERENCE_LOCAL
+    p.phase_mode = phase_mode
+    e = LidarCornersBatch(len(clouds), clouds.shape[1], p)
+    big = _ref_fields(e.extract(clouds, clicks))
+    n_bad = 0
+    for lo, hi in ((0, 24), (120, 144), (233, 257)):
+        small = _ref_fields(e.extract(clouds[lo:hi], clicks[lo:hi]))
+        assert small == big[lo:hi], (lo, hi)
+        for f in range(lo, hi):
+            if f in moved:
+                assert big[f][0] != N.OK and small[f - lo][0] != N.OK, f
+            else:
+                n_bad += big[f][0] != N.OK
+    e.close()
+    assert n_bad <= 9, n_bad
+
+
 # ----------------------------------------------------------------------------- records beyond 35 corners
 @pytest.mark.parametrize("board,grid,kw", [(synth.Board(2, 2, 0.25), None, {}),
                                            (synth.Board(17, 17, 0.08), _SMALL_GRID, dict(roi_half=(1.2, 1.6, 2.0)))],
