@@ -2,8 +2,8 @@
  * ilcc_camera_image.h -- the step BEFORE ilcc_image_corners.h: from a camera bag, or from a raw frame,
  * to the undistorted 8-bit grayscale image in device memory that K10 takes.  Implemented in
  * libilcc_hip.so: the intrinsics reader, the sensor_msgs/Image parser and the bag entries on the host
- * (csrc/camera_image_host.cpp), conversion and undistortion in one gfx950 kernel (K11,
- * csrc/k11_camera_image.hip).
+ * (csrc/camera_image_host.cpp), conversion and undistortion in one gfx950 kernel (K11 for grayscale, K11c for
+ * the colour image that ilcc_overlay.h draws LiDAR points on; csrc/k11_camera_image.hip).
  *
  *   reference                                                             here
  *   --------------------------------------------------------------------  ---------------------------
@@ -15,6 +15,8 @@
  *   cv_bridge::toCvCopy(msg, MONO8)  (test/get_image_corners_bag.cpp:26)    ilcc_image_to_mono8_device
  *   undistort_image -> cv::undistort(image, rectify, camK, distort_param,                 (K11, gfx950 kernel)
  *     camK)          (src/ImageCornersEst.cpp:63-66)
+ *   cv_bridge::toCvCopy(msg, "bgr8") + cv::undistort of the COLOUR image   ilcc_image_to_bgr8_device
+ *     (test/pcd2image.cpp:36,101)                                                        (K11c, gfx950 kernel)
  *   initUndistortRectifyMap's map, as a stage output                      ilcc_undistort_map_device
  *   imwrite of the undistorted image (test/get_image_corners_bag.cpp:110)  ilcc_bag_first_image (host pixels)
  *   ... and the MATLAB step on that image (ilcc_image_corners.h)           ilcc_bag_find_chessboard
@@ -31,6 +33,9 @@
  *   sample: x0 = iu >> 5, y0 = iv >> 5 (arithmetic: floors negative codes), a = iu & 31, b = iv & 31,
  *     weights 32 (32-a)(32-b), 32 a (32-b), 32 (32-a) b, 32 a b; a tap outside the source counts as 0, each
  *     on its own; dst = (sum + 16384) >> 15.  Colour taps are converted to Y first.
+ *   bgr8 (K11c): bgr8 is copied, rgb8 swaps channels 0 and 2, bgra8 / rgba8 drop alpha (rgba8 also swaps), mono8 is
+ *     replicated into the three channels; with a camera, the same codes and the same four weights blend each of
+ *     B, G, R on its own (the conversion permutes or replicates channels, so it commutes with the blend).
  *   Deviation from OpenCV: it accumulates x along a row and works in stripes; here every pixel is
  *   evaluated directly (order 1e-13 px: moves a 1/32-pixel code only at an exact tie).
  *
@@ -92,6 +97,13 @@ int32_t ilcc_image_parse(const uint8_t* msg, uint64_t msg_bytes, ilcc_image_layo
  * finite and non-zero, source and destination ranges that overlap (the kernel gathers). */
 int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, int32_t height, int32_t src_step, int32_t encoding,
                                    const ilcc_camera_model* camera, void* d_dst, int32_t dst_stride, void* hip_stream);
+
+/* K11c: cv_bridge::toCvCopy(msg, "bgr8") followed by cv::undistort(image, K, d, K) (pcd2image.cpp:36,101):
+ * pixels of `encoding` -> 3 bytes B,G,R per pixel, rows dst_stride bytes apart.  camera == NULL: conversion only.
+ * The checks of the mono8 entry with dst_stride >= 3 * width; not a byte outside
+ * [row * dst_stride, row * dst_stride + 3 * width) is written.  Asynchronous on hip_stream. */
+int32_t ilcc_image_to_bgr8_device(const void* d_src, int32_t width, int32_t height, int32_t src_step, int32_t encoding,
+                                  const ilcc_camera_model* camera, void* d_dst, int32_t dst_stride, void* hip_stream);
 
 /* Stage output of K11: the 1/32-pixel source coordinates of every output pixel, camera->width x
  * camera->height int32 each (device memory, row-major, packed).  Asynchronous on hip_stream. */

@@ -1,6 +1,6 @@
 """Camera images from bags or raw frames: ctypes mirror of ``include/ilcc_camera_image.h`` -- the
 intrinsics of an OpenCV YAML, the layout of a serialized sensor_msgs/Image, conversion to mono8 and
-cv::undistort in one GPU kernel (K11), and the two bag entries that end in host pixels or in the
+cv::undistort in one GPU kernel (K11; K11c keeps the colour: B, G, R), and the two bag entries that end in host pixels or in the
 chessboard's corners.  What comes out of ``to_mono8(..., camera)`` is what
 ``image_corners.find_chessboard`` takes."""
 import ctypes as C
@@ -17,7 +17,7 @@ BYTES_PER_PIXEL = {"mono8": 1, "bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4}
 MAP_OUTSIDE = -2 ** 31                                         # code of an output pixel without a source
 
 CAMERA_IMAGE_EXPORTS = ["ilcc_read_camera_yaml", "ilcc_image_parse", "ilcc_image_to_mono8_device",
-                        "ilcc_undistort_map_device", "ilcc_bag_first_image", "ilcc_bag_find_chessboard"]
+                        "ilcc_image_to_bgr8_device", "ilcc_undistort_map_device", "ilcc_bag_first_image", "ilcc_bag_find_chessboard"]
 
 
 class CameraModel(C.Structure):
@@ -62,6 +62,8 @@ def lib():
         L.ilcc_image_to_mono8_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, cam, C.c_void_p,
                                                  C.c_int32, C.c_void_p]
         L.ilcc_image_to_mono8_device.restype = C.c_int32
+        L.ilcc_image_to_bgr8_device.argtypes = L.ilcc_image_to_mono8_device.argtypes
+        L.ilcc_image_to_bgr8_device.restype = C.c_int32
         L.ilcc_undistort_map_device.argtypes = [cam, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ilcc_undistort_map_device.restype = C.c_int32
         L.ilcc_bag_first_image.argtypes = [C.c_int32, C.c_char_p, C.c_char_p, cam, C.c_void_p, C.c_uint64, i32p, i32p]
@@ -99,11 +101,8 @@ def parse_image(msg: bytes) -> ImageLayout:
     return lay
 
 
-def to_mono8(image, encoding, camera=None):
-    """K11: (rows, cols) mono8 or (rows, cols, channels) colour uint8 pixels, numpy or torch, ->
-    (rows, cols) uint8 tensor on the current HIP device: cv::undistort(mono8(image), K, d, K) with a
-    camera, mono8(image) without.  A device tensor whose pixels are contiguous is read in place with
-    stride(0) as the row pitch (a view of a pitched frame is not copied); asynchronous on the current stream."""
+def _device_pixels(image, encoding):
+    """The pixels as a device tensor (rows, cols, bytes per pixel) K11 can read in place, and its row pitch."""
     import torch
     if encoding not in ENCODINGS:
         raise ValueError("unsupported encoding %r (supported: %s)" % (encoding, ", ".join(ENCODINGS)))
@@ -119,11 +118,34 @@ def to_mono8(image, encoding, camera=None):
     rows_ok = t.stride(2) == 1 and t.stride(1) == bpp and (h == 1 or t.stride(0) >= w * bpp)
     if not (on_device and rows_ok):
         t = t.to("cuda").contiguous()
-    step = int(t.stride(0)) if h > 1 else w * bpp
+    return t, (int(t.stride(0)) if h > 1 else w * bpp)
+
+
+def to_mono8(image, encoding, camera=None):
+    """K11: (rows, cols) mono8 or (rows, cols, channels) colour uint8 pixels, numpy or torch, ->
+    (rows, cols) uint8 tensor on the current HIP device: cv::undistort(mono8(image), K, d, K) with a
+    camera, mono8(image) without.  A device tensor whose pixels are contiguous is read in place with
+    stride(0) as the row pitch (a view of a pitched frame is not copied); asynchronous on the current stream."""
+    import torch
+    t, step = _device_pixels(image, encoding)
+    h, w = int(t.shape[0]), int(t.shape[1])
     out = torch.empty((h, w), dtype=torch.uint8, device=t.device)
     stream = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
     _check(lib().ilcc_image_to_mono8_device(C.c_void_p(t.data_ptr()), w, h, step, ENCODINGS.index(encoding), _camera_ref(camera),
                                             C.c_void_p(out.data_ptr()), w, stream))
+    return out
+
+
+def to_bgr8(image, encoding, camera=None):
+    """K11c: the same pixels -> (rows, cols, 3) uint8 tensor, B, G, R: cv::undistort(bgr8(image), K, d, K) with a
+    camera, bgr8(image) without (what pcd2image draws on).  Reads device views in place like to_mono8."""
+    import torch
+    t, step = _device_pixels(image, encoding)
+    h, w = int(t.shape[0]), int(t.shape[1])
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=t.device)
+    stream = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    _check(lib().ilcc_image_to_bgr8_device(C.c_void_p(t.data_ptr()), w, h, step, ENCODINGS.index(encoding), _camera_ref(camera),
+                                           C.c_void_p(out.data_ptr()), 3 * w, stream))
     return out
 
 

@@ -18,6 +18,10 @@
 // computed addresses: the map is smooth, so the 256 pixels of a wavefront read about 256 consecutive
 // pixels of two adjacent source rows, which the L2 serves from the same few lines.  Without a camera
 // the source quad sits at a known address and is loaded as dwords where that address is aligned.
+//
+// K11c (k11_image_to_bgr8, ilcc_image_to_bgr8_device) is the same frame kept in colour for the overlay of
+// include/ilcc_overlay.h: cv_bridge::toCvCopy(msg, "bgr8") + cv::undistort (test/pcd2image.cpp:36,101).  It shares
+// the map, the weights and the thread-to-pixel map; its quad is 12 bytes, stored with one 3-dword store.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -80,23 +84,42 @@ __device__ __forceinline__ int32_t tap(const ImageArgs& a, int32_t x, int32_t y)
   return Pixel<ENC>::load(a.src + (int64_t)y * a.src_step + (int64_t)x * Pixel<ENC>::kBytes);
 }
 
+// where output pixel (j, i) samples the source: the top-left tap and the four 15-bit weights; false: no source at all
+struct Sample {
+  int32_t x0, y0;
+  int32_t w00, w10, w01, w11;   // taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1)
+};
+
+__device__ __forceinline__ bool sample_of(const LensArgs& L, int j, int i, Sample& s) {
+  int32_t iu, iv;
+  map_codes(L, j, i, iu, iv);
+  if (iu == kOutside) return false;
+  const int32_t fa = iu & 31, fb = iv & 31;
+  s.x0 = iu >> 5;
+  s.y0 = iv >> 5;
+  s.w00 = 32 * (32 - fa) * (32 - fb);
+  s.w10 = 32 * fa * (32 - fb);
+  s.w01 = 32 * (32 - fa) * fb;
+  s.w11 = 32 * fa * fb;
+  return true;
+}
+
+__device__ __forceinline__ uint32_t blend(const Sample& s, int32_t t00, int32_t t10, int32_t t01, int32_t t11) {
+  return (uint32_t)((s.w00 * t00 + s.w10 * t10 + s.w01 * t01 + s.w11 * t11 + 16384) >> 15);
+}
+
 template <int ENC>
 __device__ __forceinline__ uint32_t undistorted_pixel(const ImageArgs& a, int j, int i) {
-  int32_t iu, iv;
-  map_codes(a.lens, j, i, iu, iv);
-  if (iu == kOutside) return 0;
-  const int32_t x0 = iu >> 5, y0 = iv >> 5, fa = iu & 31, fb = iv & 31;
-  const int32_t sum = 32 * (32 - fa) * (32 - fb) * tap<ENC>(a, x0, y0) + 32 * fa * (32 - fb) * tap<ENC>(a, x0 + 1, y0) +
-                      32 * (32 - fa) * fb * tap<ENC>(a, x0, y0 + 1) + 32 * fa * fb * tap<ENC>(a, x0 + 1, y0 + 1);
-  return (uint32_t)((sum + 16384) >> 15);
+  Sample s;
+  if (!sample_of(a.lens, j, i, s)) return 0;
+  return blend(s, tap<ENC>(a, s.x0, s.y0), tap<ENC>(a, s.x0 + 1, s.y0), tap<ENC>(a, s.x0, s.y0 + 1), tap<ENC>(a, s.x0 + 1, s.y0 + 1));
 }
 
 // the source quad of a conversion without a camera: kQuad pixels = Pixel::kBytes dwords where the address allows
 template <int ENC>
-__device__ __forceinline__ void converted_quad(const ImageArgs& a, int j0, int i, int n, uint32_t (&out)[kQuad]) {
+__device__ __forceinline__ void source_quad(const ImageArgs& a, int j0, int i, int n, uint8_t (&bytes)[kQuad * Pixel<ENC>::kBytes]) {
   constexpr int B = Pixel<ENC>::kBytes;
   const uint8_t* p = a.src + (int64_t)i * a.src_step + (int64_t)j0 * B;
-  uint8_t bytes[kQuad * B];
   if (n == kQuad && ((uintptr_t)p & 3u) == 0) {
 #pragma unroll
     for (int k = 0; k < B; ++k) {
@@ -112,6 +135,13 @@ __device__ __forceinline__ void converted_quad(const ImageArgs& a, int j0, int i
 #pragma unroll
       for (int c = 0; c < B; ++c) bytes[k * B + c] = k < n ? p[k * B + c] : 0;
   }
+}
+
+template <int ENC>
+__device__ __forceinline__ void converted_quad(const ImageArgs& a, int j0, int i, int n, uint32_t (&out)[kQuad]) {
+  constexpr int B = Pixel<ENC>::kBytes;
+  uint8_t bytes[kQuad * B];
+  source_quad<ENC>(a, j0, i, n, bytes);
 #pragma unroll
   for (int k = 0; k < kQuad; ++k) out[k] = B == 1 ? bytes[k] : (uint32_t)Pixel<ENC>::gray(bytes[k * B], bytes[k * B + 1], bytes[k * B + 2]);
 }
@@ -136,6 +166,87 @@ __global__ __launch_bounds__(kImgTx* kImgTy) void k11_image_to_mono8(ImageArgs a
 #pragma unroll
     for (int k = 0; k < kQuad; ++k)
       if (k < n) q[k] = (uint8_t)px[k];
+  }
+}
+
+// ---------------------------------------------------------------- K11c: the same frame as B, G, R bytes
+// A pixel travels as B | G << 8 | R << 16.  The conversion permutes or replicates channels, so it commutes with the
+// blend: every channel is blended on its own with the weights of sample_of.
+
+template <int ENC>
+__device__ __forceinline__ uint32_t packed_bgr(const uint8_t* p) {
+  if constexpr (Pixel<ENC>::kBytes == 1) {
+    return (uint32_t)p[0] * 0x010101u;
+  } else {
+    const uint32_t c0 = p[0], c1 = p[1], c2 = p[2];
+    return Pixel<ENC>::kBlueFirst ? (c0 | (c1 << 8) | (c2 << 16)) : (c2 | (c1 << 8) | (c0 << 16));
+  }
+}
+
+template <int ENC>
+__device__ __forceinline__ uint32_t tap_bgr(const ImageArgs& a, int32_t x, int32_t y) {
+  if ((uint32_t)x >= (uint32_t)a.width || (uint32_t)y >= (uint32_t)a.height) return 0;
+  return packed_bgr<ENC>(a.src + (int64_t)y * a.src_step + (int64_t)x * Pixel<ENC>::kBytes);
+}
+
+template <int ENC>
+__device__ __forceinline__ uint32_t undistorted_bgr(const ImageArgs& a, int j, int i) {
+  Sample s;
+  if (!sample_of(a.lens, j, i, s)) return 0;
+  if constexpr (Pixel<ENC>::kBytes == 1) {   // three equal channels: blend one
+    return blend(s, tap<ENC>(a, s.x0, s.y0), tap<ENC>(a, s.x0 + 1, s.y0), tap<ENC>(a, s.x0, s.y0 + 1), tap<ENC>(a, s.x0 + 1, s.y0 + 1)) *
+           0x010101u;
+  } else {
+    const uint32_t t00 = tap_bgr<ENC>(a, s.x0, s.y0), t10 = tap_bgr<ENC>(a, s.x0 + 1, s.y0);
+    const uint32_t t01 = tap_bgr<ENC>(a, s.x0, s.y0 + 1), t11 = tap_bgr<ENC>(a, s.x0 + 1, s.y0 + 1);
+    uint32_t out = 0;
+#pragma unroll
+    for (int sh = 0; sh < 24; sh += 8)
+      out |= blend(s, (int32_t)((t00 >> sh) & 255u), (int32_t)((t10 >> sh) & 255u), (int32_t)((t01 >> sh) & 255u),
+                   (int32_t)((t11 >> sh) & 255u))
+             << sh;
+    return out;
+  }
+}
+
+struct alignas(4) Dword3 {
+  uint32_t x, y, z;
+};
+
+// The same 64 x 4 threads over 256 x 4 output pixels as k11_image_to_mono8: a thread makes kQuad adjacent pixels = 12 bytes
+// and stores them as ONE 3-dword store, so a wavefront writes 768 consecutive bytes of one output row per instruction.
+template <int ENC, bool UNDISTORT>
+__global__ __launch_bounds__(kImgTx* kImgTy) void k11_image_to_bgr8(ImageArgs a) {
+  const int j0 = (blockIdx.x * kImgTx + threadIdx.x) * kQuad;
+  const int i = blockIdx.y * kImgTy + threadIdx.y;
+  if (j0 >= a.width || i >= a.height) return;
+  const int n = min(kQuad, a.width - j0);
+  uint32_t px[kQuad];
+  if (UNDISTORT) {
+#pragma unroll
+    for (int k = 0; k < kQuad; ++k) px[k] = k < n ? undistorted_bgr<ENC>(a, j0 + k, i) : 0;
+  } else {
+    constexpr int B = Pixel<ENC>::kBytes;
+    uint8_t bytes[kQuad * B];
+    source_quad<ENC>(a, j0, i, n, bytes);
+#pragma unroll
+    for (int k = 0; k < kQuad; ++k) px[k] = packed_bgr<ENC>(bytes + k * B);
+  }
+  uint8_t* q = a.dst + (int64_t)i * a.dst_stride + (int64_t)j0 * 3;
+  if (n == kQuad && ((uintptr_t)q & 3u) == 0) {
+    Dword3 v;
+    v.x = px[0] | (px[1] << 24);
+    v.y = (px[1] >> 8) | (px[2] << 16);
+    v.z = (px[2] >> 16) | (px[3] << 8);
+    *reinterpret_cast<Dword3*>(q) = v;
+  } else {
+#pragma unroll
+    for (int k = 0; k < kQuad; ++k)
+      if (k < n) {
+        q[3 * k] = (uint8_t)px[k];
+        q[3 * k + 1] = (uint8_t)(px[k] >> 8);
+        q[3 * k + 2] = (uint8_t)(px[k] >> 16);
+      }
   }
 }
 
@@ -187,20 +298,21 @@ LensArgs lens_of(const ilcc_camera_model* c) {
   return L;
 }
 
-template <int ENC>
-void launch_to_mono8(const ImageArgs& a, bool undistort, dim3 grid, dim3 block, hipStream_t s) {
-  if (undistort) hipLaunchKernelGGL((k11_image_to_mono8<ENC, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((k11_image_to_mono8<ENC, false>), grid, block, 0, s, a);
+template <int ENC, int CHANNELS>
+void launch_image(const ImageArgs& a, bool undistort, dim3 grid, dim3 block, hipStream_t s) {
+  if constexpr (CHANNELS == 1) {
+    if (undistort) hipLaunchKernelGGL((k11_image_to_mono8<ENC, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k11_image_to_mono8<ENC, false>), grid, block, 0, s, a);
+  } else {
+    if (undistort) hipLaunchKernelGGL((k11_image_to_bgr8<ENC, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k11_image_to_bgr8<ENC, false>), grid, block, 0, s, a);
+  }
 }
 
-}  // namespace
-}  // namespace ilcc
-
-extern "C" int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, int32_t height, int32_t src_step,
-                                              int32_t encoding, const ilcc_camera_model* camera, void* d_dst,
-                                              int32_t dst_stride, void* hip_stream) {
-  using namespace ilcc;
-  const char* me = "ilcc_image_to_mono8_device";
+// both conversions: the host checks, then one launch; CHANNELS = bytes per output pixel (1: mono8, 3: bgr8)
+template <int CHANNELS>
+int32_t convert_image(const char* me, const void* d_src, int32_t width, int32_t height, int32_t src_step, int32_t encoding,
+                      const ilcc_camera_model* camera, void* d_dst, int32_t dst_stride, void* hip_stream) {
   if (!d_src || !d_dst) return refuse(me, "null pointer");
   if (width < 1 || height < 1 || width > kMaxSide || height > kMaxSide) return refuse(me, "width and height must be 1 .. 65536");
   int bpp;
@@ -213,11 +325,11 @@ extern "C" int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, 
     default: return refuse(me, "unknown encoding " + std::to_string(encoding));
   }
   if ((int64_t)src_step < (int64_t)width * bpp) return refuse(me, "src_step is shorter than a row");
-  if (dst_stride < width) return refuse(me, "dst_stride is shorter than a row");
+  if ((int64_t)dst_stride < (int64_t)width * CHANNELS) return refuse(me, "dst_stride is shorter than a row");
   if (camera)
     if (const char* why = camera_fault(camera, width, height)) return refuse(me, why);
   const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uint64_t)(height - 1) * (uint64_t)src_step + (uint64_t)width * bpp;
-  const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uint64_t)(height - 1) * (uint64_t)dst_stride + (uint64_t)width;
+  const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uint64_t)(height - 1) * (uint64_t)dst_stride + (uint64_t)width * CHANNELS;
   if (s0 < t1 && t0 < s1) return refuse(me, "source and destination overlap (the kernel gathers: it cannot run in place)");
 
   ImageArgs a;
@@ -232,11 +344,11 @@ extern "C" int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, 
   const dim3 grid((width + kImgTx * kQuad - 1) / (kImgTx * kQuad), (height + kImgTy - 1) / kImgTy);
   hipStream_t s = (hipStream_t)hip_stream;
   switch (encoding) {
-    case ILCC_ENCODING_MONO8: launch_to_mono8<ILCC_ENCODING_MONO8>(a, camera != nullptr, grid, block, s); break;
-    case ILCC_ENCODING_BGR8: launch_to_mono8<ILCC_ENCODING_BGR8>(a, camera != nullptr, grid, block, s); break;
-    case ILCC_ENCODING_RGB8: launch_to_mono8<ILCC_ENCODING_RGB8>(a, camera != nullptr, grid, block, s); break;
-    case ILCC_ENCODING_BGRA8: launch_to_mono8<ILCC_ENCODING_BGRA8>(a, camera != nullptr, grid, block, s); break;
-    default: launch_to_mono8<ILCC_ENCODING_RGBA8>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_MONO8: launch_image<ILCC_ENCODING_MONO8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_BGR8: launch_image<ILCC_ENCODING_BGR8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_RGB8: launch_image<ILCC_ENCODING_RGB8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_BGRA8: launch_image<ILCC_ENCODING_BGRA8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    default: launch_image<ILCC_ENCODING_RGBA8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -244,6 +356,22 @@ extern "C" int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, 
     return ILCC_HIP_ERROR;
   }
   return ILCC_OK;
+}
+
+}  // namespace
+}  // namespace ilcc
+
+extern "C" int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, int32_t height, int32_t src_step,
+                                              int32_t encoding, const ilcc_camera_model* camera, void* d_dst,
+                                              int32_t dst_stride, void* hip_stream) {
+  return ilcc::convert_image<1>("ilcc_image_to_mono8_device", d_src, width, height, src_step, encoding, camera, d_dst, dst_stride,
+                                hip_stream);
+}
+
+extern "C" int32_t ilcc_image_to_bgr8_device(const void* d_src, int32_t width, int32_t height, int32_t src_step, int32_t encoding,
+                                             const ilcc_camera_model* camera, void* d_dst, int32_t dst_stride, void* hip_stream) {
+  return ilcc::convert_image<3>("ilcc_image_to_bgr8_device", d_src, width, height, src_step, encoding, camera, d_dst, dst_stride,
+                                hip_stream);
 }
 
 extern "C" int32_t ilcc_undistort_map_device(const ilcc_camera_model* camera, int32_t* d_iu, int32_t* d_iv, void* hip_stream) {

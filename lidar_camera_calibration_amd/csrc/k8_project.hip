@@ -219,6 +219,21 @@ static int32_t run_project(bool sample, const void* d_xyzi, uint32_t n, const il
   return ILCC_OK;
 }
 
+int32_t project_intensity(const void* d_xyzi, uint32_t n_points, const double R[9], const double t[3], double fx, double cx, double fy,
+                          double cy, int32_t width, int32_t height, double distance_valid, double inten_low, double inten_high,
+                          void* d_hits, uint32_t* n_hits, hipStream_t s) {
+  ilcc_camera_model cam;
+  for (int k = 0; k < 9; ++k) cam.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) cam.t[k] = t[k];
+  cam.fx = fx;
+  cam.cx = cx;
+  cam.fy = fy;
+  cam.cy = cy;
+  cam.width = width;
+  cam.height = height;
+  return run_project(false, d_xyzi, n_points, &cam, distance_valid, inten_low, inten_high, nullptr, 0, d_hits, n_hits, s);
+}
+
 }  // namespace ilcc
 
 extern "C" int32_t ilcc_project_intensity_device(const void* d_xyzi, uint32_t n_points, const ilcc_camera_model* cam,

@@ -1,5 +1,5 @@
 """LiDAR -> image projection after calibration: ctypes mirror of
-``include/ilcc_project.h`` (K8).  pcd2image's per-point colour and rgblidar's XYZRGB cloud
+``include/ilcc_project.h`` (K8, K12).  pcd2image's per-point colour and its cv::circle per hit, rgblidar's XYZRGB cloud
 (/root/reference/ilcc2/test/pcd2image.cpp:40-82, test/rgblidar.cpp:45-78)."""
 import ctypes as C
 
@@ -7,7 +7,9 @@ import numpy as np
 
 from . import _native
 
-PROJECT_EXPORTS = ["ilcc_project_intensity_device", "ilcc_colourise_device"]
+PROJECT_EXPORTS = ["ilcc_project_intensity_device", "ilcc_colourise_device", "ilcc_draw_hits_scratch_bytes",
+                   "ilcc_draw_hits_device"]
+REFERENCE_STAMP = ((0, -1), (-1, 0), (0, 0), (1, 0), (0, 1))     # cv::circle(.., 0.6, .., 2): the centre and its four neighbours
 
 HIT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("index", "<u4")])
 
@@ -43,6 +45,11 @@ def _lib():
         L.ilcc_colourise_device.argtypes = [C.c_void_p, C.c_uint32, cp, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p,
                                             C.POINTER(C.c_uint32), C.c_void_p]
         L.ilcc_colourise_device.restype = C.c_int32
+        L.ilcc_draw_hits_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.ilcc_draw_hits_scratch_bytes.restype = C.c_uint64
+        L.ilcc_draw_hits_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
+                                            C.POINTER(C.c_int8), C.c_int32, C.c_void_p, C.c_void_p]
+        L.ilcc_draw_hits_device.restype = C.c_int32
         _ready = True
     return L
 
@@ -68,3 +75,18 @@ def colourise_device(d_xyzi_ptr, n_points, cam, d_image_ptr, image_step, d_out_p
                                         C.c_void_p(d_image_ptr), image_step, C.c_void_p(d_out_ptr), C.byref(n),
                                         C.c_void_p(stream)))
     return n.value
+
+
+def draw_hits_scratch_bytes(width, height) -> int:
+    return _lib().ilcc_draw_hits_scratch_bytes(width, height)
+
+
+def draw_hits_device(d_image_ptr, width, height, stride, d_hits_ptr, n_hits, d_scratch_ptr, stamp=None, stream=0):
+    """K12: draws n_hits HIT_DTYPE records into the B,G,R image at d_image_ptr in place, as pcd2image's cv::circle loop
+    would (later hits on top).  stamp: None for the reference's 5 pixels, else up to 64 (dx, dy) pairs.  Asynchronous."""
+    xy, n = None, 0
+    if stamp is not None:
+        flat = [int(v) for pair in stamp for v in pair]
+        xy, n = (C.c_int8 * max(1, len(flat)))(*flat), len(flat) // 2
+    _check(_lib().ilcc_draw_hits_device(C.c_void_p(d_image_ptr), width, height, stride, C.c_void_p(d_hits_ptr), n_hits, xy, n,
+                                        C.c_void_p(d_scratch_ptr), C.c_void_p(stream)))

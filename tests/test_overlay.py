@@ -1,0 +1,600 @@
+"""LiDAR points drawn on the undistorted colour image (include/ilcc_overlay.h): K11c (colour conversion and
+undistortion), K12 (pcd2image's cv::circle per hit) and the chain from bags, byte for byte against the numpy
+specification in overlay_ref.py.  The CPU tests guard the specification itself and the host-only entries; a test
+that needs a symbol or a program the build does not make fails, it does not skip."""
+import ctypes as C
+import functools
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import camera_image_ref as R
+import overlay_ref as O
+import rosbag_writer as W
+from lidar_camera_calibration_amd import _native as N
+from lidar_camera_calibration_amd import camera_image as CI
+from lidar_camera_calibration_amd import ingest, project
+from lidar_camera_calibration_amd import overlay as OV       # a build without the feature fails every test here
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+CLI = os.path.join(ROOT, "lidar_camera_calibration_amd", "ilcc_pcd2image")
+IMG = (R.IMAGE_TYPE, R.IMAGE_MD5)
+PC2 = ("sensor_msgs/PointCloud2", W.POINTCLOUD2_MD5)
+FILL = 0xAB
+INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
+
+# identity, barrel, pincushion (taps outside on all four edges, negative codes), and codes that are all INT32_MIN
+LENSES = {"identity": (0.0, 0.0, 0.0, 0.0, 0.0), "barrel": (-0.30, 0.10, 0.002, -0.0015, 0.05),
+          "pincushion": (0.35, 0.2, -0.01, 0.02, 0.0), "huge": (1e8, 0.0, 0.0, 0.0, 0.0)}
+
+
+def cam_for(w, h, d):
+    """The 37 x 29 camera of test_camera_image.py (fx, cx, fy, cy = 30, 17.6, 29, 14.3) scaled to w x h."""
+    return R.camera(30.0 / 37 * w, 17.6 / 37 * w, 29.0 / 29 * h, 14.3 / 29 * h, d, w, h)
+
+
+def native(cam):
+    return CI.CameraModel.make(cam.fx, cam.cx, cam.fy, cam.cy, cam.d, cam.width, cam.height)
+
+
+def noise_image(w, h, encoding, seed=1):
+    shape = (h, w) if encoding == "mono8" else (h, w, R.BPP[encoding])
+    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+
+
+def random_hits(n, w, h, seed, margin=3):
+    """Hits with centres up to `margin` pixels outside the image on every side, random colours."""
+    rng = np.random.default_rng(seed)
+    return O.make_hits(rng.integers(-margin, w + margin, n), rng.integers(-margin, h + margin, n), rng.integers(0, 256, (n, 3)))
+
+
+# ------------------------------------------------------------------------------------------ CPU: interface
+
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    return re.findall(r"^(?:int32_t|uint64_t) (ilcc_\w+)\(", text, re.M)
+
+
+def test_exports_match_headers():
+    assert sorted(_declared("ilcc_overlay.h")) == sorted(OV.OVERLAY_EXPORTS) == ["ilcc_bag_pcd2image", "ilcc_save_ppm_bgr"]
+    assert "ilcc_image_to_bgr8_device" in _declared("ilcc_camera_image.h")
+    assert {"ilcc_draw_hits_scratch_bytes", "ilcc_draw_hits_device"} <= set(_declared("ilcc_project.h"))
+    L = OV.lib()
+    for s in OV.OVERLAY_EXPORTS + ["ilcc_image_to_bgr8_device", "ilcc_draw_hits_scratch_bytes", "ilcc_draw_hits_device"]:
+        assert hasattr(L, s), s
+    assert "ilcc_image_to_bgr8_device" in CI.CAMERA_IMAGE_EXPORTS
+    assert {"ilcc_draw_hits_scratch_bytes", "ilcc_draw_hits_device"} <= set(project.PROJECT_EXPORTS)
+    # the mirrors' signatures: the colour entry takes what the mono8 entry takes; the scratch size is 64 bits wide
+    CI.lib(), project._lib()
+    assert L.ilcc_image_to_bgr8_device.argtypes == L.ilcc_image_to_mono8_device.argtypes
+    assert L.ilcc_draw_hits_scratch_bytes.restype is C.c_uint64 and len(L.ilcc_draw_hits_device.argtypes) == 10
+    assert len(L.ilcc_bag_pcd2image.argtypes) == 13 and L.ilcc_bag_pcd2image.argtypes[5]._type_ is CI.CameraModel
+    assert project.draw_hits_scratch_bytes(7, 5) == 4 * 7 * 5
+    assert project.draw_hits_scratch_bytes(65536, 65536) == 4 * 65536 * 65536          # no 32-bit wrap
+    # ilcc_overlay.h takes the lens from ilcc_camera_image.h and must not meet ilcc_project.h's struct of the same name
+    text = open(os.path.join(ROOT, "include", "ilcc_overlay.h")).read()
+    assert '#include "ilcc_camera_image.h"' in text and '#include "ilcc_project.h"' not in text
+    assert project.HIT_DTYPE == O.HIT_DTYPE and tuple(project.REFERENCE_STAMP) == O.REFERENCE_STAMP
+
+
+def test_save_ppm_round_trip(tmp_path):
+    bgr = noise_image(7, 5, "bgr8", 4)
+    path = tmp_path / "a.ppm"
+    OV.save_ppm_bgr(str(path), bgr)
+    blob = path.read_bytes()
+    header = b"P6\n7 5\n255\n"
+    assert blob.startswith(header) and len(blob) == len(header) + 7 * 5 * 3
+    rgb = O.read_ppm(str(path))
+    assert (rgb == bgr[..., ::-1]).all() and not (rgb == bgr).all()        # R and B swapped in the file
+    one = np.array([[[1, 2, 3]]], np.uint8)
+    OV.save_ppm_bgr(str(path), one)
+    assert path.read_bytes() == b"P6\n1 1\n255\n\x03\x02\x01"
+    with pytest.raises(CI.CameraImageError) as e:
+        OV.save_ppm_bgr(str(tmp_path / "no_such_dir" / "a.ppm"), bgr)
+    assert e.value.status == N.IO_ERROR
+    assert OV.lib().ilcc_save_ppm_bgr(None, None, 1, 1) == N.BAD_ARGUMENT
+    assert OV.lib().ilcc_save_ppm_bgr(str(path).encode(), bgr.ctypes.data_as(C.c_void_p), 0, 5) == N.BAD_ARGUMENT
+
+
+# ------------------------------------------------------------------------------------------ CPU: guards on the specification
+
+def test_reference_stamp_is_the_five_pixel_plus():
+    assert sorted(O.REFERENCE_STAMP) == sorted([(0, 0), (1, 0), (-1, 0), (0, 1), (0, -1)]) and len(O.REFERENCE_STAMP) == 5
+    img = np.zeros((5, 5, 3), np.uint8)
+    out = O.draw_hits(img, O.make_hits([2], [2], [(9, 8, 7)]))
+    want = np.zeros((5, 5), bool)
+    want[2, 1:4] = want[1:4, 2] = True
+    assert ((out == (9, 8, 7)).all(2) == want).all() and (out[~want] == 0).all()
+    assert (out[2, 2] == (9, 8, 7)).all()            # r in byte 0: the reference's Scalar(r, g, b) on a bgr8 image
+
+
+def test_the_two_draw_hits_forms_agree():
+    for w, h, n, seed in ((1, 1, 10, 0), (7, 5, 300, 1), (64, 48, 5000, 2), (9, 9, 0, 3)):
+        img = noise_image(w, h, "bgr8", seed)
+        hits = random_hits(n, w, h, seed)
+        a, b = O.draw_hits(img, hits), O.draw_hits_highest_wins(img, hits)
+        assert (a == b).all(), (w, h, n)
+        if n >= 300:
+            assert (a != img).any()
+    # coordinates at the ends of int32, and a stamp with the extreme offsets
+    img = noise_image(7, 5, "bgr8")
+    stamp = ((127, 127), (-128, -128), (0, 0), (-127, 127))
+    hits = O.make_hits([INT_MIN, INT_MAX, -125, 130, 3, 128], [INT_MIN, INT_MAX, -124, 131, INT_MAX, -125],
+                       np.arange(18).reshape(6, 3))
+    a, b = O.draw_hits(img, hits, stamp), O.draw_hits_highest_wins(img, hits, stamp)
+    assert (a == b).all() and (a != img).any(2).sum() == 2       # (2, 3) by hit 2 and again by hit 3's (-128, -128); (1, 2) by hit 5
+    assert tuple(a[3, 2]) == (9, 10, 11) and tuple(a[2, 1]) == (15, 16, 17)
+
+
+def test_undistort_bgr8_of_gray_is_undistort_of_gray_in_every_channel():
+    for name, d in LENSES.items():
+        cam = cam_for(37, 29, d)
+        gray = noise_image(37, 29, "mono8", 5)
+        want = R.undistort(gray, "mono8", cam)
+        for enc, src in (("mono8", gray), ("bgr8", np.repeat(gray[:, :, None], 3, 2)), ("rgba8", np.repeat(gray[:, :, None], 4, 2))):
+            got = O.undistort_bgr8(src, enc, cam)
+            assert got.shape == (29, 37, 3) and all((got[..., c] == want).all() for c in range(3)), (name, enc)
+    px = noise_image(6, 4, "rgba8")
+    assert (O.to_bgr8(px, "rgba8") == px[..., [2, 1, 0]]).all() and (O.to_bgr8(px, "bgra8") == px[..., :3]).all()
+    px = noise_image(6, 4, "rgb8")
+    assert (O.to_bgr8(px, "rgb8") == px[..., ::-1]).all() and (O.to_bgr8(px[..., ::-1], "bgr8") == px[..., ::-1]).all()
+    # the channels are blended apart: a colour image's channel c is the gray undistortion of that channel
+    cam = cam_for(37, 29, LENSES["pincushion"])
+    px = noise_image(37, 29, "bgr8", 6)
+    got = O.undistort_bgr8(px, "bgr8", cam)
+    assert all((got[..., c] == R.undistort(px[..., c], "mono8", cam)).all() for c in range(3))
+
+
+def _cli(*args, timeout=120):
+    assert os.path.exists(CLI), "build() makes lidar_camera_calibration_amd/ilcc_pcd2image"
+    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=timeout)
+
+
+def test_cli_argument_errors(tmp_path):
+    r = _cli()
+    assert r.returncode == 2 and "usage: ilcc_pcd2image" in r.stderr
+    r = _cli("--bag")
+    assert r.returncode == 2 and "unknown or incomplete argument: --bag" in r.stderr
+    r = _cli("--frobnicate", "1")
+    assert r.returncode == 2 and "--frobnicate" in r.stderr
+    full = ["--bag", str(tmp_path / "a.bag"), "--image-topic", "/camera/image_raw", "--lidar-topic", "/velodyne_points",
+            "--yaml", str(tmp_path / "missing.yaml"), "--extrinsic", str(tmp_path / "missing.bin"), "--out", str(tmp_path / "o.ppm")]
+    r = _cli(*full[:-2])                                             # --out is required
+    assert r.returncode == 2 and "usage" in r.stderr
+    r = _cli(*full)
+    assert r.returncode == 1 and "can not open" in r.stderr and "missing.yaml" in r.stderr
+    full[7] = os.path.join(GOLD, "pointgrey.yaml")
+    r = _cli(*full)
+    assert r.returncode == 1 and "can not open" in r.stderr and "missing.bin" in r.stderr
+    assert not (tmp_path / "o.ppm").exists()
+
+
+# ------------------------------------------------------------------------------------------ GPU helpers
+
+def _pitched(rows, pitch, offset, fill=None, seed=99):
+    """(h, n) bytes as rows `pitch` apart from byte `offset` of a flat device buffer (noise or `fill` elsewhere)."""
+    import torch
+    h, n = rows.shape
+    size = offset + h * pitch + 8
+    host = np.full(size, fill, np.uint8) if fill is not None else np.random.default_rng(seed).integers(0, 256, size, dtype=np.uint8)
+    body = host[offset: offset + h * pitch].reshape(h, pitch)
+    body[:, :n] = rows
+    return torch.from_numpy(host).cuda()
+
+
+def _unpitch(buf, h, n, pitch, offset, fill=FILL):
+    """The rows back on the host, and whether every byte outside them still holds `fill`."""
+    flat = buf.cpu().numpy()
+    body = flat[offset: offset + h * pitch].reshape(h, pitch)
+    untouched = (flat[:offset] == fill).all() and (flat[offset + h * pitch:] == fill).all() and (body[:, n:] == fill).all()
+    return body[:, :n].copy(), bool(untouched)
+
+
+def _run_k11c(px, encoding, cam, pitch, src_off, dst_stride, dst_off):
+    import torch
+    h, w = px.shape[:2]
+    src = _pitched(px.reshape(h, -1), pitch, src_off)
+    dst = torch.full((dst_off + h * dst_stride + 8,), FILL, dtype=torch.uint8, device="cuda")
+    st = CI.lib().ilcc_image_to_bgr8_device(C.c_void_p(src.data_ptr() + src_off), w, h, pitch, R.ENCODINGS.index(encoding),
+                                            C.byref(native(cam)) if cam is not None else None,
+                                            C.c_void_p(dst.data_ptr() + dst_off), dst_stride, None)
+    assert st == N.OK, N.lib().ilcc_last_error(None)
+    torch.cuda.synchronize()
+    got, untouched = _unpitch(dst, h, 3 * w, dst_stride, dst_off)
+    return got.reshape(h, w, 3), untouched
+
+
+def _layouts(w, bpp):
+    """(source pitch, source offset, destination stride, destination offset): every destination stride (3w, 3w + 1,
+    3w + 13) at every offset 0 .. 3, beside every source pitch (row + 1, row + 13, a multiple of 256) at every offset."""
+    row = w * bpp
+    pitches = (row + 1, row + 13, (row + 255) // 256 * 256)
+    out = []
+    for k in range(12):                      # destination k = (stride, offset) beside source 5 k + 1 mod 12: both run through all 12
+        m = (5 * k + 1) % 12
+        out.append((pitches[m // 4], m % 4, (3 * w, 3 * w + 1, 3 * w + 13)[k // 4], k % 4))
+    return out
+
+
+def _draw(image, stride, hits, stamp=None, scratch=None):
+    """ilcc_draw_hits_device on the image laid out with `stride` in a buffer of FILL; returns the image, whether the
+    padding is intact, and the scratch."""
+    import torch
+    h, w = image.shape[:2]
+    buf = _pitched(image.reshape(h, -1), stride, 2, fill=FILL)
+    d_hits = torch.from_numpy(np.frombuffer(hits.tobytes() + bytes(16), np.uint8).copy()).cuda()
+    if scratch is None:
+        scratch = torch.full((project.draw_hits_scratch_bytes(w, h),), 0xCD, dtype=torch.uint8, device="cuda")   # not zero on entry
+    project.draw_hits_device(buf.data_ptr() + 2, w, h, stride, d_hits.data_ptr(), len(hits), scratch.data_ptr(), stamp)
+    torch.cuda.synchronize()
+    got, untouched = _unpitch(buf, h, 3 * w, stride, 2)
+    return got.reshape(h, w, 3), untouched, scratch
+
+
+# ------------------------------------------------------------------------------------------ GPU: K11c
+
+def test_layouts_cover_every_stride_offset_and_pitch():
+    lay = _layouts(37, 3)
+    assert {(s - 111, o) for _, _, s, o in lay} == {(e, o) for e in (0, 1, 13) for o in range(4)}
+    assert {(p, o) for p, o, _, _ in lay} == {(p, o) for p in (112, 124, 256) for o in range(4)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(1, 1), (3, 2), (5, 3), (255, 5), (256, 4), (257, 5), (1027, 3), (320, 240)])
+def test_k11c_pixels_equal_specification(w, h):
+    for encoding in R.ENCODINGS:
+        px = noise_image(w, h, encoding, seed=w + h)
+        layouts = _layouts(w, R.BPP[encoding])
+        for k, name in enumerate([None, *LENSES]):
+            cam = cam_for(w, h, LENSES[name]) if name else None
+            want = O.convert_bgr8(px, encoding, cam)
+            if name == "huge" and w * h > 1:
+                assert (R.undistort_map(cam)[0] == R.OUTSIDE).any()
+            # every layout on the small frames; on 320 x 240 each lens takes a third of them, in turn
+            for pitch, soff, stride, doff in (layouts if w * h < 10000 else layouts[k % 3::3]):
+                got, untouched = _run_k11c(px, encoding, cam, pitch, soff, stride, doff)
+                assert (got == want).all(), (encoding, name, pitch, soff, stride, doff, int((got != want).sum()))
+                assert untouched, (encoding, name, pitch, soff, stride, doff)
+        assert (CI.to_bgr8(px, encoding).cpu().numpy() == O.to_bgr8(px, encoding)).all()      # the packed route of the mirror
+
+
+@pytest.mark.gpu
+def test_k11c_of_mono8_is_k11_in_every_channel():
+    for w, h in ((5, 3), (257, 5), (320, 240)):
+        px = noise_image(w, h, "mono8", seed=w)
+        for name in [None, *LENSES]:
+            cam = native(cam_for(w, h, LENSES[name])) if name else None
+            gray = CI.to_mono8(px, "mono8", cam).cpu().numpy()
+            bgr = CI.to_bgr8(px, "mono8", cam).cpu().numpy()
+            assert bgr.shape == (h, w, 3) and all((bgr[..., c] == gray).all() for c in range(3)), (w, h, name)
+
+
+@pytest.mark.gpu
+def test_k11c_input_checks():
+    import torch
+    L = CI.lib()
+    src = torch.zeros(64 * 64 * 4, dtype=torch.uint8, device="cuda")
+    dst = torch.full((64 * 200,), FILL, dtype=torch.uint8, device="cuda")
+    cam = native(cam_for(64, 64, LENSES["barrel"]))
+    sp, dp = C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr())
+    MONO, BGR = 0, 1
+
+    def call(s=sp, w=64, h=64, step=64, enc=MONO, camera=C.byref(cam), d=dp, stride=192):
+        return L.ilcc_image_to_bgr8_device(s, w, h, step, enc, camera, d, stride, None)
+
+    other = native(cam_for(64, 63, LENSES["barrel"]))
+    cases = [dict(s=None), dict(d=None), dict(w=0), dict(h=0), dict(w=-3), dict(w=65537), dict(step=63),
+             dict(enc=BGR, step=64 * 3 - 1), dict(stride=191), dict(stride=64), dict(camera=C.byref(other)), dict(enc=5), dict(enc=-1),
+             dict(d=sp), dict(d=C.c_void_p(src.data_ptr() + 64 * 63)),                 # in place; the last source row
+             dict(s=C.c_void_p(dst.data_ptr() + 191), h=1, camera=None)]              # the source starts on the destination's last byte
+    for kw in cases:
+        N.lib().ilcc_last_error(None)
+        assert call(**kw) == N.BAD_ARGUMENT, kw
+        assert b"ilcc_image_to_bgr8_device" in N.lib().ilcc_last_error(None), kw
+    torch.cuda.synchronize()
+    assert (dst == FILL).all() and not src.any()                # nothing was launched
+    assert call(s=C.c_void_p(dst.data_ptr() + 192), h=1, camera=None, stride=192) == N.OK   # adjacent ranges do not overlap
+    assert call(stride=200) == N.OK
+    torch.cuda.synchronize()
+    assert (dst.view(64, 200)[:, :192] == 0).all() and (dst.view(64, 200)[:, 192:] == FILL).all()
+
+
+# ------------------------------------------------------------------------------------------ GPU: K12
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(1, 1), (2, 2), (7, 5), (64, 48)])
+def test_k12_equals_the_sequential_loop(w, h):
+    img = noise_image(w, h, "bgr8", seed=w)
+    for stride in (3 * w, 3 * w + 5):
+        for n in (0, 1, 63, 64, 65, 255, 256, 257):
+            hits = random_hits(n, w, h, seed=n + w)
+            got, untouched, _ = _draw(img, stride, hits)
+            assert (got == O.draw_hits(img, hits)).all() and untouched, (stride, n)
+            if n == 0:
+                assert (got == img).all()
+
+
+@pytest.mark.gpu
+def test_k12_later_hits_win():
+    img = noise_image(7, 5, "bgr8")
+    colours = np.stack([np.arange(1000) % 251, np.arange(1000) // 4, np.arange(1000) % 7], 1)
+    assert len({tuple(c) for c in colours}) == 1000
+    hits = O.make_hits(np.full(1000, 3), np.full(1000, 2), colours)          # 1 000 hits on one pixel: the last one wins
+    got, untouched, _ = _draw(img, 21, hits)
+    assert (got == O.draw_hits(img, hits)).all() and untouched
+    assert tuple(got[2, 3]) == tuple(colours[-1] % 256) and tuple(got[1, 3]) == tuple(colours[-1] % 256)
+    for first, second in (((3, 2), (4, 2)), ((4, 2), (3, 2)), ((3, 2), (3, 3))):     # one pixel apart, in either order
+        hits = O.make_hits([first[0], second[0]], [first[1], second[1]], [(10, 20, 30), (200, 100, 50)])
+        got, _, _ = _draw(img, 21, hits)
+        assert (got == O.draw_hits(img, hits)).all()
+        assert tuple(got[first[1], first[0]]) == (200, 100, 50) and tuple(got[second[1], second[0]]) == (200, 100, 50)
+        assert (got == (10, 20, 30)).all(2).sum() == 3                       # what is left of the earlier stamp
+
+
+@pytest.mark.gpu
+def test_k12_heavy_contention():
+    img = noise_image(64, 48, "bgr8", 2)
+    hits = random_hits(200000, 64, 48, seed=7)
+    want = O.draw_hits_highest_wins(img, hits)                # equal to the sequential loop: test_the_two_draw_hits_forms_agree
+    for stride in (192, 197):
+        got, untouched, _ = _draw(img, stride, hits)
+        assert (got == want).all() and untouched
+    assert (O.draw_hits(img, hits[-3000:]) == O.draw_hits_highest_wins(img, hits[-3000:])).all()
+
+
+@pytest.mark.gpu
+def test_k12_clipping_and_untrusted_coordinates():
+    w, h = 7, 5
+    img = noise_image(w, h, "bgr8", 3)
+    rng = np.random.default_rng(5)
+    border = [(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (3, 0), (3, h - 1), (0, 2), (w - 1, 2)]     # corners and edges
+    for x, y in border:
+        hits = O.make_hits([x], [y], [(1, 2, 3)])
+        got, untouched, _ = _draw(img, 3 * w + 5, hits)
+        assert (got == O.draw_hits(img, hits)).all() and untouched, (x, y)
+        inside = sum(0 <= x + dx < w and 0 <= y + dy < h for dx, dy in O.REFERENCE_STAMP)
+        assert (got != img).any(2).sum() <= inside < 5
+    arms = {-1: 1, -2: 0, INT_MIN: 0, INT_MAX: 0}
+    for axis, size in ((0, w), (1, h)):
+        for v, n_drawn in list(arms.items()) + [(size, 1), (size + 1, 0)]:
+            centre = [3, 2]
+            centre[axis] = v
+            hits = O.make_hits([centre[0]], [centre[1]], [(255, 254, 253)])
+            got, untouched, _ = _draw(np.zeros_like(img), 3 * w, hits)
+            assert (got == O.draw_hits(np.zeros_like(img), hits)).all() and untouched, (axis, v)
+            assert (got != 0).any(2).sum() == n_drawn, (axis, v)
+    # all of them at once, both axes extreme too, among ordinary hits
+    xs = [-1, -2, w, w + 1, INT_MIN, INT_MAX, 3, 3, 3, 3, 3, 3, INT_MIN, INT_MAX, INT_MIN, INT_MAX]
+    ys = [2, 2, 2, 2, 2, 2, -1, -2, h, h + 1, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MAX, INT_MIN]
+    hits = O.make_hits(xs + [1, 5], ys + [1, 3], rng.integers(1, 256, (len(xs) + 2, 3)))
+    got, untouched, _ = _draw(img, 3 * w + 5, hits)
+    assert (got == O.draw_hits(img, hits)).all() and untouched
+
+
+@pytest.mark.gpu
+def test_k12_custom_stamp_of_64_offsets():
+    w, h = 64, 48
+    img = noise_image(w, h, "bgr8", 4)
+    rng = np.random.default_rng(11)
+    stamp = [(127, 127), (-127, 127), (127, -127), (-127, -127), (-128, -128), (0, 0)]
+    stamp += [(int(a), int(b)) for a, b in rng.integers(-128, 128, (58, 2))]
+    assert len(stamp) == 64
+    centres = [(-120, -120), (w + 120, -120), (-120, h + 120), (w + 119, h + 118), (w + 127, h + 127), (INT_MAX, INT_MIN), (30, 20)]
+    centres += [(int(a), int(b)) for a, b in rng.integers(-130, 200, (40, 2))]
+    hits = O.make_hits([c[0] for c in centres], [c[1] for c in centres], rng.integers(0, 256, (len(centres), 3)))
+    want = O.draw_hits(img, hits, stamp)
+    for k in range(5):                                                   # each extreme offset lands inside for its centre
+        px, py = centres[k][0] + stamp[k][0], centres[k][1] + stamp[k][1]
+        assert 0 <= px < w and 0 <= py < h, k
+    got, untouched, _ = _draw(img, 3 * w + 5, hits, stamp)
+    assert (got == want).all() and untouched and (got != img).any()
+    got, untouched, _ = _draw(img, 3 * w, hits, [(0, 0)])                # a stamp of one pixel
+    assert (got == O.draw_hits(img, hits, [(0, 0)])).all() and untouched
+
+
+@pytest.mark.gpu
+def test_k12_result_does_not_depend_on_the_scratch():
+    w, h = 64, 48
+    img = noise_image(w, h, "bgr8", 8)
+    a, b = random_hits(5000, w, h, seed=1), random_hits(300, w, h, seed=2)
+    got, _, scratch = _draw(img, 3 * w, a)
+    assert (got == O.draw_hits_highest_wins(img, a)).all()
+    got, untouched, scratch = _draw(img, 3 * w + 5, b, scratch=scratch)     # the owner words of 5 000 hits are still in it
+    assert (got == O.draw_hits(img, b)).all() and untouched
+    got, _, _ = _draw(img, 3 * w, b, scratch=scratch)                       # and the very same call again
+    assert (got == O.draw_hits(img, b)).all()
+
+
+@pytest.mark.gpu
+def test_k12_input_checks():
+    import torch
+    L = project._lib()
+    w, h = 16, 8
+    image = torch.full((h * 60,), FILL, dtype=torch.uint8, device="cuda")
+    hits = torch.from_numpy(np.frombuffer(random_hits(32, w, h, 1).tobytes(), np.uint8).copy()).cuda()
+    scratch = torch.full((4 * w * h + 4,), 0xCD, dtype=torch.uint8, device="cuda")
+    ip, hp, sp = C.c_void_p(image.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_void_p(scratch.data_ptr())
+    stamp = (C.c_int8 * 128)()
+
+    def call(i=ip, ww=w, hh=h, stride=48, hit=hp, n=32, st=None, ns=0, sc=sp):
+        return L.ilcc_draw_hits_device(i, ww, hh, stride, hit, n, st, ns, sc, None)
+
+    cases = [dict(i=None), dict(hit=None), dict(sc=None), dict(ww=0), dict(hh=0), dict(ww=-1), dict(ww=65537), dict(hh=65537),
+             dict(stride=47), dict(stride=-48), dict(st=stamp, ns=0), dict(st=stamp, ns=65), dict(st=stamp, ns=-1),
+             dict(n=0xFFFFFFFF)]
+    for kw in cases:
+        N.lib().ilcc_last_error(None)
+        assert call(**kw) == N.BAD_ARGUMENT, kw
+        assert b"ilcc_draw_hits_device" in N.lib().ilcc_last_error(None), kw
+    assert call(n=0) == N.OK and call(n=0, hit=None) == N.OK            # nothing to draw: nothing is touched
+    torch.cuda.synchronize()
+    assert (image == FILL).all() and (scratch == 0xCD).all()
+    assert call(stride=60) == N.OK and call(st=stamp, ns=64, stride=60) == N.OK and call(st=stamp, ns=1, stride=60) == N.OK
+    torch.cuda.synchronize()
+    body = image.view(h, 60)
+    assert (body[:, 48:] == FILL).all() and (body[:, :48] != FILL).any()
+
+
+# ------------------------------------------------------------------------------------------ GPU: the chain
+
+def small_camera():
+    """320 x 240 with the golden pointgrey.yaml's lens: its 1920 x 1200 intrinsics scaled by 1 / 6 and 1 / 5."""
+    big = CI.read_camera_yaml(os.path.join(GOLD, "pointgrey.yaml"))
+    return R.camera(big.fx / 6, big.cx / 6, big.fy / 5, big.cy / 5, tuple(big.d), 320, 240)
+
+
+def extrinsic():
+    return np.fromfile(os.path.join(GOLD, "pointgrey.bin"), dtype=np.float64).reshape(4, 4, order="F")   # the shipped pose
+
+
+def scene(n, seed):
+    """The cloud of test_project.py: points all round the sensor, with non-finite coordinates and intensities."""
+    rng = np.random.default_rng(seed)
+    pts = np.concatenate([rng.uniform(-20, 20, (n, 3)), rng.uniform(0, 255, (n, 1))], 1).astype(np.float32)
+    pts[:, 2] = rng.uniform(-2, 3, n)
+    pts[::97, 0] = np.nan
+    pts[5::101, 1] = np.inf
+    pts[7::89] = 0.0
+    pts[11::113, 3] = np.nan
+    pts[13::127, 3] = -5.0
+    return pts
+
+
+DISTANCE = 30.0
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case():
+    """Frame, cloud and the specification's undistorted frame, computed once and shared read-only."""
+    cam = small_camera()
+    frame = noise_image(320, 240, "bgr8", seed=12)
+    pts = scene(20000, 4)
+    flat = O.undistort_bgr8(frame, "bgr8", cam)
+    for a in (frame, pts, flat):
+        a.setflags(write=False)
+    return cam, frame, pts, flat
+
+
+def _project_cam(cam):
+    return project.CameraModel.from_extrinsic(extrinsic(), (cam.fx, cam.cx, cam.fy, cam.cy), (cam.width, cam.height))
+
+
+def _hits_on_gpu(pts, cam):
+    import torch
+    d_pts = torch.from_numpy(np.array(pts)).cuda()
+    d_hits = torch.zeros((len(pts), 4), dtype=torch.int32, device="cuda")
+    m = project.project_intensity_device(d_pts.data_ptr(), len(pts), _project_cam(cam), d_hits.data_ptr(), DISTANCE)
+    return d_hits, m
+
+
+@pytest.mark.gpu
+def test_chain_project_then_draw(ob):
+    import torch
+    cam, frame, pts, flat = chain_case()
+    d_hits, m = _hits_on_gpu(pts, cam)
+    hits = d_hits.cpu().numpy().view(O.HIT_DTYPE).reshape(-1)[:m]
+    want_hits = ob.project_intensity(np.array(pts), _project_cam(cam), DISTANCE)
+    assert 100 < m < len(pts) and hits.tobytes() == want_hits.tobytes()           # what test_project.py holds K8 to
+    image = CI.to_bgr8(np.array(frame), "bgr8", native(cam))
+    assert (image.cpu().numpy() == flat).all()
+    scratch = torch.empty(project.draw_hits_scratch_bytes(320, 240), dtype=torch.uint8, device="cuda")
+    project.draw_hits_device(image.data_ptr(), 320, 240, 960, d_hits.data_ptr(), m, scratch.data_ptr())
+    got = image.cpu().numpy()
+    assert (got == O.draw_hits(flat, hits)).all()
+    assert (got != flat).any(2).sum() > m                                        # stamps, not single pixels
+
+
+def _yaml_text(cam):
+    K = [cam.fx, 0, cam.cx, 0, cam.fy, cam.cy, 0, 0, 1]
+    return ("%%YAML:1.0\n\nK: !!opencv-matrix\n   rows: 3\n   cols: 3\n   dt: d\n   data: [%s]\n"
+            "d: !!opencv-matrix\n   rows: 5\n   cols: 1\n   dt: d\n   data: [%s]\n\nCamera.width: %d\nCamera.height: %d\n"
+            % (", ".join(repr(float(v)) for v in K), ", ".join(repr(float(v)) for v in cam.d), cam.width, cam.height))
+
+
+def _cloud_msg(pts):
+    a, fields, step = W.velodyne_points(np.array(pts))
+    return W.pointcloud2(a, fields, step)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bags", ["one", "two"])
+def test_from_a_bag_three_routes_one_picture(tmp_path, bags):
+    import torch
+    cam, frame, pts, flat = chain_case()
+    image_bag, yaml_path, pose_path = str(tmp_path / "a.bag"), str(tmp_path / "cam.yaml"), str(tmp_path / "pose.bin")
+    lidar_bag = image_bag if bags == "one" else str(tmp_path / "lidar.bag")
+    later = R.image_msg(noise_image(320, 240, "bgr8", 77), "bgr8", seq=2)
+    image_msgs = [("/camera/image_raw", *IMG, (1, 10), R.image_msg(np.array(frame), "bgr8", step=320 * 3 + 4, seq=1)),
+                  ("/camera/image_raw", *IMG, (2, 0), later)]
+    cloud_msgs = [("/velodyne_points", *PC2, (1, 0), _cloud_msg(pts)), ("/velodyne_points", *PC2, (3, 0), _cloud_msg(scene(50, 9)))]
+    if bags == "one":
+        bag = W.BagWriter(image_bag, "bz2")
+        bag.add_chunk(cloud_msgs[:1] + image_msgs + cloud_msgs[1:])
+        bag.write()
+    else:
+        for path, msgs in ((image_bag, image_msgs), (lidar_bag, cloud_msgs)):
+            bag = W.BagWriter(path, "lz4" if path == lidar_bag else "none")
+            bag.add_chunk(msgs)
+            bag.write()
+    open(yaml_path, "w").write(_yaml_text(cam))
+    shutil.copy(os.path.join(GOLD, "pointgrey.bin"), pose_path)
+    ncam = CI.read_camera_yaml(yaml_path)
+    assert (ncam.fx, ncam.cx, ncam.fy, ncam.cy, tuple(ncam.d)) == (cam.fx, cam.cx, cam.fy, cam.cy, cam.d)
+    T = extrinsic()
+
+    # route 1: the library entry
+    one, n_drawn = OV.bag_pcd2image(image_bag, "/camera/image_raw", "/velodyne_points", ncam, T, lidar_bag=lidar_bag,
+                                    distance_valid=DISTANCE)
+    # route 2: step by step
+    msg = ingest.bag_first_message(image_bag, "/camera/image_raw", R.IMAGE_MD5)
+    lay = CI.parse_image(msg)
+    data = np.frombuffer(msg, np.uint8, lay.data_bytes, lay.data_offset).reshape(lay.height, lay.step)
+    d_data = torch.from_numpy(data.copy()).cuda()
+    view = d_data[:, :lay.width * 3].view(lay.height, lay.width, 3) if lay.step == lay.width * 3 else \
+        d_data.as_strided((lay.height, lay.width, 3), (lay.step, 3, 1))
+    image = CI.to_bgr8(view, lay.encoding_name, ncam)
+    cloud = ingest.bag_first_cloud(lidar_bag, "/velodyne_points")
+    assert cloud.tobytes() == np.array(pts).tobytes()
+    d_hits, m = _hits_on_gpu(cloud, cam)
+    scratch = torch.empty(project.draw_hits_scratch_bytes(320, 240), dtype=torch.uint8, device="cuda")
+    project.draw_hits_device(image.data_ptr(), 320, 240, 960, d_hits.data_ptr(), m, scratch.data_ptr())
+    two = image.cpu().numpy()
+    # route 3: the program's PPM
+    ppm = tmp_path / "out.ppm"
+    r = _cli("--bag", image_bag, *(["--lidar-bag", lidar_bag] if bags == "two" else []), "--image-topic", "/camera/image_raw",
+             "--lidar-topic", "/velodyne_points", "--yaml", yaml_path, "--extrinsic", pose_path, "--out", str(ppm),
+             "--distance-valid", str(DISTANCE), timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "image 320 x 240, %d points drawn" % m in r.stdout
+    three = O.read_ppm(str(ppm))[..., ::-1]                                   # R,G,B in the file
+    hits = d_hits.cpu().numpy().view(O.HIT_DTYPE).reshape(-1)[:m]
+    want = O.draw_hits(flat, hits)
+    assert n_drawn == m > 100
+    assert (one == want).all() and (two == want).all() and (three == want).all()
+
+    if bags == "one":
+        # ILCC_CAPACITY still reports the sizes, and writes nothing
+        w, h, n = C.c_int32(0), C.c_int32(0), C.c_uint32(0)
+        small = np.zeros(1000, np.uint8)
+        Tf = np.ascontiguousarray(T).reshape(16)
+        st = OV.lib().ilcc_bag_pcd2image(0, image_bag.encode(), b"/camera/image_raw", image_bag.encode(), b"/velodyne_points",
+                                         C.byref(ncam), Tf.ctypes.data_as(C.POINTER(C.c_double)), DISTANCE,
+                                         small.ctypes.data_as(C.c_void_p), small.size, C.byref(w), C.byref(h), C.byref(n))
+        assert st == N.CAPACITY and (w.value, h.value) == (320, 240) and not small.any()
+        # a camera of another size, a topic without images, a topic without clouds
+        other = CI.CameraModel.make(cam.fx, cam.cx, cam.fy, cam.cy, cam.d, 640, 480)
+        with pytest.raises(CI.CameraImageError) as e:
+            OV.bag_pcd2image(image_bag, "/camera/image_raw", "/velodyne_points", other, T)
+        assert e.value.status == N.BAD_ARGUMENT
+        for topics in (("/velodyne_points", "/velodyne_points"), ("/camera/image_raw", "/camera/image_raw")):
+            with pytest.raises(CI.CameraImageError) as e:
+                OV.bag_pcd2image(image_bag, *topics, ncam, T)
+            assert e.value.status == N.BAD_ARGUMENT and "no message of that type on topic" in str(e.value)
+        r = _cli("--bag", image_bag, "--image-topic", "/nothing", "--lidar-topic", "/velodyne_points", "--yaml", yaml_path,
+                 "--extrinsic", pose_path, "--out", str(tmp_path / "x.ppm"))
+        assert r.returncode == 1 and "can't read lidar or image topic" in r.stderr and not (tmp_path / "x.ppm").exists()
