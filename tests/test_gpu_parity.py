@@ -74,6 +74,8 @@ def _assert_every_stage(ob, est, clouds, clicks, p, op, solver):
         clu_idx, _ = ob.cluster(clouds[f][roi_idx], clicks[f], op)
         assert np.array_equal(est.fetch_cloud(f, N.CLOUD_CLUSTER), clouds[f][roi_idx][clu_idx])
         assert np.array_equal(est.fetch_cloud(f, N.CLOUD_CHESSBOARD), ocb)
+        # ... and the plane itself (the oracle fed the cluster the GPU fetched): as pca below
+        assert np.abs(np.array(r.plane) - ob.ransac_plane(est.fetch_cloud(f, N.CLOUD_CLUSTER), op)[1]).max() < 1e-6, f
         # a4 plane frame
         assert np.abs(np.array(r.pca) - np.array(o.pca)).max() < 1e-6
         assert np.abs(est.fetch_cloud(f, N.CLOUD_PCA) - opc).max() < 1e-6
