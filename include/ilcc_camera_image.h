@@ -39,9 +39,12 @@
  *   Deviation from OpenCV: it accumulates x along a row and works in stripes; here every pixel is
  *   evaluated directly (order 1e-13 px: moves a 1/32-pixel code only at an exact tie).
  *
- * Not here: JPEG / sensor_msgs/CompressedImage decoding; 16-bit and Bayer encodings; the rational
- * (k4..k6), thin-prism and tilt terms of the distortion model; the stereo rectification of
- * undistort_stereo_image; structure recovery stays on the host (ilcc_image_corners.h).
+ * A topic that carries no sensor_msgs/Image but sensor_msgs/CompressedImage (JPEG) is read by the two bag entries
+ * all the same: K13 (ilcc_jpeg.h) decodes its first message into the frame K11 then takes.
+ *
+ * Not here: 16-bit and Bayer encodings; the rational (k4..k6), thin-prism and tilt terms of the distortion
+ * model; the stereo rectification of undistort_stereo_image; structure recovery stays on the host
+ * (ilcc_image_corners.h).
  */
 #ifndef ILCC_CAMERA_IMAGE_H_
 #define ILCC_CAMERA_IMAGE_H_
@@ -109,7 +112,7 @@ int32_t ilcc_image_to_bgr8_device(const void* d_src, int32_t width, int32_t heig
  * camera->height int32 each (device memory, row-major, packed).  Asynchronous on hip_stream. */
 int32_t ilcc_undistort_map_device(const ilcc_camera_model* camera, int32_t* d_iu, int32_t* d_iv, void* hip_stream);
 
-/* bag -> host pixels: the first sensor_msgs/Image on `topic`, converted (and undistorted when camera is
+/* bag -> host pixels: the first sensor_msgs/Image on `topic` (the first CompressedImage when it has none), converted (and undistorted when camera is
  * not NULL) on device `device`, width x height bytes, packed.  *width / *height are the image's even when
  * cap_bytes is too small (ILCC_CAPACITY). */
 int32_t ilcc_bag_first_image(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,

@@ -19,8 +19,8 @@
  *   plotChessboards.m:48-68 (dlmwrite of the X then Y block)      ilcc_save_cam_corners
  *
  * Corner positions are 0-based pixels (findCorners.m:124-125); the file adds 1 back, as the
- * reference's dump does.  Not here: JPEG decoding, multi-board output.  The undistorted image itself
- * (from a bag or a raw frame) comes from ilcc_camera_image.h.
+ * reference's dump does.  Not here: multi-board output.  The undistorted image itself
+ * (from a bag or a raw frame) comes from ilcc_camera_image.h, the pixels of a .jpg file from ilcc_jpeg.h.
  */
 #ifndef ILCC_IMAGE_CORNERS_H_
 #define ILCC_IMAGE_CORNERS_H_

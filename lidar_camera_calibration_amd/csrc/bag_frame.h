@@ -1,0 +1,33 @@
+// The first frame of a camera topic, as its publisher encoded it: the first sensor_msgs/Image, or, when the topic carries
+// none, the first sensor_msgs/CompressedImage, which K13 decodes.  ONE helper for ilcc_bag_first_image,
+// ilcc_bag_find_chessboard and ilcc_bag_pcd2image (csrc/jpeg_host.cpp), in two steps so that a caller can check its own
+// capacity and make its one hipMalloc between them.
+#ifndef ILCC_BAG_FRAME_H_
+#define ILCC_BAG_FRAME_H_
+
+#include <cstdint>
+#include <vector>
+
+#include "ilcc_jpeg.h"
+
+namespace ilcc {
+
+struct BagFrame {
+  std::vector<uint8_t> msg;     // the serialized message
+  bool compressed = false;
+  ilcc_image_layout L{};        // of the pixels on the device: width, height, step, encoding (data_offset / data_bytes: in msg)
+  ilcc_jpeg_info jpeg{};        // compressed only
+  uint64_t device_bytes = 0;    // what bag_frame_to_device needs at d_mem
+};
+
+// host only: reads and parses the message (for a CompressedImage the JPEG headers too)
+int32_t bag_frame_read(const char* bag_path, const char* topic, BagFrame* out);
+
+// d_mem: frame.device_bytes of device memory on a 256-byte boundary.  Leaves the pixels at d_mem, rows L.step apart, in
+// L.encoding, queued on the default stream of the current device (an Image: one H2D copy of data[]; a CompressedImage:
+// entropy decode here, H2D of the coefficients, K13; coefficients and scratch lie behind the pixels).
+int32_t bag_frame_to_device(const BagFrame& frame, void* d_mem);
+
+}  // namespace ilcc
+
+#endif

@@ -1,6 +1,6 @@
 // Host side of include/ilcc_camera_image.h: the intrinsics reader (what ImageCornersEst::getRectifyParam,
 // /root/reference/ilcc2/src/ImageCornersEst.cpp:15-61, takes from cv::FileStorage), the sensor_msgs/Image
-// parser, and the two bag entries that chain ilcc_bag_first_message -> parse -> H2D -> K11
+// parser, and the two bag entries that chain the topic's first frame (csrc/bag_frame.h) -> K11
 // (/root/reference/ilcc2/test/get_image_corners_bag.cpp:67-112).  Little-endian host.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "bag_frame.h"
 #include "ilcc_camera_image.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
@@ -23,8 +24,6 @@ void set_global_error(const std::string& s);   // ilcc_api.cpp
 }
 
 namespace {
-
-constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
 
 int32_t fail(int32_t code, const std::string& what) {
   ilcc::set_global_error(what);
@@ -120,7 +119,8 @@ bool read_u32(const uint8_t* m, uint64_t n, uint64_t* at, uint32_t* v) {
   return true;
 }
 
-// the first Image of the bag on the device, converted: ONE device buffer holds data[] and, behind it, the mono8 image
+// the first frame of the bag's topic on the device, converted: ONE device buffer holds the frame as the bag carries it
+// (csrc/bag_frame.h: data[] of an Image, or what K13 makes of a CompressedImage) and, behind it, the mono8 image
 struct DeviceImage {
   void* buffer = nullptr;
   uint8_t* mono8 = nullptr;
@@ -133,20 +133,11 @@ struct DeviceImage {
 // cap_pixels: refuse with ILCC_CAPACITY (sizes reported) before the GPU is touched when the image is larger
 int32_t bag_image_to_device(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
                             uint64_t cap_pixels, int32_t* width, int32_t* height, DeviceImage* out) {
-  uint64_t bytes = 0;
-  int32_t st = ilcc_bag_first_message(bag_path, topic, kImageMd5, nullptr, 0, &bytes);
-  if (st != ILCC_CAPACITY && st != ILCC_OK) return st;
-  std::vector<uint8_t> msg;
-  try {
-    msg.resize(bytes);
-  } catch (...) {   // no exception crosses the C-ABI
-    return fail(ILCC_IO_ERROR, "out of memory for the bag's message");
-  }
-  st = ilcc_bag_first_message(bag_path, topic, kImageMd5, msg.data(), bytes, &bytes);
+  ilcc::BagFrame frame;
+  int32_t st = ilcc::bag_frame_read(bag_path, topic, &frame);
   if (st != ILCC_OK) return st;
   ilcc_image_layout& L = out->L;
-  st = ilcc_image_parse(msg.data(), bytes, &L);
-  if (st != ILCC_OK) return st;
+  L = frame.L;
   if (L.width > 65536u || L.height > 65536u) return fail(ILCC_BAD_ARGUMENT, "image larger than 65536 pixels a side");
   *width = (int32_t)L.width;
   *height = (int32_t)L.height;
@@ -158,12 +149,12 @@ int32_t bag_image_to_device(int32_t device, const char* bag_path, const char* to
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
     return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
-  const uint64_t src_bytes = (uint64_t)L.step * L.height;          // <= data_bytes (ilcc_image_parse)
-  const uint64_t mono_at = (src_bytes + 255u) & ~(uint64_t)255u;   // the output starts on a 256-byte boundary
+  const uint64_t mono_at = (frame.device_bytes + 255u) & ~(uint64_t)255u;   // the output starts on a 256-byte boundary
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipMalloc(&out->buffer, mono_at + pixels);
-  if (e == hipSuccess) e = hipMemcpy(out->buffer, msg.data() + L.data_offset, src_bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
+  st = ilcc::bag_frame_to_device(frame, out->buffer);
+  if (st != ILCC_OK) return st;
   out->mono8 = (uint8_t*)out->buffer + mono_at;
   return ilcc_image_to_mono8_device(out->buffer, *width, *height, (int32_t)L.step, (int32_t)L.encoding, camera, out->mono8, *width,
                                     nullptr);

@@ -1,5 +1,5 @@
 // Host side of include/ilcc_overlay.h: pcd2image (/root/reference/ilcc2/test/pcd2image.cpp:33-104) from bags -- the first
-// Image and the first PointCloud2, H2D, K11c -> K0 -> K8 -> K12 on the default stream, D2H -- and the PPM writer that
+// frame of the camera topic (csrc/bag_frame.h) and the first PointCloud2, H2D, K11c -> K0 -> K8 -> K12 on the default stream, D2H -- and the PPM writer that
 // stands in for cv::imshow.  This file includes the lens' header (ilcc_camera_image.h through ilcc_overlay.h), so K8 and
 // K12, whose header defines another ilcc_camera_model, are reached through ilcc_internal.h.
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "bag_frame.h"
 #include "ilcc_hip.h"
 #include "ilcc_ingest.h"
 #include "ilcc_internal.h"
@@ -19,8 +20,6 @@ void set_global_error(const std::string& s);   // ilcc_api.cpp
 }
 
 namespace {
-
-constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
 
 int32_t fail(int32_t code, const std::string& what) {
   ilcc::set_global_error(what);
@@ -60,12 +59,11 @@ int32_t ilcc_bag_pcd2image(int32_t device, const char* image_bag, const char* im
     return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_pcd2image: null argument");
   *width = *height = 0;
   *n_drawn = 0;
-  std::vector<uint8_t> image_msg, cloud_msg;
-  int32_t st = first_message(image_bag, image_topic, kImageMd5, &image_msg);
+  std::vector<uint8_t> cloud_msg;
+  ilcc::BagFrame frame;
+  int32_t st = ilcc::bag_frame_read(image_bag, image_topic, &frame);
   if (st != ILCC_OK) return st;
-  ilcc_image_layout I;
-  st = ilcc_image_parse(image_msg.data(), image_msg.size(), &I);
-  if (st != ILCC_OK) return st;
+  const ilcc_image_layout& I = frame.L;
   if (I.width > 65536u || I.height > 65536u) return fail(ILCC_BAD_ARGUMENT, "image larger than 65536 pixels a side");
   if (I.step > (uint32_t)INT32_MAX) return fail(ILCC_BAD_ARGUMENT, "image step too large");
   const int32_t w = (int32_t)I.width, h = (int32_t)I.height;
@@ -85,9 +83,8 @@ int32_t ilcc_bag_pcd2image(int32_t device, const char* image_bag, const char* im
   if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
     return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
 
-  // ONE device buffer: [ image data[] | B,G,R image | cloud data[] | XYZI | hits | K12's owner words ]
-  const uint64_t src_bytes = (uint64_t)I.step * I.height;   // <= data_bytes (ilcc_image_parse)
-  const uint64_t bgr_at = rounded(src_bytes);
+  // ONE device buffer: [ the frame as the bag carries it | B,G,R image | cloud data[] | XYZI | hits | K12's owner words ]
+  const uint64_t bgr_at = rounded(frame.device_bytes);
   const uint64_t cloud_at = bgr_at + rounded(bgr_bytes);
   const uint64_t xyzi_at = cloud_at + rounded(P.data_bytes);
   const uint64_t hits_at = xyzi_at + rounded(16 * points);
@@ -96,9 +93,10 @@ int32_t ilcc_bag_pcd2image(int32_t device, const char* image_bag, const char* im
   DeviceBuffer buf;
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipMalloc(&buf.p, total);
-  if (e == hipSuccess) e = hipMemcpy(buf.p, image_msg.data() + I.data_offset, src_bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
   uint8_t* base = (uint8_t*)buf.p;
+  st = ilcc::bag_frame_to_device(frame, base);
+  if (st != ILCC_OK) return st;
   st = ilcc_image_to_bgr8_device(base, w, h, (int32_t)I.step, (int32_t)I.encoding, camera, base + bgr_at, 3 * w, nullptr);
   if (st != ILCC_OK) return st;
   if (points) {

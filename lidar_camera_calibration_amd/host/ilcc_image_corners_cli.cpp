@@ -3,6 +3,10 @@
 // with the yaml's K and d -> chessboard corners -> `<camera><i>.txt` as ilcc_calib_lidar_cam reads it.
 //   ilcc_image_corners --bag 20181101_1.bag --topic /camera/image_raw --yaml pointgrey.yaml --out pointgrey1.txt
 //                      [--pgm undistorted.pgm] [--device N]
+//   ilcc_image_corners --jpg pointgrey1.jpg [--yaml pointgrey.yaml] [--board 7x5] --out pointgrey1.txt [--device N]
+// --jpg takes the image from a JPEG file instead (libcbdetect/demo_all_pic.m:8-19 on one file).  Without --yaml the file
+// is taken as already undistorted, as the reference's process_data/<camera><i>.jpg are, and the board is --board's
+// (corners along x by corners along y, 7x5 when not given); with it, both come from the yaml as for a bag.
 // --pgm writes the undistorted image as a binary PGM (P5): it stands in for the reference's imwrite.
 // Mirrors the per-bag body of /root/reference/ilcc2/test/get_image_corners_bag.cpp:67-112 and
 // libcbdetect's findCorners / chessboardsFromCorners / plotChessboards dump.
@@ -14,14 +18,18 @@
 #include "ilcc_camera_image.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
+#include "ilcc_jpeg.h"
 
 int main(int argc, char** argv) {
-  std::string bag_path, topic, yaml_path, out_path, pgm_path;
+  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path;
   int device = 0;
+  int32_t board_w = 7, board_h = 5;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--bag" && i + 1 < argc) bag_path = argv[++i];
     else if (a == "--topic" && i + 1 < argc) topic = argv[++i];
+    else if (a == "--jpg" && i + 1 < argc) jpg_path = argv[++i];
+    else if (a == "--board" && i + 1 < argc && std::sscanf(argv[i + 1], "%dx%d", &board_w, &board_h) == 2) ++i;
     else if (a == "--yaml" && i + 1 < argc) yaml_path = argv[++i];
     else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
     else if (a == "--pgm" && i + 1 < argc) pgm_path = argv[++i];
@@ -31,24 +39,35 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if (bag_path.empty() || topic.empty() || yaml_path.empty() || out_path.empty()) {
+  const bool from_jpg = !jpg_path.empty();
+  const bool bag_ok = !bag_path.empty() && !topic.empty() && !yaml_path.empty();
+  const bool jpg_ok = bag_path.empty() && topic.empty() && pgm_path.empty();
+  if (out_path.empty() || (from_jpg ? !jpg_ok : !bag_ok)) {
     std::fprintf(stderr, "usage: ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt "
-                         "[--pgm undistorted.pgm] [--device N]\n");
+                         "[--pgm undistorted.pgm] [--device N]\n"
+                         "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n");
     return 2;
   }
-  ilcc_camera_model cam;
-  if (ilcc_read_camera_yaml(yaml_path.c_str(), &cam) != ILCC_OK) {
-    std::fprintf(stderr, "%s\n", ilcc_last_error(nullptr));   // "can not open ..." as ImageCornersEst.cpp:20-24
-    return 1;
+  ilcc_camera_model cam{};
+  if (!yaml_path.empty()) {
+    if (ilcc_read_camera_yaml(yaml_path.c_str(), &cam) != ILCC_OK) {
+      std::fprintf(stderr, "%s\n", ilcc_last_error(nullptr));   // "can not open ..." as ImageCornersEst.cpp:20-24
+      return 1;
+    }
+    // the board: corner_in_x x corner_in_y of the same yaml (ilcc_set_chessboard_param stores them + 1, smaller first)
+    ilcc_params params;
+    ilcc_default_params(&params);
+    if (ilcc_set_chessboard_param(&params, yaml_path.c_str()) != ILCC_OK) {
+      std::fprintf(stderr, "%s\n", ilcc_last_error(nullptr));
+      return 1;
+    }
+    board_w = params.board_h - 1;
+    board_h = params.board_w - 1;
   }
-  // the board: corner_in_x x corner_in_y of the same yaml (ilcc_set_chessboard_param stores them + 1, smaller first)
-  ilcc_params params;
-  ilcc_default_params(&params);
-  if (ilcc_set_chessboard_param(&params, yaml_path.c_str()) != ILCC_OK) {
-    std::fprintf(stderr, "%s\n", ilcc_last_error(nullptr));
-    return 1;
+  if (board_w < 3 || board_h < 3) {
+    std::fprintf(stderr, "the board needs at least 3 x 3 corners\n");
+    return 2;
   }
-  const int32_t board_w = params.board_h - 1, board_h = params.board_w - 1;
 
   if (!pgm_path.empty()) {
     int32_t w = 0, h = 0;
@@ -76,19 +95,23 @@ int main(int argc, char** argv) {
 
   int32_t rows = 0, cols = 0;
   std::vector<double> xy((size_t)board_w * board_h * 2);
-  const int32_t st = ilcc_bag_find_chessboard(device, bag_path.c_str(), topic.c_str(), &cam, board_w, board_h, &rows, &cols, xy.data());
+  const int32_t st = from_jpg ? ilcc_jpeg_find_chessboard(device, jpg_path.c_str(), yaml_path.empty() ? nullptr : &cam, board_w, board_h,
+                                                          &rows, &cols, xy.data())
+                              : ilcc_bag_find_chessboard(device, bag_path.c_str(), topic.c_str(), &cam, board_w, board_h, &rows, &cols,
+                                                         xy.data());
   if (st == ILCC_BOARD_NOT_FOUND || st == ILCC_AMBIGUOUS) {
     std::fprintf(stderr, "no chessboard: %s\n", ilcc_last_error(nullptr));
     return 4;
   }
   if (st != ILCC_OK) {
-    std::fprintf(stderr, "can't read image topic: %s\n", ilcc_last_error(nullptr));
+    std::fprintf(stderr, "%s: %s\n", from_jpg ? "can't read image file" : "can't read image topic", ilcc_last_error(nullptr));
     return 1;
   }
   if (ilcc_save_cam_corners(out_path.c_str(), rows, cols, xy.data()) != ILCC_OK) {
     std::fprintf(stderr, "can not write %s\n", out_path.c_str());
     return 1;
   }
-  std::printf("image %d x %d board %d x %d -> %s\n", cam.width, cam.height, rows, cols, out_path.c_str());
+  if (from_jpg) std::printf("%s board %d x %d -> %s\n", jpg_path.c_str(), rows, cols, out_path.c_str());
+  else std::printf("image %d x %d board %d x %d -> %s\n", cam.width, cam.height, rows, cols, out_path.c_str());
   return 0;
 }
