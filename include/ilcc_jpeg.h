@@ -46,7 +46,7 @@
  *   colour, cb -= 128, cr -= 128:  R = Y + ((91881 cr + 32768) >> 16);  B = Y + ((116130 cb + 32768) >> 16);
  *     G = Y + ((-22554 cb - 46802 cr + 32768) >> 16); each clamped to 0..255 and stored B, G, R.
  *
- * Not here: JPEG output, progressive JPEG, PNG.
+ * Not here: progressive JPEG, PNG.
  */
 #ifndef ILCC_JPEG_H_
 #define ILCC_JPEG_H_

@@ -24,7 +24,7 @@
  * (ilcc_camera_model: the extrinsic and the pinhole), so a translation unit includes one of the two, not both.
  *
  * Not here: show_calib_result's radius-1 circles and putText; rgblidar from bags; time-synchronised pairing;
- * JPEG output; anti-aliased drawing; display.
+ * anti-aliased drawing; display.  (JPEG output of the picture: ilcc_jpeg_write.h; CLI ilcc_pcd2image --jpg-out.)
  */
 #ifndef ILCC_OVERLAY_H_
 #define ILCC_OVERLAY_H_

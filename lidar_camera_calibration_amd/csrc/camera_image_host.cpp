@@ -119,20 +119,15 @@ bool read_u32(const uint8_t* m, uint64_t n, uint64_t* at, uint32_t* v) {
   return true;
 }
 
-// the first frame of the bag's topic on the device, converted: ONE device buffer holds the frame as the bag carries it
-// (csrc/bag_frame.h: data[] of an Image, or what K13 makes of a CompressedImage) and, behind it, the mono8 image
-struct DeviceImage {
-  void* buffer = nullptr;
-  uint8_t* mono8 = nullptr;
-  ilcc_image_layout L{};
-  ~DeviceImage() {
-    if (buffer) (void)hipFree(buffer);
-  }
-};
+}  // namespace
 
-// cap_pixels: refuse with ILCC_CAPACITY (sizes reported) before the GPU is touched when the image is larger
-int32_t bag_image_to_device(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
-                            uint64_t cap_pixels, int32_t* width, int32_t* height, DeviceImage* out) {
+ilcc::DeviceImage::~DeviceImage() {
+  if (buffer) (void)hipFree(buffer);
+}
+
+int32_t ilcc::bag_image_to_device(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
+                                  uint64_t cap_pixels, uint64_t (*extra_for)(int32_t, int32_t), int32_t* width, int32_t* height,
+                                  DeviceImage* out) {
   ilcc::BagFrame frame;
   int32_t st = ilcc::bag_frame_read(bag_path, topic, &frame);
   if (st != ILCC_OK) return st;
@@ -151,16 +146,17 @@ int32_t bag_image_to_device(int32_t device, const char* bag_path, const char* to
     return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
   const uint64_t mono_at = (frame.device_bytes + 255u) & ~(uint64_t)255u;   // the output starts on a 256-byte boundary
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&out->buffer, mono_at + pixels);
+  const uint64_t extra_at = (mono_at + pixels + 255u) & ~(uint64_t)255u;
+  const uint64_t extra_bytes = extra_for ? extra_for(*width, *height) : 0;
+  if (e == hipSuccess) e = hipMalloc(&out->buffer, extra_bytes ? extra_at + extra_bytes : mono_at + pixels);
   if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
   st = ilcc::bag_frame_to_device(frame, out->buffer);
   if (st != ILCC_OK) return st;
   out->mono8 = (uint8_t*)out->buffer + mono_at;
+  out->extra = extra_bytes ? (uint8_t*)out->buffer + extra_at : nullptr;
   return ilcc_image_to_mono8_device(out->buffer, *width, *height, (int32_t)L.step, (int32_t)L.encoding, camera, out->mono8, *width,
                                     nullptr);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -261,8 +257,8 @@ int32_t ilcc_bag_first_image(int32_t device, const char* bag_path, const char* t
                              uint8_t* mono8_out, uint64_t cap_bytes, int32_t* width, int32_t* height) {
   if (!width || !height || (!mono8_out && cap_bytes)) return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_first_image: null argument");
   *width = *height = 0;
-  DeviceImage img;
-  const int32_t st = bag_image_to_device(device, bag_path, topic, camera, cap_bytes, width, height, &img);
+  ilcc::DeviceImage img;
+  const int32_t st = ilcc::bag_image_to_device(device, bag_path, topic, camera, cap_bytes, nullptr, width, height, &img);
   if (st != ILCC_OK) return st;
   const hipError_t e = hipMemcpy(mono8_out, img.mono8, (size_t)*width * (size_t)*height, hipMemcpyDeviceToHost);   // waits for K11
   if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
@@ -273,9 +269,9 @@ int32_t ilcc_bag_find_chessboard(int32_t device, const char* bag_path, const cha
                                  int32_t board_w, int32_t board_h, int32_t* rows, int32_t* cols, double* xy) {
   if (!rows || !cols || !xy || board_w < 3 || board_h < 3) return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_find_chessboard: bad argument");
   *rows = *cols = 0;
-  DeviceImage img;
+  ilcc::DeviceImage img;
   int32_t w = 0, h = 0;
-  const int32_t st = bag_image_to_device(device, bag_path, topic, camera, ~0ull, &w, &h, &img);
+  const int32_t st = ilcc::bag_image_to_device(device, bag_path, topic, camera, ~0ull, nullptr, &w, &h, &img);
   if (st != ILCC_OK) return st;
   return ilcc_find_chessboard_device(img.mono8, w, h, w, board_w, board_h, rows, cols, xy, nullptr);   // the same (default) stream as K11
 }

@@ -21,15 +21,21 @@ const char* jpeg_last_error() { return g_jpeg_error; }
 
 }  // namespace ilcc
 
-namespace {
+namespace ilcc {
 
-int32_t refuse(const char* cause, const char* detail = nullptr) {
-  char* text = ilcc::g_jpeg_error;
-  if (detail) std::snprintf(text, sizeof(ilcc::g_jpeg_error), "jpeg: %s (%s)", cause, detail);
-  else std::snprintf(text, sizeof(ilcc::g_jpeg_error), "jpeg: %s", cause);
-  if (ilcc::jpeg_error_sink) ilcc::jpeg_error_sink(text);
+int32_t jpeg_refuse(const char* cause, const char* detail) {
+  char* text = g_jpeg_error;
+  if (detail) std::snprintf(text, sizeof(g_jpeg_error), "jpeg: %s (%s)", cause, detail);
+  else std::snprintf(text, sizeof(g_jpeg_error), "jpeg: %s", cause);
+  if (jpeg_error_sink) jpeg_error_sink(text);
   return ILCC_BAD_ARGUMENT;
 }
+
+}  // namespace ilcc
+
+namespace {
+
+int32_t refuse(const char* cause, const char* detail = nullptr) { return ilcc::jpeg_refuse(cause, detail); }
 
 // natural (row-major) index of the k-th coefficient in zigzag order
 constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -421,3 +427,9 @@ int32_t ilcc_jpeg_entropy_decode(const uint8_t* jpg, uint64_t bytes, const ilcc_
 }
 
 }  // extern "C"
+
+bool ilcc::jpeg_laid_out(const ilcc_jpeg_info& I) {
+  ilcc_jpeg_info L = I;
+  if (ilcc_jpeg_layout(&L) != ILCC_OK) return false;
+  return std::memcmp(&L, &I, sizeof(L)) == 0;
+}

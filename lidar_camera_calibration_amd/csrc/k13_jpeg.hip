@@ -29,6 +29,8 @@
 
 #include "ilcc_hip.h"
 #include "ilcc_jpeg.h"
+#include "jpeg_block8.h"
+#include "jpeg_entropy.h"
 
 namespace ilcc {
 
@@ -50,40 +52,6 @@ struct IdctArgs {
   int32_t clip_w, clip_h;    // nothing is stored at x >= clip_w or y >= clip_h
   QuantTable quant;
 };
-
-struct alignas(4) Dword2 {
-  uint32_t x, y;
-};
-struct alignas(4) Dword3 {
-  uint32_t x, y, z;
-};
-
-// the value lane (l ^ S) holds, S = 1, 2 or 4
-template <int S>
-__device__ __forceinline__ int32_t lane_xor(int32_t x) {
-  if constexpr (S == 1) return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);        // quad_perm [1, 0, 3, 2]
-  else if constexpr (S == 2) return __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);   // quad_perm [2, 3, 0, 1]
-  else return __builtin_amdgcn_ds_swizzle(x, 0x101F);                                          // bit mode: and 0x1f, or 0, xor 4
-}
-
-// one butterfly stage of the 8 x 8 transpose among eight lanes: the S x S blocks off the diagonal change places
-template <int S>
-__device__ __forceinline__ void transpose_stage(int32_t (&v)[8], bool upper) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (i & S) continue;
-    const int32_t got = lane_xor<S>(upper ? v[i] : v[i | S]);
-    if (upper) v[i] = got;
-    else v[i | S] = got;
-  }
-}
-
-// lane r of an aligned group of eight holds M[r][0..7] -> it holds M[0..7][r]
-__device__ __forceinline__ void transpose8(int32_t (&v)[8], int lane8) {
-  transpose_stage<1>(v, (lane8 & 1) != 0);
-  transpose_stage<2>(v, (lane8 & 2) != 0);
-  transpose_stage<4>(v, (lane8 & 4) != 0);
-}
 
 // libjpeg's jpeg_idct_islow pass (CONST_BITS 13), in place; the caller's SHIFT is 11 (pass 1) or 18 (pass 2)
 template <int SHIFT>
@@ -259,13 +227,6 @@ uint64_t rounded(uint64_t bytes) { return (bytes + 255u) & ~(uint64_t)255u; }   
 
 uint64_t plane_bytes(const ilcc_jpeg_component& c) { return rounded(64ull * (uint64_t)c.blocks_w * (uint64_t)c.blocks_h); }
 
-// true when the info's sizes, sampling, block counts and offsets are the ones ilcc_jpeg_layout gives
-bool laid_out(const ilcc_jpeg_info& I) {
-  ilcc_jpeg_info L = I;
-  if (ilcc_jpeg_layout(&L) != ILCC_OK) return false;
-  return std::memcmp(&L, &I, sizeof(L)) == 0;
-}
-
 void launch_idct(const ilcc_jpeg_info& I, int c, const int16_t* d_coef, uint8_t* dst, int64_t stride, int32_t clip_w, int32_t clip_h,
                  hipStream_t s) {
   IdctArgs a;
@@ -286,7 +247,7 @@ void launch_idct(const ilcc_jpeg_info& I, int c, const int16_t* d_coef, uint8_t*
 
 extern "C" uint64_t ilcc_jpeg_scratch_bytes(const ilcc_jpeg_info* info) {
   using namespace ilcc;
-  if (!info || info->n_components != 3 || !laid_out(*info)) return 0;
+  if (!info || info->n_components != 3 || !jpeg_laid_out(*info)) return 0;
   return plane_bytes(info->comp[0]) + plane_bytes(info->comp[1]) + plane_bytes(info->comp[2]);
 }
 
@@ -294,7 +255,7 @@ extern "C" int32_t ilcc_jpeg_idct_device(const ilcc_jpeg_info* info, const int16
                                          void* d_scratch, uint64_t scratch_bytes, void* hip_stream) {
   using namespace ilcc;
   if (!info || !d_coef || !d_dst) return refuse("null pointer");
-  if (!laid_out(*info)) return refuse("the info's block counts and offsets are not ilcc_jpeg_layout's");
+  if (!jpeg_laid_out(*info)) return refuse("the info's block counts and offsets are not ilcc_jpeg_layout's");
   const ilcc_jpeg_info& I = *info;
   const int bpp = I.n_components == 1 ? 1 : 3;
   if ((int64_t)dst_stride < (int64_t)bpp * I.width) return refuse("dst_stride is shorter than a row");

@@ -2,12 +2,14 @@
 // without ROS, OpenCV or MATLAB (the GPU box): the first sensor_msgs/Image of a bag -> mono8 -> undistorted
 // with the yaml's K and d -> chessboard corners -> `<camera><i>.txt` as ilcc_calib_lidar_cam reads it.
 //   ilcc_image_corners --bag 20181101_1.bag --topic /camera/image_raw --yaml pointgrey.yaml --out pointgrey1.txt
-//                      [--pgm undistorted.pgm] [--device N]
+//                      [--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]
 //   ilcc_image_corners --jpg pointgrey1.jpg [--yaml pointgrey.yaml] [--board 7x5] --out pointgrey1.txt [--device N]
 // --jpg takes the image from a JPEG file instead (libcbdetect/demo_all_pic.m:8-19 on one file).  Without --yaml the file
 // is taken as already undistorted, as the reference's process_data/<camera><i>.jpg are, and the board is --board's
 // (corners along x by corners along y, 7x5 when not given); with it, both come from the yaml as for a bag.
-// --pgm writes the undistorted image as a binary PGM (P5): it stands in for the reference's imwrite.
+// --pgm writes the undistorted image as a binary PGM (P5).  --jpg-out writes it as the reference's imwrite does
+// (get_image_corners_bag.cpp:104-110: process_data/<camera><i>.jpg, libjpeg at quality 95; include/ilcc_jpeg_write.h);
+// with it --out may be left out, which is get_image_corners_bag alone: the corners are then not searched.
 // Mirrors the per-bag body of /root/reference/ilcc2/test/get_image_corners_bag.cpp:67-112 and
 // libcbdetect's findCorners / chessboardsFromCorners / plotChessboards dump.
 #include <cstdio>
@@ -19,10 +21,11 @@
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
 #include "ilcc_jpeg.h"
+#include "ilcc_jpeg_write.h"
 
 int main(int argc, char** argv) {
-  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path;
-  int device = 0;
+  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path, jpg_out_path;
+  int device = 0, quality = 95;
   int32_t board_w = 7, board_h = 5;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -33,6 +36,8 @@ int main(int argc, char** argv) {
     else if (a == "--yaml" && i + 1 < argc) yaml_path = argv[++i];
     else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
     else if (a == "--pgm" && i + 1 < argc) pgm_path = argv[++i];
+    else if (a == "--jpg-out" && i + 1 < argc) jpg_out_path = argv[++i];
+    else if (a == "--quality" && i + 1 < argc) quality = std::atoi(argv[++i]);
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else {
       std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
@@ -41,10 +46,10 @@ int main(int argc, char** argv) {
   }
   const bool from_jpg = !jpg_path.empty();
   const bool bag_ok = !bag_path.empty() && !topic.empty() && !yaml_path.empty();
-  const bool jpg_ok = bag_path.empty() && topic.empty() && pgm_path.empty();
-  if (out_path.empty() || (from_jpg ? !jpg_ok : !bag_ok)) {
+  const bool jpg_ok = bag_path.empty() && topic.empty() && pgm_path.empty() && jpg_out_path.empty();
+  if ((out_path.empty() && (from_jpg || jpg_out_path.empty())) || (from_jpg ? !jpg_ok : !bag_ok)) {
     std::fprintf(stderr, "usage: ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt "
-                         "[--pgm undistorted.pgm] [--device N]\n"
+                         "[--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]\n"
                          "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n");
     return 2;
   }
@@ -90,6 +95,17 @@ int main(int argc, char** argv) {
     if (!ok) {
       std::fprintf(stderr, "can not write %s\n", pgm_path.c_str());
       return 1;
+    }
+  }
+
+  if (!jpg_out_path.empty()) {
+    if (ilcc_bag_save_jpeg(device, bag_path.c_str(), topic.c_str(), &cam, jpg_out_path.c_str(), quality) != ILCC_OK) {
+      std::fprintf(stderr, "can't write %s: %s\n", jpg_out_path.c_str(), ilcc_last_error(nullptr));
+      return 1;
+    }
+    if (out_path.empty()) {
+      std::printf("image %d x %d -> %s\n", cam.width, cam.height, jpg_out_path.c_str());
+      return 0;
     }
   }
 

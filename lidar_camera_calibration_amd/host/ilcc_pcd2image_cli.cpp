@@ -3,7 +3,9 @@
 // the yaml's K and d, every LiDAR point that the extrinsic projects into it drawn as a dot coloured by intensity, and the
 // picture written as a binary PPM in place of cv::imshow.
 //   ilcc_pcd2image --bag B [--lidar-bag L] --image-topic T --lidar-topic T --yaml Y --extrinsic pose.bin --out out.ppm
-//                  [--distance-valid 5]
+//                  [--distance-valid 5] [--jpg-out out.jpg] [--quality 95]
+// --jpg-out writes the same picture as a JPEG file too (include/ilcc_jpeg_write.h: what cv::imwrite would write for it,
+// 4:2:0); both files show one picture.
 // The file shows what the reference's window showed, red and blue swapped included (include/ilcc_overlay.h).
 #include <cstdio>
 #include <cstdlib>
@@ -12,10 +14,12 @@
 
 #include "ilcc_calib.h"
 #include "ilcc_hip.h"
+#include "ilcc_jpeg_write.h"
 #include "ilcc_overlay.h"
 
 int main(int argc, char** argv) {
-  std::string bag_path, lidar_bag_path, image_topic, lidar_topic, yaml_path, extrinsic_path, out_path;
+  std::string bag_path, lidar_bag_path, image_topic, lidar_topic, yaml_path, extrinsic_path, out_path, jpg_out_path;
+  int quality = 95;
   double distance_valid = 5;   // pcd2image.cpp:122
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -27,6 +31,8 @@ int main(int argc, char** argv) {
     else if (a == "--extrinsic" && i + 1 < argc) extrinsic_path = argv[++i];
     else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
     else if (a == "--distance-valid" && i + 1 < argc) distance_valid = std::atof(argv[++i]);
+    else if (a == "--jpg-out" && i + 1 < argc) jpg_out_path = argv[++i];
+    else if (a == "--quality" && i + 1 < argc) quality = std::atoi(argv[++i]);
     else {
       std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
       return 2;
@@ -35,7 +41,7 @@ int main(int argc, char** argv) {
   if (bag_path.empty() || image_topic.empty() || lidar_topic.empty() || yaml_path.empty() || extrinsic_path.empty() || out_path.empty()) {
     std::fprintf(stderr, "usage: ilcc_pcd2image --bag file.bag [--lidar-bag lidar.bag] --image-topic /camera/image_raw "
                          "--lidar-topic /velodyne_points --yaml camera.yaml --extrinsic pose.bin --out out.ppm "
-                         "[--distance-valid 5]\n");
+                         "[--distance-valid 5] [--jpg-out out.jpg] [--quality 95]\n");
     return 2;
   }
   if (lidar_bag_path.empty()) lidar_bag_path = bag_path;
@@ -63,5 +69,12 @@ int main(int argc, char** argv) {
     return 1;
   }
   std::printf("image %d x %d, %u points drawn -> %s\n", w, h, drawn, out_path.c_str());
+  if (!jpg_out_path.empty()) {
+    if (ilcc_jpeg_write_file(0, jpg_out_path.c_str(), pixels.data(), 3 * w, w, h, ILCC_ENCODING_BGR8, quality) != ILCC_OK) {
+      std::fprintf(stderr, "can not write %s: %s\n", jpg_out_path.c_str(), ilcc_last_error(nullptr));
+      return 1;
+    }
+    std::printf("quality %d -> %s\n", quality, jpg_out_path.c_str());
+  }
   return 0;
 }
