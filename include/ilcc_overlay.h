@@ -20,9 +20,6 @@
  * byte 0, so the reference's window shows red and blue swapped; ilcc_save_ppm_bgr writes B,G,R as R,G,B, so the file
  * shows what that window showed.
  *
- * This header includes ilcc_camera_image.h for the lens.  ilcc_project.h defines another struct of the same name
- * (ilcc_camera_model: the extrinsic and the pinhole), so a translation unit includes one of the two, not both.
- *
  * Not here: show_calib_result's radius-1 circles and putText; rgblidar from bags; time-synchronised pairing;
  * anti-aliased drawing; display.  (JPEG output of the picture: ilcc_jpeg_write.h; CLI ilcc_pcd2image --jpg-out.)
  */

@@ -34,12 +34,12 @@
 extern "C" {
 #endif
 
-typedef struct ilcc_camera_model {
+typedef struct ilcc_projection {
   double R[9];            /* m_R, row-major: lidar -> camera rotation (ImageCornersEst::setRt) */
   double t[3];            /* m_t */
   double fx, cx, fy, cy;  /* m_fx ... from camK */
   int32_t width, height;  /* m_image_size */
-} ilcc_camera_model;
+} ilcc_projection;
 
 /* one projected point: integer pixel, colour, index of the source point */
 typedef struct ilcc_pixel_hit {
@@ -52,14 +52,14 @@ typedef struct ilcc_pixel_hit {
  * HSVtoRGB((intensity - inten_low) / (inten_high - inten_low) * 255, 100, 100); the reference fixes
  * inten_low = 0, inten_high = 60.  d_hits has room for n_points records.  Synchronous on return
  * (*n_hits is a host value).  hip_stream: hipStream_t or NULL. */
-int32_t ilcc_project_intensity_device(const void* d_xyzi, uint32_t n_points, const ilcc_camera_model* cam,
+int32_t ilcc_project_intensity_device(const void* d_xyzi, uint32_t n_points, const ilcc_projection* cam,
                                       double distance_valid, double inten_low, double inten_high, void* d_hits,
                                       uint32_t* n_hits, void* hip_stream);
 
 /* rgblidar: XYZRGB cloud (input order) of the points that pass spaceToPlane, colour = the BGR pixel
  * at (int)u, (int)v of d_image_bgr (rows image_step bytes apart).  Output records are 16 bytes:
  * float x, y, z and PCL's packed rgb (uint32 r << 16 | g << 8 | b, stored in the 4th float's bits). */
-int32_t ilcc_colourise_device(const void* d_xyzi, uint32_t n_points, const ilcc_camera_model* cam,
+int32_t ilcc_colourise_device(const void* d_xyzi, uint32_t n_points, const ilcc_projection* cam,
                               double distance_valid, const void* d_image_bgr, uint32_t image_step, void* d_xyzrgb,
                               uint32_t* n_out, void* hip_stream);
 

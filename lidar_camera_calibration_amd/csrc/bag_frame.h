@@ -9,9 +9,21 @@
 #include <cstdint>
 #include <vector>
 
+#include "host_util.h"
 #include "ilcc_jpeg.h"
 
 namespace ilcc {
+
+// where the coefficients and the kernel's scratch (`scratch`: the bytes K13 or K14 asks for) lie behind `pixel_bytes` of pixels
+struct JpegLayout {
+  uint64_t coef_at, scratch_at, scratch_bytes, total;
+  JpegLayout(const ilcc_jpeg_info& I, uint64_t pixel_bytes, uint64_t scratch) {
+    coef_at = align256(pixel_bytes);
+    scratch_at = coef_at + align256(I.coef_count * sizeof(int16_t));
+    scratch_bytes = scratch;
+    total = scratch_at + align256(scratch_bytes);
+  }
+};
 
 struct BagFrame {
   std::vector<uint8_t> msg;     // the serialized message
@@ -32,11 +44,10 @@ int32_t bag_frame_to_device(const BagFrame& frame, void* d_mem);
 // the first frame of the bag's topic on the device, converted: ONE device buffer holds the frame as the bag carries it
 // (data[] of an Image, or what K13 makes of a CompressedImage), behind it the mono8 image, and behind that `extra`
 struct DeviceImage {
-  void* buffer = nullptr;
+  DeviceBuffer buffer;
   uint8_t* mono8 = nullptr;     // width x height, packed
   uint8_t* extra = nullptr;     // what extra_for asked for, on a 256-byte boundary; null when it asked for none
   ilcc_image_layout L{};
-  ~DeviceImage();               // hipFree(buffer)
 };
 
 // bag_frame_read -> one hipMalloc -> bag_frame_to_device -> K11 (mono8; undistorted when a camera is given), all queued on

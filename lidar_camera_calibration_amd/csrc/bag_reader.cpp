@@ -10,12 +10,11 @@
 #include <string>
 #include <vector>
 
+#include "host_util.h"
 #include "ilcc_ingest.h"
 #include "ilcc_internal.h"
 
-namespace ilcc {
-void set_global_error(const std::string& s);   // ilcc_api.cpp
-}
+using ilcc::fail;
 
 namespace {
 
@@ -221,11 +220,6 @@ struct ChunkRef {
 
 uint64_t time_key(uint64_t ros_time) {   // wire: sec (low 32), nsec (high 32) -> sortable
   return ((ros_time & 0xffffffffull) << 32) | (ros_time >> 32);
-}
-
-int32_t fail(int32_t code, const std::string& what) {
-  ilcc::set_global_error(what);
-  return code;
 }
 
 }  // namespace

@@ -14,21 +14,15 @@
 #include <vector>
 
 #include "bag_frame.h"
+#include "host_util.h"
 #include "ilcc_camera_image.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
 #include "ilcc_ingest.h"
 
-namespace ilcc {
-void set_global_error(const std::string& s);   // ilcc_api.cpp
-}
+using namespace ilcc;
 
 namespace {
-
-int32_t fail(int32_t code, const std::string& what) {
-  ilcc::set_global_error(what);
-  return code;
-}
 
 std::string trimmed(const std::string& s) {
   const size_t a = s.find_first_not_of(" \t\r\n");
@@ -112,24 +106,13 @@ struct Yaml {
   }
 };
 
-bool read_u32(const uint8_t* m, uint64_t n, uint64_t* at, uint32_t* v) {
-  if (*at > n || n - *at < 4) return false;
-  std::memcpy(v, m + *at, 4);
-  *at += 4;
-  return true;
-}
-
 }  // namespace
-
-ilcc::DeviceImage::~DeviceImage() {
-  if (buffer) (void)hipFree(buffer);
-}
 
 int32_t ilcc::bag_image_to_device(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
                                   uint64_t cap_pixels, uint64_t (*extra_for)(int32_t, int32_t), int32_t* width, int32_t* height,
                                   DeviceImage* out) {
-  ilcc::BagFrame frame;
-  int32_t st = ilcc::bag_frame_read(bag_path, topic, &frame);
+  BagFrame frame;
+  int32_t st = bag_frame_read(bag_path, topic, &frame);
   if (st != ILCC_OK) return st;
   ilcc_image_layout& L = out->L;
   L = frame.L;
@@ -141,20 +124,19 @@ int32_t ilcc::bag_image_to_device(int32_t device, const char* bag_path, const ch
   if (camera && (camera->width != *width || camera->height != *height))
     return fail(ILCC_BAD_ARGUMENT, "the camera's width / height differ from the image's");
   if (L.step > (uint32_t)INT32_MAX) return fail(ILCC_BAD_ARGUMENT, "image step too large");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-    return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
-  const uint64_t mono_at = (frame.device_bytes + 255u) & ~(uint64_t)255u;   // the output starts on a 256-byte boundary
-  hipError_t e = hipSetDevice(device);
-  const uint64_t extra_at = (mono_at + pixels + 255u) & ~(uint64_t)255u;
-  const uint64_t extra_bytes = extra_for ? extra_for(*width, *height) : 0;
-  if (e == hipSuccess) e = hipMalloc(&out->buffer, extra_bytes ? extra_at + extra_bytes : mono_at + pixels);
-  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
-  st = ilcc::bag_frame_to_device(frame, out->buffer);
+  st = select_device(device);
   if (st != ILCC_OK) return st;
-  out->mono8 = (uint8_t*)out->buffer + mono_at;
-  out->extra = extra_bytes ? (uint8_t*)out->buffer + extra_at : nullptr;
-  return ilcc_image_to_mono8_device(out->buffer, *width, *height, (int32_t)L.step, (int32_t)L.encoding, camera, out->mono8, *width,
+  const uint64_t mono_at = align256(frame.device_bytes);
+  const uint64_t extra_at = align256(mono_at + pixels);
+  const uint64_t extra_bytes = extra_for ? extra_for(*width, *height) : 0;
+  const hipError_t e = hipMalloc(&out->buffer.p, extra_bytes ? extra_at + extra_bytes : mono_at + pixels);
+  if (e != hipSuccess) return hip_fail(e);
+  uint8_t* base = (uint8_t*)out->buffer.p;
+  st = bag_frame_to_device(frame, base);
+  if (st != ILCC_OK) return st;
+  out->mono8 = base + mono_at;
+  out->extra = extra_bytes ? base + extra_at : nullptr;
+  return ilcc_image_to_mono8_device(base, *width, *height, (int32_t)L.step, (int32_t)L.encoding, camera, out->mono8, *width,
                                     nullptr);
 }
 
@@ -214,11 +196,7 @@ int32_t ilcc_image_parse(const uint8_t* m, uint64_t n, ilcc_image_layout* out) {
   const char* truncated = "Image message truncated";
   uint64_t at = 0;
   uint32_t len = 0;
-  if (!read_u32(m, n, &at, &out->seq) || !read_u32(m, n, &at, &out->stamp_sec) || !read_u32(m, n, &at, &out->stamp_nsec) ||
-      !read_u32(m, n, &at, &len) || len > n - at)
-    return fail(ILCC_BAD_ARGUMENT, truncated);
-  std::memcpy(out->frame_id, m + at, len < sizeof(out->frame_id) - 1 ? len : sizeof(out->frame_id) - 1);
-  at += len;
+  if (!read_header(m, n, &at, &out->seq, &out->stamp_sec, &out->stamp_nsec, out->frame_id)) return fail(ILCC_BAD_ARGUMENT, truncated);
   if (!read_u32(m, n, &at, &out->height) || !read_u32(m, n, &at, &out->width) || !read_u32(m, n, &at, &len) || len > n - at)
     return fail(ILCC_BAD_ARGUMENT, truncated);
   const char* enc = (const char*)m + at;
@@ -257,11 +235,11 @@ int32_t ilcc_bag_first_image(int32_t device, const char* bag_path, const char* t
                              uint8_t* mono8_out, uint64_t cap_bytes, int32_t* width, int32_t* height) {
   if (!width || !height || (!mono8_out && cap_bytes)) return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_first_image: null argument");
   *width = *height = 0;
-  ilcc::DeviceImage img;
-  const int32_t st = ilcc::bag_image_to_device(device, bag_path, topic, camera, cap_bytes, nullptr, width, height, &img);
+  DeviceImage img;
+  const int32_t st = bag_image_to_device(device, bag_path, topic, camera, cap_bytes, nullptr, width, height, &img);
   if (st != ILCC_OK) return st;
   const hipError_t e = hipMemcpy(mono8_out, img.mono8, (size_t)*width * (size_t)*height, hipMemcpyDeviceToHost);   // waits for K11
-  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e);
   return ILCC_OK;
 }
 
@@ -269,9 +247,9 @@ int32_t ilcc_bag_find_chessboard(int32_t device, const char* bag_path, const cha
                                  int32_t board_w, int32_t board_h, int32_t* rows, int32_t* cols, double* xy) {
   if (!rows || !cols || !xy || board_w < 3 || board_h < 3) return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_find_chessboard: bad argument");
   *rows = *cols = 0;
-  ilcc::DeviceImage img;
+  DeviceImage img;
   int32_t w = 0, h = 0;
-  const int32_t st = ilcc::bag_image_to_device(device, bag_path, topic, camera, ~0ull, nullptr, &w, &h, &img);
+  const int32_t st = bag_image_to_device(device, bag_path, topic, camera, ~0ull, nullptr, &w, &h, &img);
   if (st != ILCC_OK) return st;
   return ilcc_find_chessboard_device(img.mono8, w, h, w, board_w, board_h, rows, cols, xy, nullptr);   // the same (default) stream as K11
 }

@@ -359,17 +359,4 @@ hipError_t set_kernel_attributes_k7r();
 void launch_local_solve(const Ctx& c, hipStream_t s, int32_t tlw, int32_t use_oob, double* theta_t,
                         double* cost_iters /*[2]: cost, iterations*/);
 
-
-// ---------------------------------------------------------------- the stages overlay_host.cpp chains (include/ilcc_overlay.h)
-// ilcc_project.h and ilcc_camera_image.h each define a struct named ilcc_camera_model, so no translation unit includes
-// both: the host chain includes the lens' header and reaches K8 and K12 here, the camera as plain arguments.
-// K8, ilcc_project_intensity_device (k8_project.hip)
-int32_t project_intensity(const void* d_xyzi, uint32_t n_points, const double R[9], const double t[3], double fx, double cx, double fy,
-                          double cy, int32_t width, int32_t height, double distance_valid, double inten_low, double inten_high,
-                          void* d_hits, uint32_t* n_hits, hipStream_t s);
-// K12, ilcc_draw_hits_scratch_bytes / ilcc_draw_hits_device (k12_overlay.hip)
-uint64_t draw_hits_scratch_bytes(int32_t width, int32_t height);
-int32_t draw_hits(void* d_image_bgr, int32_t width, int32_t height, int32_t stride, const void* d_hits, uint32_t n_hits,
-                  const int8_t* stamp_xy, int32_t n_stamp, void* d_scratch, hipStream_t s);
-
 }  // namespace ilcc

@@ -6,11 +6,10 @@
 #include <fstream>
 #include <string>
 
+#include "host_util.h"
 #include "ilcc_internal.h"   // (the kernels' limits that params_ok enforces: kGridTableMax, kCoverageCellsMax)
 
 namespace ilcc {
-
-void set_global_error(const std::string& s);   // ilcc_api.cpp
 
 // what ilcc_create / ilcc_set_params accept: everything the kernels can run
 bool params_ok(const ilcc_params& p, std::string& why) {

@@ -9,12 +9,11 @@
 #include <string>
 #include <vector>
 
+#include "host_util.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
 
 namespace ilcc {
-
-void set_global_error(const std::string& s);
 
 int32_t image_corners(const void* d_image, int32_t w, int32_t h, int32_t stride, ilcc_image_corner* corners, int32_t capacity,
                       int32_t* n_corners, ilcc_image_corner_stages* stages, void* stream);
@@ -242,10 +241,8 @@ std::vector<Board> chessboards_from_corners(const Corners& C) {
 
 extern "C" int32_t ilcc_chessboard_from_corners(const ilcc_image_corner* corners, int32_t n_corners, int32_t board_w,
                                                 int32_t board_h, int32_t* rows, int32_t* cols, int32_t* board_index) {
-  if ((n_corners > 0 && !corners) || n_corners < 0 || !rows || !cols || !board_index || board_w < 3 || board_h < 3) {
-    ilcc::set_global_error("ilcc_chessboard_from_corners: bad argument");
-    return ILCC_BAD_ARGUMENT;
-  }
+  if ((n_corners > 0 && !corners) || n_corners < 0 || !rows || !cols || !board_index || board_w < 3 || board_h < 3)
+    return ilcc::fail(ILCC_BAD_ARGUMENT, "ilcc_chessboard_from_corners: bad argument");
   ilcc::Corners C;
   for (int i = 0; i < n_corners; ++i) {
     C.p.push_back({corners[i].u, corners[i].v});
@@ -261,16 +258,11 @@ extern "C" int32_t ilcc_chessboard_from_corners(const ilcc_image_corner* corners
       ++n_hit;
     }
   *rows = *cols = 0;
-  if (n_hit == 0) {
-    ilcc::set_global_error("no " + std::to_string(board_w) + " x " + std::to_string(board_h) + " board among " +
-                           std::to_string(boards.size()) + " recovered from " + std::to_string(n_corners) + " corners");
-    return ILCC_BOARD_NOT_FOUND;
-  }
-  if (n_hit > 1) {
-    ilcc::set_global_error(std::to_string(n_hit) + " boards of " + std::to_string(board_w) + " x " + std::to_string(board_h) +
-                           " recovered");
-    return ILCC_AMBIGUOUS;
-  }
+  if (n_hit == 0)
+    return ilcc::fail(ILCC_BOARD_NOT_FOUND, "no " + std::to_string(board_w) + " x " + std::to_string(board_h) + " board among " +
+                                                std::to_string(boards.size()) + " recovered from " + std::to_string(n_corners) + " corners");
+  if (n_hit > 1)
+    return ilcc::fail(ILCC_AMBIGUOUS, std::to_string(n_hit) + " boards of " + std::to_string(board_w) + " x " + std::to_string(board_h) + " recovered");
   *rows = hit->rows;
   *cols = hit->cols;
   for (size_t k = 0; k < hit->idx.size(); ++k) board_index[k] = hit->idx[k];
@@ -280,10 +272,7 @@ extern "C" int32_t ilcc_chessboard_from_corners(const ilcc_image_corner* corners
 extern "C" int32_t ilcc_find_chessboard_device(const void* d_image, int32_t width, int32_t height, int32_t stride,
                                                int32_t board_w, int32_t board_h, int32_t* rows, int32_t* cols, double* xy,
                                                void* hip_stream) {
-  if (!rows || !cols || !xy || board_w < 3 || board_h < 3) {
-    ilcc::set_global_error("ilcc_find_chessboard_device: bad argument");
-    return ILCC_BAD_ARGUMENT;
-  }
+  if (!rows || !cols || !xy || board_w < 3 || board_h < 3) return ilcc::fail(ILCC_BAD_ARGUMENT, "ilcc_find_chessboard_device: bad argument");
   *rows = *cols = 0;
   std::vector<ilcc_image_corner> c(4096);
   int32_t n = 0;
@@ -307,23 +296,13 @@ extern "C" int32_t ilcc_find_chessboard_device(const void* d_image, int32_t widt
 }
 
 extern "C" int32_t ilcc_save_cam_corners(const char* filename, int32_t rows, int32_t cols, const double* xy) {
-  if (!filename || !xy || rows <= 0 || cols <= 0) {
-    ilcc::set_global_error("ilcc_save_cam_corners: bad argument");
-    return ILCC_BAD_ARGUMENT;
-  }
+  if (!filename || !xy || rows <= 0 || cols <= 0) return ilcc::fail(ILCC_BAD_ARGUMENT, "ilcc_save_cam_corners: bad argument");
   FILE* f = std::fopen(filename, "wb");
-  if (!f) {
-    ilcc::set_global_error(std::string("cannot write ") + filename);
-    return ILCC_IO_ERROR;
-  }
+  if (!f) return ilcc::fail(ILCC_IO_ERROR, std::string("cannot write ") + filename);
   for (int axis = 0; axis < 2; ++axis)
     for (int r = 0; r < rows; ++r)
       for (int c = 0; c < cols; ++c)
         std::fprintf(f, c + 1 < cols ? "%.5g " : "%.5g\n", xy[2 * ((size_t)r * cols + c) + axis] + 1);
-  const bool ok = std::fclose(f) == 0;
-  if (!ok) {
-    ilcc::set_global_error(std::string("cannot write ") + filename);
-    return ILCC_IO_ERROR;
-  }
+  if (std::fclose(f) != 0) return ilcc::fail(ILCC_IO_ERROR, std::string("cannot write ") + filename);
   return ILCC_OK;
 }

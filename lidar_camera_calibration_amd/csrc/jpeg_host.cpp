@@ -10,15 +10,14 @@
 #include <vector>
 
 #include "bag_frame.h"
+#include "host_util.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
 #include "ilcc_ingest.h"
 #include "ilcc_jpeg.h"
 #include "jpeg_entropy.h"
 
-namespace ilcc {
-void set_global_error(const std::string& s);   // ilcc_api.cpp
-}
+using namespace ilcc;
 
 namespace {
 
@@ -26,36 +25,12 @@ constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
 constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 
 // the refusals of jpeg_entropy.cpp, which knows nothing of the library, arrive in ilcc_last_error
-const bool g_sink_set = (ilcc::jpeg_error_sink = [](const char* text) { ilcc::set_global_error(text); }, true);
-
-int32_t fail(int32_t code, const std::string& what) {
-  ilcc::set_global_error(what);
-  return code;
-}
-
-int32_t hip_fail(hipError_t e) { return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e)); }
-
-uint64_t rounded(uint64_t bytes) { return (bytes + 255u) & ~(uint64_t)255u; }
+const bool g_sink_set = (jpeg_error_sink = [](const char* text) { set_global_error(text); }, true);
 
 int bytes_per_pixel(const ilcc_jpeg_info& I) { return I.n_components == 1 ? 1 : 3; }
 
-struct DeviceBuffer {
-  void* p = nullptr;
-  ~DeviceBuffer() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // where the parts of a decode lie behind `pixel_bytes` of pixels
-struct DecodeLayout {
-  uint64_t coef_at, scratch_at, scratch_bytes, total;
-  DecodeLayout(const ilcc_jpeg_info& I, uint64_t pixel_bytes) {
-    coef_at = rounded(pixel_bytes);
-    scratch_at = coef_at + rounded(I.coef_count * sizeof(int16_t));
-    scratch_bytes = ilcc_jpeg_scratch_bytes(&I);
-    total = scratch_at + rounded(scratch_bytes);
-  }
-};
+JpegLayout decode_layout(const ilcc_jpeg_info& I, uint64_t pixel_bytes) { return JpegLayout(I, pixel_bytes, ilcc_jpeg_scratch_bytes(&I)); }
 
 // entropy decode on the host, coefficients to d_coef, K13 into d_pixels on `stream`
 int32_t decode_to(const uint8_t* jpg, uint64_t bytes, const ilcc_jpeg_info& I, void* d_pixels, int32_t stride, void* d_coef, void* d_scratch,
@@ -73,13 +48,6 @@ int32_t decode_to(const uint8_t* jpg, uint64_t bytes, const ilcc_jpeg_info& I, v
   return ilcc_jpeg_idct_device(&I, (const int16_t*)d_coef, d_pixels, stride, d_scratch, scratch_bytes, stream);
 }
 
-bool read_u32(const uint8_t* m, uint64_t n, uint64_t* at, uint32_t* v) {
-  if (*at > n || n - *at < 4) return false;
-  std::memcpy(v, m + *at, 4);
-  *at += 4;
-  return true;
-}
-
 bool contains(const uint8_t* text, uint32_t len, const char* word) {
   const size_t w = std::strlen(word);
   for (uint32_t i = 0; i + w <= len; ++i)
@@ -87,24 +55,12 @@ bool contains(const uint8_t* text, uint32_t len, const char* word) {
   return false;
 }
 
-int32_t read_message(const char* bag_path, const char* topic, const char* md5, std::vector<uint8_t>* msg) {
-  uint64_t bytes = 0;
-  const int32_t st = ilcc_bag_first_message(bag_path, topic, md5, nullptr, 0, &bytes);
-  if (st != ILCC_CAPACITY && st != ILCC_OK) return st;
-  try {
-    msg->resize(bytes);
-  } catch (...) {   // no exception crosses the C-ABI
-    return fail(ILCC_IO_ERROR, "out of memory for the bag's message");
-  }
-  return ilcc_bag_first_message(bag_path, topic, md5, msg->data(), bytes, &bytes);
-}
-
 }  // namespace
 
 namespace ilcc {
 
 int32_t bag_frame_read(const char* bag_path, const char* topic, BagFrame* out) {
-  int32_t st = read_message(bag_path, topic, kImageMd5, &out->msg);
+  int32_t st = read_first_message(bag_path, topic, kImageMd5, &out->msg);
   if (st == ILCC_OK) {
     out->compressed = false;
     st = ilcc_image_parse(out->msg.data(), out->msg.size(), &out->L);
@@ -114,7 +70,7 @@ int32_t bag_frame_read(const char* bag_path, const char* topic, BagFrame* out) {
   }
   if (st != ILCC_BAD_ARGUMENT) return st;
   // no sensor_msgs/Image there (or an argument both reads refuse alike): the topic's first CompressedImage
-  st = read_message(bag_path, topic, kCompressedImageMd5, &out->msg);
+  st = read_first_message(bag_path, topic, kCompressedImageMd5, &out->msg);
   if (st != ILCC_OK) return st;
   ilcc_compressed_image_layout C;
   st = ilcc_compressed_image_parse(out->msg.data(), out->msg.size(), &C);
@@ -134,7 +90,7 @@ int32_t bag_frame_read(const char* bag_path, const char* topic, BagFrame* out) {
   L.data_offset = C.data_offset;
   L.data_bytes = C.data_bytes;
   std::memcpy(L.frame_id, C.frame_id, sizeof(L.frame_id));
-  out->device_bytes = DecodeLayout(out->jpeg, (uint64_t)L.step * L.height).total;
+  out->device_bytes = decode_layout(out->jpeg, (uint64_t)L.step * L.height).total;
   return ILCC_OK;
 }
 
@@ -144,7 +100,7 @@ int32_t bag_frame_to_device(const BagFrame& f, void* d_mem) {
     const hipError_t e = hipMemcpy(d_mem, data, (uint64_t)f.L.step * f.L.height, hipMemcpyHostToDevice);
     return e == hipSuccess ? ILCC_OK : hip_fail(e);
   }
-  const DecodeLayout D(f.jpeg, (uint64_t)f.L.step * f.L.height);
+  const JpegLayout D = decode_layout(f.jpeg, (uint64_t)f.L.step * f.L.height);
   uint8_t* base = (uint8_t*)d_mem;
   return decode_to(data, f.L.data_bytes, f.jpeg, base, (int32_t)f.L.step, base + D.coef_at, base + D.scratch_at, D.scratch_bytes, nullptr);
 }
@@ -167,7 +123,7 @@ int32_t ilcc_jpeg_decode_device(const uint8_t* jpg, uint64_t bytes, void* d_dst,
   if ((int64_t)dst_stride < (int64_t)bpp * I.width) return fail(ILCC_BAD_ARGUMENT, "ilcc_jpeg_decode_device: dst_stride is shorter than a row");
   if (cap_bytes < (uint64_t)(I.height - 1) * (uint64_t)dst_stride + (uint64_t)bpp * (uint64_t)I.width)
     return fail(ILCC_CAPACITY, "image larger than the buffer");
-  const DecodeLayout D(I, 0);
+  const JpegLayout D = decode_layout(I, 0);
   DeviceBuffer buf;
   const hipError_t e = hipMalloc(&buf.p, D.total);
   if (e != hipSuccess) return hip_fail(e);
@@ -195,15 +151,13 @@ int32_t ilcc_jpeg_find_chessboard(int32_t device, const char* jpg_path, const il
   if (st != ILCC_OK) return st;
   if (camera && (camera->width != I.width || camera->height != I.height))
     return fail(ILCC_BAD_ARGUMENT, "the camera's width / height differ from the image's");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-    return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
+  st = select_device(device);
+  if (st != ILCC_OK) return st;
   // ONE device buffer: [ the file's pixels | coefficients | K13's scratch | mono8 ]
   const int32_t step = bytes_per_pixel(I) * I.width;
-  const DecodeLayout D(I, (uint64_t)step * (uint64_t)I.height);
+  const JpegLayout D = decode_layout(I, (uint64_t)step * (uint64_t)I.height);
   DeviceBuffer buf;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&buf.p, D.total + (uint64_t)I.width * (uint64_t)I.height);
+  const hipError_t e = hipMalloc(&buf.p, D.total + (uint64_t)I.width * (uint64_t)I.height);
   if (e != hipSuccess) return hip_fail(e);
   uint8_t* base = (uint8_t*)buf.p;
   uint8_t* mono8 = base + D.total;
@@ -221,11 +175,7 @@ int32_t ilcc_compressed_image_parse(const uint8_t* m, uint64_t n, ilcc_compresse
   const char* truncated = "CompressedImage message truncated";
   uint64_t at = 0;
   uint32_t len = 0;
-  if (!read_u32(m, n, &at, &out->seq) || !read_u32(m, n, &at, &out->stamp_sec) || !read_u32(m, n, &at, &out->stamp_nsec) ||
-      !read_u32(m, n, &at, &len) || len > n - at)
-    return fail(ILCC_BAD_ARGUMENT, truncated);
-  std::memcpy(out->frame_id, m + at, len < sizeof(out->frame_id) - 1 ? len : sizeof(out->frame_id) - 1);
-  at += len;
+  if (!read_header(m, n, &at, &out->seq, &out->stamp_sec, &out->stamp_nsec, out->frame_id)) return fail(ILCC_BAD_ARGUMENT, truncated);
   if (!read_u32(m, n, &at, &len) || len > n - at) return fail(ILCC_BAD_ARGUMENT, truncated);
   const uint8_t* format = m + at;
   const uint32_t format_len = len;

@@ -10,41 +10,16 @@
 #include <string>
 
 #include "bag_frame.h"
+#include "host_util.h"
 #include "ilcc_hip.h"
 #include "ilcc_jpeg_write.h"
 
-namespace ilcc {
-void set_global_error(const std::string& s);   // ilcc_api.cpp
-}
+using namespace ilcc;
 
 namespace {
 
-int32_t fail(int32_t code, const std::string& what) {
-  ilcc::set_global_error(what);
-  return code;
-}
-
-int32_t hip_fail(hipError_t e) { return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e)); }
-
-uint64_t rounded(uint64_t bytes) { return (bytes + 255u) & ~(uint64_t)255u; }
-
-struct DeviceBuffer {
-  void* p = nullptr;
-  ~DeviceBuffer() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // where the parts of an encode lie behind `pixel_bytes` of pixels
-struct EncodeLayout {
-  uint64_t coef_at, scratch_at, scratch_bytes, total;
-  EncodeLayout(const ilcc_jpeg_info& I, uint64_t pixel_bytes) {
-    coef_at = rounded(pixel_bytes);
-    scratch_at = coef_at + rounded(I.coef_count * sizeof(int16_t));
-    scratch_bytes = ilcc_jpeg_fdct_scratch_bytes(&I);
-    total = scratch_at + rounded(scratch_bytes);
-  }
-};
+JpegLayout encode_layout(const ilcc_jpeg_info& I, uint64_t pixel_bytes) { return JpegLayout(I, pixel_bytes, ilcc_jpeg_fdct_scratch_bytes(&I)); }
 
 // K14 on `stream`, the coefficients to the host, the file into [out, out + cap)
 int32_t encode_to(const ilcc_jpeg_info& I, const void* d_src, int32_t stride, int32_t encoding, void* d_coef, void* d_scratch,
@@ -87,16 +62,11 @@ int32_t encode_to_file(const ilcc_jpeg_info& I, const void* d_src, int32_t strid
 
 int32_t components_of(int32_t encoding) { return encoding == ILCC_ENCODING_MONO8 ? 1 : encoding == ILCC_ENCODING_BGR8 ? 3 : 0; }
 
-bool have_device(int32_t device) {
-  int count = 0;
-  return hipGetDeviceCount(&count) == hipSuccess && device >= 0 && device < count;
-}
-
 // device bytes behind a mono8 image of this size for its coefficients (K14 needs no scratch for one component); 0 for a
 // size the writer refuses
 uint64_t mono8_encode_bytes(int32_t width, int32_t height) {
   ilcc_jpeg_info I;
-  return ilcc_jpeg_write_info(width, height, 1, 1, 1, 95, 0, &I) == ILCC_OK ? EncodeLayout(I, 0).total : 0;
+  return ilcc_jpeg_write_info(width, height, 1, 1, 1, 95, 0, &I) == ILCC_OK ? encode_layout(I, 0).total : 0;
 }
 
 }  // namespace
@@ -114,7 +84,7 @@ int32_t ilcc_jpeg_encode_device(const void* d_src, int32_t src_stride, int32_t w
   int32_t st = ilcc_jpeg_write_info(width, height, nc, sampling_h, sampling_v, quality, restart_interval, &I);
   if (st != ILCC_OK) return st;
   if ((int64_t)src_stride < (int64_t)(nc == 1 ? 1 : 3) * width) return fail(ILCC_BAD_ARGUMENT, "ilcc_jpeg_encode_device: src_stride is shorter than a row");
-  const EncodeLayout E(I, 0);
+  const JpegLayout E = encode_layout(I, 0);
   DeviceBuffer buf;
   const hipError_t e = hipMalloc(&buf.p, E.total);
   if (e != hipSuccess) return hip_fail(e);
@@ -130,17 +100,17 @@ int32_t ilcc_jpeg_write_file(int32_t device, const char* path, const uint8_t* pi
   const int32_t nc = components_of(encoding);
   if (!nc) return fail(ILCC_BAD_ARGUMENT, "ilcc_jpeg_write_file: mono8 or bgr8 pixels only");
   ilcc_jpeg_info I;
-  const int32_t st = ilcc_jpeg_write_info(width, height, nc, 2, 2, quality, 0, &I);   // 4:2:0: libjpeg's default
+  int32_t st = ilcc_jpeg_write_info(width, height, nc, 2, 2, quality, 0, &I);   // 4:2:0: libjpeg's default
   if (st != ILCC_OK) return st;
   const uint64_t row = (uint64_t)(nc == 1 ? 1 : 3) * (uint64_t)width;
   if ((uint64_t)(stride < 0 ? 0 : stride) < row) return fail(ILCC_BAD_ARGUMENT, "ilcc_jpeg_write_file: stride is shorter than a row");
-  if (!have_device(device)) return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
+  st = select_device(device);
+  if (st != ILCC_OK) return st;
   // ONE device buffer: [ pixels | coefficients | K14's scratch ]; the last row's padding is not read
   const uint64_t pixel_bytes = (uint64_t)(height - 1) * (uint64_t)stride + row;
-  const EncodeLayout E(I, pixel_bytes);
+  const JpegLayout E = encode_layout(I, pixel_bytes);
   DeviceBuffer buf;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&buf.p, E.total);
+  hipError_t e = hipMalloc(&buf.p, E.total);
   if (e == hipSuccess) e = hipMemcpy(buf.p, pixels, pixel_bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) return hip_fail(e);
   uint8_t* base = (uint8_t*)buf.p;
@@ -150,15 +120,15 @@ int32_t ilcc_jpeg_write_file(int32_t device, const char* path, const uint8_t* pi
 int32_t ilcc_bag_save_jpeg(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
                            const char* jpg_path, int32_t quality) {
   if (!jpg_path) return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_save_jpeg: null argument");
-  ilcc::DeviceImage img;
+  DeviceImage img;
   int32_t w = 0, h = 0;
-  int32_t st = ilcc::bag_image_to_device(device, bag_path, topic, camera, ~0ull, mono8_encode_bytes, &w, &h, &img);
+  int32_t st = bag_image_to_device(device, bag_path, topic, camera, ~0ull, mono8_encode_bytes, &w, &h, &img);
   if (st != ILCC_OK) return st;
   ilcc_jpeg_info I;
   st = ilcc_jpeg_write_info(w, h, 1, 1, 1, quality, 0, &I);
   if (st != ILCC_OK) return st;
   if (!img.extra) return fail(ILCC_BAD_ARGUMENT, "ilcc_bag_save_jpeg: image larger than 65535 pixels a side");
-  const EncodeLayout E(I, 0);
+  const JpegLayout E = encode_layout(I, 0);
   return encode_to_file(I, img.mono8, w, ILCC_ENCODING_MONO8, img.extra + E.coef_at, img.extra + E.scratch_at, E.scratch_bytes, jpg_path);
 }
 

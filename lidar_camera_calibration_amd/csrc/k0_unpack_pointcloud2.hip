@@ -13,6 +13,7 @@
 // messages is one launch (height := messages * height), >= 3.6k workgroups at 128 frames.
 #include <hip/hip_runtime.h>
 
+#include "host_util.h"
 #include "ilcc_ingest.h"
 #include "ilcc_internal.h"
 
@@ -76,21 +77,14 @@ __global__ __launch_bounds__(kUnpackThreads) void k0_unpack_tiled(UnpackArgs a) 
   }
 }
 
-void set_global_error(const std::string& s);
-
 }  // namespace ilcc
 
 extern "C" int32_t ilcc_pointcloud2_unpack_device(const void* d_data, const ilcc_pointcloud2_layout* L, void* d_xyzi,
                                                   void* hip_stream) {
   using namespace ilcc;
-  if (!L || (!d_data && L->data_bytes) || !d_xyzi) {
-    set_global_error("null argument");
-    return ILCC_BAD_ARGUMENT;
-  }
-  if (L->is_bigendian) {   // pcl::fromROSMsg memcpy's fields: it is wrong on such data too; refuse instead
-    set_global_error("big-endian PointCloud2 is not supported");
-    return ILCC_BAD_ARGUMENT;
-  }
+  if (!L || (!d_data && L->data_bytes) || !d_xyzi) return fail(ILCC_BAD_ARGUMENT, "null argument");
+  // pcl::fromROSMsg memcpy's fields: it is wrong on such data too; refuse instead
+  if (L->is_bigendian) return fail(ILCC_BAD_ARGUMENT, "big-endian PointCloud2 is not supported");
   UnpackArgs a;
   a.src = (const uint8_t*)d_data;
   a.dst = (float4*)d_xyzi;
@@ -120,62 +114,34 @@ extern "C" int32_t ilcc_pointcloud2_unpack_device(const void* d_data, const ilcc
     hipLaunchKernelGGL(k0_unpack_generic, dim3(blocks), dim3(kUnpackThreads), 0, s, a);
   }
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_global_error(std::string("k0 launch: ") + hipGetErrorString(e));
-    return ILCC_HIP_ERROR;
-  }
+  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("k0 launch: ") + hipGetErrorString(e));
   return ILCC_OK;
 }
 
 extern "C" int32_t ilcc_bag_first_cloud(int32_t device, const char* bag_path, const char* topic, float* xyzi,
                                         uint32_t cap_points, uint32_t* n_points) {
   using namespace ilcc;
-  if (!n_points || (!xyzi && cap_points)) {
-    set_global_error("null argument");
-    return ILCC_BAD_ARGUMENT;
-  }
+  if (!n_points || (!xyzi && cap_points)) return fail(ILCC_BAD_ARGUMENT, "null argument");
   *n_points = 0;
-  uint64_t bytes = 0;
-  int32_t st = ilcc_bag_first_message(bag_path, topic, nullptr, nullptr, 0, &bytes);
-  if (st != ILCC_CAPACITY && st != ILCC_OK) return st;
   std::vector<uint8_t> msg;
-  try {
-    msg.resize(bytes);
-  } catch (...) {   // no exception crosses the C-ABI
-    set_global_error("out of memory for the bag's message");
-    return ILCC_IO_ERROR;
-  }
-  st = ilcc_bag_first_message(bag_path, topic, nullptr, msg.data(), bytes, &bytes);
+  int32_t st = read_first_message(bag_path, topic, nullptr, &msg);
   if (st != ILCC_OK) return st;
   ilcc_pointcloud2_layout L;
-  st = ilcc_pointcloud2_parse(msg.data(), bytes, &L);
+  st = ilcc_pointcloud2_parse(msg.data(), msg.size(), &L);
   if (st != ILCC_OK) return st;
   const uint64_t pts = (uint64_t)L.height * L.width;
   *n_points = (uint32_t)pts;
-  if (pts > cap_points) {
-    set_global_error("cloud larger than the buffer");
-    return ILCC_CAPACITY;
-  }
+  if (pts > cap_points) return fail(ILCC_CAPACITY, "cloud larger than the buffer");
   if (pts == 0) return ILCC_OK;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-    set_global_error("no HIP device: libilcc_hip has no CPU fallback");
-    return ILCC_HIP_ERROR;
-  }
-  void *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&d_in, L.data_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_out, pts * 16);
-  if (e == hipSuccess) e = hipMemcpy(d_in, msg.data() + L.data_offset, L.data_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    st = ilcc_pointcloud2_unpack_device(d_in, &L, d_out, nullptr);
-    if (st == ILCC_OK) e = hipMemcpy(xyzi, d_out, pts * 16, hipMemcpyDeviceToHost);
-  }
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (e != hipSuccess) {
-    set_global_error(std::string("hip: ") + hipGetErrorString(e));
-    return ILCC_HIP_ERROR;
-  }
-  return st;
+  st = select_device(device);
+  if (st != ILCC_OK) return st;
+  DeviceBuffer in, out;
+  hipError_t e = hipMalloc(&in.p, L.data_bytes);
+  if (e == hipSuccess) e = hipMalloc(&out.p, pts * 16);
+  if (e == hipSuccess) e = hipMemcpy(in.p, msg.data() + L.data_offset, L.data_bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_fail(e);
+  st = ilcc_pointcloud2_unpack_device(in.p, &L, out.p, nullptr);
+  if (st != ILCC_OK) return st;
+  e = hipMemcpy(xyzi, out.p, pts * 16, hipMemcpyDeviceToHost);
+  return e == hipSuccess ? ILCC_OK : hip_fail(e);
 }

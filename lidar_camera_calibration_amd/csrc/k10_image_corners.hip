@@ -23,12 +23,11 @@
 #include <string>
 #include <vector>
 
+#include "host_util.h"
 #include "ilcc_image_corners.h"
 #include "ilcc_internal.h"
 
 namespace ilcc {
-
-void set_global_error(const std::string& s);
 
 namespace {
 
@@ -464,10 +463,7 @@ int32_t image_corners(const void* d_image, int32_t w, int32_t h, int32_t stride,
   }
   *n_corners = 0;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
-    set_global_error("no HIP device: libilcc_hip has no CPU fallback");
-    return ILCC_HIP_ERROR;
-  }
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return no_device();
   hipStream_t s = (hipStream_t)stream;
   hipError_t e;
   {

@@ -27,6 +27,7 @@
 #include <cmath>
 #include <string>
 
+#include "host_util.h"
 #include "ilcc_camera_image.h"
 #include "ilcc_internal.h"
 
@@ -261,8 +262,6 @@ __global__ __launch_bounds__(kImgTx* kImgTy) void k11_undistort_map(LensArgs len
   iu[at] = cu;
   iv[at] = cv;
 }
-
-void set_global_error(const std::string& s);
 
 namespace {
 

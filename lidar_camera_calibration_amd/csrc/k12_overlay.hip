@@ -16,12 +16,11 @@
 
 #include <string>
 
+#include "host_util.h"
 #include "ilcc_internal.h"
 #include "ilcc_project.h"
 
 namespace ilcc {
-
-void set_global_error(const std::string& s);
 
 constexpr int kDrawThreads = 256;
 constexpr int kStampMax = 64;
@@ -97,20 +96,20 @@ namespace {
 // (2 * 2^15 + 2^15) >> 16 = 1 -- row y: x - 1 .. x + 1, rows y -+ 1: x only
 constexpr int8_t kReferenceStamp[10] = {0, -1, -1, 0, 0, 0, 1, 0, 0, 1};
 
-int32_t refuse(const std::string& what) {
-  set_global_error("ilcc_draw_hits_device: " + what);
-  return ILCC_BAD_ARGUMENT;
-}
+int32_t refuse(const std::string& what) { return fail(ILCC_BAD_ARGUMENT, "ilcc_draw_hits_device: " + what); }
 
 }  // namespace
+}  // namespace ilcc
 
-uint64_t draw_hits_scratch_bytes(int32_t width, int32_t height) {
+extern "C" uint64_t ilcc_draw_hits_scratch_bytes(int32_t width, int32_t height) {
   if (width < 1 || height < 1) return 0;
   return 4ull * (uint64_t)width * (uint64_t)height;
 }
 
-int32_t draw_hits(void* d_image_bgr, int32_t width, int32_t height, int32_t stride, const void* d_hits, uint32_t n_hits,
-                  const int8_t* stamp_xy, int32_t n_stamp, void* d_scratch, hipStream_t s) {
+extern "C" int32_t ilcc_draw_hits_device(void* d_image_bgr, int32_t width, int32_t height, int32_t stride, const void* d_hits,
+                                         uint32_t n_hits, const int8_t* stamp_xy, int32_t n_stamp, void* d_scratch,
+                                         void* hip_stream) {
+  using namespace ilcc;
   if (!d_image_bgr || !d_scratch || (n_hits && !d_hits)) return refuse("null pointer");
   if (width < 1 || height < 1 || width > 65536 || height > 65536) return refuse("width and height must be 1 .. 65536");
   if ((int64_t)stride < 3 * (int64_t)width) return refuse("stride is shorter than a row");
@@ -137,23 +136,11 @@ int32_t draw_hits(void* d_image_bgr, int32_t width, int32_t height, int32_t stri
   const uint64_t hit_blocks = ((uint64_t)n_hits + kDrawThreads - 1) / kDrawThreads;
   const dim3 clear_grid((uint32_t)(clear_blocks < kDrawBlocksMax ? clear_blocks : kDrawBlocksMax));
   const dim3 hit_grid((uint32_t)(hit_blocks < kDrawBlocksMax ? hit_blocks : kDrawBlocksMax));
+  hipStream_t s = (hipStream_t)hip_stream;
   hipLaunchKernelGGL(k12_clear, clear_grid, dim3(kDrawThreads), 0, s, a.owner, words);
   hipLaunchKernelGGL(k12_walk<false>, hit_grid, dim3(kDrawThreads), 0, s, a);
   hipLaunchKernelGGL(k12_walk<true>, hit_grid, dim3(kDrawThreads), 0, s, a);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_global_error(std::string("k12 launch: ") + hipGetErrorString(e));
-    return ILCC_HIP_ERROR;
-  }
+  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("k12 launch: ") + hipGetErrorString(e));
   return ILCC_OK;
-}
-
-}  // namespace ilcc
-
-extern "C" uint64_t ilcc_draw_hits_scratch_bytes(int32_t width, int32_t height) { return ilcc::draw_hits_scratch_bytes(width, height); }
-
-extern "C" int32_t ilcc_draw_hits_device(void* d_image_bgr, int32_t width, int32_t height, int32_t stride, const void* d_hits,
-                                         uint32_t n_hits, const int8_t* stamp_xy, int32_t n_stamp, void* d_scratch,
-                                         void* hip_stream) {
-  return ilcc::draw_hits(d_image_bgr, width, height, stride, d_hits, n_hits, stamp_xy, n_stamp, d_scratch, (hipStream_t)hip_stream);
 }

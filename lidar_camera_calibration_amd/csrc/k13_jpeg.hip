@@ -27,14 +27,13 @@
 #include <cstring>
 #include <string>
 
+#include "host_util.h"
 #include "ilcc_hip.h"
 #include "ilcc_jpeg.h"
 #include "jpeg_block8.h"
 #include "jpeg_entropy.h"
 
 namespace ilcc {
-
-void set_global_error(const std::string& s);   // ilcc_api.cpp
 
 constexpr int kIdctThreads = 256;                 // 32 blocks of 8 lanes
 constexpr int kBlocksPerGroup = kIdctThreads / 8;
@@ -223,9 +222,8 @@ int32_t refuse(const std::string& what) {
   return ILCC_BAD_ARGUMENT;
 }
 
-uint64_t rounded(uint64_t bytes) { return (bytes + 255u) & ~(uint64_t)255u; }   // every plane starts on a 256-byte boundary
-
-uint64_t plane_bytes(const ilcc_jpeg_component& c) { return rounded(64ull * (uint64_t)c.blocks_w * (uint64_t)c.blocks_h); }
+// every plane starts on a 256-byte boundary
+uint64_t plane_bytes(const ilcc_jpeg_component& c) { return align256(64ull * (uint64_t)c.blocks_w * (uint64_t)c.blocks_h); }
 
 void launch_idct(const ilcc_jpeg_info& I, int c, const int16_t* d_coef, uint8_t* dst, int64_t stride, int32_t clip_w, int32_t clip_h,
                  hipStream_t s) {

@@ -17,12 +17,11 @@
 #include <mutex>
 #include <string>
 
+#include "host_util.h"
 #include "ilcc_internal.h"
 #include "ilcc_project.h"
 
 namespace ilcc {
-
-void set_global_error(const std::string& s);
 
 constexpr int kProjThreads = 256;
 constexpr int kProjChunk = 4096;
@@ -30,7 +29,7 @@ constexpr int kProjChunk = 4096;
 struct ProjArgs {
   const float4* pts;
   uint32_t n;
-  ilcc_camera_model cam;
+  ilcc_projection cam;
   double dis, lo, hi;
   const uint8_t* image;
   uint32_t image_step;
@@ -41,7 +40,7 @@ struct ProjArgs {
 };
 
 // spaceToPlane (:135-155); px, py = the (int) truncation the callers apply
-__device__ __forceinline__ bool space_to_plane(const ilcc_camera_model& c, const float4 q, double dis, int32_t& px, int32_t& py) {
+__device__ __forceinline__ bool space_to_plane(const ilcc_projection& c, const float4 q, double dis, int32_t& px, int32_t& py) {
   const double X = (double)q.x, Y = (double)q.y, Z = (double)q.z;
   const double pc0 = c.R[0] * X + c.R[1] * Y + c.R[2] * Z + c.t[0];
   const double pc1 = c.R[3] * X + c.R[4] * Y + c.R[5] * Z + c.t[1];
@@ -158,23 +157,15 @@ std::mutex g_mu;
 Scratch g_scratch[16];
 }  // namespace
 
-static int32_t run_project(bool sample, const void* d_xyzi, uint32_t n, const ilcc_camera_model* cam, double dis, double lo,
+static int32_t run_project(bool sample, const void* d_xyzi, uint32_t n, const ilcc_projection* cam, double dis, double lo,
                            double hi, const void* image, uint32_t step, void* out, uint32_t* n_out, void* stream) {
-  if (!cam || !n_out || (n && (!d_xyzi || !out)) || (sample && !image) || cam->width <= 0 || cam->height <= 0) {
-    set_global_error("bad argument");
-    return ILCC_BAD_ARGUMENT;
-  }
-  if (sample && step < (uint32_t)cam->width * 3u) {
-    set_global_error("image_step smaller than a BGR row");
-    return ILCC_BAD_ARGUMENT;
-  }
+  if (!cam || !n_out || (n && (!d_xyzi || !out)) || (sample && !image) || cam->width <= 0 || cam->height <= 0)
+    return fail(ILCC_BAD_ARGUMENT, "bad argument");
+  if (sample && step < (uint32_t)cam->width * 3u) return fail(ILCC_BAD_ARGUMENT, "image_step smaller than a BGR row");
   *n_out = 0;
   if (n == 0) return ILCC_OK;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
-    set_global_error("no HIP device: libilcc_hip has no CPU fallback");
-    return ILCC_HIP_ERROR;
-  }
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return no_device();
   std::lock_guard<std::mutex> lock(g_mu);
   Scratch& sc = g_scratch[dev];
   const uint32_t chunks = (n + kProjChunk - 1) / kProjChunk;
@@ -188,10 +179,7 @@ static int32_t run_project(bool sample, const void* d_xyzi, uint32_t n, const il
     if (e == hipSuccess) sc.cap = cap;
   }
   if (e == hipSuccess && !sc.total) e = hipHostMalloc((void**)&sc.total, sizeof(uint32_t));
-  if (e != hipSuccess) {
-    set_global_error(std::string("hip: ") + hipGetErrorString(e));
-    return ILCC_HIP_ERROR;
-  }
+  if (e != hipSuccess) return hip_fail(e);
   ProjArgs a;
   a.pts = (const float4*)d_xyzi;
   a.n = n;
@@ -211,39 +199,21 @@ static int32_t run_project(bool sample, const void* d_xyzi, uint32_t n, const il
   else hipLaunchKernelGGL(k8_scatter<false>, dim3(chunks), dim3(kProjThreads), 0, s, a);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    set_global_error(std::string("k8: ") + hipGetErrorString(e));
-    return ILCC_HIP_ERROR;
-  }
+  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("k8: ") + hipGetErrorString(e));
   *n_out = *sc.total;
   return ILCC_OK;
 }
 
-int32_t project_intensity(const void* d_xyzi, uint32_t n_points, const double R[9], const double t[3], double fx, double cx, double fy,
-                          double cy, int32_t width, int32_t height, double distance_valid, double inten_low, double inten_high,
-                          void* d_hits, uint32_t* n_hits, hipStream_t s) {
-  ilcc_camera_model cam;
-  for (int k = 0; k < 9; ++k) cam.R[k] = R[k];
-  for (int k = 0; k < 3; ++k) cam.t[k] = t[k];
-  cam.fx = fx;
-  cam.cx = cx;
-  cam.fy = fy;
-  cam.cy = cy;
-  cam.width = width;
-  cam.height = height;
-  return run_project(false, d_xyzi, n_points, &cam, distance_valid, inten_low, inten_high, nullptr, 0, d_hits, n_hits, s);
-}
-
 }  // namespace ilcc
 
-extern "C" int32_t ilcc_project_intensity_device(const void* d_xyzi, uint32_t n_points, const ilcc_camera_model* cam,
+extern "C" int32_t ilcc_project_intensity_device(const void* d_xyzi, uint32_t n_points, const ilcc_projection* cam,
                                                  double distance_valid, double inten_low, double inten_high, void* d_hits,
                                                  uint32_t* n_hits, void* hip_stream) {
   return ilcc::run_project(false, d_xyzi, n_points, cam, distance_valid, inten_low, inten_high, nullptr, 0, d_hits, n_hits,
                            hip_stream);
 }
 
-extern "C" int32_t ilcc_colourise_device(const void* d_xyzi, uint32_t n_points, const ilcc_camera_model* cam,
+extern "C" int32_t ilcc_colourise_device(const void* d_xyzi, uint32_t n_points, const ilcc_projection* cam,
                                          double distance_valid, const void* d_image_bgr, uint32_t image_step, void* d_xyzrgb,
                                          uint32_t* n_out, void* hip_stream) {
   return ilcc::run_project(true, d_xyzi, n_points, cam, distance_valid, 0.0, 1.0, d_image_bgr, image_step, d_xyzrgb, n_out,

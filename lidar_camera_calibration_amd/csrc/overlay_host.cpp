@@ -1,7 +1,6 @@
 // Host side of include/ilcc_overlay.h: pcd2image (/root/reference/ilcc2/test/pcd2image.cpp:33-104) from bags -- the first
 // frame of the camera topic (csrc/bag_frame.h) and the first PointCloud2, H2D, K11c -> K0 -> K8 -> K12 on the default stream, D2H -- and the PPM writer that
-// stands in for cv::imshow.  This file includes the lens' header (ilcc_camera_image.h through ilcc_overlay.h), so K8 and
-// K12, whose header defines another ilcc_camera_model, are reached through ilcc_internal.h.
+// stands in for cv::imshow.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -10,45 +9,13 @@
 #include <vector>
 
 #include "bag_frame.h"
+#include "host_util.h"
 #include "ilcc_hip.h"
 #include "ilcc_ingest.h"
-#include "ilcc_internal.h"
 #include "ilcc_overlay.h"
+#include "ilcc_project.h"
 
-namespace ilcc {
-void set_global_error(const std::string& s);   // ilcc_api.cpp
-}
-
-namespace {
-
-int32_t fail(int32_t code, const std::string& what) {
-  ilcc::set_global_error(what);
-  return code;
-}
-
-// the first message on `topic` whose connection carries md5 (nullptr: PointCloud2's)
-int32_t first_message(const char* bag_path, const char* topic, const char* md5, std::vector<uint8_t>* msg) {
-  uint64_t bytes = 0;
-  int32_t st = ilcc_bag_first_message(bag_path, topic, md5, nullptr, 0, &bytes);
-  if (st != ILCC_CAPACITY && st != ILCC_OK) return st;
-  try {
-    msg->resize(bytes);
-  } catch (...) {   // no exception crosses the C-ABI
-    return fail(ILCC_IO_ERROR, "out of memory for the bag's message");
-  }
-  return ilcc_bag_first_message(bag_path, topic, md5, msg->data(), bytes, &bytes);
-}
-
-struct DeviceBuffer {
-  void* p = nullptr;
-  ~DeviceBuffer() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-uint64_t rounded(uint64_t bytes) { return (bytes + 255u) & ~(uint64_t)255u; }   // every part starts on a 256-byte boundary
-
-}  // namespace
+using namespace ilcc;
 
 extern "C" {
 
@@ -60,8 +27,8 @@ int32_t ilcc_bag_pcd2image(int32_t device, const char* image_bag, const char* im
   *width = *height = 0;
   *n_drawn = 0;
   std::vector<uint8_t> cloud_msg;
-  ilcc::BagFrame frame;
-  int32_t st = ilcc::bag_frame_read(image_bag, image_topic, &frame);
+  BagFrame frame;
+  int32_t st = bag_frame_read(image_bag, image_topic, &frame);
   if (st != ILCC_OK) return st;
   const ilcc_image_layout& I = frame.L;
   if (I.width > 65536u || I.height > 65536u) return fail(ILCC_BAD_ARGUMENT, "image larger than 65536 pixels a side");
@@ -72,50 +39,48 @@ int32_t ilcc_bag_pcd2image(int32_t device, const char* image_bag, const char* im
   const uint64_t bgr_bytes = 3ull * I.width * I.height;
   if (bgr_bytes > cap_bytes) return fail(ILCC_CAPACITY, "image larger than the buffer");
   if (camera->width != w || camera->height != h) return fail(ILCC_BAD_ARGUMENT, "the camera's width / height differ from the image's");
-  st = first_message(lidar_bag, lidar_topic, nullptr, &cloud_msg);
+  st = read_first_message(lidar_bag, lidar_topic, nullptr, &cloud_msg);
   if (st != ILCC_OK) return st;
   ilcc_pointcloud2_layout P;
   st = ilcc_pointcloud2_parse(cloud_msg.data(), cloud_msg.size(), &P);
   if (st != ILCC_OK) return st;
   const uint64_t points = (uint64_t)P.height * P.width;
   if (points > 0xFFFFFFFEull) return fail(ILCC_BAD_ARGUMENT, "cloud of more than 2^32 - 2 points");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-    return fail(ILCC_HIP_ERROR, "no HIP device: libilcc_hip has no CPU fallback");
+  st = select_device(device);
+  if (st != ILCC_OK) return st;
 
   // ONE device buffer: [ the frame as the bag carries it | B,G,R image | cloud data[] | XYZI | hits | K12's owner words ]
-  const uint64_t bgr_at = rounded(frame.device_bytes);
-  const uint64_t cloud_at = bgr_at + rounded(bgr_bytes);
-  const uint64_t xyzi_at = cloud_at + rounded(P.data_bytes);
-  const uint64_t hits_at = xyzi_at + rounded(16 * points);
-  const uint64_t owner_at = hits_at + rounded(16 * points);
-  const uint64_t total = owner_at + ilcc::draw_hits_scratch_bytes(w, h);
+  const uint64_t bgr_at = align256(frame.device_bytes);
+  const uint64_t cloud_at = bgr_at + align256(bgr_bytes);
+  const uint64_t xyzi_at = cloud_at + align256(P.data_bytes);
+  const uint64_t hits_at = xyzi_at + align256(16 * points);
+  const uint64_t owner_at = hits_at + align256(16 * points);
+  const uint64_t total = owner_at + ilcc_draw_hits_scratch_bytes(w, h);
   DeviceBuffer buf;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&buf.p, total);
-  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
+  hipError_t e = hipMalloc(&buf.p, total);
+  if (e != hipSuccess) return hip_fail(e);
   uint8_t* base = (uint8_t*)buf.p;
-  st = ilcc::bag_frame_to_device(frame, base);
+  st = bag_frame_to_device(frame, base);
   if (st != ILCC_OK) return st;
   st = ilcc_image_to_bgr8_device(base, w, h, (int32_t)I.step, (int32_t)I.encoding, camera, base + bgr_at, 3 * w, nullptr);
   if (st != ILCC_OK) return st;
   if (points) {
     e = hipMemcpy(base + cloud_at, cloud_msg.data() + P.data_offset, P.data_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(e);
     st = ilcc_pointcloud2_unpack_device(base + cloud_at, &P, base + xyzi_at, nullptr);
     if (st != ILCC_OK) return st;
-    const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-    const double t[3] = {T[3], T[7], T[11]};
+    const ilcc_projection proj = {{T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]}, {T[3], T[7], T[11]},
+                                  camera->fx, camera->cx, camera->fy, camera->cy, w, h};
     uint32_t hits = 0;
-    st = ilcc::project_intensity(base + xyzi_at, (uint32_t)points, R, t, camera->fx, camera->cx, camera->fy, camera->cy, w, h,
-                                 distance_valid, 0.0, 60.0, base + hits_at, &hits, nullptr);   // pcd2image.cpp:53-54
+    st = ilcc_project_intensity_device(base + xyzi_at, (uint32_t)points, &proj, distance_valid, 0.0, 60.0, base + hits_at, &hits,
+                                       nullptr);   // pcd2image.cpp:53-54
     if (st != ILCC_OK) return st;
-    st = ilcc::draw_hits(base + bgr_at, w, h, 3 * w, base + hits_at, hits, nullptr, 0, base + owner_at, nullptr);
+    st = ilcc_draw_hits_device(base + bgr_at, w, h, 3 * w, base + hits_at, hits, nullptr, 0, base + owner_at, nullptr);
     if (st != ILCC_OK) return st;
     *n_drawn = hits;
   }
   e = hipMemcpy(bgr_out, base + bgr_at, bgr_bytes, hipMemcpyDeviceToHost);   // waits for the kernels
-  if (e != hipSuccess) return fail(ILCC_HIP_ERROR, std::string("hip: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return hip_fail(e);
   return ILCC_OK;
 }
 

@@ -1,7 +1,8 @@
 """LiDAR points drawn on the undistorted colour image: ctypes mirror of ``include/ilcc_overlay.h`` -- the
 reference's pcd2image node (/root/reference/ilcc2/test/pcd2image.cpp:33-89) from bags, without ROS or OpenCV.
 The stages it chains are in ``camera_image`` (K11c ``to_bgr8``), ``ingest`` (K0) and ``project`` (K8, K12
-``draw_hits_device``).  The camera here is the lens (``camera_image.CameraModel``); the extrinsic is a 4 x 4."""
+``draw_hits_device``).  The camera is the lens (``camera_image.CameraModel``), the extrinsic a 4 x 4; the library
+makes K8's ``project.Projection`` of the two."""
 import ctypes as C
 import os
 

@@ -14,7 +14,7 @@ REFERENCE_STAMP = ((0, -1), (-1, 0), (0, 0), (1, 0), (0, 1))     # cv::circle(..
 HIT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("pad", "u1"), ("index", "<u4")])
 
 
-class CameraModel(C.Structure):
+class Projection(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3),
                 ("fx", C.c_double), ("cx", C.c_double), ("fy", C.c_double), ("cy", C.c_double),
                 ("width", C.c_int32), ("height", C.c_int32)]
@@ -38,7 +38,7 @@ def _lib():
     global _ready
     L = _native.lib()
     if not _ready:
-        cp = C.POINTER(CameraModel)
+        cp = C.POINTER(Projection)
         L.ilcc_project_intensity_device.argtypes = [C.c_void_p, C.c_uint32, cp, C.c_double, C.c_double, C.c_double,
                                                     C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
         L.ilcc_project_intensity_device.restype = C.c_int32

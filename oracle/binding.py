@@ -343,7 +343,7 @@ def hsv_to_rgb(h, s=100, v=100):
 
 
 def project_intensity(xyzi, cam, dis=50.0, lo=0.0, hi=60.0):
-    """cam: any ctypes struct laid out like orc_camera_model (the product's CameraModel is)."""
+    """cam: any ctypes struct laid out like orc_camera_model (the product's project.Projection is)."""
     a, ap = _f(xyzi)
     hits = np.zeros(len(a), HIT_DTYPE)
     m = lib().orc_project_intensity(ap, len(a), C.addressof(cam), dis, lo, hi, hits.ctypes.data)

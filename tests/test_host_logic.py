@@ -86,6 +86,23 @@ def test_ros_node_source_type_checks(tmp_path):
     assert r.returncode != 0 and "EuclideanClusters" in r.stderr
 
 
+def test_public_headers_compile_together(tmp_path):
+    """One translation unit may include every header under include/, as C++17 and as C99: no two of them define the same
+    name (ilcc_project.h's extrinsic + pinhole is ilcc_projection, the lens keeps ilcc_camera_model), so a caller can
+    use K8 and K11 from one file."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    inc = os.path.join(root, "include")
+    headers = sorted(h for h in os.listdir(inc) if h.endswith(".h"))
+    assert len(headers) >= 9 and {"ilcc_project.h", "ilcc_camera_image.h", "ilcc_overlay.h"} <= set(headers)
+    src = tmp_path / "all_headers.c"
+    src.write_text("".join('#include "%s"\n' % h for h in headers))
+    for cmd in (["g++", "-std=c++17", "-x", "c++", "-fsyntax-only", "-Wall", "-Wextra", "-Werror"],
+                ["gcc", "-std=c99", "-x", "c", "-fsyntax-only", "-Wall", "-Werror"]):
+        r = subprocess.run(cmd + ["-I" + inc, str(src)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+
+
 def test_bench_reads_its_roofline_inputs_from_committed_profiles():
     """roofline.traffic / issued_vs_credited are derived at run time from the PMC summaries committed under profiles/
     (no scaled constants): the parser finds the K6 launches of the batch sizes the bench runs."""

@@ -17,7 +17,7 @@ SIZE = (1920, 1200)
 
 def _camera():
     T = np.fromfile(os.path.join(GOLD, "pointgrey.bin"), dtype=np.float64).reshape(4, 4, order="F")   # the shipped extrinsic
-    return project.CameraModel.from_extrinsic(T, CAM, SIZE), T
+    return project.Projection.from_extrinsic(T, CAM, SIZE), T
 
 
 def test_project_exports_and_struct():
@@ -28,7 +28,7 @@ def test_project_exports_and_struct():
     assert declared == set(project.PROJECT_EXPORTS)
     for name in declared:
         assert hasattr(N.lib(), name)
-    assert C.sizeof(project.CameraModel) == 8 * 16 + 8 and project.HIT_DTYPE.itemsize == 16
+    assert C.sizeof(project.Projection) == 8 * 16 + 8 and project.HIT_DTYPE.itemsize == 16
 
 
 def test_oracle_hsv_known_answers(ob):
