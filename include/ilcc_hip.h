@@ -395,6 +395,21 @@ int32_t ilcc_debug_timeline_fetch(ilcc_handle* h, double* rows, uint32_t cap_row
  * measurements compare the two.  No batch may be in flight. */
 int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on);
 
+/* Diagnostic: where K2's workgroups keep the cell-sorted copy of a frame's ROI points.  By default a rule decides per launch: in
+ * LDS while every frame of the batch is resident on the device at once even with the copy, otherwise in the frame's slice of the
+ * cluster buffer (global memory, served from L2), which halves the workgroup's LDS and lets a large batch run in one round.
+ * ilcc_debug_cluster_home forces one home for every later launch of the handle (ILCC_CLUSTER_HOME_RULE restores the rule).  Results
+ * are identical either way.  No batch may be in flight.
+ * ilcc_debug_cluster_launch reports the last K2 launch of the handle (the online caller: its first tier) and the limits the rule
+ * works from: out[0] home used (ILCC_CLUSTER_HOME_LDS / _L2; 0: no launch yet), [1] dynamic LDS bytes per workgroup, [2] threads
+ * per workgroup, [3] the kernel's static LDS bytes, [4] the device's LDS bytes per compute unit, [5] its compute units. */
+#define ILCC_CLUSTER_HOME_RULE 0
+#define ILCC_CLUSTER_HOME_LDS 1
+#define ILCC_CLUSTER_HOME_L2 2
+#define ILCC_CLUSTER_LAUNCH_WORDS 6
+int32_t ilcc_debug_cluster_home(ilcc_handle* h, int32_t home);
+int32_t ilcc_debug_cluster_launch(const ilcc_handle* h, uint32_t out[ILCC_CLUSTER_LAUNCH_WORDS]);
+
 void ilcc_get_timing(const ilcc_handle* h, ilcc_timing* t);
 void ilcc_reset_timing(ilcc_handle* h);
 

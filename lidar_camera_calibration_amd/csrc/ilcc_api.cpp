@@ -143,6 +143,9 @@ struct ilcc_handle {
   hipEvent_t tl_ref = nullptr;       // ilcc_debug_timeline_*: reference event, rows of ILCC_TIMELINE_COLS doubles
   bool tl_on = false;
   bool separate_launches = false;    // ilcc_debug_separate_launches: K3, K4/K5, K5w and K1's two kernels as launches of their own at any batch size
+  ClusterLimits cluster_limits{};    // K2's residency limits on this device (launch_cluster's rule for the home of the sorted points)
+  int32_t cluster_home = kClusterHomeRule;   // ilcc_debug_cluster_home: the rule, or one home forced
+  ClusterLaunch cluster_last{};      // what the last k2_seeded_cluster launch used (ilcc_debug_cluster_launch)
   std::vector<double> tl_rows;
   std::string err;
 };
@@ -767,7 +770,7 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     // (one pass, one workgroup per frame, when the batch has the frames for it)
     launch_roi_crop(c, s, sl.ev[kEvCropCounted], !h->separate_launches && n_frames >= (uint32_t)kCropFrameMinFrames);
     HIP_TRY(h, hipEventRecord(sl.ev[kEvCropped], s));
-    launch_cluster(c, s);
+    h->cluster_last = launch_cluster(c, s, h->cluster_limits, h->cluster_home);
   } else {
     // get_chessboard_by_point clusters the WHOLE cloud (no ROI; setClusterTolerance(0.1), LidarCornersEst.cpp:80 -- EuclideanCluster()
     // uses 0.12, :131) and keeps the cluster around the predicted point.  Two tiers, identical results:
@@ -783,12 +786,12 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     t1.cluster_bits = cluster_bits_online();
     launch_roi_crop(t1, s, sl.ev[kEvCropCounted]);
     HIP_TRY(h, hipEventRecord(sl.ev[kEvCropped], s));
-    launch_cluster(t1, s);
+    h->cluster_last = launch_cluster(t1, s, h->cluster_limits, h->cluster_home);
     Ctx t2 = c;
     t2.online_tier = 2u;
     t2.p.roi_half[0] = t2.p.roi_half[1] = t2.p.roi_half[2] = (double)INFINITY;
     launch_roi_crop(t2, s, nullptr);
-    launch_cluster(t2, s);
+    (void)launch_cluster(t2, s, h->cluster_limits, h->cluster_home);
     HIP_TRY(h, hipMemcpyAsync(sl.h_online, sl.d_flags, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(sl.h_online + h->max_frames, sl.d_nfinite, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
   }
@@ -1250,6 +1253,8 @@ ilcc_handle* ilcc_create(int32_t device, const ilcc_params* p, uint32_t max_fram
   if ((e = set_kernel_attributes_k2()) != hipSuccess || (e = set_kernel_attributes_k6()) != hipSuccess ||
       (e = set_kernel_attributes_k7a()) != hipSuccess || (e = set_kernel_attributes_k7r()) != hipSuccess)
     return fail(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize): ") + hipGetErrorString(e));
+  if ((e = cluster_limits(h->device, &h->cluster_limits)) != hipSuccess)
+    return fail(std::string("cluster_limits: ") + hipGetErrorString(e));
   for (const Buffer& b : handle_buffers(h))
     if (b.bytes && (e = hipMalloc(b.ptr, b.bytes)) != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
   warn_hw_queues_once();
@@ -1643,6 +1648,27 @@ int32_t ilcc_debug_timeline_enable(ilcc_handle* h, int32_t on) {
 int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on) {
   if (!h || any_batch_in_flight(h, "ilcc_debug_separate_launches")) return ILCC_BAD_ARGUMENT;
   h->separate_launches = on != 0;
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_cluster_home(ilcc_handle* h, int32_t home) {
+  if (!h || any_batch_in_flight(h, "ilcc_debug_cluster_home")) return ILCC_BAD_ARGUMENT;
+  if (home != ILCC_CLUSTER_HOME_RULE && home != ILCC_CLUSTER_HOME_LDS && home != ILCC_CLUSTER_HOME_L2) {
+    h->err = "ilcc_debug_cluster_home: home must be ILCC_CLUSTER_HOME_RULE, _LDS or _L2";
+    return ILCC_BAD_ARGUMENT;
+  }
+  h->cluster_home = home;
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_cluster_launch(const ilcc_handle* h, uint32_t out[ILCC_CLUSTER_LAUNCH_WORDS]) {
+  if (!h || !out) return ILCC_BAD_ARGUMENT;
+  out[0] = (uint32_t)h->cluster_last.home;
+  out[1] = h->cluster_last.lds_bytes;
+  out[2] = h->cluster_last.threads;
+  out[3] = h->cluster_limits.static_lds;
+  out[4] = h->cluster_limits.lds_per_cu;
+  out[5] = h->cluster_limits.cus;
   return ILCC_OK;
 }
 

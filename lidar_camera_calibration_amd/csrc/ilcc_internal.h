@@ -179,7 +179,7 @@ struct Ctx {
   uint32_t* uf_count;        // K2 component sizes
   uint32_t* uf_hash_head;    // K2 spatial hash: n_frames x kClusterHashSize bucket heads
   uint32_t* uf_hash_next;    // K2 spatial hash: chain links, one per point
-  uint32_t cluster_lds_points;   // K2: ROI points per frame whose cell-sorted copy fits the workgroup's LDS; larger frames sort into HBM
+  uint32_t cluster_lds_points;   // K2: ROI points per frame whose cell-sorted copy fits the workgroup's LDS; larger frames sort into HBM (0 in a launch that keeps no copy in LDS: launch_cluster)
   uint32_t cluster_cells_cap;    // K2: occupied cells per frame the workgroup's LDS arrays hold; frames with more take the hashed-cell path (hashed_cluster_frame)
   uint32_t wide;             // per-frame kernels at their small-batch (latency) widths whatever the batch size: synchronous calls nothing overlaps with (the online caller)
   uint32_t cluster_bits;     // K2: cells of the padded bounding grid the LDS bitmap holds (a multiple of 64)
@@ -322,7 +322,18 @@ constexpr int kLocateMinFrames = 512;   // smaller batches keep the three launch
 // after_count: recorded between the count pass and the scatter; one_pass: k1_roi_crop_frame, one workgroup per frame (behind which after_count is recorded)
 void launch_roi_crop(const Ctx& c, hipStream_t s, hipEvent_t after_count = nullptr, bool one_pass = false);
 constexpr int kCropFrameMinFrames = 512;   // the one-pass crop needs a frame per workgroup slot of the chip (256 CUs x 4); smaller batches keep (chunk, frame) workgroups
-void launch_cluster(const Ctx& c, hipStream_t s);
+// K2: where a launch's workgroups keep the cell-sorted copy of the points (= ILCC_CLUSTER_HOME_* of ilcc_hip.h).  Rule: LDS while
+// the whole batch is resident at once with the copy, else the frames' slices of `cluster` (launch_cluster)
+constexpr int32_t kClusterHomeRule = 0, kClusterHomeLds = 1, kClusterHomeL2 = 2;
+struct ClusterLimits {   // of the handle's device and of k2_seeded_cluster on it (cluster_limits)
+  uint32_t cus, lds_per_cu, threads_per_cu, static_lds;
+};
+struct ClusterLaunch {   // what a k2_seeded_cluster launch used (all zero: the k2h_* chain, no such launch)
+  int32_t home;
+  uint32_t lds_bytes, threads;
+};
+hipError_t cluster_limits(int device, ClusterLimits* out);
+ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& lim, int32_t home);
 void launch_ransac_plane(const Ctx& c, hipStream_t s);
 void launch_plane_frame_hist(const Ctx& c, hipStream_t s);
 // K3 + K4/K5 (+ K5w with walk_layout) in one launch, one workgroup per frame (k345_front_end.hip): batches that would run all of

@@ -15,7 +15,8 @@
 //   neighbours (5 neighbours per 64-bit window read), skips pairs whose cells already share a root and stops a pair's
 //   tests at the first hit.  One workgroup of 256 threads (1024 in batches of <= 64 frames), ~50 KB of LDS: bitmap of the
 //   padded bounding grid + its rank directory (cell key -> dense cell id), five words per cell, the points sorted by cell
-//   (frames above the LDS point capacity keep the sorted points in HBM/L2 -- BASELINE config 5's ~12 k ROI points).
+//   (frames above the LDS point capacity keep the sorted points in HBM/L2 -- BASELINE config 5's ~12 k ROI points; and so does
+//   every frame of a launch whose batch would not be resident at once with the copy: launch_cluster).
 //   Labels are the smallest member index of a component (atomicMin over its cells), sizes are sums of cell counts: the
 //   partition, the 1-NN of the click, the reference's choice rule and the index-ordered output are what they were.
 //
@@ -404,8 +405,24 @@ struct FineLds {
   uint32_t* bm;      // fine_words(cluster_bits): occupancy bitmap of the padded bounding grid
   uint16_t* pre;     // cluster_bits / 64: occupied cells below each 64-bit word
   uint32_t *ckey, *cstart, *ccnt, *cmin, *cpar;   // per occupied cell (capacity c.cluster_cells_cap; cstart one more)
-  float *sx, *sy, *sz;   // the points sorted by cell (capacity c.cluster_lds_points)
+  float *sx, *sy, *sz;   // the points sorted by cell (capacity c.cluster_lds_points; 0 in a launch that keeps them in `cluster`)
 };
+
+// point `at` of the cell-sorted copy, in either home
+template <bool PTS_LDS>
+__device__ __forceinline__ float3 sorted_point(const FineLds& L, const float4* gpts, uint32_t at) {
+  if (PTS_LDS) return make_float3(L.sx[at], L.sy[at], L.sz[at]);
+  const float4 q = gpts[at];
+  return make_float3(q.x, q.y, q.z);
+}
+#ifndef ILCC_K2_PAIR_GROUP
+#define ILCC_K2_PAIR_GROUP 4       // (A/B builds: tools/build_variant.sh)
+#endif
+#ifndef ILCC_K2_PAIR_GROUP_LDS
+#define ILCC_K2_PAIR_GROUP_LDS 4
+#endif
+// points of B an edge test loads at once, the sorted points in `cluster` / in LDS
+constexpr uint32_t kPairGroup = ILCC_K2_PAIR_GROUP, kPairGroupLds = ILCC_K2_PAIR_GROUP_LDS;
 
 // Returns false (uniformly) when the frame does not fit the grid / the cell capacity: the caller takes the point-level path.
 template <bool PTS_LDS>
@@ -521,23 +538,28 @@ __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
         const uint32_t ra = uf_find(L.cpar, A), rb = uf_find(L.cpar, B);
         if (ra == rb) continue;   // same component already (for good)
         const uint32_t b0 = L.cstart[B], b1 = L.cstart[B + 1];
+        // A's point once per ia, B's points kGroup at a time: the group's loads are unconditional (an index past the cell's
+        // end reads its last point again: harmless) and independent, one round trip per group instead of one per test -- at L2
+        // latency (the points in `cluster`) the serial walk was the frame's chain.  Same tests, same arithmetic; which pair hits
+        // first does not matter, only whether one does
+        constexpr uint32_t kGroup = PTS_LDS ? kPairGroupLds : kPairGroup;
         bool hit = false;
         for (uint32_t ia = a0; ia < a1 && !hit; ++ia) {
-          float px, py, pz;
-          if (PTS_LDS) { px = L.sx[ia]; py = L.sy[ia]; pz = L.sz[ia]; }
-          else { const float4 q = gpts[ia]; px = q.x; py = q.y; pz = q.z; }
-          for (uint32_t ib = b0; ib < b1; ++ib) {
-            float qx, qy, qz;
-            if (PTS_LDS) { qx = L.sx[ib]; qy = L.sy[ib]; qz = L.sz[ib]; }
-            else { const float4 q = gpts[ib]; qx = q.x; qy = q.y; qz = q.z; }
-            const float ex2 = qx - px, ey2 = qy - py, ez2 = qz - pz;
-            float d2 = ex2 * ex2;
-            d2 = d2 + ey2 * ey2;
-            d2 = d2 + ez2 * ez2;
-            if (d2 < tol2) {
-              hit = true;
-              break;
+          const float3 p = sorted_point<PTS_LDS>(L, gpts, ia);
+          for (uint32_t ib = b0; ib < b1 && !hit; ib += kGroup) {
+            float3 q[kGroup];
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k) q[k] = sorted_point<PTS_LDS>(L, gpts, min(ib + k, b1 - 1u));
+            float nearest = 3.0e38f;   // of the group: some d2 < tol2 <=> their minimum is (fminf passes over a NaN as the compare does)
+#pragma unroll
+            for (uint32_t k = 0; k < kGroup; ++k) {
+              const float ex2 = q[k].x - p.x, ey2 = q[k].y - p.y, ez2 = q[k].z - p.z;
+              float d2 = ex2 * ex2;
+              d2 = d2 + ey2 * ey2;
+              d2 = d2 + ez2 * ez2;
+              nearest = fminf(nearest, d2);
             }
+            hit = nearest < tol2;
           }
         }
         if (hit) uf_unite(L.cpar, ra, rb);
@@ -1289,7 +1311,33 @@ hipError_t set_kernel_attributes_k2() {
 #endif
 }
 
-void launch_cluster(const Ctx& c, hipStream_t s) {
+hipError_t cluster_limits(int device, ClusterLimits* out) {
+  hipDeviceProp_t prop;
+  hipError_t e = hipGetDeviceProperties(&prop, device);
+  if (e != hipSuccess) return e;
+  hipFuncAttributes attr;
+  if ((e = hipFuncGetAttributes(&attr, (const void*)k2_seeded_cluster)) != hipSuccess) return e;
+  out->cus = (uint32_t)std::max(prop.multiProcessorCount, 1);
+  out->lds_per_cu = (uint32_t)prop.maxSharedMemoryPerMultiProcessor;
+  out->threads_per_cu = (uint32_t)std::max(prop.maxThreadsPerMultiProcessor, 1024);
+  out->static_lds = (uint32_t)attr.sharedSizeBytes;
+  return hipSuccess;
+}
+
+// frames (= workgroups) of one K2 launch the device holds at once, by LDS and by thread slots
+static uint32_t cluster_resident_frames(const ClusterLimits& lim, uint32_t threads, size_t dynamic_lds) {
+  const size_t per_wg = (size_t)lim.static_lds + dynamic_lds;
+  const uint32_t by_lds = (uint32_t)((size_t)lim.lds_per_cu / std::max<size_t>(per_wg, 1)), by_threads = lim.threads_per_cu / threads;
+  return lim.cus * std::min(by_lds, by_threads);
+}
+
+// The home of the cell-sorted points, per launch.  A workgroup's latency chain is about the same length wherever its pair tests
+// read from (they load B's points in groups); what the LDS copy costs is residency: 12 bytes per point of capacity, half the
+// footprint at the bench's (1792, 2560) reservation -- two workgroups per CU instead of four, and a 1024-frame batch in two rounds
+// of one frame's chain.  So: LDS while every frame of the batch is resident at once even with the copy; otherwise no copy -- every
+// frame takes fine_cluster_frame<false>, the path of frames above the capacity, the points in the frame's slice of `cluster` (L2).
+// The online caller's first tier (wide) keeps LDS: a synchronous call on windows of a few hundred points.
+ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& lim, int32_t home) {
   if (c.online_tier == 2u) {   // the frames the online caller's first tier could not vouch for: the k2h_* chain over the listed frames
     ListedFrame* lf = static_cast<ListedFrame*>(c.list_frames);
     const uint32_t grid = c.list_grid;
@@ -1304,10 +1352,17 @@ void launch_cluster(const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL(k2h_edges, dim3(grid), dim3(kListChunk), 0, s, c, lf);
     hipLaunchKernelGGL(k2h_roots, dim3(grid), dim3(kListChunk), 0, s, c, lf);
     hipLaunchKernelGGL(k2h_finish, dim3(c.n_frames), dim3(1024), 0, s, c, lf);
-    return;
+    return ClusterLaunch{};
   }
   const int threads = (c.n_frames <= (uint32_t)kSmallBatchFrames || c.wide) ? 1024 : kFrameThreads;   // (small batches: latency, not CU footprint, matters)
-  hipLaunchKernelGGL(k2_seeded_cluster, dim3(c.n_frames), dim3(threads), cluster_lds_bytes(c.cluster_lds_points, c.cluster_cells_cap, c.cluster_bits), s, c);
+  const size_t with_copy = cluster_lds_bytes(c.cluster_lds_points, c.cluster_cells_cap, c.cluster_bits);
+  if (home == kClusterHomeRule)
+    home = (c.wide || c.n_frames <= cluster_resident_frames(lim, (uint32_t)threads, with_copy)) ? kClusterHomeLds : kClusterHomeL2;
+  Ctx k = c;
+  if (home == kClusterHomeL2) k.cluster_lds_points = 0u;   // no frame fits "the capacity": fine_cluster_frame<false> for all
+  const size_t lds = cluster_lds_bytes(k.cluster_lds_points, k.cluster_cells_cap, k.cluster_bits);
+  hipLaunchKernelGGL(k2_seeded_cluster, dim3(k.n_frames), dim3(threads), lds, s, k);
+  return ClusterLaunch{home, (uint32_t)lds, (uint32_t)threads};
 }
 
 }  // namespace ilcc

@@ -253,6 +253,22 @@ class LidarCornersBatch:
         if st != N.OK:
             raise IlccError(st, self._err())
 
+    def debug_cluster_home(self, home: int):
+        """Diagnostic: force where K2 keeps the cell-sorted points (``N.CLUSTER_HOME_LDS`` / ``N.CLUSTER_HOME_L2``), or give the
+        choice back to the per-launch rule (``N.CLUSTER_HOME_RULE``).  Results are identical either way."""
+        st = self._lib.ilcc_debug_cluster_home(self._h, int(home))
+        if st != N.OK:
+            raise IlccError(st, self._err())
+
+    def debug_cluster_launch(self) -> dict:
+        """What the handle's last K2 launch used and the limits the rule works from: home, dynamic LDS bytes and threads per
+        workgroup; the kernel's static LDS bytes, the device's LDS bytes per compute unit and its compute units."""
+        out = (C.c_uint32 * N.CLUSTER_LAUNCH_WORDS)()
+        st = self._lib.ilcc_debug_cluster_launch(self._h, out)
+        if st != N.OK:
+            raise IlccError(st, self._err())
+        return dict(zip(("home", "lds_bytes", "threads", "static_lds_bytes", "lds_per_cu", "cus"), (int(v) for v in out)))
+
     def wait_compact(self, ticket) -> np.ndarray:
         """The batch's compact records: [n_frames, RECORD_HEADER + 3 * board corners] float32 (layout:
         ``sharding.pack_records``; tag = frame index within the batch)."""
