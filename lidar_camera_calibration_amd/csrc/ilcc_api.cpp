@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ilcc_internal.h"
+#include "k6_common.h"
 #include "k7_common.h"
 
 using namespace ilcc;
@@ -396,16 +397,16 @@ struct GroupPrepassPlan {
 };
 GroupPrepassPlan group_prepass_plan(const ilcc_params& p) {
   GroupPrepassPlan g;
-  // box pre-pass (k6_grid_cost.hip): its monotonicity argument needs a tile's box narrower than one square on both axes
+  // box pre-pass (k6_common.h: box_term): its monotonicity argument needs a tile's box narrower than one square on both axes
   const bool box = p.grid_prune != 0 && 3.0 * p.ty_step < 0.9 * p.grid_length && 3.0 * p.tz_step < 0.9 * p.grid_length;
   // ... and, for the points the common pre-pass leaves out, every translation of the tables keeping the board's centre inside the board
   const double gl = p.grid_length;
   const double ty_hi = p.ty_min + (p.n_ty - 1) * p.ty_step, tz_hi = p.tz_min + (p.n_tz - 1) * p.tz_step;
   const bool centre_in = p.ty_min > -0.45 * p.board_w * gl && ty_hi < 0.45 * p.board_w * gl && p.tz_min > -0.45 * p.board_h * gl &&
                          tz_hi < 0.45 * p.board_h * gl;
-  const uint32_t n_tiles = (uint32_t)(((p.n_ty + 3) / 4) * ((p.n_tz + 3) / 4));
+  const uint32_t n_tiles = (uint32_t)grid_tiles(p.n_ty, p.n_tz);
   g.box = box;
-  g.on = box && p.n_th >= kThetaGroup && centre_in && n_tiles <= 4096u;
+  g.on = box && p.n_th >= kThetaGroup && centre_in && n_tiles <= (uint32_t)kBoxTilesMax;
   g.groups = (uint32_t)((p.n_th + kThetaGroup - 1) / kThetaGroup);
   g.words = (n_tiles + 31u) / 32u;
   return g;
@@ -564,7 +565,7 @@ hipStream_t late_stream(const ilcc_handle* h) {
 // K2's workgroup keeps bitmap + per-cell arrays + (up to cluster_lds_points) sorted points in LDS: when the cell arrays have
 // grown large (dense clouds), give up LDS points first -- frames of that size sort into HBM anyway
 void fit_cluster_lds(ilcc_handle* h) {
-  while (cluster_lds_bytes(h->cluster_lds_points, h->cluster_cells_cap, cluster_bits_online()) > 156u * 1024u && h->cluster_lds_points > 0)
+  while (cluster_lds_bytes(h->cluster_lds_points, h->cluster_cells_cap, cluster_bits_online()) > (size_t)kClusterLdsMax && h->cluster_lds_points > 0)
     h->cluster_lds_points = h->cluster_lds_points > 512u ? h->cluster_lds_points - 512u : 0u;
 }
 
@@ -622,7 +623,7 @@ GridPass seed_pass(const ilcc_handle* h, const Slot& sl, const Ctx& c) {
 GridPass refine_pass(const ilcc_handle* h, const Slot& sl, const Ctx& c, int32_t refine_radius) {
   GridPass g = whole_grid_pass(c, h->grid, sl.d_partial3);
   g.seed = GridSeed{sl.d_partial2, (uint32_t)h->seed_grid.n_th, h->seed_map};
-  g.window_tiles = h->seed_map.stride_t > 2 * kTileA ? 4 : 2;
+  g.window_tiles = h->seed_map.stride_t > 2 * kTile ? 4 : 2;
   g.radius_th = (refine_radius / kRefineThetaStride) * kRefineThetaStride;
   g.step_th = kRefineThetaStride;
   g.blocks = std::min((uint32_t)(2 * (g.radius_th / kRefineThetaStride) + 1), h->max_theta);
@@ -702,7 +703,7 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
     const LocatePlan lp = locate_plan(h, sl, c);
     // one launch, one workgroup per frame (k6_locate) when the batch has the frames to fill the chip that way
     const bool fused = n_frames >= (uint32_t)kLocateMinFrames && lp.seed.n_th <= 16 &&
-                       locate_lds_bytes(lp.sample_cap, h->grid.n_ty, h->grid.n_tz, lp.seed.n_ty, lp.seed.n_tz) <= 60u * 1024u;
+                       locate_lds_bytes(lp.sample_cap, h->grid.n_ty, h->grid.n_tz, lp.seed.n_ty, lp.seed.n_tz) <= (size_t)kLocateLdsMax;
     if (fused) {
       launch_locate(c, s, lp);
       HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));   // (the whole locate launch is accounted as the "seed" span)
@@ -1027,8 +1028,8 @@ void raise_capacities(ilcc_handle* h, uint32_t grid_points, uint32_t cluster_poi
 // K6 / K7 staging: the largest labelled-point count so far, rounded up to 256 points.  (Not to a power of two: 1 781 points -- the
 // largest of the bench frames -- need 21.8 KB per K6 workgroup at 1 792 and 24.9 KB at 2 048: seven instead of six workgroups per
 // CU -- which, the kernel being VALU-bound, measured no difference: 248.8 k vs 250 k frames/s.)
-// ... but never, on its own, past the capacity at which TWO workgroups of the K6 full pass still share a CU's 160 KB (12 bytes per
-// staged point + the (ty, tz) tables + ~3 KB of static LDS: 6 400 points for both BASELINE grids).  Round 6: a stream of 64-ring
+// ... but never, on its own, past the capacity at which TWO workgroups of the K6 full pass still share a CU (grid_points_two_per_cu:
+// 6 400 points for both BASELINE grids).  Round 6: a stream of 64-ring
 // frames whose closest boards hold 6 682 labelled points (the first 128 frames: 6 170) grew the staging to 6 912 points, ONE
 // workgroup per CU, and every frame's full pass took 1.15 ms instead of 0.74 ms per 128 frames.  The few frames above the capacity
 // walk their points through L2 (grid_cost_body<LDS_POINTS = false>); ilcc_reserve may still ask for more, explicitly.
@@ -1036,8 +1037,16 @@ void raise_capacities(ilcc_handle* h, uint32_t grid_points, uint32_t cluster_poi
 // workgroups of other batches.  Its per-cell arrays: the most occupied cells a frame of the batch needed (+ 1/8), steps of 256.
 // Frames the LDS cell grid cannot hold at any capacity (bounding grid too large: un-cropped clouds; more cells than the largest
 // capacity) take the hashed-cell path of their own workgroup (k2_cluster.hip).
+constexpr int kGridStaticLds = 3072;   // static LDS of a full-pass workgroup (bests, counters, the box pre-pass's mask and list), rounded up
+// the largest multiple of 256 staged points with which two full-pass workgroups on an n_ty x n_tz grid fit a CU's LDS (0: none)
+constexpr uint32_t grid_points_two_per_cu(int n_ty, int n_tz) {
+  const int64_t room = (int64_t)kCuLdsBytes / 2 - kGridStaticLds - (int64_t)grid_lds_bytes(0, n_ty, n_tz);
+  return room > 0 ? (uint32_t)(room / (int64_t)grid_lds_bytes(1, 0, 0)) & ~255u : 0u;
+}
+static_assert(grid_points_two_per_cu(40, 40) == 6400, "BASELINE config 2 (the default grid: 40 x 40 translations)");
+static_assert(grid_points_two_per_cu(129, 129) == 6400, "BASELINE config 5 (129 x 129 translations)");
 void grow_capacities(ilcc_handle* h, const BatchCounts& n, uint64_t cells_needed) {
-  const uint32_t two_per_cu = (uint32_t)(((160u * 1024u / 2u) - 3072u - 4u * (uint32_t)(h->p.n_ty + h->p.n_tz)) / 12u) & ~255u;
+  const uint32_t two_per_cu = grid_points_two_per_cu(h->p.n_ty, h->p.n_tz);
   raise_capacities(h, std::min(grid_lds_capacity(n.max_lab), std::max(1024u, two_per_cu)), cluster_lds_capacity(n.max_roi, 0u),
                    cluster_cells_capacity(cells_needed + cells_needed / 8));
 }

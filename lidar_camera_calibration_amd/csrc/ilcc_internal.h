@@ -11,6 +11,12 @@
 
 namespace ilcc {
 
+// The LDS of a CU, and the bounds derived from it (the library is built for gfx950 only)
+constexpr int kCuLdsBytes = 160 * 1024;
+constexpr int kClusterLdsMax = kCuLdsBytes - 4 * 1024;   // K2: dynamic LDS the handle lets k2_seeded_cluster's capacities grow to (fit_cluster_lds); its limit in a build with the timers' static LDS
+constexpr int kLocateLdsMax = 3 * (kCuLdsBytes / 8);     // K6: dynamic LDS up to which a batch takes k6_locate (60 KiB: two of its workgroups share a CU); above, the separate launches
+constexpr int kSolveLdsMax = kCuLdsBytes - 16 * 1024;    // K7a: dynamic LDS bound (144 KiB = two frames staged at kGridLdsPointsMax, k7_common.h)
+
 // block sizes (multiples of the 64-lane wavefront)
 constexpr int kCropThreads = 256;      // K1
 constexpr int kCropChunk = 4096;       // points per K1 block
@@ -47,16 +53,11 @@ constexpr int kGridThreadsLarge = ILCC_K6_THREADS_LARGE;   // K6 on frames stage
 #define ILCC_K6_LARGE_FROM 2048
 #endif
 constexpr int kGridLargeFrom = ILCC_K6_LARGE_FROM;
-constexpr int kTileA = 4;              // K6 candidate tile: ty values per wavefront pass
-#ifndef ILCC_TILE_B
-#define ILCC_TILE_B 4
-#endif
-constexpr int kTileB = ILCC_TILE_B;    // K6 candidate tile: tz values per wavefront pass (4 or 8)
 #ifndef ILCC_K6_GROUP
 #define ILCC_K6_GROUP 7   // round 4 (config 2 / config 5, k frames/s): 2: 821 / 50.9, 3: 837 / 54.5, 4: 837 / 55.1, 5: 842 / 56.2, 7: 841 / 56.3; round 6, the per-theta pre-pass skipped behind a valid mask: 3: 1 235 / 82.9, 4: 1 250 / 83.9, 5: 1 276 / 89.7, 7: 1 280 / 91.5, 9: 1 283 / 92.6, 11: 1 271 / 92.2, 15: 1 177 / 90.8
 #endif
 constexpr int kThetaGroup = ILCC_K6_GROUP;   // K6: consecutive thetas that share one common box pre-pass (k6_group_prepass)
-constexpr int kGridLdsPointsMax = 8192;   // K6 LDS staging upper bound (12 B per point -> 96 KiB)
+constexpr int kGridLdsPointsMax = 8192;   // K6 LDS staging upper bound (grid_lds_bytes, k6_common.h: 96 KiB of points)
 constexpr int kGridTableMax = 8192;       // K6: n_ty + n_tz bound (their tables sit in LDS behind the points: 32 KiB)
 #ifndef ILCC_K7_THREADS
 #define ILCC_K7_THREADS 256
@@ -303,7 +304,7 @@ __device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* scratch, uin
   return base + in_wave;
 }
 
-// k6_locate (k6_grid_cost.hip): seed + refinement + anchor of the grid search in one launch, one workgroup per frame
+// k6_locate (k6_locate.hip): seed + refinement + anchor of the grid search in one launch, one workgroup per frame
 struct LocatePlan {
   GridTables seed;                        // the seed's decimated tables ...
   SeedMap map;                            // ... and where their entries sit in the full ones (Ctx::grid)
@@ -312,7 +313,7 @@ struct LocatePlan {
   GridPartial* out;                       // one record per frame: the anchor's best candidate (full-table flat index, (a << 16) | b)
 };
 
-size_t locate_lds_bytes(uint32_t sample_cap, int n_ty, int n_tz, int n_ty2, int n_tz2);
+size_t locate_lds_bytes(uint32_t sample_cap, int n_ty, int n_tz, int n_ty2, int n_tz2);   // k6_locate's dynamic LDS (its own carve, locate_lds)
 void launch_locate(const Ctx& c, hipStream_t s, const LocatePlan& lp);
 void launch_anchor(const Ctx& c, const GridPass& pass, hipStream_t s);   // one anchor round of the separate locate launches (pass.seed -> pass.out, pass.blocks thetas)
 constexpr int kRefineThetaStride = 2;  // the refinement scores every other theta of its range (the anchor covers the ones in between)
@@ -342,9 +343,9 @@ void launch_front_end(const Ctx& c, hipStream_t s, bool walk_layout);
 inline bool front_end_fusable(const Ctx& c) {
   return kPlaneThreads == kHistThreads && kHistThreads == kWalkThreads && c.n_frames > (uint32_t)kSmallBatchFrames && !c.wide;
 }
-void launch_walk_order(const Ctx& c, hipStream_t s);   // K5w (k6_grid_cost.hip): before any launch_grid_cost on the frames
-void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/, bool prune);
-void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // in front of the full pass it is given: writes full.grp_alive / grp_mask
+void launch_walk_order(const Ctx& c, hipStream_t s);   // K5w (k5w_walk_order.hip): before any launch_grid_cost on the frames
+void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/, bool prune);   // k6_grid_cost.hip
+void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // k6_group_prepass.hip, in front of the full pass it is given: writes full.grp_alive / grp_mask
 uint32_t grid_cost_evals_per_count();   // (point, candidate) evaluations behind one count of Ctx::grid_iters
 // K7a on every frame of the batch (REFERENCE_LOCAL mode: solve_slots(c.p) solves per frame, k7_common.h)
 void launch_reference_solve(const Ctx& c, hipStream_t s);
@@ -363,7 +364,7 @@ hipError_t set_kernel_attributes_k2();
 size_t cluster_lds_bytes(uint32_t pts_cap, uint32_t cells_cap, uint32_t bits);   // K2's dynamic LDS for these capacities (bits: cells the bitmap holds)
 uint32_t cluster_bits_default();
 uint32_t cluster_bits_online();
-hipError_t set_kernel_attributes_k6();
+hipError_t set_kernel_attributes_k6();   // every K6 file's kernels (k6_common.h: raise_grid_lds_limit)
 hipError_t set_kernel_attributes_k7a();
 hipError_t set_kernel_attributes_k7r();
 // stand-alone local solve on the labelled points of frame 0 (test entry)

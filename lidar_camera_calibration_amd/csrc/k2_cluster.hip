@@ -1301,13 +1301,13 @@ __global__ __launch_bounds__(1024) void k2_seeded_cluster(Ctx c) {
   point_level_cluster_frame(c, f, L.sc);
 }
 
-// up to 160 KiB of dynamic LDS (> the 64 KiB default cap).  Called by ilcc_create for the handle's device: the attribute
+// up to a CU's whole LDS as dynamic LDS (> the 64 KiB default cap).  Called by ilcc_create for the handle's device: the attribute
 // is kept per (function, device).
 hipError_t set_kernel_attributes_k2() {
 #ifdef ILCC_K2_TIMING
-  return hipFuncSetAttribute((const void*)k2_seeded_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);   // (the timers' static LDS)
+  return hipFuncSetAttribute((const void*)k2_seeded_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, kClusterLdsMax);   // (the timers' static LDS)
 #else
-  return hipFuncSetAttribute((const void*)k2_seeded_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return hipFuncSetAttribute((const void*)k2_seeded_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, kCuLdsBytes);
 #endif
 }
 

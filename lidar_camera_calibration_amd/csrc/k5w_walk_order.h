@@ -1,4 +1,4 @@
-// K5w -- the frame's labelled points in K6's walk layout (k5w_walk_order in k6_grid_cost.hip, k345_front_end in
+// K5w -- the frame's labelled points in K6's walk layout (k5w_walk_order in k5w_walk_order.hip, k345_front_end in
 // k345_front_end.hip).
 #pragma once
 

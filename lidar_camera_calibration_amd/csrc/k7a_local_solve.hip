@@ -102,7 +102,6 @@ __device__ __forceinline__ void huber(double a, double r, double s, double& rho0
 
 // ------------------------------------------------------------------ wavefront-wide evaluation
 constexpr int kSolveWaves = kSolveThreads / ILCC_WAVE;   // solves per K7a workgroup
-constexpr int kSolveLdsMax = 144 * 1024;                 // K7a: dynamic LDS bound (a CU has 160 KB)
 #ifndef ILCC_K7A_WIDE_MAX
 #define ILCC_K7A_WIDE_MAX 256
 #endif
