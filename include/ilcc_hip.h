@@ -377,6 +377,21 @@ int32_t ilcc_get_theta_t(ilcc_handle* h, const float* yz, const uint8_t* label, 
                          int32_t topleft_white, int32_t use_oob, double theta_t[3], double* cost,
                          int32_t* iterations);
 
+/* Diagnostic: the REFERENCE_LOCAL back end (K7a's two-pass solves and K7b's phase choice, coverage and corners) as the pipeline
+ * launches it, on n_frames frames of caller-supplied labelled points (host buffers; frame f = points offsets[f] .. offsets[f + 1]).
+ * Each frame's record starts zeroed with status = status_in[f]: a frame whose status is not ILCC_OK is one the front end failed.
+ * The handle's LDS staging capacity is used as it is and never grown (*lds_points reports it): frames with more labelled points
+ * take the global-memory path.  Out, per frame and phase slot k (2 slots per frame; with phase_mode != 2 only slot 0 is solved):
+ * rec_f64[(2 f + k) * ILCC_SOLVE_REC_DOUBLES ..] = theta, ty, tz, cost_a, cost_b, sel (the with-OOB cost the phase is chosen by),
+ * rec_i32[(2 f + k) * ILCC_SOLVE_REC_INTS ..] = iters_a, iters_b, phase, valid (a slot the launch did not write: every bit set);
+ * results[f] = the frame's record after K7b.  Refuses a busy ticket 0, more frames than max_frames, more points than the handle
+ * holds, and a handle that is not in ILCC_SOLVER_REFERENCE_LOCAL mode. */
+#define ILCC_SOLVE_REC_DOUBLES 6
+#define ILCC_SOLVE_REC_INTS 4
+int32_t ilcc_debug_reference_solve(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets,
+                                   const int32_t* status_in, uint32_t n_frames, double* rec_f64, int32_t* rec_i32,
+                                   ilcc_result* results, uint32_t* lds_points);
+
 /* Diagnostic (ABI 5): the real timeline of the batches, without a profiler.  While enabled, every completed batch appends one row
  * of ILCC_TIMELINE_COLS doubles: slot, then the times in ms -- relative to a reference event recorded when the timeline was
  * enabled -- of the batch's HIP events: start, after K1's count pass, after K1, K2, K3, K4/K5, K5w, seed, refinement, anchor,

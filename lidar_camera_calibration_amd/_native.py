@@ -34,12 +34,13 @@ EXPORTS = [
     "ilcc_save_corners2txt", "ilcc_read_lidar_corners",
     "ilcc_set_result_mode", "ilcc_wait_compact", "ilcc_record_floats", "ilcc_fetch_results",
     "ilcc_debug_timeline_enable", "ilcc_debug_timeline_fetch", "ilcc_debug_separate_launches",
-    "ilcc_debug_cluster_home", "ilcc_debug_cluster_launch",
+    "ilcc_debug_cluster_home", "ilcc_debug_cluster_launch", "ilcc_debug_reference_solve",
 ]
 ABI_VERSION = 5            # the layout of Params / Result / Timing below is ILCC_ABI_VERSION 5 of include/ilcc_hip.h
 RESULTS_FULL, RESULTS_COMPACT = 0, 1
 CLUSTER_HOME_RULE, CLUSTER_HOME_LDS, CLUSTER_HOME_L2 = 0, 1, 2
 CLUSTER_LAUNCH_WORDS = 6
+SOLVE_REC_DOUBLES, SOLVE_REC_INTS = 6, 4
 
 
 class Params(C.Structure):
@@ -226,6 +227,9 @@ def lib():
             L.ilcc_debug_cluster_home.restype = C.c_int32
             L.ilcc_debug_cluster_launch.argtypes = [vp, C.POINTER(C.c_uint32)]
             L.ilcc_debug_cluster_launch.restype = C.c_int32
+        L.ilcc_debug_reference_solve.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_uint32,
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), rp, C.POINTER(C.c_uint32)]
+        L.ilcc_debug_reference_solve.restype = C.c_int32
         L.ilcc_fetch_results.argtypes = [vp, C.c_uint32, C.c_uint32, rp]
         L.ilcc_fetch_results.restype = C.c_int32
         _lib = L

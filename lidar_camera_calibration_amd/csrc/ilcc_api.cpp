@@ -1608,6 +1608,66 @@ int32_t ilcc_get_theta_t(ilcc_handle* h, const float* yz, const uint8_t* label, 
   return ILCC_OK;
 }
 
+int32_t ilcc_debug_reference_solve(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets,
+                                   const int32_t* status_in, uint32_t n_frames, double* rec_f64, int32_t* rec_i32,
+                                   ilcc_result* results, uint32_t* lds_points) {
+  if (!h || !status_in || !rec_f64 || !rec_i32 || !results) return ILCC_BAD_ARGUMENT;
+  Slot& sl = h->slots[0];
+  if (sl.busy) {
+    h->err = "diagnostic entry while ticket 0 is in flight";
+    return ILCC_BAD_ARGUMENT;
+  }
+  if (h->p.solver != ILCC_SOLVER_REFERENCE_LOCAL) {
+    h->err = "ilcc_debug_reference_solve needs ILCC_SOLVER_REFERENCE_LOCAL";
+    return ILCC_BAD_ARGUMENT;
+  }
+  ILCC_TRY(check_offsets(h, offsets, n_frames));
+  const uint64_t total = offsets[n_frames];
+  if (total > 0 && (!yz || !label)) return ILCC_BAD_ARGUMENT;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const hipStream_t s = h->stream[take_stream(h)];
+  // what K4/K5 leave behind for the back end: offsets, labelled counts (+ walk strides), and a record per frame -- zeroed but for
+  // the caller's status
+  std::vector<uint32_t> n_lab(n_frames), stride(n_frames);
+  std::vector<ilcc_result> res(n_frames);
+  std::memset(res.data(), 0, sizeof(ilcc_result) * n_frames);
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    n_lab[f] = (uint32_t)(offsets[f + 1] - offsets[f]);
+    stride[f] = walk_stride(n_lab[f]);
+    res[f].status = status_in[f];
+  }
+  HIP_TRY(h, hipMemcpyAsync(sl.d_off, offsets, sizeof(uint64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_res, res.data(), sizeof(ilcc_result) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_nlab, n_lab.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_walk, stride.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  if (total > 0) {
+    HIP_TRY(h, hipMemcpyAsync(sl.d_yz, yz, sizeof(float2) * total, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(sl.d_lab, label, total, hipMemcpyHostToDevice, s));
+  }
+  // (a record slot the launch does not write comes back with every bit set: valid == -1, never 0 or 1)
+  HIP_TRY(h, hipMemsetAsync(sl.d_solverec, 0xFF, sizeof(SolveRec) * 2 * n_frames, s));
+  sl.n_frames = 0;   // the stage buffers no longer describe a batch
+  // the handle's capacities as they are (diagnostic_ctx would grow the staging to the frame): the caller decides which frames
+  // stay in global memory
+  const Ctx c = make_ctx(h, sl, nullptr, nullptr, n_frames, 1);
+  launch_reference_solve(c, s);
+  launch_corners(c, s, solve_slots(c.p));
+  HIP_TRY(h, hipGetLastError());
+  std::vector<SolveRec> rec(2 * (size_t)n_frames);
+  HIP_TRY(h, hipMemcpyAsync(rec.data(), sl.d_solverec, sizeof(SolveRec) * rec.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipMemcpyAsync(results, sl.d_res, sizeof(ilcc_result) * n_frames, hipMemcpyDeviceToHost, s));
+  ILCC_TRY(sync_own(h, s));
+  for (size_t k = 0; k < rec.size(); ++k) {
+    const SolveRec& r = rec[k];
+    const double d[ILCC_SOLVE_REC_DOUBLES] = {r.x[0], r.x[1], r.x[2], r.cost_a, r.cost_b, r.sel};
+    const int32_t i[ILCC_SOLVE_REC_INTS] = {r.iters_a, r.iters_b, r.phase, r.valid};
+    std::memcpy(rec_f64 + ILCC_SOLVE_REC_DOUBLES * k, d, sizeof(d));
+    std::memcpy(rec_i32 + ILCC_SOLVE_REC_INTS * k, i, sizeof(i));
+  }
+  if (lds_points) *lds_points = c.grid_lds_points;
+  return ILCC_OK;
+}
+
 int32_t ilcc_pattern_refine(ilcc_handle* h, const float* yz, const uint8_t* label, uint32_t m, int32_t lat[3],
                             int32_t* phase, int64_t* cost_q, int64_t* alt_cost_q, int32_t* rounds, int32_t* hops) {
   if (!h || !lat || !phase) return ILCC_BAD_ARGUMENT;

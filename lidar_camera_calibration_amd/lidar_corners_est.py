@@ -495,6 +495,38 @@ class LidarCornersBatch:
             raise IlccError(st, self._err())
         return t, cost.value, it.value
 
+    def debug_reference_solve(self, frames, status_in=None) -> dict:
+        """The REFERENCE_LOCAL back end (K7a then K7b, as the pipeline launches them) on a batch of caller-supplied labelled
+        frames: ``frames`` is a sequence of (yz[m, 2], label[m]); ``status_in[f]`` != OK marks frame f as failed by the front end.
+        -> dict(x[F, 2, 3], cost_a / cost_b / sel [F, 2], iters_a / iters_b / phase / valid [F, 2] -- the two phase slots of
+        every frame, valid == -1 where the launch wrote nothing -- results: the frames' records after K7b, lds_points: the
+        staging capacity the launch ran with; the handle's capacities are not grown).  Diagnostic entry."""
+        f = len(frames)
+        counts = [len(lab) for _, lab in frames]
+        offsets = np.zeros(f + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(counts, dtype=np.uint64)
+        yz = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 2) for a, _ in frames] or
+                                                 [np.zeros((0, 2), np.float32)]), dtype=np.float32)
+        label = np.ascontiguousarray(np.concatenate([np.asarray(b, np.uint8).reshape(-1) for _, b in frames] or
+                                                    [np.zeros(0, np.uint8)]), dtype=np.uint8)
+        status = np.ascontiguousarray(np.zeros(f, np.int32) if status_in is None else status_in, dtype=np.int32)
+        if len(status) != f:
+            raise IlccError(N.BAD_ARGUMENT, "debug_reference_solve: one status per frame")
+        d = np.zeros((f, 2, N.SOLVE_REC_DOUBLES), dtype=np.float64)
+        i = np.zeros((f, 2, N.SOLVE_REC_INTS), dtype=np.int32)
+        res = (N.Result * max(f, 1))()
+        lds = C.c_uint32(0)
+        st = self._lib.ilcc_debug_reference_solve(self._h, N.fptr(yz), label.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  status.ctypes.data_as(C.POINTER(C.c_int32)), f,
+                                                  d.ctypes.data_as(C.POINTER(C.c_double)), i.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  res, C.byref(lds))
+        if st != N.OK:
+            raise IlccError(st, self._err())
+        return dict(x=d[:, :, 0:3].copy(), cost_a=d[:, :, 3].copy(), cost_b=d[:, :, 4].copy(), sel=d[:, :, 5].copy(),
+                    iters_a=i[:, :, 0].copy(), iters_b=i[:, :, 1].copy(), phase=i[:, :, 2].copy(), valid=i[:, :, 3].copy(),
+                    results=res, lds_points=int(lds.value))
+
     def timing(self) -> N.Timing:
         t = N.Timing()
         self._lib.ilcc_get_timing(self._h, C.byref(t))

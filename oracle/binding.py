@@ -113,6 +113,14 @@ def lib():
         L.orc_cost.restype = C.c_double
         L.orc_get_theta_t.argtypes = [fp, C.c_int32, dp, pp, C.c_int32, C.c_int32, dp, dp]
         L.orc_get_theta_t.restype = C.c_int32
+        L.orc_reference_solve.argtypes = [fp, fp, bp, C.c_int32, pp, C.c_int32, dp, dp, dp, dp, ip, ip]
+        L.orc_reference_solve.restype = None
+        L.orc_coverage.argtypes = [dp, fp, fp, C.c_int32, pp, ip, ip]
+        L.orc_coverage.restype = None
+        L.orc_trace_reset.argtypes = []
+        L.orc_trace_reset.restype = None
+        L.orc_trace_get.argtypes = [ip]
+        L.orc_trace_get.restype = None
         L.orc_grid_search.argtypes = [fp, fp, bp, C.c_int32, pp, C.c_int32, dp, dp]
         L.orc_grid_search.restype = C.c_int32
         L.orc_cost_q.argtypes = [dp, fp, fp, bp, C.c_int32, pp, C.c_int32, C.c_int32]
@@ -260,6 +268,48 @@ def get_theta_t(pts_pca, gz, p, tlw, use_oob, theta_t0=(0.0, 0.0, 0.0)):
     it = lib().orc_get_theta_t(xp, len(x), gp, C.byref(p), int(tlw), int(use_oob),
                                t.ctypes.data_as(C.POINTER(C.c_double)), C.byref(c))
     return t, c.value, it
+
+
+def reference_solve(y, z, label, p, phase, x0=(0.0, 0.0, 0.0)):
+    """ORC_SOLVER_REFERENCE_LOCAL's solve of one colour phase (pass A, pass B, with-OOB cost) from x0
+    -> dict(x, cost_a, cost_b, sel, iters_a, iters_b)"""
+    yy, yp = _f(y)
+    zz, zp = _f(z)
+    lab = np.ascontiguousarray(label, dtype=np.int8)
+    x = np.array(x0, dtype=np.float64)
+    ca, cb, sel = C.c_double(0), C.c_double(0), C.c_double(0)
+    ia, ib = C.c_int32(0), C.c_int32(0)
+    lib().orc_reference_solve(yp, zp, lab.ctypes.data_as(C.POINTER(C.c_int8)), len(yy), C.byref(p), int(phase),
+                              x.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ca), C.byref(cb), C.byref(sel), C.byref(ia), C.byref(ib))
+    return dict(x=x, cost_a=ca.value, cost_b=cb.value, sel=sel.value, iters_a=ia.value, iters_b=ib.value)
+
+
+def coverage(theta_t, y, z, p):
+    """-> (cells of the virtual board that hold a point, points outside the outline) under theta_t"""
+    t, tp = _d(theta_t)
+    yy, yp = _f(y)
+    zz, zp = _f(z)
+    cells, oob = C.c_int32(0), C.c_int32(0)
+    lib().orc_coverage(tp, yp, zp, len(yy), C.byref(p), C.byref(cells), C.byref(oob))
+    return cells.value, oob.value
+
+
+# the branch counters of the trust-region minimiser, in the order of ilcc_oracle.h's ORC_TRACE_* enum
+TRACE_NAMES = ("solves", "gauss_newton_inside", "subspace_boundary", "boundary_reused", "one_dim_subspace", "traditional_fallback",
+               "mu_escalation", "linear_solver_failure", "invalid_step", "rejected", "accepted_grow", "accepted_keep",
+               "accepted_halve", "end_iteration_cap", "end_gradient_tolerance", "end_gradient_tolerance_at_0", "end_min_radius",
+               "end_invalid_steps", "end_parameter_tolerance", "end_function_tolerance")
+
+
+def trace_reset():
+    lib().orc_trace_reset()
+
+
+def trace_get() -> dict:
+    """{branch: times taken since trace_reset()} over every minimisation the oracle ran"""
+    out = (C.c_int32 * len(TRACE_NAMES))()
+    lib().orc_trace_get(out)
+    return dict(zip(TRACE_NAMES, (int(v) for v in out)))
 
 
 def grid_search(y, z, label, p, use_oob, want_volume=False):

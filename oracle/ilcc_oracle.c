@@ -951,6 +951,13 @@ static void min_on_circle(const double B[4], const double g[2], double radius, d
   }
 }
 
+/* Branch trace of trust_region_minimize / dogleg_compute_step: plain counters, one per branch (orc_trace_reset / orc_trace_get).
+ * They change no arithmetic; a test reads them to state which code a case runs.  One set per process (not thread safe). */
+static int32_t g_trace[ORC_TRACE_COUNT];
+#define TRACE(k) (++g_trace[k])
+void orc_trace_reset(void) { memset(g_trace, 0, sizeof(g_trace)); }
+void orc_trace_get(int32_t out[ORC_TRACE_COUNT]) { memcpy(out, g_trace, sizeof(g_trace)); }
+
 typedef struct {
   int np;
   double radius, mu;
@@ -1005,6 +1012,7 @@ static void dogleg_traditional(dogleg_state* s, double* step) {
 static int dogleg_compute_step(dogleg_state* s, int32_t n, const double* J, const double* r,
                                double* step) {
   const int np = s->np;
+  const int reused = s->reuse;
   if (!s->reuse) {
     s->reuse = 1;
     double JtJ[ORC_MAXP * ORC_MAXP] = {0}, Jtr[ORC_MAXP] = {0};
@@ -1044,8 +1052,12 @@ static int dogleg_compute_step(dogleg_state* s, int32_t n, const double* J, cons
         break;
       }
       s->mu *= 10.0;
+      TRACE(ORC_TRACE_MU_ESCALATION);
     }
-    if (!ok) return 0;
+    if (!ok) {
+      TRACE(ORC_TRACE_LINEAR_SOLVER_FAILURE);
+      return 0;
+    }
     for (int c = 0; c < np; ++c) s->gn[c] *= -s->diagonal[c];
     /* subspace model: orthonormal basis of span{gradient, gn} (Gram-Schmidt with pivoting,
      * standing in for Eigen::ColPivHouseholderQR; signs of the basis do not matter) */
@@ -1099,9 +1111,11 @@ static int dogleg_compute_step(dogleg_state* s, int32_t n, const double* J, cons
   if (gnn <= s->radius) {
     for (int c = 0; c < np; ++c) step[c] = s->gn[c] / s->diagonal[c];
     s->step_norm = gnn;
+    TRACE(ORC_TRACE_GAUSS_NEWTON_INSIDE);
     return 1;
   }
   if (s->one_dim) {
+    TRACE(ORC_TRACE_ONE_DIM_SUBSPACE);
     const double gn_ = vnorm(s->gradient, np);
     for (int c = 0; c < np; ++c) step[c] = -(s->radius / gn_) * s->gradient[c] / s->diagonal[c];
     s->step_norm = s->radius;
@@ -1110,9 +1124,12 @@ static int dogleg_compute_step(dogleg_state* s, int32_t n, const double* J, cons
   double y2[2];
   min_on_circle(s->sB, s->sg, s->radius, y2);
   if (!isfinite(y2[0]) || !isfinite(y2[1])) {
+    TRACE(ORC_TRACE_TRADITIONAL_FALLBACK);
     dogleg_traditional(s, step);
     return 1;
   }
+  TRACE(ORC_TRACE_SUBSPACE_BOUNDARY);
+  if (reused) TRACE(ORC_TRACE_BOUNDARY_REUSED);
   for (int c = 0; c < np; ++c)
     step[c] = (s->basis[c][0] * y2[0] + s->basis[c][1] * y2[1]) / s->diagonal[c];
   s->step_norm = s->radius;
@@ -1129,6 +1146,7 @@ static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* fi
     *final_cost = 0;
     return 0;
   }
+  TRACE(ORC_TRACE_SOLVES);
   double* r = (double*)malloc(sizeof(double) * (size_t)n);
   double* J = (double*)malloc(sizeof(double) * (size_t)np * (size_t)n);
   double scale[ORC_MAXP];
@@ -1157,11 +1175,21 @@ static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* fi
   int invalid = 0;
   for (;;) {
     /* FinalizeIterationAndCheckIfMinimizerCanContinue */
-    if (iter >= max_iter) break;
+    if (iter >= max_iter) {
+      TRACE(ORC_TRACE_END_ITERATION_CAP);
+      break;
+    }
     double gmax = 0;
     for (int c = 0; c < np; ++c) gmax = fmax(gmax, fabs(grad[c]));
-    if (gmax <= 1e-10) break;
-    if (st.radius <= 1e-32) break;
+    if (gmax <= 1e-10) {
+      TRACE(ORC_TRACE_END_GRADIENT_TOLERANCE);
+      if (iter == 0) TRACE(ORC_TRACE_END_GRADIENT_TOLERANCE_AT_0);
+      break;
+    }
+    if (st.radius <= 1e-32) {
+      TRACE(ORC_TRACE_END_MIN_RADIUS);
+      break;
+    }
     ++iter;
 
     double step[ORC_MAXP];
@@ -1176,7 +1204,11 @@ static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* fi
       valid = model_cost_change > 0.0;
     }
     if (!valid) {
-      if (++invalid >= 5) break;
+      TRACE(ORC_TRACE_INVALID_STEP);
+      if (++invalid >= 5) {
+        TRACE(ORC_TRACE_END_INVALID_STEPS);
+        break;
+      }
       st.mu *= 10.0; /* StepIsInvalid */
       st.reuse = 0;
       continue;
@@ -1192,12 +1224,19 @@ static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* fi
     double dn = 0;
     for (int c = 0; c < np; ++c) dn += (x[c] - cand[c]) * (x[c] - cand[c]);
     const double step_norm = sqrt(dn);
-    if (step_norm <= 1e-8 * (x_norm + 1e-8)) break;
+    if (step_norm <= 1e-8 * (x_norm + 1e-8)) {
+      TRACE(ORC_TRACE_END_PARAMETER_TOLERANCE);
+      break;
+    }
     /* FunctionToleranceReached */
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= 1e-6 * x_cost) break;
+    if (fabs(cost_change) <= 1e-6 * x_cost) {
+      TRACE(ORC_TRACE_END_FUNCTION_TOLERANCE);
+      break;
+    }
     const double rel = cost_change / model_cost_change;
     if (rel > 1e-3) {
+      TRACE(rel < 0.25 ? ORC_TRACE_ACCEPTED_HALVE : rel > 0.75 ? ORC_TRACE_ACCEPTED_GROW : ORC_TRACE_ACCEPTED_KEEP);
       /* HandleSuccessfulStep */
       for (int c = 0; c < np; ++c) x[c] = cand[c];
       x_norm = vnorm(x, np);
@@ -1214,6 +1253,7 @@ static int32_t trust_region_minimize(const lsq_problem* q, double* x, double* fi
       st.mu = fmax(1e-8, 2.0 * st.mu / 10.0);
       st.reuse = 0;
     } else {
+      TRACE(ORC_TRACE_REJECTED);
       st.radius *= 0.5; /* StepRejected */
       st.reuse = 1;
     }
@@ -1382,6 +1422,25 @@ int32_t orc_get_theta_t(const float* pts_pca, int32_t m, const double gray_zone[
   free(z);
   free(lab);
   return it;
+}
+
+/* LidarCornersEst::get_corners' two local solves for one colour phase (:398-409): pass A with the out-of-board term, pass B
+ * without it from A's result, then the with-OOB cost at the final point -- what ORC_SOLVER_REFERENCE_LOCAL selects a phase by. */
+void orc_reference_solve(const float* y, const float* z, const int8_t* label, int32_t m, const orc_params* p, int32_t phase,
+                         double x[3], double* cost_a, double* cost_b, double* sel, int32_t* iters_a, int32_t* iters_b) {
+  lsq_problem q;
+  memset(&q, 0, sizeof(q));
+  q.n = m;
+  q.y = y;
+  q.z = z;
+  q.lab = label;
+  q.p = p;
+  q.tlw = phase;
+  q.oob = 1; /* pass A :403-405 */
+  *iters_a = trust_region_minimize(&q, x, cost_a);
+  q.oob = 0; /* pass B :406-408 */
+  *iters_b = trust_region_minimize(&q, x, cost_b);
+  *sel = orc_cost(x, y, z, label, m, p, phase, 1);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -1704,14 +1763,6 @@ int32_t orc_extract(const float* xyzi, int32_t n, const float click[3], const or
       out->basin_margin = ((double)alt - (double)c) / (double)(c > 0 ? c : 1);
       if (p->ambiguity_eps > 0.0 && out->basin_margin < p->ambiguity_eps) status = ORC_AMBIGUOUS;
     } else {
-    double th[3] = {0, 0, 0};
-    lsq_problem q;
-    memset(&q, 0, sizeof(q));
-    q.n = nl;
-    q.y = y;
-    q.z = z;
-    q.lab = lab;
-    q.p = p;
     /* phases to try: the reference's first loop turn uses topleftWhite=false (:379,398-401); the user's 'd' key
      * toggles it (Visualization.cpp:45-48).  phase_mode 2 replaces the key press by trying both
      * from (0,0,0) and keeping the lower final cost measured WITH the out-of-board term. */
@@ -1720,14 +1771,10 @@ int32_t orc_extract(const float* xyzi, int32_t n, const float click[3], const or
     else { ph_lo = ph_hi = (p->phase_mode == 1); }
     double best_sel = DBL_MAX;
     for (int32_t ph = ph_lo; ph <= ph_hi; ++ph) {
-      double t[3] = {th[0], th[1], th[2]};
-      double ca = 0, cb = 0;
-      q.tlw = ph;
-      q.oob = 1; /* pass A :403-405 */
-      const int32_t ia = trust_region_minimize(&q, t, &ca);
-      q.oob = 0; /* pass B :406-408 */
-      const int32_t ib = trust_region_minimize(&q, t, &cb);
-      const double sel = orc_cost(t, y, z, lab, nl, p, ph, 1);
+      double t[3] = {0, 0, 0};
+      double ca = 0, cb = 0, sel = 0;
+      int32_t ia = 0, ib = 0;
+      orc_reference_solve(y, z, lab, nl, p, ph, t, &ca, &cb, &sel, &ia, &ib);
       if (sel < best_sel) {
         best_sel = sel;
         out->iters_a = ia;

@@ -177,6 +177,41 @@ int32_t orc_get_theta_t(const float* pts_pca, int32_t m, const double gray_zone[
                         const orc_params* p, int32_t topleft_white, int32_t use_oob,
                         double theta_t[3], double* cost);
 
+/* ORC_SOLVER_REFERENCE_LOCAL's solve of one colour phase on labelled points: pass A (out-of-board term on) from x, pass B (off)
+ * from A's result, x in/out; *sel = the with-OOB cost at the final x (what the phase is chosen by).  orc_extract calls it from
+ * (0,0,0) for each phase it tries. */
+void orc_reference_solve(const float* y, const float* z, const int8_t* label, int32_t m, const orc_params* p, int32_t phase,
+                         double x[3], double* cost_a, double* cost_b, double* sel, int32_t* iters_a, int32_t* iters_b);
+
+/* Branch trace of the trust-region minimiser (every caller: orc_get_theta_t, orc_reference_solve, orc_extract,
+ * orc_solve_pose_3d2d): one counter per branch since the last orc_trace_reset.  Counting changes no arithmetic.  Process-wide,
+ * not thread safe: test infrastructure. */
+enum {
+  ORC_TRACE_SOLVES = 0,               /* minimisations started (n > 0) */
+  ORC_TRACE_GAUSS_NEWTON_INSIDE,      /* dogleg: the Gauss-Newton step lies inside the radius */
+  ORC_TRACE_SUBSPACE_BOUNDARY,        /* dogleg: step on the boundary of the 2-D subspace model (min_on_circle) */
+  ORC_TRACE_BOUNDARY_REUSED,          /* ... on a linearisation kept from a rejected step */
+  ORC_TRACE_ONE_DIM_SUBSPACE,         /* dogleg: gradient and Gauss-Newton step parallel -> step along the gradient */
+  ORC_TRACE_TRADITIONAL_FALLBACK,     /* dogleg: min_on_circle not finite -> traditional dogleg */
+  ORC_TRACE_MU_ESCALATION,            /* dogleg: Cholesky failed, mu x 10 */
+  ORC_TRACE_LINEAR_SOLVER_FAILURE,    /* dogleg: no mu < 1 factorises */
+  ORC_TRACE_INVALID_STEP,             /* no step, or model_cost_change <= 0 */
+  ORC_TRACE_REJECTED,                 /* step rejected (radius halved, linearisation kept) */
+  ORC_TRACE_ACCEPTED_GROW,            /* step accepted, rel > 0.75 (radius = max(radius, 3 |step|)) */
+  ORC_TRACE_ACCEPTED_KEEP,            /* step accepted, 0.25 <= rel <= 0.75 */
+  ORC_TRACE_ACCEPTED_HALVE,           /* step accepted, rel < 0.25 (radius halved) */
+  ORC_TRACE_END_ITERATION_CAP,
+  ORC_TRACE_END_GRADIENT_TOLERANCE,
+  ORC_TRACE_END_GRADIENT_TOLERANCE_AT_0, /* ... before the first iteration (also counted in the line above) */
+  ORC_TRACE_END_MIN_RADIUS,
+  ORC_TRACE_END_INVALID_STEPS,        /* the fifth invalid step in a row */
+  ORC_TRACE_END_PARAMETER_TOLERANCE,
+  ORC_TRACE_END_FUNCTION_TOLERANCE,
+  ORC_TRACE_COUNT
+};
+void orc_trace_reset(void);
+void orc_trace_get(int32_t out[ORC_TRACE_COUNT]);
+
 /* exhaustive grid (spec of the GPU search): both phases, chosen OOB flag; returns winning flat index
  * ((k*n_ty + a)*n_tz + b)*2 + phase ; cost_out (optional) full volume [n_th*n_ty*n_tz*2].
  * Candidates are ordered by the fixed-point cost (orc_cost_q); the doubles returned are cost_q * 2^-40. */

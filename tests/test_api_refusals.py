@@ -166,10 +166,13 @@ def test_synchronous_and_diagnostic_calls_are_refused_while_ticket_0_is_in_fligh
         lambda: L.ilcc_grid_cost(h, N.fptr(yz), labp, 8, 1, None, None, None),
         lambda: L.ilcc_get_theta_t(h, N.fptr(yz), labp, 8, 0, 1, theta_t, None, None),
         lambda: L.ilcc_pattern_refine(h, N.fptr(yz), labp, 8, lat, C.byref(phase), None, None, None, None),
+        lambda: L.ilcc_debug_reference_solve(h, N.fptr(yz), labp, (C.c_uint64 * 2)(0, 8), (C.c_int32 * 1)(0), 1, (C.c_double * 12)(),
+                                             (C.c_int32 * 8)(), res, None),
     ]
     for call in calls:
         e.refused(call(), N.BAD_ARGUMENT)
         assert e.busy(0)
+    assert "ticket 0 is in flight" in e.err()
     assert e.wait(0) == w.ref
     assert e.wait(e.accepted(*w.host)) == w.ref
 
