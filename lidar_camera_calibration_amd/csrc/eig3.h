@@ -1,13 +1,20 @@
 // eig3.h -- 3x3 symmetric eigen-decomposition (cyclic Jacobi, double), ascending eigenvalues.
 // Stands in for Eigen::SelfAdjointEigenSolver<Matrix3f> (LidarCornersEst.cpp:337-339) and for
-// pcl::eigen33 inside SACSegmentation's coefficient refinement.  Single-thread device code.
+// pcl::eigen33 inside SACSegmentation's coefficient refinement.  Single-thread device code; plain C++ for a host-only build
+// (seed_host.cpp, which also builds without HIP).
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define ILCC_EIG3_FN __host__ __device__ inline
+#else
+#include <cmath>
+#define ILCC_EIG3_FN inline
+#endif
 
 namespace ilcc {
 
 // a: row-major symmetric 3x3.  w[c] ascending, v[c][*] = unit eigenvector c.
-__device__ inline void eig3_sym(const double a_in[9], double w[3], double v[3][3]) {
+ILCC_EIG3_FN void eig3_sym(const double a_in[9], double w[3], double v[3][3]) {
   double a[3][3], q[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) a[i][j] = a_in[3 * i + j];

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ilcc_internal.h"
+#include "k15_seed.h"
 #include "k6_common.h"
 #include "k7_common.h"
 
@@ -1211,6 +1212,12 @@ Ctx diagnostic_ctx(ilcc_handle* h, Slot& sl, uint32_t m) {
 namespace ilcc {
 // text behind ilcc_last_error(NULL) for the handle-less entry points in other translation units
 void set_global_error(const std::string& s) { g_err = s; }
+// what the seed entries (seed_api.cpp) need of a handle
+HandleView handle_view(const ilcc_handle* h) { return HandleView{h->device, h->p, h->max_frames, h->max_points}; }
+int32_t handle_fail(ilcc_handle* h, int32_t code, const std::string& what) {
+  h->err = what;
+  return code;
+}
 }  // namespace ilcc
 
 extern "C" {

@@ -6,7 +6,8 @@
 
 namespace ilcc_host {
 
-LidarCornersEst::LidarCornersEst(int device, uint32_t max_points) : m_device(device), m_max_points(max_points) {
+LidarCornersEst::LidarCornersEst(int device, uint32_t max_points, uint32_t max_frames)
+    : m_device(device), m_max_points(max_points), m_max_frames(max_frames < 1 ? 1 : max_frames) {
   ilcc_default_params(&m_params);
   m_cloud_ROI.reset(new myPointCloud);
   m_cloud_chessboard.reset(new myPointCloud);
@@ -37,21 +38,46 @@ void LidarCornersEst::setROI(myPointCloudPtr cloud, PointXYZI point) {
   m_done = false;
 }
 
+bool LidarCornersEst::ensure_handle() {
+  if (m_handle) return true;
+  if (ilcc_abi_version() != ILCC_ABI_VERSION) {   // a stale libilcc_hip.so: ilcc_result / ilcc_params would be read at the wrong offsets
+    std::cerr << "libilcc_hip.so implements ABI " << ilcc_abi_version() << ", this host was compiled against ABI "
+              << ILCC_ABI_VERSION << std::endl;
+    return false;
+  }
+  m_handle = ilcc_create(m_device, &m_params, m_max_frames, (uint64_t)m_max_points * m_max_frames);
+  if (!m_handle) {
+    std::cerr << "ilcc_create failed: " << ilcc_last_error(nullptr) << std::endl;
+    return false;
+  }
+  return true;
+}
+
+bool LidarCornersEst::find_board(myPointCloudPtr cloud, const ilcc_seed_params* seed_params) {
+  if (!cloud || !ensure_handle()) return false;
+  ilcc_seed_params sp;
+  if (seed_params) {
+    sp = *seed_params;
+  } else {
+    ilcc_default_seed_params(&m_params, &sp);
+    if ((uint32_t)sp.max_seeds > m_max_frames) sp.max_seeds = (int32_t)m_max_frames;
+  }
+  ilcc_result picked{};
+  float seed[3] = {0.f, 0.f, 0.f};
+  int32_t rank = -1;
+  const int32_t st = ilcc_extract_auto(m_handle, reinterpret_cast<const float*>(cloud->data()), (uint32_t)cloud->size(), &sp, &picked, seed, &rank);
+  if (st != ILCC_OK) {
+    std::cerr << "ilcc_extract_auto: " << ilcc_strerror(st) << " " << ilcc_last_error(m_handle) << std::endl;
+    return false;
+  }
+  setROI(cloud, PointXYZI{seed[0], seed[1], seed[2], 0.f});   // the stages run on this seed as on a click
+  return rank >= 0;
+}
+
 bool LidarCornersEst::run() {
   if (m_done) return true;
   if (!m_input) return false;
-  if (!m_handle) {
-    if (ilcc_abi_version() != ILCC_ABI_VERSION) {   // a stale libilcc_hip.so: ilcc_result / ilcc_params would be read at the wrong offsets
-      std::cerr << "libilcc_hip.so implements ABI " << ilcc_abi_version() << ", this host was compiled against ABI "
-                << ILCC_ABI_VERSION << std::endl;
-      return false;
-    }
-    m_handle = ilcc_create(m_device, &m_params, 1, m_max_points);
-    if (!m_handle) {
-      std::cerr << "ilcc_create failed: " << ilcc_last_error(nullptr) << std::endl;
-      return false;
-    }
-  }
+  if (!ensure_handle()) return false;
   const float click[3] = {m_click_point.x, m_click_point.y, m_click_point.z};
   static_assert(sizeof(PointXYZI) == 16, "packed XYZI");
   const int32_t st = ilcc_extract(m_handle, reinterpret_cast<const float*>(m_input->data()),

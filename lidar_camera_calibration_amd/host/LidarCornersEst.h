@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ilcc_hip.h"
+#include "ilcc_seed.h"
 
 namespace ilcc_host {
 
@@ -25,7 +26,8 @@ class LidarCornersEst {
  public:
   typedef std::shared_ptr<LidarCornersEst> Ptr;
 
-  explicit LidarCornersEst(int device = -1, uint32_t max_points = 200000);
+  // max_frames: the proposals find_board may try per scan (each is a frame of one batch of max_points points)
+  explicit LidarCornersEst(int device = -1, uint32_t max_points = 200000, uint32_t max_frames = 1);
   ~LidarCornersEst();
   LidarCornersEst(const LidarCornersEst&) = delete;
   LidarCornersEst& operator=(const LidarCornersEst&) = delete;
@@ -36,6 +38,10 @@ class LidarCornersEst {
 
   bool set_chessboard_param(std::string cam_yaml);            // LidarCornersEst.cpp:20-46
   void setROI(myPointCloudPtr cloud, PointXYZI point);        // :48-70
+  // setROI without the click (include/ilcc_seed.h): proposes seeds on the whole cloud, runs the path on each and keeps the first
+  // it accepts.  true: m_click_point is that seed and the scan is set up as setROI(cloud, m_click_point) leaves it.  seed_params:
+  // nullptr = ilcc_default_seed_params with at most max_frames seeds
+  bool find_board(myPointCloudPtr cloud, const ilcc_seed_params* seed_params = nullptr);
   bool EuclideanCluster();                                    // :124-186
   void PCA();                                                 // :366-372
   bool get_corners(std::vector<std::array<double, 3>>& corners);   // :374-450
@@ -57,6 +63,7 @@ class LidarCornersEst {
 
  private:
   bool run();
+  bool ensure_handle();
   myPointCloudPtr fetch(int32_t which);
 
   ilcc_params m_params{};
@@ -66,6 +73,7 @@ class LidarCornersEst {
   bool m_done = false;
   int m_device;
   uint32_t m_max_points;
+  uint32_t m_max_frames;
 };
 
 // get_lidar_corners.cpp:27-36

@@ -4,6 +4,7 @@
 //                [--solver grid|reference] [--device N] [--accept-ambiguous] [--accept-low-coverage]
 //   ilcc_corners --bag 20181101_1.bag [--topic /velodyne_points] --click x y z ... (first PointCloud2
 //                of the bag, read without ROS: include/ilcc_ingest.h)
+//   --auto in place of --click x y z: the seed is proposed from the cloud itself (include/ilcc_seed.h) and printed
 // Mirrors the per-bag body of /root/reference/ilcc2/test/get_lidar_corners.cpp:133-204.
 #include <cstdio>
 #include <cstdlib>
@@ -21,7 +22,7 @@ int main(int argc, char** argv) {
   std::string cloud_path, bag_path, topic = "/velodyne_points", yaml_path, out_path, solver = "grid";
   PointXYZI click{0, 0, 0, 0};
   int device = -1;
-  bool have_click = false, accept_ambiguous = false, accept_low_coverage = false;
+  bool have_click = false, auto_seed = false, accept_ambiguous = false, accept_low_coverage = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--cloud" && i + 1 < argc) cloud_path = argv[++i];
@@ -33,6 +34,7 @@ int main(int argc, char** argv) {
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--accept-ambiguous") accept_ambiguous = true;
     else if (a == "--accept-low-coverage") accept_low_coverage = true;
+    else if (a == "--auto") auto_seed = true;
     else if (a == "--click" && i + 3 < argc) {
       click.x = (float)std::atof(argv[++i]);
       click.y = (float)std::atof(argv[++i]);
@@ -43,8 +45,8 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if ((cloud_path.empty() == bag_path.empty()) || out_path.empty() || !have_click) {
-    std::fprintf(stderr, "usage: ilcc_corners (--cloud frame.bin | --bag file.bag [--topic /velodyne_points]) --click x y z "
+  if ((cloud_path.empty() == bag_path.empty()) || out_path.empty() || have_click == auto_seed) {
+    std::fprintf(stderr, "usage: ilcc_corners (--cloud frame.bin | --bag file.bag [--topic /velodyne_points]) (--click x y z | --auto) "
                          "[--yaml board.yaml] --out file.txt [--solver grid|reference] [--device N] [--accept-ambiguous] [--accept-low-coverage]\n");
     return 2;
   }
@@ -73,14 +75,22 @@ int main(int argc, char** argv) {
     in.read(reinterpret_cast<char*>(cloud->data()), (std::streamsize)(cloud->size() * sizeof(PointXYZI)));
   }
 
-  LidarCornersEst est(device, (uint32_t)cloud->size() + 1);
+  LidarCornersEst est(device, (uint32_t)cloud->size() + 1, auto_seed ? 4u : 1u);
   est.params().solver = (solver == "reference") ? ILCC_SOLVER_REFERENCE_LOCAL : ILCC_SOLVER_GRID;
   est.accept_ambiguous = accept_ambiguous;
   est.accept_low_coverage = accept_low_coverage;
   est.register_viewer();
   if (!yaml_path.empty() && !est.set_chessboard_param(yaml_path)) return 1;
 
-  est.setROI(cloud, click);                          // get_lidar_corners.cpp:183
+  if (auto_seed) {
+    if (!est.find_board(cloud)) {
+      std::printf("no chessboard found\n");
+      return 3;
+    }
+    std::printf("seed %.9g %.9g %.9g\n", est.m_click_point.x, est.m_click_point.y, est.m_click_point.z);
+  } else {
+    est.setROI(cloud, click);                        // get_lidar_corners.cpp:183
+  }
   if (!est.EuclideanCluster()) return 3;             // :188
   est.PCA();                                         // :191
   std::vector<std::array<double, 3>> lidar_corner;

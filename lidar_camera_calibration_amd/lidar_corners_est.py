@@ -110,6 +110,29 @@ class LidarCornersEst:
         self.m_click_point = self._click.copy()
         self._result = None
 
+    def find_board(self, cloud: np.ndarray, seed_params=None):
+        """setROI without the click (include/ilcc_seed.h): proposes seeds on the whole cloud, runs the path on each and keeps
+        the first it accepts.  Returns ``(found, seed)``; the scan is then set up as ``setROI(cloud, seed)`` would have left
+        it, so ``EuclideanCluster`` / ``PCA`` / ``get_corners`` follow as usual.  At most ``max_frames`` (the constructor's)
+        proposals are tried per scan."""
+        from . import seed as S
+        self.setROI(cloud, (0.0, 0.0, 0.0))
+        h = self._handle()
+        sp = seed_params if seed_params is not None else S.default_seed_params(self.params)
+        if seed_params is None:
+            sp.max_seeds = max(1, min(sp.max_seeds, self._max_frames))
+        res, seeds, ranks = S.extract_auto(self, self._cloud, None, sp)
+        self._click = seeds[0].copy()
+        self.m_click_point = self._click.copy()
+        if ranks[0] < 0:
+            self._result = None
+            return False, self._click
+        # the handle's clouds are those of the candidate batch: run the accepted seed as the one frame get_corners fetches from
+        res1 = N.Result()
+        self._check(self._lib.ilcc_extract(h, N.fptr(self._cloud), len(self._cloud), N.fptr(self._click), C.byref(res1)))
+        self._result = res1
+        return True, self._click
+
     def _run(self):
         if self._result is None:
             if self._cloud is None:

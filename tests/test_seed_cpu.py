@@ -1,0 +1,126 @@
+"""The seed proposer, the part that needs no GPU: the numpy restatement (tests/seed_ref.py) against the CPU oracle's
+clusters and the true board poses on 64 config-2 frames, the committed closed-loop seeds, and the host finishing
+(csrc/seed_host.cpp) as a stand-alone program under AddressSanitizer and UBSan against the restatement."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import seed_cases as K
+import seed_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FRAMES = 64
+
+
+def test_every_euclidean_cluster_lies_inside_one_component(ob):
+    """Cells of edge >= tol with 26-connectivity: two points within tol of each other are in the same or adjacent cells, so
+    every single-linkage cluster of the oracle's ROI cloud has ONE root key."""
+    clouds, clicks, _, _ = K.config2(FRAMES)
+    p = ob.default_params()
+    n_clusters = 0
+    for f in range(FRAMES):
+        _, keep, roots = K.restated2(FRAMES)[f]
+        root_of_point = np.full(len(clouds[f]), -1, np.int64)
+        root_of_point[keep] = roots
+        idx = ob.roi_crop(clouds[f], clicks[f], p)
+        _, lab = ob.cluster(clouds[f][idx], clicks[f], p)
+        assert (root_of_point[idx] >= 0).all()
+        for c in np.unique(lab):
+            members = idx[lab == c]
+            assert len(np.unique(root_of_point[members])) == 1, (f, int(c))
+            n_clusters += 1
+    assert n_clusters >= FRAMES
+
+
+def test_board_component_centroid_is_near_the_true_centre():
+    clouds, _, _, poses = K.config2(FRAMES)
+    sp = R.SeedParams()
+    gated = 0
+    for f in range(FRAMES):
+        recs, keep, roots = K.restated2(FRAMES)[f]
+        kept = clouds[f][keep][:, :3]
+        board_key = int(roots[np.argmin(np.linalg.norm(kept - poses[f].centre, axis=1))])
+        for sd in R.finish(recs, sp):
+            if sd.key == board_key:
+                gated += 1
+                assert np.linalg.norm(sd.centroid - poses[f].centre) < 0.1, f
+    assert gated == FRAMES     # (measured: the board's component passes the gates on every one of the 1024 bench frames)
+
+
+def test_committed_closed_loop_seeds_are_the_restatement_s():
+    _, _, _, poses = K.config2(FRAMES)
+    assert [e[0] for e in K.CLOSED_LOOP_2] == list(range(32)) and [e[0] for e in K.CLOSED_LOOP_5] == [0, 1]
+    for (f, key, centroid) in K.CLOSED_LOOP_2:
+        seeds = R.finish(K.restated2(FRAMES)[f][0], R.SeedParams())
+        assert [(s.key, tuple(float(v) for v in s.centroid)) for s in seeds] == [(key, centroid)], f
+        assert np.linalg.norm(np.array(centroid) - poses[f].centre) < 0.1
+    clouds5, _, _, poses5 = K.config5(2)
+    for (f, key, centroid) in K.CLOSED_LOOP_5:
+        seeds = R.propose(clouds5[f], K.params5())
+        assert [(s.key, tuple(float(v) for v in s.centroid)) for s in seeds] == [(key, centroid)], f
+        assert np.linalg.norm(np.array(centroid) - poses5[f].centre) < 0.1
+
+
+def test_scene_without_a_board_has_no_seed():
+    assert R.propose(K.no_board_frame(), R.SeedParams()) == []
+
+
+def test_restated_components_of_constructed_plates():
+    sp = K.small_params()
+    for step in ((1, 0, 0), (1, 1, 0), (1, -1, 1)):
+        near, far = R.components(K.two_plates(step, 1), sp), R.components(K.two_plates(step, 2), sp)
+        assert [r[1] for r in near] == [50] and sorted(r[1] for r in far) == [25, 25], step
+
+
+@pytest.fixture(scope="module")
+def host_check(tmp_path_factory):
+    """The stand-alone program: tests/seed_host_check.cpp + csrc/seed_host.cpp only, under ASan and UBSan."""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a C++ compiler is needed"
+    out = tmp_path_factory.mktemp("seed_host_check")
+    exe = str(out / "seed_host_check")
+    csrc = os.path.join(ROOT, "lidar_camera_calibration_amd", "csrc")
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "seed_host_check.cpp"),
+                    os.path.join(csrc, "seed_host.cpp"), "-o", exe], check=True, timeout=300)
+    return exe, out
+
+
+# default gates; and gates wide enough for several components per frame to pass, so that the order among many is exercised
+# (sides within a factor 12 keep the eigenvalue ratio below 2^10: eigvalsh's absolute error stays below 1e-12 of the smaller one)
+@pytest.mark.parametrize("max_seeds,lo,hi,max_rms", [(4, 0.7, 1.3, 0.03), (64, 0.5, 12.0, 0.03), (2, 0.5, 12.0, 1.0)])
+def test_host_finishing_under_sanitizers_equals_the_restatement(host_check, max_seeds, lo, hi, max_rms):
+    exe, out = host_check
+    frames = [K.restated2(FRAMES)[f][0] for f in range(FRAMES)]
+    frames.append([])                                                             # a frame without records
+    frames.append(R.components(K.range_limit(), K.small_params()))                # one record, zero covariance, the largest sums
+    frames.append(R.components(K.two_plates((1, 0, 0), 2), K.small_params()))
+    src, dst = str(out / "records.txt"), str(out / "seeds.txt")
+    with open(src, "w") as fh:
+        fh.write("%d %r %r %r\n" % (max_seeds, lo, hi, max_rms))
+        for recs in frames:
+            fh.write("%d\n" % len(recs))
+            for r in recs:
+                fh.write(" ".join(str(v) for v in r) + "\n")
+    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    assert "frames %d" % len(frames) in r.stdout
+    lines = open(dst).read().split("\n")
+    at, n_seeds = 0, 0
+    sp = R.SeedParams(max_seeds=max_seeds, size_lo=lo, size_hi=hi, max_rms=max_rms)
+    for recs in frames:
+        want = R.finish(recs, sp)
+        assert int(lines[at]) == len(want)
+        for k, w in enumerate(want):
+            v = lines[at + 1 + k].split()
+            assert (int(v[0]), int(v[1])) == (w.key, w.n)                          # identical order
+            for got, ref in ((float(v[2]), w.l1), (float(v[3]), w.l2), (float(v[5]), w.score)):
+                assert abs(got - ref) <= 1e-12 * abs(ref), (got, ref)
+            assert [np.float32(float(x)) for x in v[6:9]] == list(w.centroid)
+        at += 1 + len(want)
+        n_seeds += len(want)
+    assert n_seeds >= FRAMES
