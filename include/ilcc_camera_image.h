@@ -11,7 +11,9 @@
  *     K, d, Camera.width / Camera.height of pointgrey.yaml
  *   rosbag View + first sensor_msgs/Image                                  ilcc_bag_first_message (ilcc_ingest.h)
  *     (test/get_image_corners_bag.cpp:78-84)                                with the Image md5sum
- *   ros::serialization of sensor_msgs/Image (message layout)               ilcc_image_parse
+ *   ros::serialization of sensor_msgs/Image (message layout)               ilcc_image_parse, ilcc_image_parse_any
+ *   cv_bridge's demosaicing of a raw colour-camera topic (bayer_*8), on    the two K11 entries, per tap
+ *     the way to MONO8 or "bgr8"  (cv::cvtColor, COLOR_Bayer*2GRAY / 2BGR)               (csrc/bayer_tap.h)
  *   cv_bridge::toCvCopy(msg, MONO8)  (test/get_image_corners_bag.cpp:26)    ilcc_image_to_mono8_device
  *   undistort_image -> cv::undistort(image, rectify, camK, distort_param,                 (K11, gfx950 kernel)
  *     camK)          (src/ImageCornersEst.cpp:63-66)
@@ -36,13 +38,33 @@
  *   bgr8 (K11c): bgr8 is copied, rgb8 swaps channels 0 and 2, bgra8 / rgba8 drop alpha (rgba8 also swaps), mono8 is
  *     replicated into the three channels; with a camera, the same codes and the same four weights blend each of
  *     B, G, R on its own (the conversion permutes or replicates channels, so it commutes with the blend).
+ *   Bayer sources (bayer_rggb8, bayer_bggr8, bayer_gbrg8, bayer_grbg8; one byte per pixel, the name gives the colours
+ *   of pixels (0,0) (1,0) of row 0 and (0,1) (1,1) of row 1, period 2 on both axes, odd sizes allowed) are demosaiced as
+ *   OpenCV 3's scalar Bayer2RGB_ / Bayer2Gray_ do it (imgproc/src/demosaicing.cpp), which cv_bridge reaches with
+ *   bayer_rggb8 -> COLOR_BayerBG2*, bggr8 -> BayerRG, gbrg8 -> BayerGR, grbg8 -> BayerGB.  S(x, y): the raw byte.
+ *     interior (1 <= x <= w-2, 1 <= y <= h-2), integer sums:
+ *       at an R or B site: own colour S(x,y); G = (S(x-1,y) + S(x+1,y) + S(x,y-1) + S(x,y+1) + 2) >> 2;
+ *         the opposite colour (S(x-1,y-1) + S(x+1,y-1) + S(x-1,y+1) + S(x+1,y+1) + 2) >> 2
+ *       at a G site: G = S(x,y); the colour of this row's non-green sites (S(x-1,y) + S(x+1,y) + 1) >> 1; the other
+ *         colour (S(x,y-1) + S(x,y+1) + 1) >> 1
+ *       gray, from the raw sums (NOT the gray of that B,G,R: one rounding, not two), cR = 4899, cG = 9617, cB = 1868:
+ *         R / B site: Y = (4 c_own S(x,y) + cG (the 4 cross neighbours) + c_opp (the 4 diagonals) + 32768) >> 16
+ *         G site:     Y = (2 cG S(x,y) + c_h (S(x-1,y) + S(x+1,y)) + c_v (S(x,y-1) + S(x,y+1)) + 16384) >> 15,
+ *                     c_h / c_v: the coefficient of the row's / the column's non-green colour
+ *     border: D(x, y) = I(clamp(x, 1, w-2), clamp(y, 1, h-2)), I the interior rule, colour and gray (OpenCV copies
+ *       column 1 into column 0 and column w-2 into column w-1, then row 1 into row 0 and row h-2 into row h-1)
+ *     with a camera the map, the codes, the weights and the rounding are the ones above: a tap inside the source is
+ *       D(x, y) (gray for mono8; B, G, R each blended on its own for bgr8), a tap outside counts as 0.
+ *     OpenCV's vectorised gray path works in 16-bit mulhi arithmetic and may differ from its own scalar path by a grey
+ *     level; the scalar path is what is specified here.  The colour path is exact in both.
+ *     Deviation: a Bayer image with width < 3 or height < 3 is refused (OpenCV returns zeros there).
  *   Deviation from OpenCV: it accumulates x along a row and works in stripes; here every pixel is
  *   evaluated directly (order 1e-13 px: moves a 1/32-pixel code only at an exact tie).
  *
  * A topic that carries no sensor_msgs/Image but sensor_msgs/CompressedImage (JPEG) is read by the two bag entries
  * all the same: K13 (ilcc_jpeg.h) decodes its first message into the frame K11 then takes.
  *
- * Not here: 16-bit and Bayer encodings; the rational (k4..k6), thin-prism and tilt terms of the distortion
+ * Not here: 16-bit encodings (mono16, bayer_*16); the rational (k4..k6), thin-prism and tilt terms of the distortion
  * model; the stereo rectification of undistort_stereo_image; structure recovery stays on the host
  * (ilcc_image_corners.h).
  */
@@ -67,7 +89,13 @@ enum ilcc_image_encoding {
   ILCC_ENCODING_BGR8 = 1,
   ILCC_ENCODING_RGB8 = 2,
   ILCC_ENCODING_BGRA8 = 3,
-  ILCC_ENCODING_RGBA8 = 4
+  ILCC_ENCODING_RGBA8 = 4,
+  /* 5 .. 15: not used, refused.  Raw colour-camera frames, one byte per pixel; taken by ilcc_image_parse_any, the two
+   * K11 entries and the bag entries, not by ilcc_image_parse nor by ilcc_jpeg_write.h */
+  ILCC_ENCODING_BAYER_RGGB8 = 16,
+  ILCC_ENCODING_BAYER_BGGR8 = 17,
+  ILCC_ENCODING_BAYER_GBRG8 = 18,
+  ILCC_ENCODING_BAYER_GRBG8 = 19
 };
 
 typedef struct ilcc_image_layout {
@@ -88,15 +116,19 @@ int32_t ilcc_read_camera_yaml(const char* path, ilcc_camera_model* out);
 
 /* layout of a serialized sensor_msgs/Image (md5sum 060021388200f6f0f447d0fcd9c64743).  Refused with
  * ILCC_BAD_ARGUMENT: a truncated message or a length field that runs past it, an empty image, an
- * encoding outside ilcc_image_encoding (the last-error text names it), step < width * bytes per
+ * encoding other than mono8 .. rgba8 (the last-error text names it; the Bayer names too: layout.encoding is 0 .. 4), step < width * bytes per
  * pixel, data_bytes < step * height.  Allocates nothing.  Host only. */
 int32_t ilcc_image_parse(const uint8_t* msg, uint64_t msg_bytes, ilcc_image_layout* out);
+
+/* ilcc_image_parse plus bayer_rggb8, bayer_bggr8, bayer_gbrg8 and bayer_grbg8 (layout.encoding 16 .. 19, step >= width);
+ * a Bayer image narrower or lower than 3 pixels is refused.  What the bag entries read a topic's frame with. */
+int32_t ilcc_image_parse_any(const uint8_t* msg, uint64_t msg_bytes, ilcc_image_layout* out);
 
 /* K11: pixels of `encoding` in device memory (rows src_step bytes apart) -> 8-bit grayscale in device
  * memory (rows dst_stride bytes apart): cv::undistort(mono8(src), K, d, K) with a camera, mono8(src)
  * with camera == NULL.  On hip_stream (a hipStream_t, NULL = default stream); asynchronous.  Checked on
  * the host before any launch (ILCC_BAD_ARGUMENT): null pointers, width / height outside 1 .. 65536,
- * strides shorter than a row, an unknown encoding, a camera of another size or with fx or fy not
+ * strides shorter than a row, an unknown encoding, a Bayer image below 3 x 3, a camera of another size or with fx or fy not
  * finite and non-zero, source and destination ranges that overlap (the kernel gathers). */
 int32_t ilcc_image_to_mono8_device(const void* d_src, int32_t width, int32_t height, int32_t src_step, int32_t encoding,
                                    const ilcc_camera_model* camera, void* d_dst, int32_t dst_stride, void* hip_stream);

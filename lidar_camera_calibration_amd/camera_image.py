@@ -1,6 +1,7 @@
 """Camera images from bags or raw frames: ctypes mirror of ``include/ilcc_camera_image.h`` -- the
 intrinsics of an OpenCV YAML, the layout of a serialized sensor_msgs/Image, conversion to mono8 and
-cv::undistort in one GPU kernel (K11; K11c keeps the colour: B, G, R), and the two bag entries that end in host pixels or in the
+cv::undistort in one GPU kernel (K11; K11c keeps the colour: B, G, R; both demosaic the raw bayer_*8 frames of a colour camera
+on the way, as cv_bridge does), and the two bag entries that end in host pixels or in the
 chessboard's corners.  What comes out of ``to_mono8(..., camera)`` is what
 ``image_corners.find_chessboard`` takes."""
 import ctypes as C
@@ -13,11 +14,21 @@ from .image_corners import BoardNotFound
 
 IMAGE_MD5 = "060021388200f6f0f447d0fcd9c64743"
 ENCODINGS = ("mono8", "bgr8", "rgb8", "bgra8", "rgba8")       # index = ilcc_image_encoding
-BYTES_PER_PIXEL = {"mono8": 1, "bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4}
+BAYER_ENCODINGS = {"bayer_rggb8": 16, "bayer_bggr8": 17, "bayer_gbrg8": 18, "bayer_grbg8": 19}   # raw colour-camera frames
+BYTES_PER_PIXEL = {"mono8": 1, "bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4, **{name: 1 for name in BAYER_ENCODINGS}}
 MAP_OUTSIDE = -2 ** 31                                         # code of an output pixel without a source
 
-CAMERA_IMAGE_EXPORTS = ["ilcc_read_camera_yaml", "ilcc_image_parse", "ilcc_image_to_mono8_device",
+CAMERA_IMAGE_EXPORTS = ["ilcc_read_camera_yaml", "ilcc_image_parse", "ilcc_image_parse_any", "ilcc_image_to_mono8_device",
                         "ilcc_image_to_bgr8_device", "ilcc_undistort_map_device", "ilcc_bag_first_image", "ilcc_bag_find_chessboard"]
+
+
+def encoding_code(name) -> int:
+    """ilcc_image_encoding of an encoding's name: 0 .. 4 for ENCODINGS, 16 .. 19 for BAYER_ENCODINGS."""
+    if name in BAYER_ENCODINGS:
+        return BAYER_ENCODINGS[name]
+    if name in ENCODINGS:
+        return ENCODINGS.index(name)
+    raise ValueError("unsupported encoding %r (supported: %s)" % (name, ", ".join(ENCODINGS + tuple(BAYER_ENCODINGS))))
 
 
 class CameraModel(C.Structure):
@@ -38,6 +49,9 @@ class ImageLayout(C.Structure):
 
     @property
     def encoding_name(self):
+        for name, code in BAYER_ENCODINGS.items():
+            if code == self.encoding:
+                return name
         return ENCODINGS[self.encoding]
 
 
@@ -59,6 +73,8 @@ def lib():
         L.ilcc_read_camera_yaml.restype = C.c_int32
         L.ilcc_image_parse.argtypes = [C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(ImageLayout)]
         L.ilcc_image_parse.restype = C.c_int32
+        L.ilcc_image_parse_any.argtypes = L.ilcc_image_parse.argtypes
+        L.ilcc_image_parse_any.restype = C.c_int32
         L.ilcc_image_to_mono8_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, cam, C.c_void_p,
                                                  C.c_int32, C.c_void_p]
         L.ilcc_image_to_mono8_device.restype = C.c_int32
@@ -101,11 +117,18 @@ def parse_image(msg: bytes) -> ImageLayout:
     return lay
 
 
+def parse_image_any(msg: bytes) -> ImageLayout:
+    """parse_image, and the four Bayer encodings as well (layout.encoding 16 .. 19): what the bag entries read with."""
+    lay = ImageLayout()
+    arr = (C.c_uint8 * max(1, len(msg))).from_buffer_copy(msg if msg else b"\0")
+    _check(lib().ilcc_image_parse_any(arr, len(msg), C.byref(lay)))
+    return lay
+
+
 def _device_pixels(image, encoding):
     """The pixels as a device tensor (rows, cols, bytes per pixel) K11 can read in place, and its row pitch."""
     import torch
-    if encoding not in ENCODINGS:
-        raise ValueError("unsupported encoding %r (supported: %s)" % (encoding, ", ".join(ENCODINGS)))
+    encoding_code(encoding)                                    # ValueError for a name that is none of the nine
     bpp = BYTES_PER_PIXEL[encoding]
     t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
     if t.dim() == 2 and bpp == 1:
@@ -122,7 +145,7 @@ def _device_pixels(image, encoding):
 
 
 def to_mono8(image, encoding, camera=None):
-    """K11: (rows, cols) mono8 or (rows, cols, channels) colour uint8 pixels, numpy or torch, ->
+    """K11: (rows, cols) mono8 or Bayer, or (rows, cols, channels) colour uint8 pixels, numpy or torch, ->
     (rows, cols) uint8 tensor on the current HIP device: cv::undistort(mono8(image), K, d, K) with a
     camera, mono8(image) without.  A device tensor whose pixels are contiguous is read in place with
     stride(0) as the row pitch (a view of a pitched frame is not copied); asynchronous on the current stream."""
@@ -131,7 +154,7 @@ def to_mono8(image, encoding, camera=None):
     h, w = int(t.shape[0]), int(t.shape[1])
     out = torch.empty((h, w), dtype=torch.uint8, device=t.device)
     stream = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-    _check(lib().ilcc_image_to_mono8_device(C.c_void_p(t.data_ptr()), w, h, step, ENCODINGS.index(encoding), _camera_ref(camera),
+    _check(lib().ilcc_image_to_mono8_device(C.c_void_p(t.data_ptr()), w, h, step, encoding_code(encoding), _camera_ref(camera),
                                             C.c_void_p(out.data_ptr()), w, stream))
     return out
 
@@ -144,7 +167,7 @@ def to_bgr8(image, encoding, camera=None):
     h, w = int(t.shape[0]), int(t.shape[1])
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=t.device)
     stream = C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-    _check(lib().ilcc_image_to_bgr8_device(C.c_void_p(t.data_ptr()), w, h, step, ENCODINGS.index(encoding), _camera_ref(camera),
+    _check(lib().ilcc_image_to_bgr8_device(C.c_void_p(t.data_ptr()), w, h, step, encoding_code(encoding), _camera_ref(camera),
                                            C.c_void_p(out.data_ptr()), 3 * w, stream))
     return out
 

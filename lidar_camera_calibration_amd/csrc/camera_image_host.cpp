@@ -106,6 +106,62 @@ struct Yaml {
   }
 };
 
+// every encoding name a layout can carry; `wide`: taken by ilcc_image_parse_any only (callers of ilcc_image_parse index
+// the first five with layout.encoding)
+const struct {
+  const char* name;
+  uint32_t encoding, bpp;
+  bool wide;
+} kKnownEncodings[] = {{"mono8", ILCC_ENCODING_MONO8, 1, false},
+                       {"bgr8", ILCC_ENCODING_BGR8, 3, false},
+                       {"rgb8", ILCC_ENCODING_RGB8, 3, false},
+                       {"bgra8", ILCC_ENCODING_BGRA8, 4, false},
+                       {"rgba8", ILCC_ENCODING_RGBA8, 4, false},
+                       {"bayer_rggb8", ILCC_ENCODING_BAYER_RGGB8, 1, true},
+                       {"bayer_bggr8", ILCC_ENCODING_BAYER_BGGR8, 1, true},
+                       {"bayer_gbrg8", ILCC_ENCODING_BAYER_GBRG8, 1, true},
+                       {"bayer_grbg8", ILCC_ENCODING_BAYER_GRBG8, 1, true}};
+
+// ilcc_image_parse (wide = false) and ilcc_image_parse_any (wide = true)
+int32_t parse_image(const uint8_t* m, uint64_t n, ilcc_image_layout* out, bool wide) {
+  if (!m || !out) return fail(ILCC_BAD_ARGUMENT, wide ? "ilcc_image_parse_any: null argument" : "ilcc_image_parse: null argument");
+  std::memset(out, 0, sizeof(*out));
+  const char* truncated = "Image message truncated";
+  uint64_t at = 0;
+  uint32_t len = 0;
+  if (!read_header(m, n, &at, &out->seq, &out->stamp_sec, &out->stamp_nsec, out->frame_id)) return fail(ILCC_BAD_ARGUMENT, truncated);
+  if (!read_u32(m, n, &at, &out->height) || !read_u32(m, n, &at, &out->width) || !read_u32(m, n, &at, &len) || len > n - at)
+    return fail(ILCC_BAD_ARGUMENT, truncated);
+  const char* enc = (const char*)m + at;
+  const uint32_t enc_len = len;
+  at += len;
+  uint32_t data_len = 0;
+  if (n - at < 1) return fail(ILCC_BAD_ARGUMENT, truncated);
+  out->is_bigendian = m[at++];
+  if (!read_u32(m, n, &at, &out->step) || !read_u32(m, n, &at, &data_len)) return fail(ILCC_BAD_ARGUMENT, truncated);
+  out->data_offset = at;
+  out->data_bytes = data_len;
+  if (data_len > n - at) return fail(ILCC_BAD_ARGUMENT, "Image data[] length runs past the message");
+  uint32_t bpp = 0;
+  bool bayer = false;
+  for (const auto& k : kKnownEncodings)
+    if ((wide || !k.wide) && std::strlen(k.name) == enc_len && std::memcmp(k.name, enc, enc_len) == 0) {
+      out->encoding = k.encoding;
+      bpp = k.bpp;
+      bayer = k.wide;
+    }
+  if (!bpp) {
+    char text[96];
+    std::snprintf(text, sizeof(text), "unsupported Image encoding '%.*s'", (int)(enc_len < 40 ? enc_len : 40), enc);
+    return fail(ILCC_BAD_ARGUMENT, text);
+  }
+  if (out->width == 0 || out->height == 0) return fail(ILCC_BAD_ARGUMENT, "empty Image");
+  if (bayer && (out->width < 3 || out->height < 3)) return fail(ILCC_BAD_ARGUMENT, "a Bayer Image must be at least 3 x 3");
+  if ((uint64_t)out->step < (uint64_t)out->width * bpp) return fail(ILCC_BAD_ARGUMENT, "Image step is shorter than a row");
+  if (out->data_bytes < (uint64_t)out->step * out->height) return fail(ILCC_BAD_ARGUMENT, "Image data[] is shorter than step * height");
+  return ILCC_OK;
+}
+
 }  // namespace
 
 int32_t ilcc::bag_image_to_device(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
@@ -190,46 +246,9 @@ int32_t ilcc_read_camera_yaml(const char* path, ilcc_camera_model* out) {
   }
 }
 
-int32_t ilcc_image_parse(const uint8_t* m, uint64_t n, ilcc_image_layout* out) {
-  if (!m || !out) return fail(ILCC_BAD_ARGUMENT, "ilcc_image_parse: null argument");
-  std::memset(out, 0, sizeof(*out));
-  const char* truncated = "Image message truncated";
-  uint64_t at = 0;
-  uint32_t len = 0;
-  if (!read_header(m, n, &at, &out->seq, &out->stamp_sec, &out->stamp_nsec, out->frame_id)) return fail(ILCC_BAD_ARGUMENT, truncated);
-  if (!read_u32(m, n, &at, &out->height) || !read_u32(m, n, &at, &out->width) || !read_u32(m, n, &at, &len) || len > n - at)
-    return fail(ILCC_BAD_ARGUMENT, truncated);
-  const char* enc = (const char*)m + at;
-  const uint32_t enc_len = len;
-  at += len;
-  uint32_t data_len = 0;
-  if (n - at < 1) return fail(ILCC_BAD_ARGUMENT, truncated);
-  out->is_bigendian = m[at++];
-  if (!read_u32(m, n, &at, &out->step) || !read_u32(m, n, &at, &data_len)) return fail(ILCC_BAD_ARGUMENT, truncated);
-  out->data_offset = at;
-  out->data_bytes = data_len;
-  if (data_len > n - at) return fail(ILCC_BAD_ARGUMENT, "Image data[] length runs past the message");
-  static const struct {
-    const char* name;
-    uint32_t encoding, bpp;
-  } kKnown[] = {{"mono8", ILCC_ENCODING_MONO8, 1}, {"bgr8", ILCC_ENCODING_BGR8, 3}, {"rgb8", ILCC_ENCODING_RGB8, 3},
-                {"bgra8", ILCC_ENCODING_BGRA8, 4}, {"rgba8", ILCC_ENCODING_RGBA8, 4}};
-  uint32_t bpp = 0;
-  for (const auto& k : kKnown)
-    if (std::strlen(k.name) == enc_len && std::memcmp(k.name, enc, enc_len) == 0) {
-      out->encoding = k.encoding;
-      bpp = k.bpp;
-    }
-  if (!bpp) {
-    char text[96];
-    std::snprintf(text, sizeof(text), "unsupported Image encoding '%.*s'", (int)(enc_len < 40 ? enc_len : 40), enc);
-    return fail(ILCC_BAD_ARGUMENT, text);
-  }
-  if (out->width == 0 || out->height == 0) return fail(ILCC_BAD_ARGUMENT, "empty Image");
-  if ((uint64_t)out->step < (uint64_t)out->width * bpp) return fail(ILCC_BAD_ARGUMENT, "Image step is shorter than a row");
-  if (out->data_bytes < (uint64_t)out->step * out->height) return fail(ILCC_BAD_ARGUMENT, "Image data[] is shorter than step * height");
-  return ILCC_OK;
-}
+int32_t ilcc_image_parse(const uint8_t* m, uint64_t n, ilcc_image_layout* out) { return parse_image(m, n, out, false); }
+
+int32_t ilcc_image_parse_any(const uint8_t* m, uint64_t n, ilcc_image_layout* out) { return parse_image(m, n, out, true); }
 
 int32_t ilcc_bag_first_image(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera,
                              uint8_t* mono8_out, uint64_t cap_bytes, int32_t* width, int32_t* height) {

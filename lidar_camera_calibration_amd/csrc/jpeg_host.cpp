@@ -63,9 +63,9 @@ int32_t bag_frame_read(const char* bag_path, const char* topic, BagFrame* out) {
   int32_t st = read_first_message(bag_path, topic, kImageMd5, &out->msg);
   if (st == ILCC_OK) {
     out->compressed = false;
-    st = ilcc_image_parse(out->msg.data(), out->msg.size(), &out->L);
+    st = ilcc_image_parse_any(out->msg.data(), out->msg.size(), &out->L);   // Bayer topics too: K11 demosaics them
     if (st != ILCC_OK) return st;
-    out->device_bytes = (uint64_t)out->L.step * out->L.height;   // <= data_bytes (ilcc_image_parse)
+    out->device_bytes = (uint64_t)out->L.step * out->L.height;   // <= data_bytes (ilcc_image_parse_any)
     return ILCC_OK;
   }
   if (st != ILCC_BAD_ARGUMENT) return st;

@@ -19,6 +19,11 @@
 // pixels of two adjacent source rows, which the L2 serves from the same few lines.  Without a camera
 // the source quad sits at a known address and is loaded as dwords where that address is aligned.
 //
+// Bayer sources (bayer_rggb8 .. bayer_grbg8) are demosaiced in the same launch, tap by tap, by csrc/bayer_tap.h: a tap is
+// D(x, y) of the header, made from the 3 x 3 raw neighbourhood of its clamped position.  With a camera the four taps of
+// a pixel share ONE 4 x 4 raw window (four dword loads at any alignment, not 36 bytes); without one a thread's quad
+// takes three 6-column rows (a dword and two bytes each where the address allows).  No demosaiced image exists.
+//
 // K11c (k11_image_to_bgr8, ilcc_image_to_bgr8_device) is the same frame kept in colour for the overlay of
 // include/ilcc_overlay.h: cv_bridge::toCvCopy(msg, "bgr8") + cv::undistort (test/pcd2image.cpp:36,101).  It shares
 // the map, the weights and the thread-to-pixel map; its quad is 12 bytes, stored with one 3-dword store.
@@ -27,6 +32,7 @@
 #include <cmath>
 #include <string>
 
+#include "bayer_tap.h"
 #include "host_util.h"
 #include "ilcc_camera_image.h"
 #include "ilcc_internal.h"
@@ -64,9 +70,13 @@ __device__ __forceinline__ void map_codes(const LensArgs& L, int j, int i, int32
   iv = ok ? (int32_t)rint(sv) : kOutside;
 }
 
+constexpr bool is_bayer(int enc) { return enc >= ILCC_ENCODING_BAYER_RGGB8 && enc <= ILCC_ENCODING_BAYER_GRBG8; }
+
 template <int ENC>
 struct Pixel {
-  static constexpr int kBytes = ENC == ILCC_ENCODING_MONO8 ? 1 : (ENC == ILCC_ENCODING_BGR8 || ENC == ILCC_ENCODING_RGB8) ? 3 : 4;
+  static constexpr bool kBayer = is_bayer(ENC);
+  static constexpr int kPattern = ENC - ILCC_ENCODING_BAYER_RGGB8;   // of bayer_tap.h; meaningful when kBayer
+  static constexpr int kBytes = (ENC == ILCC_ENCODING_MONO8 || kBayer) ? 1 : (ENC == ILCC_ENCODING_BGR8 || ENC == ILCC_ENCODING_RGB8) ? 3 : 4;
   static constexpr bool kBlueFirst = ENC == ILCC_ENCODING_BGR8 || ENC == ILCC_ENCODING_BGRA8;
   __device__ static __forceinline__ int32_t gray(uint32_t c0, uint32_t c1, uint32_t c2) {
     const uint32_t r = kBlueFirst ? c2 : c0, b = kBlueFirst ? c0 : c2;
@@ -109,11 +119,42 @@ __device__ __forceinline__ uint32_t blend(const Sample& s, int32_t t00, int32_t 
   return (uint32_t)((s.w00 * t00 + s.w10 * t10 + s.w01 * t01 + s.w11 * t11 + 16384) >> 15);
 }
 
+// the four taps of a sample on a Bayer source, from one 4 x 4 raw window: Y when GRAY, else B | G << 8 | R << 16
+template <int ENC, bool GRAY>
+__device__ __forceinline__ void bayer_taps(const ImageArgs& a, const Sample& s, uint32_t (&t)[4]) {
+  const bool any = s.x0 >= -1 && s.x0 < a.width && s.y0 >= -1 && s.y0 < a.height;
+  if (!any) {
+    t[0] = t[1] = t[2] = t[3] = 0;
+    return;
+  }
+  const BayerWindow W = bayer_window(a.src, a.src_step, a.width, a.height, s.x0, s.y0);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t[k] = bayer_window_tap(W, a.width, a.height, Pixel<ENC>::kPattern, GRAY, s.x0 + (k & 1), s.y0 + (k >> 1));
+}
+
+// kQuad adjacent pixels of a Bayer source without a camera: three 6-column rows, then every pixel's own 3 x 3 of them
+template <int ENC, bool GRAY>
+__device__ __forceinline__ void bayer_quad(const ImageArgs& a, int j0, int i, int n, uint32_t (&out)[kQuad]) {
+  const int lo = bayer_clamp(j0, a.width) - 1;
+  const uint8_t* row = a.src + (int64_t)(bayer_clamp(i, a.height) - 1) * a.src_step;
+  const uint64_t r0 = bayer_row6(row, a.width, lo), r1 = bayer_row6(row + a.src_step, a.width, lo),
+                 r2 = bayer_row6(row + 2 * a.src_step, a.width, lo);
+#pragma unroll
+  for (int k = 0; k < kQuad; ++k)
+    out[k] = k < n ? bayer_row6_pixel(r0, r1, r2, lo, a.width, a.height, Pixel<ENC>::kPattern, GRAY, j0 + k, i) : 0;
+}
+
 template <int ENC>
 __device__ __forceinline__ uint32_t undistorted_pixel(const ImageArgs& a, int j, int i) {
   Sample s;
   if (!sample_of(a.lens, j, i, s)) return 0;
-  return blend(s, tap<ENC>(a, s.x0, s.y0), tap<ENC>(a, s.x0 + 1, s.y0), tap<ENC>(a, s.x0, s.y0 + 1), tap<ENC>(a, s.x0 + 1, s.y0 + 1));
+  if constexpr (Pixel<ENC>::kBayer) {
+    uint32_t t[4];
+    bayer_taps<ENC, true>(a, s, t);
+    return blend(s, (int32_t)t[0], (int32_t)t[1], (int32_t)t[2], (int32_t)t[3]);
+  } else {
+    return blend(s, tap<ENC>(a, s.x0, s.y0), tap<ENC>(a, s.x0 + 1, s.y0), tap<ENC>(a, s.x0, s.y0 + 1), tap<ENC>(a, s.x0 + 1, s.y0 + 1));
+  }
 }
 
 // the source quad of a conversion without a camera: kQuad pixels = Pixel::kBytes dwords where the address allows
@@ -157,6 +198,8 @@ __global__ __launch_bounds__(kImgTx* kImgTy) void k11_image_to_mono8(ImageArgs a
   if (UNDISTORT) {
 #pragma unroll
     for (int k = 0; k < kQuad; ++k) px[k] = k < n ? undistorted_pixel<ENC>(a, j0 + k, i) : 0;
+  } else if constexpr (Pixel<ENC>::kBayer) {
+    bayer_quad<ENC, true>(a, j0, i, n, px);
   } else {
     converted_quad<ENC>(a, j0, i, n, px);
   }
@@ -190,23 +233,31 @@ __device__ __forceinline__ uint32_t tap_bgr(const ImageArgs& a, int32_t x, int32
   return packed_bgr<ENC>(a.src + (int64_t)y * a.src_step + (int64_t)x * Pixel<ENC>::kBytes);
 }
 
+// four packed B,G,R taps -> the packed pixel: every channel blended on its own
+__device__ __forceinline__ uint32_t blend_bgr(const Sample& s, uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11) {
+  uint32_t out = 0;
+#pragma unroll
+  for (int sh = 0; sh < 24; sh += 8)
+    out |= blend(s, (int32_t)((t00 >> sh) & 255u), (int32_t)((t10 >> sh) & 255u), (int32_t)((t01 >> sh) & 255u),
+                 (int32_t)((t11 >> sh) & 255u))
+           << sh;
+  return out;
+}
+
 template <int ENC>
 __device__ __forceinline__ uint32_t undistorted_bgr(const ImageArgs& a, int j, int i) {
   Sample s;
   if (!sample_of(a.lens, j, i, s)) return 0;
-  if constexpr (Pixel<ENC>::kBytes == 1) {   // three equal channels: blend one
+  if constexpr (Pixel<ENC>::kBayer) {
+    uint32_t t[4];
+    bayer_taps<ENC, false>(a, s, t);
+    return blend_bgr(s, t[0], t[1], t[2], t[3]);
+  } else if constexpr (Pixel<ENC>::kBytes == 1) {   // three equal channels: blend one
     return blend(s, tap<ENC>(a, s.x0, s.y0), tap<ENC>(a, s.x0 + 1, s.y0), tap<ENC>(a, s.x0, s.y0 + 1), tap<ENC>(a, s.x0 + 1, s.y0 + 1)) *
            0x010101u;
   } else {
-    const uint32_t t00 = tap_bgr<ENC>(a, s.x0, s.y0), t10 = tap_bgr<ENC>(a, s.x0 + 1, s.y0);
-    const uint32_t t01 = tap_bgr<ENC>(a, s.x0, s.y0 + 1), t11 = tap_bgr<ENC>(a, s.x0 + 1, s.y0 + 1);
-    uint32_t out = 0;
-#pragma unroll
-    for (int sh = 0; sh < 24; sh += 8)
-      out |= blend(s, (int32_t)((t00 >> sh) & 255u), (int32_t)((t10 >> sh) & 255u), (int32_t)((t01 >> sh) & 255u),
-                   (int32_t)((t11 >> sh) & 255u))
-             << sh;
-    return out;
+    return blend_bgr(s, tap_bgr<ENC>(a, s.x0, s.y0), tap_bgr<ENC>(a, s.x0 + 1, s.y0), tap_bgr<ENC>(a, s.x0, s.y0 + 1),
+                     tap_bgr<ENC>(a, s.x0 + 1, s.y0 + 1));
   }
 }
 
@@ -226,6 +277,8 @@ __global__ __launch_bounds__(kImgTx* kImgTy) void k11_image_to_bgr8(ImageArgs a)
   if (UNDISTORT) {
 #pragma unroll
     for (int k = 0; k < kQuad; ++k) px[k] = k < n ? undistorted_bgr<ENC>(a, j0 + k, i) : 0;
+  } else if constexpr (Pixel<ENC>::kBayer) {
+    bayer_quad<ENC, false>(a, j0, i, n, px);
   } else {
     constexpr int B = Pixel<ENC>::kBytes;
     uint8_t bytes[kQuad * B];
@@ -316,13 +369,19 @@ int32_t convert_image(const char* me, const void* d_src, int32_t width, int32_t 
   if (width < 1 || height < 1 || width > kMaxSide || height > kMaxSide) return refuse(me, "width and height must be 1 .. 65536");
   int bpp;
   switch (encoding) {
-    case ILCC_ENCODING_MONO8: bpp = 1; break;
+    case ILCC_ENCODING_MONO8:
+    case ILCC_ENCODING_BAYER_RGGB8:
+    case ILCC_ENCODING_BAYER_BGGR8:
+    case ILCC_ENCODING_BAYER_GBRG8:
+    case ILCC_ENCODING_BAYER_GRBG8: bpp = 1; break;
     case ILCC_ENCODING_BGR8:
     case ILCC_ENCODING_RGB8: bpp = 3; break;
     case ILCC_ENCODING_BGRA8:
     case ILCC_ENCODING_RGBA8: bpp = 4; break;
     default: return refuse(me, "unknown encoding " + std::to_string(encoding));
   }
+  if (is_bayer(encoding) && (width < kBayerMinSide || height < kBayerMinSide))
+    return refuse(me, "a Bayer image must be at least 3 x 3 (a smaller one has no interior pixel)");
   if ((int64_t)src_step < (int64_t)width * bpp) return refuse(me, "src_step is shorter than a row");
   if ((int64_t)dst_stride < (int64_t)width * CHANNELS) return refuse(me, "dst_stride is shorter than a row");
   if (camera)
@@ -347,6 +406,10 @@ int32_t convert_image(const char* me, const void* d_src, int32_t width, int32_t 
     case ILCC_ENCODING_BGR8: launch_image<ILCC_ENCODING_BGR8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
     case ILCC_ENCODING_RGB8: launch_image<ILCC_ENCODING_RGB8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
     case ILCC_ENCODING_BGRA8: launch_image<ILCC_ENCODING_BGRA8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_BAYER_RGGB8: launch_image<ILCC_ENCODING_BAYER_RGGB8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_BAYER_BGGR8: launch_image<ILCC_ENCODING_BAYER_BGGR8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_BAYER_GBRG8: launch_image<ILCC_ENCODING_BAYER_GBRG8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
+    case ILCC_ENCODING_BAYER_GRBG8: launch_image<ILCC_ENCODING_BAYER_GRBG8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
     default: launch_image<ILCC_ENCODING_RGBA8, CHANNELS>(a, camera != nullptr, grid, block, s); break;
   }
   const hipError_t e = hipGetLastError();

@@ -1,4 +1,4 @@
-"""HIP-event ms of K11 (ilcc_image_to_mono8_device) on a 1920 x 1200 frame in each encoding, with the
+"""HIP-event ms of K11 (ilcc_image_to_mono8_device) on a 1920 x 1200 frame in each encoding, the four Bayer ones included, with the
 golden pointgrey.yaml camera (conversion + undistortion) and without one (conversion only), beside the
 algorithmic byte count (source + destination, each once) and the rate that makes.  A run is --calls
 back-to-back calls between two events, divided by their number (one launch alone is mostly launch gap);
@@ -26,9 +26,10 @@ def main():
     cam = CI.read_camera_yaml(os.path.join(ROOT, "tests", "golden", "pointgrey.yaml"))
     w, h = cam.width, cam.height
     rng = np.random.default_rng(0)
-    for encoding in CI.ENCODINGS:
+    for encoding in CI.ENCODINGS + tuple(CI.BAYER_ENCODINGS):
         bpp = CI.BYTES_PER_PIXEL[encoding]
-        src = torch.from_numpy(rng.integers(0, 256, (h, w, bpp), dtype=np.uint8)).cuda()
+        shape = (h, w) if encoding in CI.BAYER_ENCODINGS else (h, w, bpp)      # a Bayer frame is (rows, cols)
+        src = torch.from_numpy(rng.integers(0, 256, shape, dtype=np.uint8)).cuda()
         for camera in (cam, None):
             CI.to_mono8(src, encoding, camera)
             torch.cuda.synchronize()
