@@ -30,9 +30,34 @@
  * the side of a uniformly covered rectangle).  Score = |L1 - W g| / (W g) + |L2 - H g| / (H g); seeds ascend by score, ties by key;
  * at most max_seeds are kept.
  *
- * LIMITS.  A board whose component touches something else -- a hand, a stand, ground closer than two cells -- fails the size gate
- * and is not proposed.  The proposal is the centroid of a superset component, not of the reference's cluster: the pipeline behind
- * it does the exact work, the seed only has to fall within the ROI's reach of the board.
+ * Planar seeds (K15p; the ilcc_*_planar entries).  A second way of forming the components, for a board that touches the ground,
+ * a stand or a hand.  Quantisation, cells, the hash set and the per-cell moments are the ones above; then every occupied cell is
+ * classified, and the components are the 26-connected components of the CORE cells alone:
+ *   block      n_b, sum q, sum q q^T over the occupied cells of the cell's 3 x 3 x 3 block (a neighbour index outside [0, N) on an
+ *              axis is skipped, never wrapped), translated exactly, in integers, to the cell's origin o = cq (cell index): q' = q - o,
+ *              |q'| <= 2 cq.  C = n_b sum q' q'^T - sum q' sum q'^T is formed in int64: a frame is admitted only while
+ *              n_points 2 cq < 2^31 (8.7 M points at the default cell; ILCC_BAD_ARGUMENT beyond).  The six entries of C are converted
+ *              to fp64 once each (round to nearest) and eig3_sym (cyclic Jacobi, csrc/eig3.h) gives w0 <= w1 <= w2 and the unit
+ *              normal v0.  Everything in fp64 is unfused IEEE + - x / sqrt in the order written here.
+ *   flat       w0 <= (n_b n_b) ((1024 planar_rms) (1024 planar_rms))
+ *   surface    12 w1 >= (n_b n_b) ((1024 min_spread) (1024 min_spread))      (a single LiDAR ring is a line and has no normal)
+ *   own        with m_a = (double) (sum_b q'_a) / n_b, n_o, s_a, ss_ab the cell's OWN translated moments as fp64 (exact), and
+ *              A_ab = ((ss_ab - m_a s_b) - m_b s_a) + (n_o m_a) m_b,   r_a = (A_a0 v0_0 + A_a1 v0_1) + A_a2 v0_2:
+ *              (v0_0 r_0 + v0_1 r_1) + v0_2 r_2 <= n_o ((1024 own_rms) (1024 own_rms))      (the cell's own points lie in the patch)
+ *   core       flat and surface and own.
+ *   records    as above, of the core components of n >= cluster_min: the smallest key among the component's core cells, then the
+ *              sums over the own points of its core cells.  Gates, score and order are the ordinary ones, with max_rms 0.05 by
+ *              default: a component's rim cells still hold some floor.
+ * tests/seed_planar_ref.py restates this bit for bit.
+ *
+ * LIMITS.  The ordinary entries propose a board only when its component touches nothing else: a hand, a stand or ground closer than
+ * two cells joins it and fails the size gate.  The planar entries cut the board from a floor it stands on or in, from a pole and
+ * from whatever meets it at an angle, because the cells along the joint hold two surfaces and are not core.  Not covered by either:
+ * a board parallel to a wall less than two cells away (the block holds both planes); a board so far away that a block holds a single
+ * ring (the surface test fails); and anything that is itself a board-sized flat rectangle, which is proposed like a board -- the
+ * pipeline behind the seed decides.  The proposal is the centroid of a superset component (ordinary) or of the board's core cells
+ * (planar), not of the reference's cluster: the pipeline behind it does the exact work, the seed only has to fall within the ROI's
+ * reach of the board.
  */
 #ifndef ILCC_SEED_H_
 #define ILCC_SEED_H_
@@ -129,6 +154,42 @@ int32_t ilcc_extract_auto_batch(ilcc_handle* h, const float* xyzi, const uint64_
                                 const ilcc_seed_params* sp, ilcc_result* out, float* out_seed, int32_t* out_rank);
 int32_t ilcc_extract_auto(ilcc_handle* h, const float* xyzi, uint32_t n, const ilcc_seed_params* sp, ilcc_result* out,
                           float out_seed[3], int32_t* out_rank);
+
+/* ---- planar seeds (K15p): the contract of each entry is its sibling's above; what differs is stated here */
+
+typedef struct ilcc_seed_planar_params {
+  double planar_rms;       /* m; a block is flat when its smallest rms extent is at most this (default params.ransac_thresh) */
+  double min_spread;       /* m; ... and a surface when sqrt(12 w1) / n_b, the side of its second extent, is at least this (default cell / 2) */
+  double own_rms;          /* m; rms distance of the cell's own points from the block's plane through its centroid (default 0.02) */
+} ilcc_seed_planar_params;
+
+/* sp as ilcc_default_seed_params sets it, but max_rms = 0.05; pp the defaults above */
+void ilcc_default_seed_planar_params(const ilcc_params* p, ilcc_seed_params* sp, ilcc_seed_planar_params* pp);
+
+/* the ordinary scratch followed by one byte per point */
+uint64_t ilcc_seed_planar_scratch_bytes(uint32_t n_frames, uint64_t total_points, const ilcc_seed_params* sp);
+
+/* Further refusals (ILCC_BAD_ARGUMENT, nothing launched, outputs untouched): pp null, a threshold that is not positive, a frame of
+ * n points with n 2 ceil(1024 cell) >= 2^31.  One scratch buffer of ilcc_seed_planar_scratch_bytes serves planar and ordinary calls
+ * in any order. */
+int32_t ilcc_propose_seeds_planar_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames,
+                                         const ilcc_seed_params* sp, const ilcc_seed_planar_params* pp, void* d_scratch,
+                                         ilcc_seed* out_seeds, int32_t* out_counts, void* hip_stream);
+int32_t ilcc_propose_seeds_planar(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
+                                  const ilcc_seed_params* sp, const ilcc_seed_planar_params* pp, ilcc_seed* out_seeds, int32_t* out_counts);
+int32_t ilcc_debug_seed_planar_components(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
+                                          const ilcc_seed_params* sp, const ilcc_seed_planar_params* pp, void* d_scratch, uint32_t frame,
+                                          int64_t* out_records, uint32_t cap_records, int32_t* out_n);
+
+/* the spans of clear, insert, moments, classify, union, reduce, pack in the calling thread's last planar seed call */
+#define ILCC_SEED_PLANAR_LAUNCHES 7
+void ilcc_debug_seed_planar_launch_ms(float out[ILCC_SEED_PLANAR_LAUNCHES]);
+
+int32_t ilcc_extract_auto_planar_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames,
+                                       const ilcc_seed_params* sp, const ilcc_seed_planar_params* pp, ilcc_result* out, float* out_seed,
+                                       int32_t* out_rank);
+int32_t ilcc_extract_auto_planar(ilcc_handle* h, const float* xyzi, uint32_t n, const ilcc_seed_params* sp,
+                                 const ilcc_seed_planar_params* pp, ilcc_result* out, float out_seed[3], int32_t* out_rank);
 
 #ifdef __cplusplus
 }

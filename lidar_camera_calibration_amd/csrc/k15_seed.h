@@ -42,9 +42,14 @@ struct SeedCtx {         // passed by value to every K15 kernel
   uint32_t* parent;      // union-find over ordinals; key[parent[c]] <= key[c]
   long long* mom;        // kSeedMoments per cell
   long long* packed;     // n_frames x max_components x ILCC_SEED_RECORD_WORDS
+  // planar seeds (K15p) only; core == nullptr selects the ordinary components
+  uint8_t* core;         // per cell: 1 = CORE (the classify launch writes every occupied cell's flag), behind every ordinary part
+  double flat_q2, spread_q2, own_q2;   // (1024 planar_rms)^2, (1024 min_spread)^2, (1024 own_rms)^2: squared thresholds in quanta
 };
-constexpr int kSeedLaunches = 6;   // clear, insert, moments, union, reduce, pack
-// between: nullptr, or kSeedLaunches + 1 events recorded in front of, between and behind the launches
+constexpr int kSeedLaunches = 6;         // clear, insert, moments, union, reduce, pack
+constexpr int kSeedPlanarLaunches = 7;   // clear, insert, moments, classify, union, reduce, pack
+// between: nullptr, or (launches + 1) events recorded in front of, between and behind the launches: kSeedLaunches of them, or
+// kSeedPlanarLaunches where c.core is set
 void launch_seed_components(const SeedCtx& c, uint32_t max_frame_points, hipStream_t s, const hipEvent_t* between);   // k15_seed_components.hip
 #endif
 
@@ -63,5 +68,9 @@ int32_t handle_fail(ilcc_handle* h, int32_t code, const std::string& what);   //
 bool seed_grid(const ilcc_seed_params& sp, uint64_t max_total_points, SeedGrid* g);
 // gates, score and order on n_rec records (sorted by key): writes at most sp.max_seeds seeds, returns their number
 int32_t seed_rank(const int64_t* records, int32_t n_rec, const ilcc_seed_params& sp, ilcc_seed* out);
+// K15p: the squared thresholds in quanta, each (1024 t)^2 as two fp64 products; false: a threshold that is not positive and finite
+bool seed_planar_thresholds(const ilcc_seed_planar_params& pp, double* flat_q2, double* spread_q2, double* own_q2);
+// K15p: whether a frame of n points keeps the block covariance in int64 (n 2 cq < 2^31)
+bool seed_planar_frame_fits(uint64_t n_points, const SeedGrid& g);
 
 }  // namespace ilcc

@@ -16,10 +16,20 @@
 //   reduce    one lane per cell: a cell that is not its component's root adds its moments to the root's, a wavefront's cells of one
 //             root as one sum
 //   pack      one lane per cell: a root of n >= cluster_min claims a record
+// Planar seeds (K15p; a set SeedCtx::core selects them): a `classify` launch between moments and union flags the cells whose
+// 3 x 3 x 3 block is one flat two-dimensional patch that the cell's own points lie in (CORE cells), and union, reduce and pack
+// then form the components of the core cells alone -- a board standing on the floor or on a pole is cut from them where the
+// blocks hold two surfaces or a line.  The same properties hold: every loop has a stated bound, no workgroup waits for another,
+// only ordinary vector atomics and vector stores are used, and the flag is a pure function of exact integer sums (one conversion
+// to fp64 each, then unfused IEEE + - x / sqrt in a fixed order), so nothing decided depends on thread order.
+//   classify  one lane per cell: 27 look-ups, up to 270 int64 loads (L2-resident), the block's covariance in int64, one
+//             thread-serial Jacobi (eig3.h), three comparisons, one byte stored.  Block sum and eigen-solve share the kernel: the
+//             sums are dead once the six covariance entries are converted, so they do not add to the solver's registers
 // The passes over points are HBM-bound (16 B read per point each, plus the set's traffic in L2); the passes over cells touch a
 // fraction of that.  They are separate launches because each needs the one before it complete for the whole frame.
 #include <hip/hip_runtime.h>
 
+#include "eig3.h"
 #include "k15_seed.h"
 
 namespace ilcc {
@@ -162,6 +172,92 @@ __global__ __launch_bounds__(kSeedThreads) void k15_moments(SeedCtx c) {
   }
 }
 
+// ---- K15p classify.  The order of every fp64 operation below is part of the specification (include/ilcc_seed.h, K15p);
+// tests/seed_planar_ref.py restates it operation for operation.
+
+// a cell's ten moments about the origin o (quanta): q' = q - o.  Unsigned arithmetic: exact modulo 2^64 whatever the size of the
+// intermediate products, and the translated sums are small (|q'| <= 2 cq for every point of the block)
+__device__ __forceinline__ void translate(const long long m[kSeedMoments], const long long o[3], long long t[kSeedMoments]) {
+  typedef unsigned long long u64;
+  const u64 n = (u64)m[0], ox = (u64)o[0], oy = (u64)o[1], oz = (u64)o[2];
+  const u64 sx = (u64)m[1], sy = (u64)m[2], sz = (u64)m[3];
+  t[0] = m[0];
+  t[1] = (long long)(sx - n * ox);
+  t[2] = (long long)(sy - n * oy);
+  t[3] = (long long)(sz - n * oz);
+  t[4] = (long long)((u64)m[4] - ox * sx - ox * sx + n * ox * ox);
+  t[5] = (long long)((u64)m[5] - ox * sy - oy * sx + n * ox * oy);
+  t[6] = (long long)((u64)m[6] - ox * sz - oz * sx + n * ox * oz);
+  t[7] = (long long)((u64)m[7] - oy * sy - oy * sy + n * oy * oy);
+  t[8] = (long long)((u64)m[8] - oy * sz - oz * sy + n * oy * oz);
+  t[9] = (long long)((u64)m[9] - oz * sz - oz * sz + n * oz * oz);
+}
+
+__global__ __launch_bounds__(kSeedThreads) void k15_classify(SeedCtx c) {
+  const uint32_t f = blockIdx.y;
+  const SeedFrame fr = c.fr[f];
+  const uint32_t n_cells = c.counters[2 * f];
+  const uint32_t* tab = c.tab_key + fr.tab_beg;
+  const int32_t N = c.g.N;
+  const uint32_t stride = gridDim.x * kSeedThreads;
+  // ceil(n_cells / stride) trips
+  for (uint32_t i = blockIdx.x * kSeedThreads + threadIdx.x; i < n_cells; i += stride) {
+    const uint32_t k = c.cell_key[fr.pt_beg + i];
+    const int32_t ix = (int32_t)(k % (uint32_t)N), iy = (int32_t)((k / (uint32_t)N) % (uint32_t)N), iz = (int32_t)(k / (uint32_t)(N * N));
+    long long b[kSeedMoments];   // the block's sums, untranslated
+#pragma unroll
+    for (int m = 0; m < kSeedMoments; ++m) b[m] = 0;
+    // the 27 cells of the block, the centre among them; an index outside [0, N) on any axis is skipped, never wrapped: 27 trips
+    for (int32_t d = 0; d < 27; ++d) {
+      const int32_t jx = ix + d % 3 - 1, jy = iy + (d / 3) % 3 - 1, jz = iz + d / 9 - 1;
+      if (jx < 0 || jx >= N || jy < 0 || jy >= N || jz < 0 || jz >= N) continue;
+      const uint32_t slot = d == 13 ? 0u : find_slot(tab, fr, (uint32_t)(jx + N * (jy + N * jz)));
+      if (slot == kSeedEmpty) continue;
+      const uint32_t j = d == 13 ? i : c.tab_ord[fr.tab_beg + slot];
+      const long long* src = c.mom + (fr.pt_beg + j) * kSeedMoments;
+#pragma unroll
+      for (int m = 0; m < kSeedMoments; ++m) b[m] += src[m];
+    }
+    long long own[kSeedMoments];
+    {
+      const long long* src = c.mom + (fr.pt_beg + i) * kSeedMoments;
+#pragma unroll
+      for (int m = 0; m < kSeedMoments; ++m) own[m] = src[m];
+    }
+    // exact translation to the centre cell's origin; then n_b sum q' q'^T - sum q' sum q'^T stays in int64: the host admits a
+    // frame only while n 2 cq < 2^31, and |q'| <= 2 cq
+    const long long o[3] = {(long long)c.g.cq * (ix - c.g.off), (long long)c.g.cq * (iy - c.g.off), (long long)c.g.cq * (iz - c.g.off)};
+    long long tb[kSeedMoments], to[kSeedMoments];
+    translate(b, o, tb);
+    translate(own, o, to);
+    const long long nb_i = tb[0];
+    const double cxx = (double)(nb_i * tb[4] - tb[1] * tb[1]), cxy = (double)(nb_i * tb[5] - tb[1] * tb[2]), cxz = (double)(nb_i * tb[6] - tb[1] * tb[3]);
+    const double cyy = (double)(nb_i * tb[7] - tb[2] * tb[2]), cyz = (double)(nb_i * tb[8] - tb[2] * tb[3]), czz = (double)(nb_i * tb[9] - tb[3] * tb[3]);
+    const double cov[9] = {cxx, cxy, cxz, cxy, cyy, cyz, cxz, cyz, czz};
+    double w[3], v[3][3];
+    eig3_sym(cov, w, v);
+    const double nb = (double)nb_i, nb2 = nb * nb;
+    const bool flat = w[0] <= nb2 * c.flat_q2;
+    const bool surface = 12.0 * w[1] >= nb2 * c.spread_q2;
+    // A = the second moment of the cell's OWN points about the block's centroid m = sum_b q' / n_b
+    const double no = (double)to[0];
+    const double mc[3] = {(double)tb[1] / nb, (double)tb[2] / nb, (double)tb[3] / nb};
+    const double sd[3] = {(double)to[1], (double)to[2], (double)to[3]};
+    const double ssd[3][3] = {{(double)to[4], (double)to[5], (double)to[6]}, {(double)to[5], (double)to[7], (double)to[8]}, {(double)to[6], (double)to[8], (double)to[9]}};
+    double r[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double A[3];
+#pragma unroll
+      for (int e = 0; e < 3; ++e) A[e] = ((ssd[a][e] - mc[a] * sd[e]) - mc[e] * sd[a]) + (no * mc[a]) * mc[e];
+      r[a] = (A[0] * v[0][0] + A[1] * v[0][1]) + A[2] * v[0][2];
+    }
+    const double quad = (v[0][0] * r[0] + v[0][1] * r[1]) + v[0][2] * r[2];
+    const bool own_in = quad <= no * c.own_q2;
+    c.core[fr.pt_beg + i] = (flat && surface && own_in) ? 1 : 0;
+  }
+}
+
 // root of x, with path halving.  key[parent[c]] < key[c] for every non-root c, so the keys along the chain strictly decrease:
 // at most (cells of the frame) steps.  Halving only ever replaces a non-root's parent by that parent's parent -- an ancestor with
 // a smaller key still -- and never touches a root, so it cannot undo or fake a link
@@ -202,6 +298,8 @@ __device__ __forceinline__ void unite(uint32_t* parent, const uint32_t* key, uin
   }
 }
 
+// kCore (K15p): only core cells are united, with core cells
+template <bool kCore>
 __global__ __launch_bounds__(kSeedThreads) void k15_union(SeedCtx c) {
   const uint32_t f = blockIdx.y;
   const SeedFrame fr = c.fr[f];
@@ -213,6 +311,7 @@ __global__ __launch_bounds__(kSeedThreads) void k15_union(SeedCtx c) {
   const uint32_t stride = gridDim.x * kSeedThreads;
   // ceil(n_cells / stride) trips
   for (uint32_t i = blockIdx.x * kSeedThreads + threadIdx.x; i < n_cells; i += stride) {
+    if (kCore && !c.core[fr.pt_beg + i]) continue;
     const uint32_t k = key[i];
     const int32_t ix = (int32_t)(k % (uint32_t)N), iy = (int32_t)((k / (uint32_t)N) % (uint32_t)N), iz = (int32_t)(k / (uint32_t)(N * N));
     // the 13 neighbours with a larger key: (dz, dy, dx) > (0, 0, 0) in that order = offsets 14 .. 26 of the 3 x 3 x 3 block: 13 trips
@@ -221,11 +320,15 @@ __global__ __launch_bounds__(kSeedThreads) void k15_union(SeedCtx c) {
       const int32_t jx = ix + dx, jy = iy + dy, jz = iz + dz;
       if (jx < 0 || jx >= N || jy < 0 || jy >= N || jz < 0 || jz >= N) continue;
       const uint32_t slot = find_slot(tab, fr, (uint32_t)(jx + N * (jy + N * jz)));
-      if (slot != kSeedEmpty) unite(parent, key, i, c.tab_ord[fr.tab_beg + slot]);
+      if (slot == kSeedEmpty) continue;
+      const uint32_t j = c.tab_ord[fr.tab_beg + slot];
+      if (kCore && !c.core[fr.pt_beg + j]) continue;
+      unite(parent, key, i, j);
     }
   }
 }
 
+// (K15p: a cell that is not core was never united, so it is its own root and adds nothing: only core non-roots add to their root)
 __global__ __launch_bounds__(kSeedThreads) void k15_reduce(SeedCtx c) {
   const uint32_t f = blockIdx.y;
   const SeedFrame fr = c.fr[f];
@@ -263,6 +366,8 @@ __global__ __launch_bounds__(kSeedThreads) void k15_reduce(SeedCtx c) {
   }
 }
 
+// kCore (K15p): only core roots claim a record
+template <bool kCore>
 __global__ __launch_bounds__(kSeedThreads) void k15_pack(SeedCtx c) {
   const uint32_t f = blockIdx.y;
   const SeedFrame fr = c.fr[f];
@@ -271,6 +376,7 @@ __global__ __launch_bounds__(kSeedThreads) void k15_pack(SeedCtx c) {
   // ceil(n_cells / stride) trips
   for (uint32_t i = blockIdx.x * kSeedThreads + threadIdx.x; i < n_cells; i += stride) {
     if (c.parent[fr.pt_beg + i] != i) continue;
+    if (kCore && !c.core[fr.pt_beg + i]) continue;
     const long long* m = c.mom + (fr.pt_beg + i) * kSeedMoments;
     if (m[0] < (long long)c.cluster_min) continue;
     const uint32_t at = atomicAdd(&c.counters[2 * f + 1], 1u);   // the count goes on past max_components: the host reports ILCC_CAPACITY
@@ -299,11 +405,20 @@ void launch_seed_components(const SeedCtx& c, uint32_t max_frame_points, hipStre
   mark();
   hipLaunchKernelGGL(k15_moments, grid, block, 0, s, c);
   mark();
-  hipLaunchKernelGGL(k15_union, grid, block, 0, s, c);
+  if (c.core) {
+    hipLaunchKernelGGL(k15_classify, grid, block, 0, s, c);
+    mark();
+    hipLaunchKernelGGL(k15_union<true>, grid, block, 0, s, c);
+  } else {
+    hipLaunchKernelGGL(k15_union<false>, grid, block, 0, s, c);
+  }
   mark();
   hipLaunchKernelGGL(k15_reduce, grid, block, 0, s, c);
   mark();
-  hipLaunchKernelGGL(k15_pack, grid, block, 0, s, c);
+  if (c.core)
+    hipLaunchKernelGGL(k15_pack<true>, grid, block, 0, s, c);
+  else
+    hipLaunchKernelGGL(k15_pack<false>, grid, block, 0, s, c);
   mark();
 }
 

@@ -1,5 +1,6 @@
 // seed_api.cpp -- the entries of include/ilcc_seed.h: the scratch layout and host chain of K15 (k15_seed_components.hip), the
 // host finishing behind it (seed_host.cpp), and ilcc_extract_auto*, which lays every proposal out as a frame of one ordinary batch.
+// Every planar entry (K15p) is its ordinary sibling with a set ilcc_seed_planar_params pointer: one implementation each.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@ namespace {
 
 struct Layout {   // byte offsets of the parts of the scratch, each on a 256-byte boundary
   uint64_t frames, counters, tab_key, tab_ord, cell_key, parent, mom, packed, total, slots;
+  uint64_t core, total_planar;   // K15p: the flag array lies behind the ordinary parts, which keep their places
 };
 
 // hash-set slots that serve any split of `points` into `frames`: a frame's set is max(64, < 4 n) slots
@@ -39,6 +41,8 @@ Layout layout(uint32_t frames, uint64_t points, uint32_t max_components) {
   l.mom = part(8ull * kSeedMoments * cells);
   l.packed = part(8ull * ILCC_SEED_RECORD_WORDS * max_components * frames);
   l.total = at;
+  l.core = part(cells);
+  l.total_planar = at;
   return l;
 }
 
@@ -49,21 +53,23 @@ bool counts_ok(const ilcc_seed_params& sp) {
 
 using Record = std::array<int64_t, ILCC_SEED_RECORD_WORDS>;
 
-thread_local float g_launch_ms[kSeedLaunches] = {};   // ilcc_debug_seed_launch_ms
+thread_local float g_launch_ms[kSeedLaunches] = {};                // ilcc_debug_seed_launch_ms
+thread_local float g_planar_launch_ms[kSeedPlanarLaunches] = {};   // ilcc_debug_seed_planar_launch_ms
 
 struct LaunchEvents {   // HIP events in front of, between and behind K15's launches, destroyed on scope exit
-  hipEvent_t ev[kSeedLaunches + 1] = {};
+  hipEvent_t ev[kSeedPlanarLaunches + 1] = {};
   ~LaunchEvents() {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
 
-// K15 on a batch in HBM: per frame the sorted records (records[f]) and whether the frame overflowed max_components
+// K15 on a batch in HBM: per frame the sorted records (records[f]) and whether the frame overflowed max_components.
+// planar: false = the ordinary components (pp is not read); true = the components of core cells under *pp
 int32_t seed_components(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
-                        void* d_scratch, hipStream_t s, std::vector<std::vector<Record>>* records, std::vector<uint8_t>* overflow) {
+                        bool planar, const ilcc_seed_planar_params* pp, void* d_scratch, hipStream_t s, std::vector<std::vector<Record>>* records, std::vector<uint8_t>* overflow) {
   if (!h) return ILCC_BAD_ARGUMENT;
-  if (!d_xyzi || !offsets || !sp || !d_scratch || n_frames == 0) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null pointer or no frames");
+  if (!d_xyzi || !offsets || !sp || !d_scratch || n_frames == 0 || (planar && !pp)) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null pointer or no frames");
   if ((reinterpret_cast<uintptr_t>(d_scratch) & 255u) != 0) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: scratch must be 256-byte aligned");
   const HandleView hv = handle_view(h);
   if (n_frames > hv.max_frames || n_frames > 65535u) return handle_fail(h, ILCC_CAPACITY, "seed: n_frames exceeds the handle's max_frames (or 65535)");
@@ -79,6 +85,11 @@ int32_t seed_components(ilcc_handle* h, const float* d_xyzi, const uint64_t* off
   if (!counts_ok(*sp)) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: cluster_min, max_components, max_seeds and the board must be positive");
   SeedGrid g{};
   if (!seed_grid(*sp, hv.max_points, &g)) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: cell and range must be positive, range / cell at most 511 cells");
+  double flat_q2 = 0, spread_q2 = 0, own_q2 = 0;
+  if (planar) {
+    if (!seed_planar_thresholds(*pp, &flat_q2, &spread_q2, &own_q2)) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: planar_rms, min_spread and own_rms must be positive");
+    if (!seed_planar_frame_fits(max_n, g)) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: planar seeds need points 2 ceil(1024 cell) < 2^31 in every frame");
+  }
 
   hipError_t e;
   if ((e = hipSetDevice(hv.device)) != hipSuccess) return handle_fail(h, ILCC_HIP_ERROR, std::string("hipSetDevice: ") + hipGetErrorString(e));
@@ -109,6 +120,10 @@ int32_t seed_components(ilcc_handle* h, const float* d_xyzi, const uint64_t* off
   c.parent = reinterpret_cast<uint32_t*>(base + l.parent);
   c.mom = reinterpret_cast<long long*>(base + l.mom);
   c.packed = reinterpret_cast<long long*>(base + l.packed);
+  c.core = planar ? base + l.core : nullptr;
+  c.flat_q2 = flat_q2;
+  c.spread_q2 = spread_q2;
+  c.own_q2 = own_q2;
 
   std::vector<uint32_t> counters(2ull * n_frames);
   std::vector<int64_t> packed((uint64_t)ILCC_SEED_RECORD_WORDS * sp->max_components * n_frames);
@@ -118,15 +133,17 @@ int32_t seed_components(ilcc_handle* h, const float* d_xyzi, const uint64_t* off
   int32_t st;
   if ((st = hip(hipMemcpyAsync(base + l.frames, fr.data(), sizeof(SeedFrame) * n_frames, hipMemcpyHostToDevice, s), "hipMemcpyAsync")) != ILCC_OK) return st;
   LaunchEvents le;
-  for (hipEvent_t& e : le.ev)
-    if ((st = hip(hipEventCreate(&e), "hipEventCreate")) != ILCC_OK) return st;
+  const int n_launches = planar ? kSeedPlanarLaunches : kSeedLaunches;
+  for (int k = 0; k <= n_launches; ++k)
+    if ((st = hip(hipEventCreate(&le.ev[k]), "hipEventCreate")) != ILCC_OK) return st;
   launch_seed_components(c, max_n, s, le.ev);
   if ((st = hip(hipGetLastError(), "K15 launch")) != ILCC_OK) return st;
   if ((st = hip(hipMemcpyAsync(counters.data(), c.counters, 8ull * n_frames, hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) != ILCC_OK) return st;
   if ((st = hip(hipMemcpyAsync(packed.data(), c.packed, 8ull * packed.size(), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) != ILCC_OK) return st;
   if ((st = hip(hipStreamSynchronize(s), "hipStreamSynchronize")) != ILCC_OK) return st;
-  for (int k = 0; k < kSeedLaunches; ++k)
-    if (hipEventElapsedTime(&g_launch_ms[k], le.ev[k], le.ev[k + 1]) != hipSuccess) g_launch_ms[k] = 0.f;
+  float* launch_ms = planar ? g_planar_launch_ms : g_launch_ms;
+  for (int k = 0; k < n_launches; ++k)
+    if (hipEventElapsedTime(&launch_ms[k], le.ev[k], le.ev[k + 1]) != hipSuccess) launch_ms[k] = 0.f;
 
   records->assign(n_frames, {});
   overflow->assign(n_frames, 0);
@@ -149,10 +166,10 @@ struct HostBatch {
   DeviceBuffer xyzi, scratch;
 };
 
-int32_t stage_host_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp, bool want_scratch,
-                         HostBatch* b) {
+int32_t stage_host_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp, bool planar,
+                         const ilcc_seed_planar_params* pp, bool want_scratch, HostBatch* b) {
   if (!h) return ILCC_BAD_ARGUMENT;
-  if (!xyzi || !offsets || !sp || n_frames == 0) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null pointer or no frames");
+  if (!xyzi || !offsets || !sp || n_frames == 0 || (planar && !pp)) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null pointer or no frames");
   const HandleView hv = handle_view(h);
   if (n_frames > hv.max_frames || n_frames > 65535u) return handle_fail(h, ILCC_CAPACITY, "seed: n_frames exceeds the handle's max_frames (or 65535)");
   if (offsets[0] != 0) return handle_fail(h, ILCC_BAD_ARGUMENT, "offsets[0] must be 0");
@@ -164,7 +181,8 @@ int32_t stage_host_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offs
   hipError_t e;
   if ((e = hipSetDevice(hv.device)) != hipSuccess) return handle_fail(h, ILCC_HIP_ERROR, std::string("hipSetDevice: ") + hipGetErrorString(e));
   if ((e = hipMalloc(&b->xyzi.p, 16 * (total ? total : 1))) != hipSuccess) return handle_fail(h, ILCC_HIP_ERROR, std::string("hipMalloc: ") + hipGetErrorString(e));
-  if (want_scratch && (e = hipMalloc(&b->scratch.p, ilcc_seed_scratch_bytes(n_frames, total, sp))) != hipSuccess)
+  const Layout l = layout(n_frames, total, (uint32_t)sp->max_components);
+  if (want_scratch && (e = hipMalloc(&b->scratch.p, planar ? l.total_planar : l.total)) != hipSuccess)
     return handle_fail(h, ILCC_HIP_ERROR, std::string("hipMalloc: ") + hipGetErrorString(e));
   if (total && (e = hipMemcpy(b->xyzi.p, xyzi, 16 * total, hipMemcpyHostToDevice)) != hipSuccess)
     return handle_fail(h, ILCC_HIP_ERROR, std::string("hipMemcpy: ") + hipGetErrorString(e));
@@ -176,26 +194,13 @@ bool accepted(const ilcc_result& r, const ilcc_seed_params& sp) {
   return r.status == ILCC_OK && !(r.flags & ILCC_FLAG_LOW_COVERAGE) && (double)r.n_oob <= sp.max_oob_share * (double)(r.n_black + r.n_white);
 }
 
-}  // namespace
-
-extern "C" {
-
-uint64_t ilcc_seed_scratch_bytes(uint32_t n_frames, uint64_t total_points, const ilcc_seed_params* sp) {
-  if (!sp || sp->max_components < 1) return 0;
-  return layout(n_frames, total_points, (uint32_t)sp->max_components).total;
-}
-
-void ilcc_debug_seed_launch_ms(float out[ILCC_SEED_LAUNCHES]) {
-  for (int k = 0; k < kSeedLaunches; ++k) out[k] = g_launch_ms[k];
-}
-
-int32_t ilcc_propose_seeds_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
-                                  void* d_scratch, ilcc_seed* out_seeds, int32_t* out_counts, void* hip_stream) {
+int32_t propose_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp, bool planar,
+                       const ilcc_seed_planar_params* pp, void* d_scratch, ilcc_seed* out_seeds, int32_t* out_counts, void* hip_stream) {
   if (!h) return ILCC_BAD_ARGUMENT;
   if (!out_seeds || !out_counts) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null output");
   std::vector<std::vector<Record>> records;
   std::vector<uint8_t> overflow;
-  const int32_t st = seed_components(h, d_xyzi, offsets, n_frames, sp, d_scratch, static_cast<hipStream_t>(hip_stream), &records, &overflow);
+  const int32_t st = seed_components(h, d_xyzi, offsets, n_frames, sp, planar, pp, d_scratch, static_cast<hipStream_t>(hip_stream), &records, &overflow);
   if (st != ILCC_OK) return st;
   for (uint32_t f = 0; f < n_frames; ++f) {
     if (overflow[f]) {
@@ -207,26 +212,26 @@ int32_t ilcc_propose_seeds_device(ilcc_handle* h, const float* d_xyzi, const uin
   return ILCC_OK;
 }
 
-int32_t ilcc_propose_seeds(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
-                           ilcc_seed* out_seeds, int32_t* out_counts) {
+int32_t propose_host(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp, bool planar,
+                     const ilcc_seed_planar_params* pp, ilcc_seed* out_seeds, int32_t* out_counts) {
   if (!h) return ILCC_BAD_ARGUMENT;
   if (!out_seeds || !out_counts) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null output");
   HostBatch b;
-  const int32_t st = stage_host_batch(h, xyzi, offsets, n_frames, sp, true, &b);
+  const int32_t st = stage_host_batch(h, xyzi, offsets, n_frames, sp, planar, pp, true, &b);
   if (st != ILCC_OK) return st;
-  return ilcc_propose_seeds_device(h, static_cast<const float*>(b.xyzi.p), offsets, n_frames, sp, b.scratch.p, out_seeds, out_counts, nullptr);
+  return propose_device(h, static_cast<const float*>(b.xyzi.p), offsets, n_frames, sp, planar, pp, b.scratch.p, out_seeds, out_counts, nullptr);
 }
 
-int32_t ilcc_debug_seed_components(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
-                                   void* d_scratch, uint32_t frame, int64_t* out_records, uint32_t cap_records, int32_t* out_n) {
+int32_t debug_components(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp, bool planar,
+                         const ilcc_seed_planar_params* pp, void* d_scratch, uint32_t frame, int64_t* out_records, uint32_t cap_records, int32_t* out_n) {
   if (!h) return ILCC_BAD_ARGUMENT;
   if (!out_records || !out_n || frame >= n_frames) return handle_fail(h, ILCC_BAD_ARGUMENT, "seed: null output or no such frame");
   HostBatch b;
-  int32_t st = stage_host_batch(h, xyzi, offsets, n_frames, sp, d_scratch == nullptr, &b);
+  int32_t st = stage_host_batch(h, xyzi, offsets, n_frames, sp, planar, pp, d_scratch == nullptr, &b);
   if (st != ILCC_OK) return st;
   std::vector<std::vector<Record>> records;
   std::vector<uint8_t> overflow;
-  st = seed_components(h, static_cast<const float*>(b.xyzi.p), offsets, n_frames, sp, d_scratch ? d_scratch : b.scratch.p, nullptr, &records, &overflow);
+  st = seed_components(h, static_cast<const float*>(b.xyzi.p), offsets, n_frames, sp, planar, pp, d_scratch ? d_scratch : b.scratch.p, nullptr, &records, &overflow);
   if (st != ILCC_OK) return st;
   if (overflow[frame] || records[frame].size() > cap_records) return handle_fail(h, ILCC_CAPACITY, "seed: more components than max_components / cap_records in this frame");
   if (!records[frame].empty()) std::memcpy(out_records, records[frame].data(), sizeof(Record) * records[frame].size());
@@ -234,16 +239,16 @@ int32_t ilcc_debug_seed_components(ilcc_handle* h, const float* xyzi, const uint
   return ILCC_OK;
 }
 
-int32_t ilcc_extract_auto_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
-                                ilcc_result* out, float* out_seed, int32_t* out_rank) {
+int32_t extract_auto_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp, bool planar,
+                           const ilcc_seed_planar_params* pp, ilcc_result* out, float* out_seed, int32_t* out_rank) {
   if (!h) return ILCC_BAD_ARGUMENT;
   if (!out || !out_seed || !out_rank) return handle_fail(h, ILCC_BAD_ARGUMENT, "extract_auto: null output");
   HostBatch b;
-  int32_t st = stage_host_batch(h, xyzi, offsets, n_frames, sp, true, &b);
+  int32_t st = stage_host_batch(h, xyzi, offsets, n_frames, sp, planar, pp, true, &b);
   if (st != ILCC_OK) return st;
   std::vector<ilcc_seed> seeds((uint64_t)n_frames * sp->max_seeds);
   std::vector<int32_t> counts(n_frames);
-  st = ilcc_propose_seeds_device(h, static_cast<const float*>(b.xyzi.p), offsets, n_frames, sp, b.scratch.p, seeds.data(), counts.data(), nullptr);
+  st = propose_device(h, static_cast<const float*>(b.xyzi.p), offsets, n_frames, sp, planar, pp, b.scratch.p, seeds.data(), counts.data(), nullptr);
   if (st != ILCC_OK) return st;
 
   // every candidate becomes a frame of one ordinary batch
@@ -308,10 +313,74 @@ int32_t ilcc_extract_auto_batch(ilcc_handle* h, const float* xyzi, const uint64_
   return ILCC_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+uint64_t ilcc_seed_scratch_bytes(uint32_t n_frames, uint64_t total_points, const ilcc_seed_params* sp) {
+  if (!sp || sp->max_components < 1) return 0;
+  return layout(n_frames, total_points, (uint32_t)sp->max_components).total;
+}
+
+uint64_t ilcc_seed_planar_scratch_bytes(uint32_t n_frames, uint64_t total_points, const ilcc_seed_params* sp) {
+  if (!sp || sp->max_components < 1) return 0;
+  return layout(n_frames, total_points, (uint32_t)sp->max_components).total_planar;
+}
+
+void ilcc_debug_seed_launch_ms(float out[ILCC_SEED_LAUNCHES]) {
+  for (int k = 0; k < kSeedLaunches; ++k) out[k] = g_launch_ms[k];
+}
+
+void ilcc_debug_seed_planar_launch_ms(float out[ILCC_SEED_PLANAR_LAUNCHES]) {
+  for (int k = 0; k < kSeedPlanarLaunches; ++k) out[k] = g_planar_launch_ms[k];
+}
+
+int32_t ilcc_propose_seeds_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                  void* d_scratch, ilcc_seed* out_seeds, int32_t* out_counts, void* hip_stream) {
+  return propose_device(h, d_xyzi, offsets, n_frames, sp, false, nullptr, d_scratch, out_seeds, out_counts, hip_stream);
+}
+int32_t ilcc_propose_seeds_planar_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                         const ilcc_seed_planar_params* pp, void* d_scratch, ilcc_seed* out_seeds, int32_t* out_counts, void* hip_stream) {
+  return propose_device(h, d_xyzi, offsets, n_frames, sp, true, pp, d_scratch, out_seeds, out_counts, hip_stream);
+}
+
+int32_t ilcc_propose_seeds(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                           ilcc_seed* out_seeds, int32_t* out_counts) {
+  return propose_host(h, xyzi, offsets, n_frames, sp, false, nullptr, out_seeds, out_counts);
+}
+int32_t ilcc_propose_seeds_planar(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                  const ilcc_seed_planar_params* pp, ilcc_seed* out_seeds, int32_t* out_counts) {
+  return propose_host(h, xyzi, offsets, n_frames, sp, true, pp, out_seeds, out_counts);
+}
+
+int32_t ilcc_debug_seed_components(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                   void* d_scratch, uint32_t frame, int64_t* out_records, uint32_t cap_records, int32_t* out_n) {
+  return debug_components(h, xyzi, offsets, n_frames, sp, false, nullptr, d_scratch, frame, out_records, cap_records, out_n);
+}
+int32_t ilcc_debug_seed_planar_components(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                          const ilcc_seed_planar_params* pp, void* d_scratch, uint32_t frame, int64_t* out_records,
+                                          uint32_t cap_records, int32_t* out_n) {
+  return debug_components(h, xyzi, offsets, n_frames, sp, true, pp, d_scratch, frame, out_records, cap_records, out_n);
+}
+
+int32_t ilcc_extract_auto_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                ilcc_result* out, float* out_seed, int32_t* out_rank) {
+  return extract_auto_batch(h, xyzi, offsets, n_frames, sp, false, nullptr, out, out_seed, out_rank);
+}
+int32_t ilcc_extract_auto_planar_batch(ilcc_handle* h, const float* xyzi, const uint64_t* offsets, uint32_t n_frames, const ilcc_seed_params* sp,
+                                       const ilcc_seed_planar_params* pp, ilcc_result* out, float* out_seed, int32_t* out_rank) {
+  return extract_auto_batch(h, xyzi, offsets, n_frames, sp, true, pp, out, out_seed, out_rank);
+}
+
 int32_t ilcc_extract_auto(ilcc_handle* h, const float* xyzi, uint32_t n, const ilcc_seed_params* sp, ilcc_result* out, float out_seed[3],
                           int32_t* out_rank) {
   const uint64_t off[2] = {0, n};
-  return ilcc_extract_auto_batch(h, xyzi, off, 1, sp, out, out_seed, out_rank);
+  return extract_auto_batch(h, xyzi, off, 1, sp, false, nullptr, out, out_seed, out_rank);
+}
+int32_t ilcc_extract_auto_planar(ilcc_handle* h, const float* xyzi, uint32_t n, const ilcc_seed_params* sp, const ilcc_seed_planar_params* pp,
+                                 ilcc_result* out, float out_seed[3], int32_t* out_rank) {
+  const uint64_t off[2] = {0, n};
+  return extract_auto_batch(h, xyzi, off, 1, sp, true, pp, out, out_seed, out_rank);
 }
 
 }  // extern "C"

@@ -59,7 +59,30 @@ int32_t seed_rank(const int64_t* records, int32_t n_rec, const ilcc_seed_params&
   return keep;
 }
 
+bool seed_planar_thresholds(const ilcc_seed_planar_params& pp, double* flat_q2, double* spread_q2, double* own_q2) {
+  const double t[3] = {pp.planar_rms, pp.min_spread, pp.own_rms};
+  double* out[3] = {flat_q2, spread_q2, own_q2};
+  for (int k = 0; k < 3; ++k) {
+    if (!(t[k] > 0) || !(t[k] < 1e9)) return false;   // NaN fails too
+    const double q = 1024.0 * t[k];
+    *out[k] = q * q;
+  }
+  return true;
+}
+
+bool seed_planar_frame_fits(uint64_t n_points, const SeedGrid& g) { return n_points * 2ull * (uint64_t)g.cq < (1ull << 31); }
+
 }  // namespace ilcc
+
+extern "C" void ilcc_default_seed_planar_params(const ilcc_params* p, ilcc_seed_params* sp, ilcc_seed_planar_params* pp) {
+  if (!p || !sp || !pp) return;
+  ilcc_default_seed_params(p, sp);
+  sp->max_rms = 0.05;   // a component of core cells keeps a rim of cells that also hold floor: DESIGN.md section 9
+  *pp = ilcc_seed_planar_params{};
+  pp->planar_rms = p->ransac_thresh;
+  pp->min_spread = sp->cell / 2;
+  pp->own_rms = 0.02;
+}
 
 extern "C" void ilcc_default_seed_params(const ilcc_params* p, ilcc_seed_params* sp) {
   if (!p || !sp) return;

@@ -53,19 +53,28 @@ bool LidarCornersEst::ensure_handle() {
   return true;
 }
 
-bool LidarCornersEst::find_board(myPointCloudPtr cloud, const ilcc_seed_params* seed_params) {
+bool LidarCornersEst::find_board(myPointCloudPtr cloud, const ilcc_seed_params* seed_params) { return find_board_by(cloud, seed_params, false, nullptr); }
+
+bool LidarCornersEst::find_board_planar(myPointCloudPtr cloud, const ilcc_seed_params* seed_params, const ilcc_seed_planar_params* planar_params) {
+  return find_board_by(cloud, seed_params, true, planar_params);
+}
+
+bool LidarCornersEst::find_board_by(myPointCloudPtr cloud, const ilcc_seed_params* seed_params, bool planar, const ilcc_seed_planar_params* planar_params) {
   if (!cloud || !ensure_handle()) return false;
-  ilcc_seed_params sp;
-  if (seed_params) {
-    sp = *seed_params;
-  } else {
-    ilcc_default_seed_params(&m_params, &sp);
-    if ((uint32_t)sp.max_seeds > m_max_frames) sp.max_seeds = (int32_t)m_max_frames;
-  }
+  ilcc_seed_params sp, sp_planar;
+  ilcc_seed_planar_params pp;
+  ilcc_default_seed_params(&m_params, &sp);
+  ilcc_default_seed_planar_params(&m_params, &sp_planar, &pp);
+  if (planar) sp = sp_planar;
+  if ((uint32_t)sp.max_seeds > m_max_frames) sp.max_seeds = (int32_t)m_max_frames;
+  if (seed_params) sp = *seed_params;
+  if (planar_params) pp = *planar_params;
   ilcc_result picked{};
   float seed[3] = {0.f, 0.f, 0.f};
   int32_t rank = -1;
-  const int32_t st = ilcc_extract_auto(m_handle, reinterpret_cast<const float*>(cloud->data()), (uint32_t)cloud->size(), &sp, &picked, seed, &rank);
+  const float* xyzi = reinterpret_cast<const float*>(cloud->data());
+  const int32_t st = planar ? ilcc_extract_auto_planar(m_handle, xyzi, (uint32_t)cloud->size(), &sp, &pp, &picked, seed, &rank)
+                            : ilcc_extract_auto(m_handle, xyzi, (uint32_t)cloud->size(), &sp, &picked, seed, &rank);
   if (st != ILCC_OK) {
     std::cerr << "ilcc_extract_auto: " << ilcc_strerror(st) << " " << ilcc_last_error(m_handle) << std::endl;
     return false;

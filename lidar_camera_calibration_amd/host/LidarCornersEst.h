@@ -42,6 +42,8 @@ class LidarCornersEst {
   // it accepts.  true: m_click_point is that seed and the scan is set up as setROI(cloud, m_click_point) leaves it.  seed_params:
   // nullptr = ilcc_default_seed_params with at most max_frames seeds
   bool find_board(myPointCloudPtr cloud, const ilcc_seed_params* seed_params = nullptr);
+  // the same on planar seeds (K15p): finds a board that stands on the floor or on a stand.  nullptr = ilcc_default_seed_planar_params
+  bool find_board_planar(myPointCloudPtr cloud, const ilcc_seed_params* seed_params = nullptr, const ilcc_seed_planar_params* planar_params = nullptr);
   bool EuclideanCluster();                                    // :124-186
   void PCA();                                                 // :366-372
   bool get_corners(std::vector<std::array<double, 3>>& corners);   // :374-450
@@ -64,6 +66,7 @@ class LidarCornersEst {
  private:
   bool run();
   bool ensure_handle();
+  bool find_board_by(myPointCloudPtr cloud, const ilcc_seed_params* seed_params, bool planar, const ilcc_seed_planar_params* planar_params);
   myPointCloudPtr fetch(int32_t which);
 
   ilcc_params m_params{};

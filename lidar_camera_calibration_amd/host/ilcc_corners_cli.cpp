@@ -5,6 +5,7 @@
 //   ilcc_corners --bag 20181101_1.bag [--topic /velodyne_points] --click x y z ... (first PointCloud2
 //                of the bag, read without ROS: include/ilcc_ingest.h)
 //   --auto in place of --click x y z: the seed is proposed from the cloud itself (include/ilcc_seed.h) and printed
+//   --auto-planar likewise, from planar seeds: for a board that stands on the floor, on a stand or in a hand
 // Mirrors the per-bag body of /root/reference/ilcc2/test/get_lidar_corners.cpp:133-204.
 #include <cstdio>
 #include <cstdlib>
@@ -22,7 +23,7 @@ int main(int argc, char** argv) {
   std::string cloud_path, bag_path, topic = "/velodyne_points", yaml_path, out_path, solver = "grid";
   PointXYZI click{0, 0, 0, 0};
   int device = -1;
-  bool have_click = false, auto_seed = false, accept_ambiguous = false, accept_low_coverage = false;
+  bool have_click = false, auto_seed = false, auto_planar = false, accept_ambiguous = false, accept_low_coverage = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--cloud" && i + 1 < argc) cloud_path = argv[++i];
@@ -35,6 +36,7 @@ int main(int argc, char** argv) {
     else if (a == "--accept-ambiguous") accept_ambiguous = true;
     else if (a == "--accept-low-coverage") accept_low_coverage = true;
     else if (a == "--auto") auto_seed = true;
+    else if (a == "--auto-planar") auto_planar = true;
     else if (a == "--click" && i + 3 < argc) {
       click.x = (float)std::atof(argv[++i]);
       click.y = (float)std::atof(argv[++i]);
@@ -45,8 +47,8 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if ((cloud_path.empty() == bag_path.empty()) || out_path.empty() || have_click == auto_seed) {
-    std::fprintf(stderr, "usage: ilcc_corners (--cloud frame.bin | --bag file.bag [--topic /velodyne_points]) (--click x y z | --auto) "
+  if ((cloud_path.empty() == bag_path.empty()) || out_path.empty() || (int)have_click + (int)auto_seed + (int)auto_planar != 1) {
+    std::fprintf(stderr, "usage: ilcc_corners (--cloud frame.bin | --bag file.bag [--topic /velodyne_points]) (--click x y z | --auto | --auto-planar) "
                          "[--yaml board.yaml] --out file.txt [--solver grid|reference] [--device N] [--accept-ambiguous] [--accept-low-coverage]\n");
     return 2;
   }
@@ -75,15 +77,15 @@ int main(int argc, char** argv) {
     in.read(reinterpret_cast<char*>(cloud->data()), (std::streamsize)(cloud->size() * sizeof(PointXYZI)));
   }
 
-  LidarCornersEst est(device, (uint32_t)cloud->size() + 1, auto_seed ? 4u : 1u);
+  LidarCornersEst est(device, (uint32_t)cloud->size() + 1, (auto_seed || auto_planar) ? 4u : 1u);
   est.params().solver = (solver == "reference") ? ILCC_SOLVER_REFERENCE_LOCAL : ILCC_SOLVER_GRID;
   est.accept_ambiguous = accept_ambiguous;
   est.accept_low_coverage = accept_low_coverage;
   est.register_viewer();
   if (!yaml_path.empty() && !est.set_chessboard_param(yaml_path)) return 1;
 
-  if (auto_seed) {
-    if (!est.find_board(cloud)) {
+  if (auto_seed || auto_planar) {
+    if (!(auto_planar ? est.find_board_planar(cloud) : est.find_board(cloud))) {
       std::printf("no chessboard found\n");
       return 3;
     }

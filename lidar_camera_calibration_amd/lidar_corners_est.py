@@ -110,18 +110,27 @@ class LidarCornersEst:
         self.m_click_point = self._click.copy()
         self._result = None
 
-    def find_board(self, cloud: np.ndarray, seed_params=None):
+    def find_board(self, cloud: np.ndarray, seed_params=None, planar=False, planar_params=None):
         """setROI without the click (include/ilcc_seed.h): proposes seeds on the whole cloud, runs the path on each and keeps
         the first it accepts.  Returns ``(found, seed)``; the scan is then set up as ``setROI(cloud, seed)`` would have left
         it, so ``EuclideanCluster`` / ``PCA`` / ``get_corners`` follow as usual.  At most ``max_frames`` (the constructor's)
-        proposals are tried per scan."""
+        proposals are tried per scan.  ``planar``: planar seeds (K15p), for a board that stands on the floor or on a stand."""
         from . import seed as S
         self.setROI(cloud, (0.0, 0.0, 0.0))
         h = self._handle()
-        sp = seed_params if seed_params is not None else S.default_seed_params(self.params)
+        if planar:
+            sp, pp = S.default_seed_planar_params(self.params)
+            pp = planar_params if planar_params is not None else pp
+        else:
+            sp = S.default_seed_params(self.params)
         if seed_params is None:
             sp.max_seeds = max(1, min(sp.max_seeds, self._max_frames))
-        res, seeds, ranks = S.extract_auto(self, self._cloud, None, sp)
+        else:
+            sp = seed_params
+        if planar:
+            res, seeds, ranks = S.extract_auto_planar(self, self._cloud, None, sp, pp)
+        else:
+            res, seeds, ranks = S.extract_auto(self, self._cloud, None, sp)
         self._click = seeds[0].copy()
         self.m_click_point = self._click.copy()
         if ranks[0] < 0:

@@ -1,0 +1,164 @@
+"""The planar seed proposer (K15p), the part that needs no GPU: the numpy restatement (tests/seed_planar_ref.py) on constructed
+clouds whose answer is known by construction, its two statements of eig3_sym against each other, the committed scene frames
+against the conditions they were chosen by, and the new host code of csrc/seed_host.cpp as a stand-alone program under
+AddressSanitizer and UBSan."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import seed_planar_cases as C
+import seed_planar_ref as P
+import seed_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SP = C.small_params()
+
+
+def test_vectorised_eig3_equals_the_scalar_restatement_bit_for_bit():
+    rng = np.random.default_rng(0)
+    m = rng.normal(size=(400, 3, 3))
+    m = m + m.transpose(0, 2, 1)
+    m[:50] *= 1e12                                   # the size of a block covariance in quanta
+    m[50:60, 0, 1] = m[50:60, 1, 0] = 0.0            # a rotation skipped
+    m[60:65] = 0.0                                   # off == 0 at once
+    m[65:70] = np.eye(3)
+    m[70:80, 2, :] = m[70:80, :, 2] = 0.0            # rank two: a flat patch
+    cells = P.classify(C.ell(), C.PP, C.G)           # and real block covariances are exercised through classify below
+    assert cells.core.any() and not cells.core.all()
+    w, v = P.eig3_sym_many(m.reshape(-1, 9))
+    for i in range(len(m)):
+        ws, vs = P.eig3_sym([float(x) for x in m[i].reshape(-1)])
+        assert ws == w[i].tolist() and vs == v[i].tolist(), i
+        assert ws[0] <= ws[1] <= ws[2]
+
+
+def test_dense_plate_every_cell_is_core_and_the_record_is_the_ordinary_one():
+    cloud = C.dense_plate()
+    recs, cells = P.components(cloud, SP, C.PP, want_cells=True)
+    assert len(cells.key) == 36 and cells.core.all()
+    assert recs == R.components(cloud, SP) and len(recs) == 1 and recs[0][1] == len(cloud)
+
+
+@pytest.mark.parametrize("normals", [(2, 0), (1, 0), (2, 1)])
+def test_ell_is_one_ordinary_component_and_two_planar_ones(normals):
+    cloud = C.ell(*normals)
+    assert [r[1] for r in R.components(cloud, SP)] == [len(cloud)]
+    recs, cells = P.components(cloud, SP, C.PP, want_cells=True)
+    assert len(recs) == 2 and recs[0][1] == recs[1][1]
+    # the cells within one cell of the shared edge hold both sheets in their block and belong to neither component
+    o = np.array([-4, 3, -2]) + C.G.off
+    a, b = normals
+    near_edge = (cells.index[:, a] <= o[a] + 1) & (cells.index[:, b] <= o[b] + 1)
+    assert near_edge.any() and not cells.core[near_edge].any() and cells.core[~near_edge].all()
+    assert sum(r[1] for r in recs) == sum(int(m[0]) for m in cells.mom[cells.core]) < len(cloud)
+
+
+def test_line_has_no_core_cell_and_no_record():
+    recs, cells = P.components(C.line(), SP, C.PP, want_cells=True)
+    assert len(cells.key) >= 10 and not cells.core.any() and recs == []
+    assert [r[1] for r in R.components(C.line(), SP)] == [400]
+
+
+def test_slabs_a_factor_two_below_and_above_planar_rms():
+    thin, cells = P.components(C.slab(0.5), SP, C.PP, want_cells=True)
+    assert cells.core.all() and [r[1] for r in thin] == [len(C.slab(0.5))]
+    thick, cells = P.components(C.slab(2.0), SP, C.PP, want_cells=True)
+    assert not cells.core.any() and thick == []
+
+
+def test_plate_with_a_hanging_line_keeps_the_plate():
+    cloud = C.plate_with_line()
+    recs, cells = P.components(cloud, SP, C.PP, want_cells=True)
+    n_plate = len(cloud) - 240
+    assert len(recs) == 1 and n_plate <= recs[0][1] < len(cloud)      # the line's far cells are a line: not core
+    assert not cells.core.all()
+
+
+def test_blocks_at_the_grid_s_edge_do_not_wrap():
+    for axis in range(3):
+        cloud = C.edge_plates(axis)
+        recs, cells = P.components(cloud, C.EDGE_SP, C.PP, C.EDGE_G, want_cells=True)
+        assert (cells.index[:, axis] == C.EDGE_G.N - 1).any() and (cells.index[:, axis] == 0).any()
+        assert cells.core.all() and [r[1] for r in recs] == [len(cloud) // 2] * 2, axis     # a wrapped index would join the two ends
+
+
+def test_one_cell_and_empty_clouds():
+    recs, cells = P.components(C.one_cell(), SP, C.PP, want_cells=True)
+    assert len(cells.key) == 1 and not cells.core.any() and recs == []
+    assert P.components(np.zeros((0, 4), np.float32), SP, C.PP) == []
+
+
+def test_committed_scene_frames_hold_the_conditions_they_were_chosen_by(ob):
+    """(c) on every committed frame; (a) and (b), which need the oracle, on the first two of each list"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import dev_seed_planar_recall as T
+    lists = [("floor5", C.FLOOR5_FRAMES, "vlp16"), ("in2", C.IN2_FRAMES, "vlp16"), ("pole", C.POLE_FRAMES, "vlp16")]
+    lists += [(scene, [f], "hdl64") for scene, f in C.HDL64_FRAMES]
+    assert (len(C.FLOOR5_FRAMES), len(C.IN2_FRAMES), len(C.POLE_FRAMES), len(C.HDL64_FRAMES)) == (8, 8, 2, 2)
+    for scene, frames, lidar in lists:
+        sp, pp = C.seed_params(lidar)
+        osp = R.SeedParams(board_w=sp.board_w, board_h=sp.board_h, grid_length=sp.grid_length)
+        for k, f in enumerate(frames):
+            cloud, pose, _ = C.scene_cached(scene, f, lidar)
+            assert not any(np.linalg.norm(s.centroid - pose.centre) < 0.3 for s in R.propose(cloud, osp)), (scene, f)
+            seeds = P.propose(cloud, sp, pp)
+            assert seeds and np.linalg.norm(seeds[0].centroid - pose.centre) < 0.3, (scene, f)
+            if k < 2 and lidar == "vlp16":
+                p = T.oracle_params(lidar)
+                assert T.accepted(ob.extract(cloud, pose.centre.astype(np.float32), p)), (scene, f)
+                assert T.accepted(ob.extract(cloud, seeds[0].centroid, p)), (scene, f)
+
+
+@pytest.fixture(scope="module")
+def host_check(tmp_path_factory):
+    """The stand-alone program: tests/seed_planar_host_check.cpp + csrc/seed_host.cpp only, under ASan and UBSan."""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a C++ compiler is needed"
+    out = tmp_path_factory.mktemp("seed_planar_host_check")
+    exe = str(out / "seed_planar_host_check")
+    csrc = os.path.join(ROOT, "lidar_camera_calibration_amd", "csrc")
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "seed_planar_host_check.cpp"),
+                    os.path.join(csrc, "seed_host.cpp"), "-o", exe], check=True, timeout=300)
+    return exe, out
+
+
+def test_planar_host_code_under_sanitizers_equals_the_restatement(host_check):
+    exe, out = host_check
+    sp, pp = C.seed_params()
+    frames = [P.components(C.scene_cached("floor5", f)[0], sp, pp) for f in C.FLOOR5_FRAMES[:4]]
+    frames.append([])
+    frames.append(P.components(C.dense_plate(), SP, C.PP))
+    src, dst = str(out / "records.txt"), str(out / "seeds.txt")
+    with open(src, "w") as fh:
+        for recs in frames:
+            fh.write("%d\n" % len(recs))
+            for r in recs:
+                fh.write(" ".join(str(v) for v in r) + "\n")
+    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    lines = dict(ln.split(" ", 1) for ln in r.stdout.strip().split("\n"))
+    assert [float(v) for v in lines["defaults"].split()] == [sp.max_rms, pp.planar_rms, pp.min_spread, pp.own_rms] == [0.05, 0.03, 0.06, 0.02]
+    assert [float(v) for v in lines["thresholds"].split()] == [(1024.0 * t) * (1024.0 * t) for t in (pp.planar_rms, pp.min_spread, pp.own_rms)]
+    assert lines["fits"].split() == ["1", "0", "0"]
+    assert (P.frame_fits(8729608, C.G), P.frame_fits(8729609, C.G)) == (True, False)
+    assert int(lines["frames"]) == len(frames)
+    got = open(dst).read().split("\n")
+    at, n_seeds = 0, 0
+    for recs in frames:
+        want = R.finish(recs, sp)
+        assert int(got[at]) == len(want)
+        for k, w in enumerate(want):
+            v = got[at + 1 + k].split()
+            assert (int(v[0]), int(v[1])) == (w.key, w.n)
+            for have, ref in ((float(v[2]), w.l1), (float(v[3]), w.l2), (float(v[5]), w.score)):
+                assert abs(have - ref) <= 1e-12 * abs(ref), (have, ref)
+            assert [np.float32(float(x)) for x in v[6:9]] == list(w.centroid)
+        at += 1 + len(want)
+        n_seeds += len(want)
+    assert n_seeds >= 4
