@@ -7,11 +7,13 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "host_util.h"
 #include "ilcc_ingest.h"
+#include "ilcc_sequence.h"
 #include "ilcc_internal.h"
 
 using ilcc::fail;
@@ -224,14 +226,16 @@ uint64_t time_key(uint64_t ros_time) {   // wire: sec (low 32), nsec (high 32) -
 
 }  // namespace
 
-extern "C" {
-
-static int32_t bag_first_message_impl(const char* bag_path, const char* topic, const char* md5sum, uint8_t* msg, uint64_t cap,
-                                      uint64_t* msg_bytes) {
-  if (!bag_path || !topic || !msg_bytes || (!msg && cap)) return fail(ILCC_BAD_ARGUMENT, "null argument");
-  const std::string want_md5 = md5sum ? md5sum : kPointCloud2Md5;
-  *msg_bytes = 0;
+// What both readers share: the opened file, the connections on the topic and the chunks that hold a message of one of them
+// (in index-section order).  The refusals and their texts are ilcc_bag_first_message's.
+struct BagIndex {
   File file;
+  std::map<uint32_t, bool> conn_ok;   // connections on the topic -> md5 matches
+  std::vector<ChunkRef> chunks;
+};
+
+static int32_t open_index(const char* bag_path, const char* topic, const std::string& want_md5, BagIndex* ix) {
+  File& file = ix->file;
   file.f = std::fopen(bag_path, "rb");
   if (!file.f) return fail(ILCC_IO_ERROR, std::string("cannot open ") + bag_path);
   if (!file.measure()) return fail(ILCC_IO_ERROR, "cannot determine the size of the bag file");
@@ -252,8 +256,8 @@ static int32_t bag_first_message_impl(const char* bag_path, const char* topic, c
   if (index_pos == 0) return fail(ILCC_IO_ERROR, "bag is unindexed (rosbag refuses it too: run rosbag reindex)");
 
   // index section: connection records, then chunk infos
-  std::map<uint32_t, bool> conn_ok;   // connections on the topic -> md5 matches
-  std::vector<ChunkRef> chunks;
+  std::map<uint32_t, bool>& conn_ok = ix->conn_ok;
+  std::vector<ChunkRef>& chunks = ix->chunks;
   uint64_t pos = index_pos;
   const uint64_t n_index_records = (uint64_t)conn_count + (uint64_t)chunk_count;   // (a u32 sum could wrap)
   if (n_index_records > file.size / 8) return fail(ILCC_IO_ERROR, "bag header declares more index records than the file can hold");
@@ -290,41 +294,76 @@ static int32_t bag_first_message_impl(const char* bag_path, const char* topic, c
     }
     pos = dpos + dl;
   }
+  return ILCC_OK;
+}
+
+// the chunk record at c.pos, inflated into *plain
+static int32_t load_chunk(File& file, const ChunkRef& c, std::vector<uint8_t>* plain) {
+  Fields h;
+  uint32_t dl;
+  uint64_t dpos;
+  uint8_t op = 0;
+  if (!file.record_at(c.pos, &h, &dl, &dpos) || !h.get("op", &op) || op != 0x05) return fail(ILCC_IO_ERROR, "chunk record missing");
+  uint32_t size = 0;
+  h.get("size", &size);
+  std::vector<uint8_t> raw(dl);
+  if (dl && !file.read_at(dpos, raw.data(), dl)) return fail(ILCC_IO_ERROR, "chunk truncated");
+  std::string err;
+  plain->clear();
+  if (!inflate_chunk(h.str("compression"), raw, size, plain, &err)) return fail(ILCC_IO_ERROR, err);
+  return ILCC_OK;
+}
+
+// walks the message-data records of an inflated chunk that belong to an accepted connection: fn(time key, offset of the record
+// inside the chunk, data, length)
+template <typename Fn>
+static int32_t for_each_message(const std::vector<uint8_t>& plain, const std::map<uint32_t, bool>& conn_ok, Fn fn) {
+  uint64_t at = 0;
+  while (at < plain.size()) {
+    Record r;
+    const uint64_t used = read_record(plain.data() + at, plain.size() - at, &r);
+    if (!used) return fail(ILCC_IO_ERROR, "bad record inside a chunk");
+    const uint64_t rec_at = at;
+    at += used;
+    if (r.op != 0x02) continue;
+    uint32_t conn;
+    uint64_t t;
+    if (!r.hdr.get("conn", &conn) || !r.hdr.get("time", &t)) return fail(ILCC_IO_ERROR, "bad message record");
+    auto it = conn_ok.find(conn);
+    if (it == conn_ok.end() || !it->second) continue;   // other topic, or instantiate<>() would return NULL
+    fn(time_key(t), rec_at, r.data, r.data_len);
+  }
+  return ILCC_OK;
+}
+
+extern "C" {
+
+static int32_t bag_first_message_impl(const char* bag_path, const char* topic, const char* md5sum, uint8_t* msg, uint64_t cap,
+                                      uint64_t* msg_bytes) {
+  if (!bag_path || !topic || !msg_bytes || (!msg && cap)) return fail(ILCC_BAD_ARGUMENT, "null argument");
+  const std::string want_md5 = md5sum ? md5sum : kPointCloud2Md5;
+  *msg_bytes = 0;
+  BagIndex ix;
+  int32_t st = open_index(bag_path, topic, want_md5, &ix);
+  if (st != ILCC_OK) return st;
+  std::vector<ChunkRef>& chunks = ix.chunks;
   std::stable_sort(chunks.begin(), chunks.end(), [](const ChunkRef& a, const ChunkRef& b) { return a.start < b.start; });
 
   // View order = message time; a chunk can hold an earlier message only if it starts no later than the best so far
   bool found = false;
   uint64_t best_time = ~0ull;
-  std::vector<uint8_t> best;
+  std::vector<uint8_t> best, plain;
   for (const ChunkRef& c : chunks) {
     if (found && c.start > best_time) break;
-    Fields h;
-    if (!file.record_at(c.pos, &h, &dl, &dpos) || !h.get("op", &op) || op != 0x05) return fail(ILCC_IO_ERROR, "chunk record missing");
-    uint32_t size = 0;
-    h.get("size", &size);
-    std::vector<uint8_t> raw(dl), plain;
-    if (dl && !file.read_at(dpos, raw.data(), dl)) return fail(ILCC_IO_ERROR, "chunk truncated");
-    std::string err;
-    if (!inflate_chunk(h.str("compression"), raw, size, &plain, &err)) return fail(ILCC_IO_ERROR, err);
-    uint64_t at = 0;
-    while (at < plain.size()) {
-      Record r;
-      const uint64_t used = read_record(plain.data() + at, plain.size() - at, &r);
-      if (!used) return fail(ILCC_IO_ERROR, "bad record inside a chunk");
-      at += used;
-      if (r.op != 0x02) continue;
-      uint32_t conn;
-      uint64_t t;
-      if (!r.hdr.get("conn", &conn) || !r.hdr.get("time", &t)) return fail(ILCC_IO_ERROR, "bad message record");
-      auto it = conn_ok.find(conn);
-      if (it == conn_ok.end() || !it->second) continue;   // other topic, or instantiate<>() would return NULL
-      const uint64_t tk = time_key(t);
+    if ((st = load_chunk(ix.file, c, &plain)) != ILCC_OK) return st;
+    st = for_each_message(plain, ix.conn_ok, [&](uint64_t tk, uint64_t, const uint8_t* data, uint32_t len) {
       if (!found || tk < best_time) {
         found = true;
         best_time = tk;
-        best.assign(r.data, r.data + r.data_len);
+        best.assign(data, data + len);
       }
-    }
+    });
+    if (st != ILCC_OK) return st;
   }
   if (!found) return fail(ILCC_BAD_ARGUMENT, std::string("no message of that type on topic ") + topic);
   *msg_bytes = best.size();
@@ -346,6 +385,103 @@ int32_t ilcc_bag_first_message(const char* bag_path, const char* topic, const ch
     return fail(ILCC_IO_ERROR, "bag reader: unknown failure");
   }
 }
+
+}  // extern "C"
+
+// ---- every message of a topic (include/ilcc_sequence.h)
+struct ilcc_bag_topic {
+  struct Entry {
+    uint64_t time;        // sortable key
+    uint32_t chunk;       // into ix.chunks, which open sorts by position in the file
+    uint64_t rec_at;      // offset of the message-data record inside the inflated chunk
+    uint32_t len;         // of the message
+  };
+  BagIndex ix;
+  std::vector<Entry> entries;
+  std::vector<uint8_t> plain;   // the one inflated chunk
+  int64_t plain_chunk = -1;
+};
+
+static int32_t bag_topic_open_impl(const char* bag_path, const char* topic, const char* md5sum, ilcc_bag_topic** out) {
+  if (!out) return fail(ILCC_BAD_ARGUMENT, "null argument");
+  *out = nullptr;
+  if (!bag_path || !topic) return fail(ILCC_BAD_ARGUMENT, "null argument");
+  std::unique_ptr<ilcc_bag_topic> it(new ilcc_bag_topic);
+  int32_t st = open_index(bag_path, topic, md5sum ? md5sum : kPointCloud2Md5, &it->ix);
+  if (st != ILCC_OK) return st;
+  std::vector<ChunkRef>& chunks = it->ix.chunks;
+  std::sort(chunks.begin(), chunks.end(), [](const ChunkRef& a, const ChunkRef& b) { return a.pos < b.pos; });
+  for (size_t c = 0; c < chunks.size(); ++c) {
+    if ((st = load_chunk(it->ix.file, chunks[c], &it->plain)) != ILCC_OK) return st;
+    it->plain_chunk = (int64_t)c;
+    st = for_each_message(it->plain, it->ix.conn_ok, [&](uint64_t tk, uint64_t rec_at, const uint8_t*, uint32_t len) {
+      it->entries.push_back(ilcc_bag_topic::Entry{tk, (uint32_t)c, rec_at, len});
+    });
+    if (st != ILCC_OK) return st;
+  }
+  if (it->entries.empty()) return fail(ILCC_BAD_ARGUMENT, std::string("no message of that type on topic ") + topic);
+  // entries were collected by (chunk position, offset): a stable sort by time leaves exactly that order among equal times
+  std::stable_sort(it->entries.begin(), it->entries.end(),
+                   [](const ilcc_bag_topic::Entry& a, const ilcc_bag_topic::Entry& b) { return a.time < b.time; });
+  *out = it.release();
+  return ILCC_OK;
+}
+
+static int32_t bag_topic_read_impl(ilcc_bag_topic* it, uint64_t i, uint8_t* msg, uint64_t cap, uint64_t* msg_bytes) {
+  if (!it || !msg_bytes || (!msg && cap)) return fail(ILCC_BAD_ARGUMENT, "null argument");
+  *msg_bytes = 0;
+  if (i >= it->entries.size()) return fail(ILCC_BAD_ARGUMENT, "message index beyond the topic's count");
+  const ilcc_bag_topic::Entry& e = it->entries[i];
+  *msg_bytes = e.len;
+  if (e.len > cap) return fail(ILCC_CAPACITY, "message larger than the buffer");
+  if (it->plain_chunk != (int64_t)e.chunk) {
+    it->plain_chunk = -1;
+    const int32_t st = load_chunk(it->ix.file, it->ix.chunks[e.chunk], &it->plain);
+    if (st != ILCC_OK) return st;
+    it->plain_chunk = (int64_t)e.chunk;
+  }
+  Record r;   // parsed again: the file may have changed under us since open
+  if (e.rec_at >= it->plain.size() || !read_record(it->plain.data() + e.rec_at, it->plain.size() - e.rec_at, &r) || r.op != 0x02 ||
+      r.data_len != e.len)
+    return fail(ILCC_IO_ERROR, "bad record inside a chunk");
+  if (e.len) std::memcpy(msg, r.data, e.len);
+  return ILCC_OK;
+}
+
+template <typename Fn>
+static int32_t bag_guard(Fn fn) {   // No exception crosses the C-ABI
+  try {
+    return fn();
+  } catch (const std::bad_alloc&) {
+    return fail(ILCC_IO_ERROR, "out of memory while reading the bag");
+  } catch (const std::exception& e) {
+    return fail(ILCC_IO_ERROR, std::string("bag reader: ") + e.what());
+  } catch (...) {
+    return fail(ILCC_IO_ERROR, "bag reader: unknown failure");
+  }
+}
+
+extern "C" {
+
+int32_t ilcc_bag_topic_open(const char* bag_path, const char* topic, const char* md5sum, ilcc_bag_topic** it) {
+  return bag_guard([&] { return bag_topic_open_impl(bag_path, topic, md5sum, it); });
+}
+
+uint64_t ilcc_bag_topic_count(const ilcc_bag_topic* it) { return it ? it->entries.size() : 0; }
+
+int32_t ilcc_bag_topic_time(const ilcc_bag_topic* it, uint64_t i, uint32_t* sec, uint32_t* nsec) {
+  if (!it || !sec || !nsec) return fail(ILCC_BAD_ARGUMENT, "null argument");
+  if (i >= it->entries.size()) return fail(ILCC_BAD_ARGUMENT, "message index beyond the topic's count");
+  *sec = (uint32_t)(it->entries[i].time >> 32);
+  *nsec = (uint32_t)(it->entries[i].time & 0xffffffffull);
+  return ILCC_OK;
+}
+
+int32_t ilcc_bag_topic_read(ilcc_bag_topic* it, uint64_t i, uint8_t* msg, uint64_t cap, uint64_t* msg_bytes) {
+  return bag_guard([&] { return bag_topic_read_impl(it, i, msg, cap, msg_bytes); });
+}
+
+void ilcc_bag_topic_close(ilcc_bag_topic* it) { delete it; }
 
 int32_t ilcc_pointcloud2_parse(const uint8_t* m, uint64_t n, ilcc_pointcloud2_layout* out) {
   if (!m || !out) return fail(ILCC_BAD_ARGUMENT, "null argument");

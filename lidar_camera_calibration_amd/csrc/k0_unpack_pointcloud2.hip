@@ -16,65 +16,18 @@
 #include "host_util.h"
 #include "ilcc_ingest.h"
 #include "ilcc_internal.h"
+#include "k0_unpack.h"   // the device code of a tile and of a generic point, shared with K0b
 
 namespace ilcc {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kUnpackThreads = 256;
-constexpr int kUnpackTile = 1024;   // points per workgroup
-
-struct UnpackArgs {
-  const uint8_t* src;
-  float4* dst;
-  uint64_t n_points;
-  uint32_t width, point_step, row_step;
-  uint32_t off[4];   // x y z intensity, ILCC_FIELD_ABSENT -> 0
-};
-
-__device__ __forceinline__ float load_f32_bytes(const uint8_t* p) {
-  const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  return __uint_as_float(v);
-}
-
 __global__ __launch_bounds__(kUnpackThreads) void k0_unpack_generic(UnpackArgs a) {
-  const uint64_t i = (uint64_t)blockIdx.x * kUnpackThreads + threadIdx.x;
-  if (i >= a.n_points) return;
-  const uint64_t row = i / a.width, col = i - row * a.width;
-  const uint8_t* p = a.src + row * a.row_step + col * a.point_step;
-  float v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (a.off[k] == ILCC_FIELD_ABSENT) ? 0.f : load_f32_bytes(p + a.off[k]);
-  a.dst[i] = make_float4(v[0], v[1], v[2], v[3]);
+  unpack_generic_point(a, (uint64_t)blockIdx.x * kUnpackThreads + threadIdx.x);
 }
 
-// STEP16 = point_step / 16 (1..4): points are packed back to back (row_step == width * point_step)
 template <int STEP16>
 __global__ __launch_bounds__(kUnpackThreads) void k0_unpack_tiled(UnpackArgs a) {
   __shared__ u32x4 tile[kUnpackTile * STEP16];
-  const uint64_t p0 = (uint64_t)blockIdx.x * kUnpackTile;
-  const uint64_t left = a.n_points - p0;
-  const uint32_t pts = left < (uint64_t)kUnpackTile ? (uint32_t)left : (uint32_t)kUnpackTile;
-  const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(a.src) + p0 * STEP16;
-  const uint32_t pieces = pts * STEP16;
-#pragma unroll
-  for (int k = 0; k < (kUnpackTile * STEP16) / kUnpackThreads; ++k) {
-    const uint32_t j = k * kUnpackThreads + threadIdx.x;
-    if (j < pieces) tile[j] = __builtin_nontemporal_load(src + j);
-  }
-  __syncthreads();
-  const uint32_t* words = reinterpret_cast<const uint32_t*>(tile);
-#pragma unroll
-  for (int k = 0; k < kUnpackTile / kUnpackThreads; ++k) {
-    const uint32_t j = k * kUnpackThreads + threadIdx.x;
-    if (j < pts) {
-      const uint32_t* w = words + j * (STEP16 * 4);
-      float v[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) v[c] = (a.off[c] == ILCC_FIELD_ABSENT) ? 0.f : __uint_as_float(w[a.off[c] >> 2]);
-      a.dst[p0 + j] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
+  unpack_tile<STEP16>(a, (uint64_t)blockIdx.x * kUnpackTile, tile);
 }
 
 }  // namespace ilcc
@@ -86,24 +39,13 @@ extern "C" int32_t ilcc_pointcloud2_unpack_device(const void* d_data, const ilcc
   // pcl::fromROSMsg memcpy's fields: it is wrong on such data too; refuse instead
   if (L->is_bigendian) return fail(ILCC_BAD_ARGUMENT, "big-endian PointCloud2 is not supported");
   UnpackArgs a;
-  a.src = (const uint8_t*)d_data;
-  a.dst = (float4*)d_xyzi;
-  a.n_points = (uint64_t)L->height * L->width;
-  a.width = L->width;
-  a.point_step = L->point_step;
-  a.row_step = L->row_step;
-  a.off[0] = L->off_x;
-  a.off[1] = L->off_y;
-  a.off[2] = L->off_z;
-  a.off[3] = L->off_intensity;
+  unpack_args_from_layout(*L, d_data, d_xyzi, &a);
   if (a.n_points == 0) return ILCC_OK;
   hipStream_t s = (hipStream_t)hip_stream;
-  bool aligned = (L->point_step % 16 == 0) && L->point_step <= 64 && ((uintptr_t)d_data % 16 == 0) &&
-                 (L->height == 1 || L->row_step == (uint64_t)L->width * L->point_step);
-  for (int k = 0; k < 4; ++k) aligned = aligned && (a.off[k] == ILCC_FIELD_ABSENT || a.off[k] % 4 == 0);
-  if (aligned) {
+  const int cls = unpack_class(*L, d_data);
+  if (cls) {
     const uint32_t blocks = (uint32_t)((a.n_points + kUnpackTile - 1) / kUnpackTile);
-    switch (L->point_step / 16) {
+    switch (cls) {
       case 1: hipLaunchKernelGGL(k0_unpack_tiled<1>, dim3(blocks), dim3(kUnpackThreads), 0, s, a); break;
       case 2: hipLaunchKernelGGL(k0_unpack_tiled<2>, dim3(blocks), dim3(kUnpackThreads), 0, s, a); break;
       case 3: hipLaunchKernelGGL(k0_unpack_tiled<3>, dim3(blocks), dim3(kUnpackThreads), 0, s, a); break;
