@@ -425,6 +425,17 @@ int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on);
 int32_t ilcc_debug_cluster_home(ilcc_handle* h, int32_t home);
 int32_t ilcc_debug_cluster_launch(const ilcc_handle* h, uint32_t out[ILCC_CLUSTER_LAUNCH_WORDS]);
 
+/* Diagnostic: a read-only view of what K6's common pre-pass (k6_group_prepass: one box pre-pass per group of 7 consecutive thetas,
+ * in front of the full pass) left behind for frame 0 of ticket 0 -- after ilcc_grid_solve: for the caller's points.  dims_out[0] =
+ * theta groups (0: the handle's grid has no common pre-pass, nothing else but *bound_out is written), dims_out[1] = 32-bit mask
+ * words per group; states_out[groups]: 0 every tile of the group rejected, 1 the group's mask is valid, 2 no common pre-pass for
+ * the group; mask_out[groups x words]: bit q of a state-1 group = tile q (tile row qa = q / ceil(n_tz / 4) along ty) rejected;
+ * *bound_out: the float bits of the frame's bound word as the full pass left it.  states_out, mask_out and bound_out may be NULL.
+ * Launches nothing and changes no launch.  No batch may be in flight.
+ * ilcc_debug_solve_walk: the walk layout of the same frame (what ilcc_fetch_walk returns for a frame of a completed batch). */
+int32_t ilcc_debug_group_prepass(ilcc_handle* h, uint32_t* states_out, uint32_t* mask_out, uint32_t dims_out[2], uint32_t* bound_out);
+int64_t ilcc_debug_solve_walk(ilcc_handle* h, float* out_yz, uint8_t* out_label, uint64_t cap_points, uint32_t counts[2]);
+
 void ilcc_get_timing(const ilcc_handle* h, ilcc_timing* t);
 void ilcc_reset_timing(ilcc_handle* h);
 

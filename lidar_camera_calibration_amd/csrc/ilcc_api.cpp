@@ -1748,6 +1748,38 @@ int32_t ilcc_debug_cluster_launch(const ilcc_handle* h, uint32_t out[ILCC_CLUSTE
   return ILCC_OK;
 }
 
+int32_t ilcc_debug_group_prepass(ilcc_handle* h, uint32_t* states_out, uint32_t* mask_out, uint32_t dims_out[2], uint32_t* bound_out) {
+  if (!h || !dims_out || any_batch_in_flight(h, "ilcc_debug_group_prepass")) return ILCC_BAD_ARGUMENT;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const Slot& sl = h->slots[0];
+  // (the conditions under which enqueue_grid_search launches k6_group_prepass for a one-frame call)
+  const GroupPrepassPlan gp = group_prepass_plan(h->p);
+  const bool ran = gp.on && sl.d_grp_alive && sl.d_grp_mask && gp.groups <= sl.grp_alive_cap && (size_t)gp.groups * gp.words <= sl.grp_mask_cap;
+  dims_out[0] = ran ? gp.groups : 0u;
+  dims_out[1] = ran ? gp.words : 0u;
+  if (bound_out && sl.d_bound) HIP_TRY(h, hipMemcpy(bound_out, sl.d_bound, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (!ran) return ILCC_OK;
+  if (states_out) HIP_TRY(h, hipMemcpy(states_out, sl.d_grp_alive, sizeof(uint32_t) * gp.groups, hipMemcpyDeviceToHost));
+  if (mask_out) HIP_TRY(h, hipMemcpy(mask_out, sl.d_grp_mask, sizeof(uint32_t) * gp.groups * gp.words, hipMemcpyDeviceToHost));
+  return ILCC_OK;
+}
+
+int64_t ilcc_debug_solve_walk(ilcc_handle* h, float* out_yz, uint8_t* out_label, uint64_t cap_points, uint32_t counts[2]) {
+  if (!h || any_batch_in_flight(h, "ilcc_debug_solve_walk")) return -(int64_t)ILCC_BAD_ARGUMENT;
+  if (hipSetDevice(h->device) != hipSuccess) return -(int64_t)ILCC_HIP_ERROR;
+  const Slot& sl = h->slots[0];
+  if (!sl.d_nlab || !sl.d_walk_yz || !sl.d_walk_lab || !sl.d_walk_mi || !sl.d_walk_nrim) return -(int64_t)ILCC_BAD_ARGUMENT;
+  uint32_t n = 0;
+  if (hipMemcpy(&n, sl.d_nlab, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return -(int64_t)ILCC_HIP_ERROR;
+  if (n > (uint32_t)kGridLdsPointsMax || n > h->max_points) n = 0;   // such a frame is walked through global memory: no layout
+  if (counts) {
+    if (hipMemcpy(&counts[0], sl.d_walk_mi, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&counts[1], sl.d_walk_nrim, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+      return -(int64_t)ILCC_HIP_ERROR;
+  }
+  return fetch_labelled_points(sl.d_walk_yz, sl.d_walk_lab, n, out_yz, out_label, cap_points);
+}
+
 int32_t ilcc_debug_timeline_fetch(ilcc_handle* h, double* rows, uint32_t cap_rows) {
   if (!h || (!rows && cap_rows)) return -ILCC_BAD_ARGUMENT;
   const size_t have = h->tl_rows.size() / ILCC_TIMELINE_COLS;

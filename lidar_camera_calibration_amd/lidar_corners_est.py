@@ -470,6 +470,37 @@ class LidarCornersBatch:
         self._lib.ilcc_fetch_walk(self._h, frame, N.fptr(yz), lab.ctypes.data_as(C.POINTER(C.c_uint8)), n, counts)
         return yz[:n], lab[:n], int(counts[0]), int(counts[1])
 
+    def fetch_solve_walk(self):
+        """``fetch_walk`` for the points of the last ``grid_solve`` (a diagnostic call is no batch: ``fetch_walk`` refuses it)."""
+        counts = (C.c_uint32 * 2)()
+        n = self._lib.ilcc_debug_solve_walk(self._h, None, None, 0, counts)
+        if n < 0:
+            raise IlccError(-n, self._err())
+        yz = np.zeros((max(n, 1), 2), dtype=np.float32)
+        lab = np.zeros(max(n, 1), dtype=np.uint8)
+        self._lib.ilcc_debug_solve_walk(self._h, N.fptr(yz), lab.ctypes.data_as(C.POINTER(C.c_uint8)), n, counts)
+        return yz[:n], lab[:n], int(counts[0]), int(counts[1])
+
+    def fetch_group_prepass(self) -> dict:
+        """What K6's common pre-pass left behind for the last ``grid_solve`` (read-only): states[groups] (0: every tile of the theta
+        group rejected, 1: the mask is valid, 2: no common pre-pass for the group), mask[groups, words] (bit q: tile q rejected;
+        meaningful for state 1), the frame's bound as the full pass left it; groups == 0 when the grid has no common pre-pass."""
+        dims = (C.c_uint32 * 2)()
+        bound = C.c_uint32(0)
+        u32p = C.POINTER(C.c_uint32)
+        st = self._lib.ilcc_debug_group_prepass(self._h, None, None, dims, C.byref(bound))   # the sizes (the handle's own grid)
+        if st != N.OK:
+            raise IlccError(st, self._err())
+        groups, words = int(dims[0]), int(dims[1])
+        states = np.zeros(max(groups, 1), dtype=np.uint32)
+        mask = np.zeros(max(groups * words, 1), dtype=np.uint32)
+        if groups:
+            st = self._lib.ilcc_debug_group_prepass(self._h, states.ctypes.data_as(u32p), mask.ctypes.data_as(u32p), dims, C.byref(bound))
+            if st != N.OK:
+                raise IlccError(st, self._err())
+        return dict(groups=groups, words=words, states=states[:groups].copy(), mask=mask[:groups * words].reshape(groups, words).copy(),
+                    bound=float(np.array([bound.value], np.uint32).view(np.float32)[0]))
+
     def grid_cost(self, yz: np.ndarray, label: np.ndarray, use_oob: bool = True, want_volume: bool = False):
         yz = np.ascontiguousarray(yz, dtype=np.float32).reshape(-1, 2)
         label = np.ascontiguousarray(label, dtype=np.uint8)

@@ -290,3 +290,21 @@ def test_fetches_are_refused_outside_the_last_completed_batch(w):
     assert all(n >= 0 for n in fetches(h, F - 1))
     assert L.ilcc_fetch_results(h, 0, F, res) == N.OK and _key(res, F) == w.ref
     assert e.wait(e.accepted(*w.host)) == w.ref
+
+
+def test_the_views_of_the_last_grid_solve_are_refused_while_a_batch_is_in_flight(w):
+    """ilcc_debug_group_prepass / ilcc_debug_solve_walk read slot 0's buffers: refused (status and text) while any ticket is in
+    flight, the batch undisturbed; afterwards they answer, and the next batch delivers what it always does."""
+    e, L, h = w.e, w.e.L, w.e.h
+    dims, bound, counts = (C.c_uint32 * 2)(), C.c_uint32(0), (C.c_uint32 * 2)()
+    t = e.accepted(*w.host)
+    e.refused(L.ilcc_debug_group_prepass(h, None, None, dims, C.byref(bound)), N.BAD_ARGUMENT)
+    assert "with a batch in flight" in e.err() and e.busy(t)
+    assert L.ilcc_debug_solve_walk(h, None, None, 0, counts) == -N.BAD_ARGUMENT
+    assert "with a batch in flight" in e.err() and e.busy(t)
+    assert e.wait(t) == w.ref
+    assert L.ilcc_debug_group_prepass(h, None, None, None, None) == N.BAD_ARGUMENT        # no place for the sizes
+    assert L.ilcc_debug_group_prepass(h, None, None, dims, C.byref(bound)) == N.OK, e.err()
+    assert (dims[0], dims[1]) == (9, 4)        # the default grid: 61 thetas in groups of 7, 40 x 40 translations = 100 tiles of 4 x 4
+    assert L.ilcc_debug_solve_walk(h, None, None, 0, counts) >= 0
+    assert e.wait(e.accepted(*w.host)) == w.ref
