@@ -80,7 +80,7 @@ struct Slot {
   uint32_t *d_flags = nullptr, *d_nfinite = nullptr, *d_counts_fin = nullptr;   // the online caller's two tiers (Ctx::frame_flags, n_finite, crop_fin)
   uint32_t* h_online = nullptr;   // pinned: flags then finite counts of the last online batch
   uint32_t* d_list = nullptr;     // tier 2: [0] count, [1..] listed frames
-  void* d_list_frames = nullptr;  // tier 2: 64 bytes per frame
+  void* d_list_frames = nullptr;  // tier 2: kListedFrameBytes per frame
   GridPartial *d_partial = nullptr, *d_partial2 = nullptr, *d_partial3 = nullptr, *d_partial4 = nullptr;
   SolveRec* d_solverec = nullptr;
   uint32_t *d_bound = nullptr, *d_bound_sub = nullptr;
@@ -319,7 +319,7 @@ auto slot_device_buffers(const ilcc_handle* h, Slot& sl) {
       buffer(sl.d_flags, mf),
       buffer(sl.d_nfinite, mf),
       buffer(sl.d_list, mf + 1),
-      Buffer{&sl.d_list_frames, 64 * mf},
+      Buffer{&sl.d_list_frames, kListedFrameBytes * mf},
       buffer(sl.d_masks, chunks * (kCropChunk / 64)),
       buffer(sl.d_parent, np),
       buffer(sl.d_count, np),
@@ -793,7 +793,7 @@ int32_t enqueue_impl(ilcc_handle* h, int si, hipStream_t s, const float4* d_xyzi
     t2.online_tier = 2u;
     t2.p.roi_half[0] = t2.p.roi_half[1] = t2.p.roi_half[2] = (double)INFINITY;
     launch_roi_crop(t2, s, nullptr);
-    (void)launch_cluster(t2, s, h->cluster_limits, h->cluster_home);
+    launch_cluster_listed(t2, s);
     HIP_TRY(h, hipMemcpyAsync(sl.h_online, sl.d_flags, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(sl.h_online + h->max_frames, sl.d_nfinite, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
   }
@@ -1037,7 +1037,7 @@ void raise_capacities(ilcc_handle* h, uint32_t grid_points, uint32_t cluster_poi
 // K2's one-workgroup LDS path likewise (ROI points per frame, steps of 512): what it does not hold of a CU's 160 KiB is room for K6
 // workgroups of other batches.  Its per-cell arrays: the most occupied cells a frame of the batch needed (+ 1/8), steps of 256.
 // Frames the LDS cell grid cannot hold at any capacity (bounding grid too large: un-cropped clouds; more cells than the largest
-// capacity) take the hashed-cell path of their own workgroup (k2_cluster.hip).
+// capacity) take the hashed-cell path of their own workgroup (k2_cluster.hip, k2_hashed.h).
 constexpr int kGridStaticLds = 3072;   // static LDS of a full-pass workgroup (bests, counters, the box pre-pass's mask and list), rounded up
 // the largest multiple of 256 staged points with which two full-pass workgroups on an n_ty x n_tz grid fit a CU's LDS (0: none)
 constexpr uint32_t grid_points_two_per_cu(int n_ty, int n_tz) {

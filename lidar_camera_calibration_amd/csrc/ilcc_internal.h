@@ -21,7 +21,7 @@ constexpr int kSolveLdsMax = kCuLdsBytes - 16 * 1024;    // K7a: dynamic LDS bou
 constexpr int kCropThreads = 256;      // K1
 constexpr int kCropChunk = 4096;       // points per K1 block
 #ifndef ILCC_K2_THREADS
-#define ILCC_K2_THREADS 256    // round 4: the clustering runs on cells (k2_cluster.hip); rounds 1-3: 1024 threads and 100 KB of LDS per frame
+#define ILCC_K2_THREADS 256    // round 4: the clustering runs on cells (k2_common.h); rounds 1-3: 1024 threads and 100 KB of LDS per frame
 #endif
 constexpr int kFrameThreads = ILCC_K2_THREADS;    // K2: one workgroup per frame (1024 threads in batches of <= kSmallBatchFrames frames)
 #ifndef ILCC_K3_THREADS
@@ -195,7 +195,7 @@ struct Ctx {
   uint32_t* crop_fin;        // n_frames x crop_chunks: finite points per K1 chunk (tier 1)
   uint32_t* list_count;      // tier 2: number of listed (flagged) frames ...
   uint32_t* list;            // ... and their indices
-  void* list_frames;         // tier 2: one 64-byte ListedFrame (k2_cluster.hip) per frame
+  void* list_frames;         // tier 2: one ListedFrame (k2h_listed.hip) of kListedFrameBytes per frame
   uint32_t list_grid;        // tier 2: workgroups of the kernels over (listed frame, chunk) items
   GridPartial* partial;      // n_frames x grid_blocks: the records of K6's full pass (K7r takes their argmin)
   SolveRec* solve_rec;       // n_frames x 2
@@ -329,12 +329,18 @@ constexpr int32_t kClusterHomeRule = 0, kClusterHomeLds = 1, kClusterHomeL2 = 2;
 struct ClusterLimits {   // of the handle's device and of k2_seeded_cluster on it (cluster_limits)
   uint32_t cus, lds_per_cu, threads_per_cu, static_lds;
 };
-struct ClusterLaunch {   // what a k2_seeded_cluster launch used (all zero: the k2h_* chain, no such launch)
+struct ClusterLaunch {   // what a k2_seeded_cluster launch used
   int32_t home;
   uint32_t lds_bytes, threads;
 };
 hipError_t cluster_limits(int device, ClusterLimits* out);
-ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& lim, int32_t home);
+ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& lim, int32_t home);   // k2_cluster.hip: every frame, tiers 0 and 1
+void launch_cluster_listed(const Ctx& c, hipStream_t s);   // k2h_listed.hip: the online caller's second tier, the k2h_* chain on the flagged frames
+constexpr size_t kListedFrameBytes = 64;   // of Ctx::list_frames per frame: one ListedFrame (k2h_listed.hip)
+hipError_t set_kernel_attributes_k2();   // once per (process, device), as those of K6 and K7 below
+size_t cluster_lds_bytes(uint32_t pts_cap, uint32_t cells_cap, uint32_t bits);   // K2's dynamic LDS for these capacities (bits: cells the bitmap holds)
+uint32_t cluster_bits_default();
+uint32_t cluster_bits_online();
 void launch_ransac_plane(const Ctx& c, hipStream_t s);
 void launch_plane_frame_hist(const Ctx& c, hipStream_t s);
 // K3 + K4/K5 (+ K5w with walk_layout) in one launch, one workgroup per frame (k345_front_end.hip): batches that would run all of
@@ -360,10 +366,6 @@ void launch_store_to_host(const void* d_src, void* h_dst, size_t bytes, hipStrea
 // stand-alone K7r on the labelled points of frame 0 (test entry)
 void launch_pattern_refine_test(const Ctx& c, hipStream_t s, RefineOut* d_io);
 // once per (process, device): raise the dynamic-LDS limits of the kernels that need more than 64 KiB
-hipError_t set_kernel_attributes_k2();
-size_t cluster_lds_bytes(uint32_t pts_cap, uint32_t cells_cap, uint32_t bits);   // K2's dynamic LDS for these capacities (bits: cells the bitmap holds)
-uint32_t cluster_bits_default();
-uint32_t cluster_bits_online();
 hipError_t set_kernel_attributes_k6();   // every K6 file's kernels (k6_common.h: raise_grid_lds_limit)
 hipError_t set_kernel_attributes_k7a();
 hipError_t set_kernel_attributes_k7r();

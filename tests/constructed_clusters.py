@@ -18,7 +18,7 @@ pulled in by 2^-21 m must link.
 """
 import numpy as np
 
-CELL_OVER_TOL = np.float32(0.57)          # k2_cluster.hip: kFineCellOverTol
+CELL_OVER_TOL = np.float32(0.57)          # k2_common.h: kFineCellOverTol
 FINE_BITS = 96 * 1024                     # kFineBits: cells of the padded bounding grid the LDS bitmap holds
 CELLS_CAP_FRESH = 512                     # kClusterCellsMin: occupied cells a fresh handle's LDS arrays hold
 LDS_POINTS_FRESH = 2048                   # a fresh handle's LDS capacity for the cell-sorted points ...
