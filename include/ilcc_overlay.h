@@ -20,8 +20,8 @@
  * byte 0, so the reference's window shows red and blue swapped; ilcc_save_ppm_bgr writes B,G,R as R,G,B, so the file
  * shows what that window showed.
  *
- * Not here: show_calib_result's radius-1 circles and putText; rgblidar from bags; time-synchronised pairing;
- * anti-aliased drawing; display.  (JPEG output of the picture: ilcc_jpeg_write.h; CLI ilcc_pcd2image --jpg-out.)
+ * Not here: show_calib_result's radius-1 circles and putText; anti-aliased drawing; display.  (JPEG output of the picture:
+ * ilcc_jpeg_write.h; CLI ilcc_pcd2image --jpg-out.  rgblidar over every time-paired scan and image of a recording: ilcc_paired.h.)
  */
 #ifndef ILCC_OVERLAY_H_
 #define ILCC_OVERLAY_H_

@@ -20,11 +20,9 @@
 #include "host_util.h"
 #include "ilcc_internal.h"
 #include "ilcc_project.h"
+#include "k8_space_to_plane.h"   // space_to_plane, kProjThreads, kProjChunk: shared with K8b
 
 namespace ilcc {
-
-constexpr int kProjThreads = 256;
-constexpr int kProjChunk = 4096;
 
 struct ProjArgs {
   const float4* pts;
@@ -38,23 +36,6 @@ struct ProjArgs {
   void* out;
   uint32_t* total;
 };
-
-// spaceToPlane (:135-155); px, py = the (int) truncation the callers apply
-__device__ __forceinline__ bool space_to_plane(const ilcc_projection& c, const float4 q, double dis, int32_t& px, int32_t& py) {
-  const double X = (double)q.x, Y = (double)q.y, Z = (double)q.z;
-  const double pc0 = c.R[0] * X + c.R[1] * Y + c.R[2] * Z + c.t[0];
-  const double pc1 = c.R[3] * X + c.R[4] * Y + c.R[5] * Z + c.t[1];
-  const double pc2 = c.R[6] * X + c.R[7] * Y + c.R[8] * Z + c.t[2];
-  if (pc2 < 0 || pc2 > dis) return false;   // NaN depth passes this test, like the reference, and fails below
-  const double u = pc0 / pc2, v = pc1 / pc2;
-  const double cu = c.fx * u + c.cx, cv = c.fy * v + c.cy;
-  if (cu > 0 && cu < (double)c.width && cv > 0 && cv < (double)c.height) {
-    px = (int32_t)cu;
-    py = (int32_t)cv;
-    return true;
-  }
-  return false;
-}
 
 // float -> unsigned char the way an x86-64 build converts (cvttss2si, low byte)
 __device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)(int32_t)v; }
@@ -128,8 +109,7 @@ __global__ __launch_bounds__(kProjThreads) void k8_scatter(ProjArgs a) {
     const uint32_t rank = block_rank(keep, sc, tot);
     if (keep) {
       if (SAMPLE_IMAGE) {
-        const uint8_t* p = a.image + (uint64_t)py * a.image_step + (uint32_t)px * 3u;
-        const uint32_t rgb = ((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | (uint32_t)p[0];   // rgblidar.cpp:63-65
+        const uint32_t rgb = sample_bgr_as_rgb(a.image, a.image_step, px, py);
         reinterpret_cast<float4*>(a.out)[running + rank] = make_float4(q.x, q.y, q.z, __uint_as_float(rgb));
       } else {
         const double h = ((double)q.w - a.lo) / (a.hi - a.lo) * 255;   // pcd2image.cpp:71
