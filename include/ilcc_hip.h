@@ -392,6 +392,18 @@ int32_t ilcc_debug_reference_solve(ilcc_handle* h, const float* yz, const uint8_
                                    const int32_t* status_in, uint32_t n_frames, double* rec_f64, int32_t* rec_i32,
                                    ilcc_result* results, uint32_t* lds_points);
 
+/* Diagnostic: k6_locate -- seed, refinement and anchor of the grid search in one launch, what batches of >= 512 frames run in front
+ * of the full pass -- behind K5w's walk layout, at ANY frame count, on n_frames frames of caller-supplied labelled points (host
+ * buffers; frame f = points offsets[f] .. offsets[f + 1]), every frame with status ILCC_OK.  The handle's LDS staging capacity is
+ * used as it is and never grown: the anchor walks frames of at most that many labelled points from LDS, the others from global
+ * memory.  Out, per frame: records_out[4 f ..] = the launch's record -- the bits of the fp32 cost of the anchor's best complete
+ * candidate, its squared index distance to the candidate nearest zero, its flat index ((k n_ty + a) n_tz + b) 2 + phase, and
+ * (a << 16) | b; a record the launch did not write: every bit set -- and bound_out[f] = the frame's bound word behind the launch.
+ * Refuses a busy ticket 0, more frames than max_frames, more points than the handle holds, a handle that is not in
+ * ILCC_SOLVER_GRID mode, and (ILCC_CAPACITY) a grid or capacity the pipeline would not run k6_locate on. */
+int32_t ilcc_debug_locate(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets, uint32_t n_frames,
+                          uint32_t* records_out, uint32_t* bound_out);
+
 /* Diagnostic (ABI 5): the real timeline of the batches, without a profiler.  While enabled, every completed batch appends one row
  * of ILCC_TIMELINE_COLS doubles: slot, then the times in ms -- relative to a reference event recorded when the timeline was
  * enabled -- of the batch's HIP events: start, after K1's count pass, after K1, K2, K3, K4/K5, K5w, seed, refinement, anchor,

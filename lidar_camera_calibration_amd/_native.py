@@ -35,7 +35,7 @@ EXPORTS = [
     "ilcc_set_result_mode", "ilcc_wait_compact", "ilcc_record_floats", "ilcc_fetch_results",
     "ilcc_debug_timeline_enable", "ilcc_debug_timeline_fetch", "ilcc_debug_separate_launches",
     "ilcc_debug_cluster_home", "ilcc_debug_cluster_launch", "ilcc_debug_reference_solve",
-    "ilcc_debug_group_prepass", "ilcc_debug_solve_walk",
+    "ilcc_debug_group_prepass", "ilcc_debug_solve_walk", "ilcc_debug_locate",
 ]
 ABI_VERSION = 5            # the layout of Params / Result / Timing below is ILCC_ABI_VERSION 5 of include/ilcc_hip.h
 RESULTS_FULL, RESULTS_COMPACT = 0, 1
@@ -236,6 +236,10 @@ def lib():
             L.ilcc_debug_group_prepass.restype = C.c_int32
             L.ilcc_debug_solve_walk.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint32)]
             L.ilcc_debug_solve_walk.restype = C.c_int64
+        if hasattr(L, "ilcc_debug_locate"):              # (likewise)
+            L.ilcc_debug_locate.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint32)]
+            L.ilcc_debug_locate.restype = C.c_int32
         L.ilcc_fetch_results.argtypes = [vp, C.c_uint32, C.c_uint32, rp]
         L.ilcc_fetch_results.restype = C.c_int32
         _lib = L

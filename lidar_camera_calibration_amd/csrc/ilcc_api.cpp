@@ -660,6 +660,7 @@ LocatePlan locate_plan(const ilcc_handle* h, const Slot& sl, const Ctx& c) {
   lp.refine_radius = std::max(1, h->seed_map.stride_th / ILCC_REFINE_RADIUS_DIV);
   lp.sample_min = (uint32_t)ILCC_SEED_POINTS;
   lp.sample_cap = std::max((uint32_t)ILCC_SEED_POINTS, ((c.grid_lds_points >> 3) + 63u) & ~63u);
+  lp.stage_cap = ILCC_LOCATE_STAGE_ANCHOR ? c.grid_lds_points : 0u;
   lp.out = sl.d_partial4;
   return lp;
 }
@@ -704,7 +705,7 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
     const LocatePlan lp = locate_plan(h, sl, c);
     // one launch, one workgroup per frame (k6_locate) when the batch has the frames to fill the chip that way
     const bool fused = n_frames >= (uint32_t)kLocateMinFrames && lp.seed.n_th <= 16 &&
-                       locate_lds_bytes(lp.sample_cap, h->grid.n_ty, h->grid.n_tz, lp.seed.n_ty, lp.seed.n_tz) <= (size_t)kLocateLdsMax;
+                       locate_lds_bytes(lp, h->grid.n_ty, h->grid.n_tz) <= (size_t)kLocateLdsMax;
     if (fused) {
       launch_locate(c, s, lp);
       HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));   // (the whole locate launch is accounted as the "seed" span)
@@ -1672,6 +1673,64 @@ int32_t ilcc_debug_reference_solve(ilcc_handle* h, const float* yz, const uint8_
     std::memcpy(rec_i32 + ILCC_SOLVE_REC_INTS * k, i, sizeof(i));
   }
   if (lds_points) *lds_points = c.grid_lds_points;
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_locate(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets, uint32_t n_frames,
+                          uint32_t* records_out, uint32_t* bound_out) {
+  if (!h || !records_out || !bound_out) return ILCC_BAD_ARGUMENT;
+  Slot& sl = h->slots[0];
+  if (sl.busy) {
+    h->err = "diagnostic entry while ticket 0 is in flight";
+    return ILCC_BAD_ARGUMENT;
+  }
+  if (h->p.solver != ILCC_SOLVER_GRID) {
+    h->err = "ilcc_debug_locate needs ILCC_SOLVER_GRID";
+    return ILCC_BAD_ARGUMENT;
+  }
+  ILCC_TRY(check_offsets(h, offsets, n_frames));
+  const uint64_t total = offsets[n_frames];
+  if (total > 0 && (!yz || !label)) return ILCC_BAD_ARGUMENT;
+  HIP_TRY(h, hipSetDevice(h->device));
+  // the handle's capacities as they are (see ilcc_debug_reference_solve): the caller decides which frames the anchor stages
+  const Ctx c = make_ctx(h, sl, nullptr, nullptr, n_frames, 1);
+  const LocatePlan lp = locate_plan(h, sl, c);
+  if (!(h->seed_grid.n_th > 0 && h->p.n_th >= 8 && h->p.n_ty >= 8 && h->p.n_tz >= 8) || lp.seed.n_th > 16 ||
+      locate_lds_bytes(lp, h->grid.n_ty, h->grid.n_tz) > (size_t)kLocateLdsMax) {
+    h->err = "ilcc_debug_locate: this grid (or LDS capacity) does not take k6_locate";
+    return ILCC_CAPACITY;
+  }
+  const hipStream_t s = h->stream[take_stream(h)];
+  // what K4/K5 leave behind for the grid search and what K1 resets: offsets, labelled counts (+ walk strides), an OK record and an
+  // infinite bound per frame, the batch's counters
+  std::vector<uint32_t> n_lab(n_frames), stride(n_frames), bound(n_frames, 0x7f800000u);
+  std::vector<ilcc_result> res(n_frames);
+  std::memset(res.data(), 0, sizeof(ilcc_result) * n_frames);
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    n_lab[f] = (uint32_t)(offsets[f + 1] - offsets[f]);
+    stride[f] = walk_stride(n_lab[f]);
+    res[f].status = ILCC_OK;
+  }
+  HIP_TRY(h, hipMemcpyAsync(sl.d_off, offsets, sizeof(uint64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_res, res.data(), sizeof(ilcc_result) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_nlab, n_lab.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_walk, stride.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_bound, bound.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemsetAsync(sl.d_iters, 0, sizeof(unsigned long long) * kBatchWords, s));
+  if (total > 0) {
+    HIP_TRY(h, hipMemcpyAsync(sl.d_yz, yz, sizeof(float2) * total, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(sl.d_lab, label, total, hipMemcpyHostToDevice, s));
+  }
+  // (a record the launch does not write comes back with every bit set)
+  HIP_TRY(h, hipMemsetAsync(lp.out, 0xFF, sizeof(GridPartial) * n_frames, s));
+  sl.n_frames = 0;   // the stage buffers no longer describe a batch
+  launch_walk_order(c, s);
+  launch_locate(c, s, lp);
+  HIP_TRY(h, hipGetLastError());
+  static_assert(sizeof(GridPartial) == 4 * sizeof(uint32_t), "records_out: four words per frame");
+  HIP_TRY(h, hipMemcpyAsync(records_out, lp.out, sizeof(GridPartial) * n_frames, hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipMemcpyAsync(bound_out, sl.d_bound, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
+  ILCC_TRY(sync_own(h, s));
   return ILCC_OK;
 }
 

@@ -64,7 +64,7 @@ constexpr int kGridTableMax = 8192;       // K6: n_ty + n_tz bound (their tables
 #endif
 constexpr int kSolveThreads = ILCC_K7_THREADS;     // K7: wavefronts x 64 per (frame, phase)
 #ifndef ILCC_K7R_THREADS
-#define ILCC_K7R_THREADS 192   // 3 wavefronts, one per theta of the stencil: measured 192: 230 k, 384-768: 225 k, 1024: 219 k frames/s
+#define ILCC_K7R_THREADS 192   // 3 wavefronts, one per theta of the stencil: measured 192: 230 k, 384-768: 225 k, 1024: 219 k frames/s; round 13, in the pipeline and with silent points: 192: 1 372 k, 384: 1 237 k
                                // (the kernel's latency is set by the few frames that walk 30+ rounds; small workgroups leave the CUs to K6)
 #endif
 constexpr int kRefineThreads = ILCC_K7R_THREADS;   // K7r: one workgroup per frame
@@ -310,10 +310,14 @@ struct LocatePlan {
   SeedMap map;                            // ... and where their entries sit in the full ones (Ctx::grid)
   int32_t refine_radius;                  // refinement: theta within +- this many steps of the seed's
   uint32_t sample_min, sample_cap;        // the sample: max(sample_min, M >> kSeedShift) walk positions, at most sample_cap (LDS)
+  uint32_t stage_cap;                     // anchor: frames of at most this many labelled points walk their layout from LDS (0: none), the others from global memory
   GridPartial* out;                       // one record per frame: the anchor's best candidate (full-table flat index, (a << 16) | b)
 };
 
-size_t locate_lds_bytes(uint32_t sample_cap, int n_ty, int n_tz, int n_ty2, int n_tz2);   // k6_locate's dynamic LDS (its own carve, locate_lds)
+#ifndef ILCC_LOCATE_STAGE_ANCHOR
+#define ILCC_LOCATE_STAGE_ANCHOR 1   // k6_locate's anchor walks the frame's layout from LDS.  Round 13 (k frames/s): 0 (every frame from global memory): 1 350, 1: 1 372
+#endif
+size_t locate_lds_bytes(const LocatePlan& lp, int n_ty, int n_tz);   // k6_locate's dynamic LDS (its own carve, locate_lds)
 void launch_locate(const Ctx& c, hipStream_t s, const LocatePlan& lp);
 void launch_anchor(const Ctx& c, const GridPass& pass, hipStream_t s);   // one anchor round of the separate locate launches (pass.seed -> pass.out, pass.blocks thetas)
 constexpr int kRefineThetaStride = 2;  // the refinement scores every other theta of its range (the anchor covers the ones in between)
