@@ -17,6 +17,7 @@
  *   chessboardsFromCorners.m, initChessboard.m, growChessboard.m,
  *   chessboardEnergy.m                                            ilcc_chessboard_from_corners (host)
  *   plotChessboards.m:48-68 (dlmwrite of the X then Y block)      ilcc_save_cam_corners
+ *   (a batch of images in one go, every image of a bag fused)     ilcc_image_sequence.h (K10b: the same stage bodies)
  *
  * Corner positions are 0-based pixels (findCorners.m:124-125); the file adds 1 back, as the
  * reference's dump does.  Not here: multi-board output.  The undistorted image itself

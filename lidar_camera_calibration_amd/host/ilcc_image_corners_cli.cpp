@@ -4,6 +4,10 @@
 //   ilcc_image_corners --bag 20181101_1.bag --topic /camera/image_raw --yaml pointgrey.yaml --out pointgrey1.txt
 //                      [--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]
 //   ilcc_image_corners --jpg pointgrey1.jpg [--yaml pointgrey.yaml] [--board 7x5] --out pointgrey1.txt [--device N]
+//   ilcc_image_corners --bag ... --topic ... --yaml ... --out pointgrey1.txt --all-images [--first N] [--stride N] [--max-images N]
+//                      [--gate PX] [--report FILE]
+// --all-images reads EVERY sensor_msgs/Image of the topic (include/ilcc_image_sequence.h): the boards of the images that hold one
+// are fused into ONE board, written in the same format; --report writes one line per image.  It takes no --jpg, --jpg-out or --pgm.
 // --jpg takes the image from a JPEG file instead (libcbdetect/demo_all_pic.m:8-19 on one file).  Without --yaml the file
 // is taken as already undistorted, as the reference's process_data/<camera><i>.jpg are, and the board is --board's
 // (corners along x by corners along y, 7x5 when not given); with it, both come from the yaml as for a bag.
@@ -20,12 +24,65 @@
 #include "ilcc_camera_image.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
+#include "ilcc_image_sequence.h"
 #include "ilcc_jpeg.h"
 #include "ilcc_jpeg_write.h"
 
+namespace {
+
+const char* kUsage =
+    "usage: ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt "
+    "[--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]\n"
+    "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n"
+    "       ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt --all-images "
+    "[--first N] [--stride N] [--max-images N] [--gate PX] [--report FILE] [--device N]\n";
+
+// --all-images: every image of the topic, the fused board into out_path
+int run_all_images(int device, const std::string& bag_path, const std::string& topic, const ilcc_camera_model& cam, int32_t board_w, int32_t board_h,
+                   const ilcc_image_sequence_params& sp, const std::string& out_path, const std::string& report) {
+  ilcc_image_sequence_result r;
+  std::vector<ilcc_image_record> images(1);
+  // one record is too few for most bags: the refusal says how many are needed, and nothing has run
+  int32_t st = ilcc_bag_corners_all_images(device, bag_path.c_str(), topic.c_str(), &cam, board_w, board_h, &sp, &r, images.data(), 1);
+  if (st == ILCC_CAPACITY && r.n_images > 1) {
+    images.resize((size_t)r.n_images);
+    st = ilcc_bag_corners_all_images(device, bag_path.c_str(), topic.c_str(), &cam, board_w, board_h, &sp, &r, images.data(), (uint32_t)images.size());
+  }
+  if (st != ILCC_OK && st != ILCC_AMBIGUOUS && st != ILCC_BOARD_NOT_FOUND) {
+    std::fprintf(stderr, "all images: %s: %s\n", ilcc_strerror(st), ilcc_last_error(nullptr));
+    return 1;
+  }
+  if (!report.empty()) {
+    std::FILE* f = std::fopen(report.c_str(), "w");
+    if (!f) {
+      std::fprintf(stderr, "can not write %s\n", report.c_str());
+      return 1;
+    }
+    for (int32_t k = 0; k < r.n_images; ++k)
+      std::fprintf(f, "image %d message %u stamp %u.%09u status %d accepted %d used %d distance_px %.3f\n", k, images[k].message, images[k].stamp_sec,
+                   images[k].stamp_nsec, images[k].status, images[k].accepted, images[k].used, images[k].distance < 0 ? -1.0 : images[k].distance);
+    std::fclose(f);
+  }
+  int rc = st == ILCC_OK ? 0 : 4;
+  if (st == ILCC_OK && ilcc_save_cam_corners(out_path.c_str(), r.rows, r.cols, r.xy) != ILCC_OK) {
+    std::fprintf(stderr, "can not write %s\n", out_path.c_str());
+    rc = 1;
+  }
+  if (st != ILCC_OK) std::fprintf(stderr, "no chessboard: %s\n", ilcc_last_error(nullptr));
+  std::printf("all images: status %d images %d accepted %d used %d batches %d gate_px %.3f spread_rms_px %.3f spread_max_px %.3f ref_image %d board %d x %d -> %s\n",
+              st, r.n_images, r.n_ok, r.n_used, r.n_batches, r.gate, r.spread_rms, r.spread_max, r.ref_image, r.rows, r.cols,
+              st == ILCC_OK && rc == 0 ? out_path.c_str() : "-");
+  return rc;
+}
+
+}  // namespace
+
 int main(int argc, char** argv) {
-  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path, jpg_out_path;
+  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path, jpg_out_path, report;
   int device = 0, quality = 95;
+  bool all_images = false, sequence_option = false;
+  ilcc_image_sequence_params sp;
+  ilcc_default_image_sequence_params(&sp);
   int32_t board_w = 7, board_h = 5;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -39,6 +96,12 @@ int main(int argc, char** argv) {
     else if (a == "--jpg-out" && i + 1 < argc) jpg_out_path = argv[++i];
     else if (a == "--quality" && i + 1 < argc) quality = std::atoi(argv[++i]);
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
+    else if (a == "--all-images") all_images = true;
+    else if (a == "--first" && i + 1 < argc) { sp.first = (uint32_t)std::strtoul(argv[++i], nullptr, 10); sequence_option = true; }
+    else if (a == "--stride" && i + 1 < argc) { sp.stride = (uint32_t)std::strtoul(argv[++i], nullptr, 10); sequence_option = true; }
+    else if (a == "--max-images" && i + 1 < argc) { sp.max_images = (uint32_t)std::strtoul(argv[++i], nullptr, 10); sequence_option = true; }
+    else if (a == "--gate" && i + 1 < argc) { sp.gate_px = std::atof(argv[++i]); sequence_option = true; }
+    else if (a == "--report" && i + 1 < argc) { report = argv[++i]; sequence_option = true; }
     else {
       std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
       return 2;
@@ -48,9 +111,11 @@ int main(int argc, char** argv) {
   const bool bag_ok = !bag_path.empty() && !topic.empty() && !yaml_path.empty();
   const bool jpg_ok = bag_path.empty() && topic.empty() && pgm_path.empty() && jpg_out_path.empty();
   if ((out_path.empty() && (from_jpg || jpg_out_path.empty())) || (from_jpg ? !jpg_ok : !bag_ok)) {
-    std::fprintf(stderr, "usage: ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt "
-                         "[--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]\n"
-                         "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n");
+    std::fprintf(stderr, "%s", kUsage);
+    return 2;
+  }
+  if (all_images ? (from_jpg || !jpg_out_path.empty() || !pgm_path.empty() || out_path.empty()) : sequence_option) {
+    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate and --report need it\n", kUsage);
     return 2;
   }
   ilcc_camera_model cam{};
@@ -73,6 +138,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "the board needs at least 3 x 3 corners\n");
     return 2;
   }
+
+  if (all_images) return run_all_images(device, bag_path, topic, cam, board_w, board_h, sp, out_path, report);
 
   if (!pgm_path.empty()) {
     int32_t w = 0, h = 0;

@@ -1,0 +1,258 @@
+"""Camera corners from every image of a bag, the part that needs no GPU (include/ilcc_image_sequence.h): the exported symbols
+against the header, the fusion of per-image boards against its restatement (tests/image_sequence_ref.py) on constructed boards,
+the selection and the cut into batches against theirs on bags of 64 x 48 images, and the fusion alone as a stand-alone program
+under AddressSanitizer and UBSan."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import image_sequence_cases as K
+import image_sequence_ref as R
+from lidar_camera_calibration_amd import _native as N
+from lidar_camera_calibration_amd import image_sequence as IS
+from lidar_camera_calibration_amd import sequence
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_exports_match_header():
+    hdr = open(os.path.join(ROOT, "include", "ilcc_image_sequence.h")).read()
+    declared = re.findall(r"^(?:int32_t|uint32_t|uint64_t|void|ilcc_image_corner_plan\*) (ilcc_\w+)\(", hdr, re.M)
+    assert sorted(declared) == sorted(IS.IMAGE_SEQUENCE_EXPORTS)
+    L = IS.lib()
+    for s in IS.IMAGE_SEQUENCE_EXPORTS:
+        assert hasattr(L, s), s
+    # the layouts the header declares: 4 x 8 ints + 3 doubles + 512 doubles, and so on
+    assert C.sizeof(IS.FusedImageCorners) == 32 + 24 + 4096
+    assert C.sizeof(IS.ImageSequenceParams) == 40
+    assert C.sizeof(IS.ImageRecord) == 48 + 8 + 4096
+    assert C.sizeof(IS.ImageSequenceResult) == 32 + 32 + 4096
+    # the other headers keep their lists
+    for name in ("ilcc_image_corners.h", "ilcc_sequence.h", "ilcc_camera_image.h"):
+        other = open(os.path.join(ROOT, "include", name)).read()
+        assert not set(re.findall(r"\b(ilcc_\w+)\s*\(", other)) & set(IS.IMAGE_SEQUENCE_EXPORTS)
+    assert "ilcc_image_sequence.h" in open(os.path.join(ROOT, "include", "ilcc_image_corners.h")).read()
+
+
+def _same(got, used, dist, want):
+    assert (got.status, got.n_images, got.n_ok, got.n_used, got.ref_image, got.rows, got.cols) == \
+        (want.status, want.n_images, want.n_ok, want.n_used, want.ref_image, want.rows, want.cols)
+    assert list(used) == list(want.used)
+    assert got.gate == want.gate and got.spread_max == want.spread_max and got.spread_rms == want.spread_rms      # exactly
+    assert got.board().tobytes() == np.ascontiguousarray(want.xy, np.float64).tobytes()                                # every double
+    assert np.array_equal(dist, want.dist)
+    if want.status != R.OK:
+        assert not np.ctypeslib.as_array(got.xy).any()
+
+
+CASES = K.fusion_cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_fusion_equals_the_restatement_on_constructed_boards(case):
+    name, boards, accepted, a, b, gate = case
+    want = R.fuse(boards, accepted, a, b, gate)
+    got, used, dist = IS.fuse_image_corners(boards, accepted, (a, b), gate)
+    _same(got, used, dist, want)
+
+
+def test_constructed_cases_are_what_they_are_named():
+    by = {c[0]: R.fuse(*c[1:]) for c in CASES}
+    for n in (9, 8):
+        f = by["variants_7x5_n%d" % n]
+        assert (f.status, f.n_used, f.rows, f.cols) == (R.OK, n, 5, 7) and list(f.variants) == [k % 8 for k in range(n)]
+        assert f.spread_max <= 16 * K.Q * 2 ** 0.5 and abs(f.gate - K.SQUARE / 2) < 0.1
+    s = by["variants_5x5_square"]
+    assert s.status == R.OK and list(s.variants) == [k % 8 for k in range(9)] and (s.rows, s.cols) == (5, 5)
+    t = by["transposed_reference"]
+    assert (t.status, t.rows, t.cols, t.ref_image) == (R.OK, 7, 5, 0) and list(t.variants) == [0, 4, 4, 4, 4]
+    assert np.abs(t.xy - np.asarray(K.numbered(K.lattice(5, 7), 4))).max() <= 8 * K.Q
+    o = by["one_square_off"]
+    assert o.status == R.OK and [i for i in range(6) if not o.used[i]] == [3]
+    assert abs(o.dist[3] - (K.SQUARE ** 2 + 1) ** 0.5) < 0.05 and o.dist[3] > 2 * o.gate - 0.05      # one square = two gates away
+    g = by["at_gate"]
+    assert (g.n_used, bool(g.used[2])) == (5, True)
+    assert np.array_equal(g.xy, K.lattice(5, 7))                                                  # the moved corner is outvoted
+    assert (g.dist[2], g.gate) == (5.0, 5.0)                                                      # d2 == gate^2 exactly
+    below = by["gate_one_ulp_below"]
+    assert (below.status, below.n_used, bool(below.used[2])) == (R.OK, 4, False)
+    h = by["exactly_half"]
+    assert (h.status, h.n_ok, h.n_used, h.xy.size) == (R.AMBIGUOUS, 4, 2, 0)
+    assert (by["none_used"].status, by["none_used"].n_used) == (R.AMBIGUOUS, 0)
+    assert (by["none_accepted"].status, by["none_accepted"].n_ok) == (R.BOARD_NOT_FOUND, 0)
+    assert (by["no_images"].status, by["no_images"].n_images) == (R.BOARD_NOT_FOUND, 0)
+    nn = by["nan_not_accepted"]
+    assert (nn.status, nn.n_ok, nn.ref_image, nn.n_used) == (R.OK, 3, 1, 3)
+    assert (by["single"].status, by["single"].n_used, by["single"].spread_max) == (R.OK, 1, 0.0)
+    # an odd count of used images takes the middle value, an even count the mean of the two middle ones
+    assert by["variants_7x5_n9"].n_used % 2 == 1 and by["variants_7x5_n8"].n_used % 2 == 0
+
+
+REFUSALS = K.refusal_cases()
+
+
+@pytest.mark.parametrize("case", REFUSALS, ids=[c[0] for c in REFUSALS])
+def test_fusion_refusals(case):
+    name, boards, accepted, a, b, gate = case
+    assert R.fuse(boards, accepted, a, b, gate).status == R.BAD_ARGUMENT
+    got, _, _ = IS.fuse_image_corners(boards, accepted, (a, b), gate)
+    assert (got.status, got.rows, got.cols, got.ref_image) == (N.BAD_ARGUMENT, 0, 0, -1)
+    assert not np.ctypeslib.as_array(got.xy).any()
+
+
+def test_fusion_refuses_null_pointers():
+    L = IS.lib()
+    out = IS.FusedImageCorners()
+    one = np.zeros(70)
+    i32 = np.array([5], np.int32)
+    acc = np.array([1], np.uint8)
+    f64p, i32p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    args = [one.ctypes.data_as(f64p), i32.ctypes.data_as(i32p), i32.ctypes.data_as(i32p), acc.ctypes.data_as(u8p)]
+    for k in range(4):
+        a = list(args)
+        a[k] = None
+        assert L.ilcc_fuse_image_corners(*a, 1, 7, 5, 0.0, C.byref(out), None, None) == N.BAD_ARGUMENT
+    assert L.ilcc_fuse_image_corners(*args, 1, 7, 5, 0.0, None, None, None) == N.BAD_ARGUMENT
+
+
+# ---- selection and batches: bags of 64 x 48 images -------------------------------------------------------------------------------
+
+def _small_bag(tmp_path, n=11, steps=None):
+    rng = np.random.default_rng(5)
+    msgs = []
+    for k in range(n):
+        step = (steps or {}).get(k)
+        msgs.append(K.CR.image_msg(rng.integers(0, 256, (48, 64), dtype=np.uint8), "mono8", seq=k, stamp=(10 + k, k), step=step))
+    return K.write_bag(tmp_path / "small.bag", msgs, per_chunk=3), msgs
+
+
+def test_scratch_bytes_equal_the_restatement():
+    for w, h in ((34, 34), (64, 48), (160, 128), (161, 131), (480, 400), (1920, 1200), (33, 100), (100, 33)):
+        assert IS.scratch_bytes(w, h) == R.scratch_bytes(w, h), (w, h)
+    assert R.nms_blocks(160) * R.nms_blocks(128) == 1008
+
+
+@pytest.mark.parametrize("first,stride,max_images", [(0, 1, 0), (2, 3, 0), (1, 2, 3), (10, 1, 0), (0, 0, 4)])
+def test_selection_and_cut_on_a_bag(tmp_path, first, stride, max_images):
+    """The lengths the chain cuts with are the messages' own, read through the topic iterator; image 4 has padded rows, so the
+    messages differ in length."""
+    path, msgs = _small_bag(tmp_path, steps={4: 80})
+    sel = R.select(len(msgs), first, stride, max_images)
+    with sequence.BagTopic(path, K.TOPIC, K.CR.IMAGE_MD5) as it:
+        assert len(it) == len(msgs)
+        raw = [it.size(i) for i in sel]
+    assert raw == [len(msgs[i]) for i in sel]
+    per = R.device_bytes_per_image(64, 48)
+    assert per == 3072 + IS.scratch_bytes(64, 48)
+    one_raw, padded_raw = R._up(len(msgs[0])), R._up(len(msgs[4]))
+    assert padded_raw > one_raw
+    budgets = [(0, 0), (one_raw, 0), (2 * one_raw, 0), (2 * one_raw + 1, 0), (padded_raw + one_raw, 0), (0, per), (0, 3 * per), (0, 3 * per - 1),
+               (3 * one_raw, 2 * per), (2 * one_raw, 5 * per)]
+    seen = set()
+    for staging, device in budgets:
+        want = R.cut(raw, per, staging, device)
+        if want == R.CAPACITY:
+            with pytest.raises(IS.ImageSequenceError) as e:
+                IS.sequence_cut(raw, per, staging, device)
+            assert e.value.status == N.CAPACITY
+            seen.add("capacity")
+            continue
+        assert IS.sequence_cut(raw, per, staging, device) == want, (staging, device)
+        sizes = np.diff(want)
+        assert sizes.sum() == len(sel) and (sizes > 0).all()
+        for b0, b1 in zip(want[:-1], want[1:]):        # every batch fits both budgets, and would not with the next image
+            assert sum(R._up(r) for r in raw[b0:b1]) <= (staging or R.DEFAULT_STAGING_BYTES)
+            assert (b1 - b0) * per <= (device or R.DEFAULT_DEVICE_BYTES)
+            if b1 < len(sel):
+                assert sum(R._up(r) for r in raw[b0:b1 + 1]) > (staging or R.DEFAULT_STAGING_BYTES) or (b1 - b0 + 1) * per > (device or R.DEFAULT_DEVICE_BYTES)
+        seen.add(len(want) - 1)
+    if (first, stride, max_images) == (0, 1, 0):
+        assert seen >= {1, 4, 6, 11, "capacity"}, seen     # one batch, several, one image each, and the refusal
+        assert R.cut(raw, per, one_raw, 0) == R.CAPACITY              # the padded image alone is above that staging budget
+        assert R.cut(raw[:4], per, one_raw, 0) == [0, 1, 2, 3, 4]
+
+
+def test_cut_of_nothing_and_one_image_above_the_device_budget():
+    assert IS.sequence_cut([], 100) == [0] == R.cut([], 100)
+    with pytest.raises(IS.ImageSequenceError) as e:
+        IS.sequence_cut([10, 10], 1000, 0, 999)
+    assert e.value.status == N.CAPACITY == R.cut([10, 10], 1000, 0, 999)
+
+
+# ---- the fusion alone, under sanitizers ----------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def host_check(tmp_path_factory):
+    """The stand-alone program: tests/image_sequence_host_check.cpp + csrc/image_sequence_host.cpp only, under ASan and UBSan."""
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a C++ compiler is needed"
+    out = tmp_path_factory.mktemp("image_sequence_host_check")
+    exe = str(out / "image_sequence_host_check")
+    csrc = os.path.join(ROOT, "lidar_camera_calibration_amd", "csrc")
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "image_sequence_host_check.cpp"),
+                    os.path.join(csrc, "image_sequence_host.cpp"), "-o", exe], check=True, timeout=300)
+    return exe, out
+
+
+def _hex(values):
+    vals = ["nan" if np.isnan(v) else float(v).hex() for v in np.asarray(values, np.float64).reshape(-1)]
+    return " ".join(vals) if vals else "-"
+
+
+def _ints(values):
+    vals = [str(int(v)) for v in values]
+    return " ".join(vals) if vals else "-"
+
+
+def _case_text(case):
+    name, boards, accepted, a, b, gate = case
+    n, size = len(accepted), 2 * a * b
+    w = R.fuse(boards, accepted, a, b, gate)
+    rows, cols, xy = [], [], np.full((n, size), np.nan)
+    for i, bd in enumerate(boards):
+        bd = np.asarray(bd, np.float64)
+        rows.append(bd.shape[0])
+        cols.append(bd.shape[1])
+        flat = bd.reshape(-1)[:size]
+        xy[i, :len(flat)] = flat
+    lines = ["%s %d %d %d %s" % (name, n, a, b, "nan" if np.isnan(gate) else float(gate).hex()), _ints(accepted), _ints(rows), _ints(cols), _hex(xy),
+             "%d %d %d %d %d %d %s %s %s" % (w.status, w.n_ok, w.n_used, w.ref_image, w.rows, w.cols, float(w.gate).hex(), float(w.spread_max).hex(),
+                                               float(w.spread_rms).hex()),
+             _ints(w.used), _hex(w.dist), _hex(w.xy) if w.status == R.OK else "-"]
+    return lines
+
+
+def test_fusion_under_sanitizers_equals_the_restatement(host_check):
+    """Every constructed case and every refusal with the restatement's answer beside it; the program compares and exits non-zero
+    on a mismatch."""
+    exe, out = host_check
+    every = CASES + REFUSALS
+    lines = [str(len(every))]
+    for case in every:
+        lines += _case_text(case)
+    cuts = [([3000, 3000, 3100, 2900, 5000], 1000, 6144, 0), ([3000] * 7, 1000, 0, 2500), ([3000] * 3, 1000, 2000, 0), ([], 5, 0, 0)]
+    for raw, per, staging, device in cuts:
+        want = R.cut(raw, per, staging, device)
+        lines += ["cut %d %d %d %d" % (len(raw), per, staging, device), _ints(raw),
+                  "%d" % R.CAPACITY if want == R.CAPACITY else "0 " + _ints(want)]
+    src = str(out / "cases.txt")
+    open(src, "w").write("\n".join(lines) + "\n")
+    r = subprocess.run([exe, src], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+    assert "cases %d ok, cuts %d ok" % (len(every), len(cuts)) in r.stdout
+    # and it does notice a mismatch: one expected coordinate of the first case moved by one ulp
+    k = 1 + 8
+    vals = lines[k].split()
+    vals[0] = float(np.nextafter(float.fromhex(vals[0]), np.inf)).hex()
+    wrong = list(lines)
+    wrong[k] = " ".join(vals)
+    open(str(out / "wrong.txt"), "w").write("\n".join(wrong) + "\n")
+    r = subprocess.run([exe, str(out / "wrong.txt")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1 and "mismatch" in r.stdout
