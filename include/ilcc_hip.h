@@ -422,6 +422,28 @@ int32_t ilcc_debug_timeline_fetch(ilcc_handle* h, double* rows, uint32_t cap_row
  * measurements compare the two.  No batch may be in flight. */
 int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on);
 
+/* Diagnostic: how the full pass of the grid search is launched.  Behind K6's common pre-pass, which lists the (frame, theta)
+ * workgroups that have anything to do, the full pass runs either as the (n_th, n_frames) grid, where a workgroup that is not listed
+ * returns on its first instructions, or as the LISTED launch: `workgroups` workgroups for the first as many items of the list, and
+ * a small launch behind it for any items beyond them.  By default a rule decides per batch (ILCC_FULL_PASS_RULE): the workgroups
+ * come from the live counts of the handle's recently completed batches, and the grid form is kept while none has completed or
+ * where nearly every workgroup is alive.  ilcc_debug_full_pass_launch forces the grid form (ILCC_FULL_PASS_GRID) or the listed form
+ * with `workgroups` >= 1 (ILCC_FULL_PASS_LISTED; capped at one per record) for every later batch and ilcc_grid_solve call of the
+ * handle; a grid without a common pre-pass, or a cut-free full pass, keeps the grid form regardless.  Results are identical either
+ * way, but for what depends on timing in any run (the count of listed near ties and ILCC_FLAG_TIE_OVERFLOW).  No batch may be in flight.
+ * ilcc_debug_full_pass_rule: the rule itself, without a handle (host arithmetic only): observed_live = the live workgroups a batch
+ * of n_frames is expected to list (< 0: nothing observed yet); returns the form the rule takes (ILCC_FULL_PASS_GRID / _LISTED) and
+ * writes the workgroups the listed form would start (>= 1, <= n_th x n_frames) to *workgroups.
+ * ilcc_debug_full_pass_last: out[0] the form of the handle's last full pass (0: none yet), [1] its workgroups, [2] the live
+ * workgroups the last completed batch listed, [3] that batch's frames. */
+#define ILCC_FULL_PASS_RULE 0
+#define ILCC_FULL_PASS_GRID 1
+#define ILCC_FULL_PASS_LISTED 2
+#define ILCC_FULL_PASS_LAST_WORDS 4
+int32_t ilcc_debug_full_pass_launch(ilcc_handle* h, int32_t mode, uint32_t workgroups);
+int32_t ilcc_debug_full_pass_rule(int64_t observed_live, uint32_t n_th, uint32_t n_frames, uint32_t* workgroups);
+int32_t ilcc_debug_full_pass_last(const ilcc_handle* h, uint32_t out[ILCC_FULL_PASS_LAST_WORDS]);
+
 /* Diagnostic: where K2's workgroups keep the cell-sorted copy of a frame's ROI points.  By default a rule decides per launch: in
  * LDS while every frame of the batch is resident on the device at once even with the copy, otherwise in the frame's slice of the
  * cluster buffer (global memory, served from L2), which halves the workgroup's LDS and lets a large batch run in one round.

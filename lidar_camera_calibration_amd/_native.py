@@ -36,7 +36,10 @@ EXPORTS = [
     "ilcc_debug_timeline_enable", "ilcc_debug_timeline_fetch", "ilcc_debug_separate_launches",
     "ilcc_debug_cluster_home", "ilcc_debug_cluster_launch", "ilcc_debug_reference_solve",
     "ilcc_debug_group_prepass", "ilcc_debug_solve_walk", "ilcc_debug_locate",
+    "ilcc_debug_full_pass_launch", "ilcc_debug_full_pass_rule", "ilcc_debug_full_pass_last",
 ]
+FULL_PASS_RULE, FULL_PASS_GRID, FULL_PASS_LISTED = 0, 1, 2
+FULL_PASS_LAST_WORDS = 4
 ABI_VERSION = 5            # the layout of Params / Result / Timing below is ILCC_ABI_VERSION 5 of include/ilcc_hip.h
 RESULTS_FULL, RESULTS_COMPACT = 0, 1
 CLUSTER_HOME_RULE, CLUSTER_HOME_LDS, CLUSTER_HOME_L2 = 0, 1, 2
@@ -240,6 +243,13 @@ def lib():
             L.ilcc_debug_locate.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint32)]
             L.ilcc_debug_locate.restype = C.c_int32
+        if hasattr(L, "ilcc_debug_full_pass_launch"):    # (likewise)
+            L.ilcc_debug_full_pass_launch.argtypes = [vp, C.c_int32, C.c_uint32]
+            L.ilcc_debug_full_pass_launch.restype = C.c_int32
+            L.ilcc_debug_full_pass_rule.argtypes = [C.c_int64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+            L.ilcc_debug_full_pass_rule.restype = C.c_int32
+            L.ilcc_debug_full_pass_last.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.ilcc_debug_full_pass_last.restype = C.c_int32
         L.ilcc_fetch_results.argtypes = [vp, C.c_uint32, C.c_uint32, rp]
         L.ilcc_fetch_results.restype = C.c_int32
         _lib = L

@@ -89,6 +89,8 @@ struct Slot {
   unsigned long long* d_iters = nullptr;
   uint32_t *d_grp_alive = nullptr, *d_grp_mask = nullptr;   // K6's common pre-pass per (frame, group of kThetaGroup thetas): state word, rejected-tile mask
   size_t grp_alive_cap = 0, grp_mask_cap = 0;   // sized from (max_frames, the handle's grid) in alloc_slot / ilcc_set_params, never in the submit path
+  uint32_t* d_work_list = nullptr;   // ... and the pre-pass's hand-over to the full pass (GridPass::work_list): max_frames x n_th items, sized with them
+  size_t work_list_cap = 0;
   float* h_rec_dev = nullptr;               // the DEVICE address of h_rec (pinned, mapped): K9 stores the batch's compact records straight into it
   unsigned long long* h_iters_dev = nullptr;   // ... and of h_iters
   // pinned host staging
@@ -100,6 +102,7 @@ struct Slot {
   std::vector<uint64_t> off;
   uint32_t n_frames = 0;
   bool busy = false, grid = false;
+  bool listed = false;       // the batch in flight / last completed ran a common pre-pass that handed over its list: h_iters[kLiveWord] is its live count
   BatchKind kind = kRoiPipeline;   // of the batch in flight
   bool h_res_valid = false;  // h_res holds the last completed batch's full (trimmed) records
   bool compact = false;      // what was enqueued with the batch in flight: the K9 records (true) or the trimmed full records
@@ -144,6 +147,14 @@ struct ilcc_handle {
   ilcc_timing timing{};
   hipEvent_t tl_ref = nullptr;       // ilcc_debug_timeline_*: reference event, rows of ILCC_TIMELINE_COLS doubles
   bool tl_on = false;
+  // The full pass's launch form (enqueue_grid_search).  live_hist: the live (frame, theta) workgroups per frame, in 1/65536, of the
+  // last kLiveHist completed batches that listed them (finish) -- a rate, so that a batch of another size can use it
+  int32_t full_pass_mode = ILCC_FULL_PASS_RULE;   // ilcc_debug_full_pass_launch
+  uint32_t full_pass_forced_g = 0;                // ILCC_FULL_PASS_LISTED: its workgroups
+  static constexpr int kLiveHist = 8;
+  uint64_t live_hist[kLiveHist]{};
+  int live_hist_n = 0, live_hist_at = 0;
+  uint32_t full_pass_last[ILCC_FULL_PASS_LAST_WORDS]{};   // ilcc_debug_full_pass_last
   bool separate_launches = false;    // ilcc_debug_separate_launches: K3, K4/K5, K5w and K1's two kernels as launches of their own at any batch size
   ClusterLimits cluster_limits{};    // K2's residency limits on this device (launch_cluster's rule for the home of the sorted points)
   int32_t cluster_home = kClusterHomeRule;   // ilcc_debug_cluster_home: the rule, or one home forced
@@ -337,6 +348,7 @@ auto slot_device_buffers(const ilcc_handle* h, Slot& sl) {
       buffer(sl.d_iters, kBatchWords),
       buffer(sl.d_grp_alive, 0),   // the common pre-pass's two follow the grid: size_group_prepass
       buffer(sl.d_grp_mask, 0),
+      buffer(sl.d_work_list, 0),
   };
 }
 
@@ -433,7 +445,53 @@ int32_t size_group_prepass(ilcc_handle* h, Slot& sl) {
     HIP_TRY(h, hipMalloc((void**)&sl.d_grp_mask, sizeof(uint32_t) * need_mask));
     sl.grp_mask_cap = need_mask;
   }
+  const size_t need_list = (size_t)h->max_frames * (size_t)h->p.n_th;   // one item per (frame, theta): every workgroup of the full pass alive
+  if (need_list > sl.work_list_cap && need_list <= 0xFFFFFFFFull) {     // (an item is a 32-bit record index; a larger batch keeps the (n_th, F) launch)
+    if (sl.d_work_list) (void)hipFree(sl.d_work_list);
+    sl.d_work_list = nullptr;
+    sl.work_list_cap = 0;
+    HIP_TRY(h, hipMalloc((void**)&sl.d_work_list, sizeof(uint32_t) * need_list));
+    sl.work_list_cap = need_list;
+  }
   return ILCC_OK;
+}
+
+// ---- The full pass's launch form.  k6_group_prepass lists the live (frame, theta) workgroups (GridPass::work_list); the listed
+// launch starts G workgroups for them instead of n_th x n_frames of which most return at once.  The host cannot know the count of
+// the batch it is enqueueing without a synchronisation, so G comes from the batches that have completed: the live share is a
+// property of the data (how well the locate launches bound a frame), steady from batch to batch.  Correctness never depends on
+// G: items beyond G are run by the looping launch behind the listed one, workgroups beyond the count find nothing to do.
+//   observed < 0: no batch has come back yet -> the (n_th, F) launch.
+//   G = observed + 1/4 + 64, rounded up to a multiple of 256 (the device's compute units), within [1, n_th x n_frames].  The margin
+//   is wide on measurement: workgroups that find no item cost nothing that shows, items beyond G wait for the
+//   second, looping launch (G at 3/4 of the count: the full pass + 40 %).
+//   G above 3/4 of the full grid: the (n_th, F) launch -- with nearly every workgroup alive the listed launch measured 1.2 % SLOWER
+//   (669 -> 677 us), with a third alive 4-7 % faster; the two lines cross at 70-80 %.
+// Returns the form; *workgroups = G (what the listed form would start, also when the rule does not take it).
+int32_t full_pass_rule(int64_t observed, uint32_t n_th, uint32_t n_frames, uint32_t* workgroups) {
+  const uint64_t full = (uint64_t)n_th * n_frames;
+  uint64_t g = full;
+  if (observed >= 0) {
+    const uint64_t o = (uint64_t)observed;
+    g = (o + o / 4u + 64u + 255u) & ~(uint64_t)255u;
+  }
+  g = std::max<uint64_t>(1u, std::min<uint64_t>(g, std::min<uint64_t>(full, 0x7FFFFFFFull)));
+  *workgroups = (uint32_t)g;
+  return observed >= 0 && full > 0 && g * 4u <= full * 3u ? ILCC_FULL_PASS_LISTED : ILCC_FULL_PASS_GRID;
+}
+
+// the live workgroups a batch of n_frames is expected to list: the largest rate among the handle's recently completed batches (-1: none)
+int64_t expected_live(const ilcc_handle* h, uint32_t n_frames) {
+  if (h->live_hist_n == 0) return -1;
+  uint64_t rate = 0;
+  for (int k = 0; k < h->live_hist_n; ++k) rate = std::max(rate, h->live_hist[k]);
+  return (int64_t)((rate * n_frames + 65535u) >> 16);
+}
+void note_live(ilcc_handle* h, uint64_t live, uint32_t n_frames) {
+  if (n_frames == 0) return;
+  h->live_hist[h->live_hist_at] = ((live << 16) + n_frames - 1u) / n_frames;
+  h->live_hist_at = (h->live_hist_at + 1) % ilcc_handle::kLiveHist;
+  h->live_hist_n = std::min(h->live_hist_n + 1, (int)ilcc_handle::kLiveHist);
 }
 
 int32_t alloc_slot_parts(ilcc_handle* h, Slot& sl) {
@@ -730,6 +788,10 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
     full.grp_mask = sl.d_grp_mask;
     full.grp_count = gp.groups;
     full.grp_words = gp.words;
+    if ((size_t)n_frames * full.blocks <= sl.work_list_cap) {   // (sized with the masks)
+      full.work_list = sl.d_work_list;
+      full.work_count = reinterpret_cast<uint32_t*>(c.grid_iters + kLiveWord);   // (little-endian: the word's low half; K1 / the diagnostic entries reset it)
+    }
     launch_group_prepass(c, full, s);
   } else if (full.box_points != 0u && gp.on) {
     // eligible grid, buffers too small for this batch (never expected: size_group_prepass sized them): slower, not wrong -- say so once
@@ -743,7 +805,22 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
   if (chain && h->k6_last >= 0 && h->k6_last != si && h->slots[h->k6_last].busy)
     HIP_TRY(h, hipStreamWaitEvent(s, h->slots[h->k6_last].k6_done, 0));
   HIP_TRY(h, hipEventRecord(sl.ev[kEvFullStart], s));
-  launch_grid_cost(c, full, s, /*use_oob=*/1, nullptr, prune);
+  // the listed launch needs the hand-over and is the pruning full pass; every other full pass keeps the (n_th, F) launch
+  uint32_t g = 0;
+  int32_t form = full_pass_rule(expected_live(h, n_frames), full.blocks, n_frames, &g);
+  if (h->full_pass_mode == ILCC_FULL_PASS_GRID) form = ILCC_FULL_PASS_GRID;
+  if (h->full_pass_mode == ILCC_FULL_PASS_LISTED) {
+    form = ILCC_FULL_PASS_LISTED;
+    g = std::min(h->full_pass_forced_g, full.blocks * n_frames);
+  }
+  if (full.work_list == nullptr || !prune || n_frames == 0) form = ILCC_FULL_PASS_GRID;
+  sl.listed = full.work_list != nullptr;
+  if (form == ILCC_FULL_PASS_LISTED)
+    launch_grid_cost_listed(c, full, s, g);
+  else
+    launch_grid_cost(c, full, s, /*use_oob=*/1, nullptr, prune);
+  h->full_pass_last[0] = (uint32_t)form;
+  h->full_pass_last[1] = form == ILCC_FULL_PASS_LISTED ? g : full.blocks * n_frames;
   if (chain) {
     HIP_TRY(h, hipEventRecord(sl.k6_done, s));
     h->k6_last = si;
@@ -1061,6 +1138,11 @@ int32_t finish(ilcc_handle* h, Slot& sl, ilcc_result* out, float* out_compact = 
   const BatchCounts n = count_batch(h, sl);
   ILCC_TRY(account_timing(h, sl, n.evals));
   grow_capacities(h, n, sl.h_iters[3 * kIterSlots]);
+  if (sl.grid && sl.listed) {   // the batch's live count came back with its counters: the next submits size their full pass by it
+    note_live(h, sl.h_iters[kLiveWord], sl.n_frames);
+    h->full_pass_last[2] = (uint32_t)sl.h_iters[kLiveWord];
+    h->full_pass_last[3] = sl.n_frames;
+  }
   return ILCC_OK;
 }
 
@@ -1313,6 +1395,7 @@ int32_t ilcc_set_params(ilcc_handle* h, const ilcc_params* p) {
   int32_t st = upload_tables(h);
   for (Slot& sl : h->slots)   // the common pre-pass's buffers follow the grid (no batch is in flight here)
     if (st == ILCC_OK && sl.allocated) st = size_group_prepass(h, sl);
+  h->live_hist_n = h->live_hist_at = 0;   // (live workgroups per frame of another grid or bound say nothing about this one)
   if (st != ILCC_OK) {
     // the device tables may be partly overwritten: put the previous parameter set back on the device as well, and refuse
     // further work if even that fails
@@ -1783,6 +1866,30 @@ int32_t ilcc_debug_timeline_enable(ilcc_handle* h, int32_t on) {
 int32_t ilcc_debug_separate_launches(ilcc_handle* h, int32_t on) {
   if (!h || any_batch_in_flight(h, "ilcc_debug_separate_launches")) return ILCC_BAD_ARGUMENT;
   h->separate_launches = on != 0;
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_full_pass_launch(ilcc_handle* h, int32_t mode, uint32_t workgroups) {
+  if (!h || any_batch_in_flight(h, "ilcc_debug_full_pass_launch")) return ILCC_BAD_ARGUMENT;
+  if ((mode != ILCC_FULL_PASS_RULE && mode != ILCC_FULL_PASS_GRID && mode != ILCC_FULL_PASS_LISTED) || (mode == ILCC_FULL_PASS_LISTED && workgroups == 0u)) {
+    h->err = "ilcc_debug_full_pass_launch: mode must be ILCC_FULL_PASS_RULE, _GRID or _LISTED, the last with at least one workgroup";
+    return ILCC_BAD_ARGUMENT;
+  }
+  h->full_pass_mode = mode;
+  h->full_pass_forced_g = mode == ILCC_FULL_PASS_LISTED ? workgroups : 0u;
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_full_pass_rule(int64_t observed_live, uint32_t n_th, uint32_t n_frames, uint32_t* workgroups) {
+  uint32_t g = 0;
+  const int32_t form = full_pass_rule(observed_live, n_th, n_frames, &g);
+  if (workgroups) *workgroups = g;
+  return form;
+}
+
+int32_t ilcc_debug_full_pass_last(const ilcc_handle* h, uint32_t out[ILCC_FULL_PASS_LAST_WORDS]) {
+  if (!h || !out) return ILCC_BAD_ARGUMENT;
+  for (int k = 0; k < ILCC_FULL_PASS_LAST_WORDS; ++k) out[k] = h->full_pass_last[k];
   return ILCC_OK;
 }
 

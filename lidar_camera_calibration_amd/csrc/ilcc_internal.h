@@ -74,7 +74,8 @@ constexpr int kTieCap = 256;           // K6 -> K7r: near-tie candidates kept pe
 constexpr float kTieEps = 2e-5f;       // relative cost window of a near-tie (fp32 sums of ~1e3 terms agree to ~1e-6)
 constexpr int kCoverageCellsMax = 1024;   // K7b: board squares tracked by the coverage mask (board_w x board_h)
 constexpr int kIterSlots = 64;         // K6 executed-iteration counters (spread to avoid one hot atomic); [0,64): all points, [64,128): interior-class points, [128,192): (point, tile) evaluations of the box pre-pass
-constexpr int kBatchWords = 3 * kIterSlots + 2;   // Ctx::grid_iters: the K6 counters, then K2's: [192] most occupied cells a frame's LDS cell grid needed ([193] spare)
+constexpr int kBatchWords = 3 * kIterSlots + 2;   // Ctx::grid_iters: the K6 counters, then K2's: [192] most occupied cells a frame's LDS cell grid needed, then [193]:
+constexpr int kLiveWord = 3 * kIterSlots + 1;     // the live (frame, theta) workgroups k6_group_prepass listed for the full pass (its low 32 bits are the list's count word)
 constexpr int kClusterHashSize = 1 << 17;    // K2: hash buckets per frame (global memory)
 constexpr int kClusterLdsPointsMax = 4096;   // K2: largest LDS capacity for the cell-sorted points (ROI points per frame); larger frames keep them in HBM/L2
 constexpr int kClusterLdsPointsMin = 1024;   // K2: smallest (the handle grows it in steps of 512 with the ROI sizes it sees)
@@ -147,6 +148,12 @@ struct GridPass {
   uint32_t* grp_alive;
   uint32_t* grp_mask;
   uint32_t grp_count, grp_words;   // theta groups per frame = ceil(n_th / kThetaGroup); mask words per group = ceil(tiles / 32)
+  // ... and hands the full pass its LIVE workgroups (nullptr: no hand-over): work_list[0 .. *work_count) holds f * blocks + kblk -- the
+  // index of the workgroup's record in `out` -- of every (frame, theta) whose group ended in state 1, or in state 2 on a frame with
+  // status ILCC_OK, in no particular order; the records of all the others are written (no_candidate) by the pre-pass itself.  The
+  // listed launch (k6_grid_cost_listed) runs those items only; the (n_th, F) launch ignores the list.
+  uint32_t* work_list;       // n_frames x blocks items at most
+  uint32_t* work_count;      // a batch word (Ctx::grid_iters[kLiveWord]): K1 resets it, the batch's counters carry it to the host
 };
 
 // what is true for a whole batch, passed by value to every kernel
@@ -355,7 +362,8 @@ inline bool front_end_fusable(const Ctx& c) {
 }
 void launch_walk_order(const Ctx& c, hipStream_t s);   // K5w (k5w_walk_order.hip): before any launch_grid_cost on the frames
 void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t use_oob, float* cost_volume /*nullable*/, bool prune);   // k6_grid_cost.hip
-void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // k6_group_prepass.hip, in front of the full pass it is given: writes full.grp_alive / grp_mask
+void launch_group_prepass(const Ctx& c, const GridPass& full, hipStream_t s);   // k6_group_prepass.hip, in front of the full pass it is given: writes full.grp_alive / grp_mask, hands over full.work_list
+void launch_grid_cost_listed(const Ctx& c, const GridPass& full, hipStream_t s, uint32_t workgroups);   // k6_grid_cost.hip: the full pass on full.work_list, as a 1-D grid of `workgroups` (>= 1)
 uint32_t grid_cost_evals_per_count();   // (point, candidate) evaluations behind one count of Ctx::grid_iters
 // K7a on every frame of the batch (REFERENCE_LOCAL mode: solve_slots(c.p) solves per frame, k7_common.h)
 void launch_reference_solve(const Ctx& c, hipStream_t s);

@@ -140,9 +140,8 @@ __device__ __forceinline__ void publish_record(const Ctx& c, uint32_t f, Best be
 template <bool OOB, bool VOLUME, bool LDS_POINTS, bool PRUNE, int THREADS, bool OVERFLOW = false>
 __device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pass, float* volume, float2* s_ij, float* s_hw, Best* s_best,
                                                uint32_t* s_iters, uint32_t* s_cnt, float* s_ay, float* s_az, uint32_t* s_dead, uint16_t* s_live,
-                                               uint32_t* s_next, const uint32_t kblk) {
-  // kblk: this workgroup's index within the frame (= blockIdx.x)
-  const uint32_t f = blockIdx.y;
+                                               uint32_t* s_next, const uint32_t kblk, const uint32_t f) {
+  // kblk: this workgroup's index within the frame, f: its frame (blockIdx.x, blockIdx.y of the (n_th, F) launch; from the item of the listed one)
   uint32_t k = kblk;   // theta index (a launch with a window: set from the seed below)
   [[maybe_unused]] const unsigned long long t_entry = K6_NOW();
   [[maybe_unused]] unsigned long long t_rej = 0, t_surv = 0, n_rej = 0, n_surv = 0, n_done = 0, p_surv = 0;
@@ -701,8 +700,10 @@ __global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, GridPass pass, fl
   // benchmark runs each 1 222 k against 1 241 k frames/s (medians; config 5: 96.9 against 96.3 k, inside its spread))
   const uint32_t M = pass.walk_limit ? walk_sample(Mall, pass.walk_limit) : Mall;
   (void)M;
+  // (the choice of form below, and the LDS declared and carved above, have a COPY for the listed launch: listed_item and
+  // K6_FULL_PASS_LDS further down -- a change here is a change there)
   if (Mall <= c.grid_lds_points) {   // (k5w_walk_order has laid out every frame of at most kGridLdsPointsMax points)
-    grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
+    grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x, blockIdx.y);
     return;
   }
   if constexpr (OOB && !VOLUME && PRUNE) {
@@ -714,13 +715,81 @@ __global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, GridPass pass, fl
       // (= box_sample, written out: called here, the helper compiles both pipeline instances to another schedule, + 24 instructions)
       if (Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShift), Mall - Mi) <= c.grid_lds_points) {
         grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS, true>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next,
-                                                                blockIdx.x);
+                                                                blockIdx.x, blockIdx.y);
         return;
       }
     }
   }
-  grid_cost_body<OOB, VOLUME, false, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x);
+  grid_cost_body<OOB, VOLUME, false, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x, blockIdx.y);
 }
+
+// ---- The full pass behind k6_group_prepass's hand-over (GridPass::work_list): only the listed (frame, theta) workgroups are started;
+// the pre-pass has already written the records of all the others.  Same body, same sums, same records as the (n_th, F) launch.
+
+// item `i` of the list: the form choice of k6_grid_cost above for the item's frame.  (A copy, not a shared helper: with the choice
+// moved into a function of both kernels, the two pipeline instances of k6_grid_cost compile to another schedule -- 9.8 k of their
+// 9.4 k lines of gfx950 assembly differ --, which this kernel is known not to take lightly: see (void)M above.)
+template <int THREADS>
+__device__ __forceinline__ void listed_item(const Ctx& c, const GridPass& pass, uint32_t i, float2* s_ij, float* s_hw, Best* s_best, uint32_t* s_iters,
+                                            uint32_t* s_cnt, float* s_ay, float* s_az, uint32_t* s_dead, uint16_t* s_live, uint32_t* s_next) {
+  const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)pass.work_list[i]);
+  if (item >= c.n_frames * pass.blocks) return;   // (never: an item is the index of a record)
+  const uint32_t f = item / pass.blocks, kblk = item - f * pass.blocks;
+  const uint32_t Mall = c.n_lab[f];
+  if (Mall <= c.grid_lds_points) {
+    grid_cost_body<true, false, true, true, THREADS>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
+    return;
+  }
+  if (pass.walk_limit == 0u && pass.box_points != 0u && Mall <= (uint32_t)kGridLdsPointsMax) {   // OVERFLOW: the same conditions as in k6_grid_cost
+    const uint32_t Mi = c.walk_mi[f];
+    if (Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShiftOf<THREADS>), Mall - Mi) <= c.grid_lds_points) {
+      grid_cost_body<true, false, true, true, THREADS, true>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
+      return;
+    }
+  }
+  grid_cost_body<true, false, false, true, THREADS>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
+}
+
+// the LDS of a full-pass workgroup, as k6_grid_cost declares and carves it
+#define K6_FULL_PASS_LDS(THREADS)                                                        \
+  extern __shared__ __align__(16) unsigned char smem[];                                  \
+  __shared__ Best s_best[THREADS / ILCC_WAVE];                                           \
+  __shared__ uint32_t s_iters[THREADS / ILCC_WAVE];                                      \
+  __shared__ uint32_t s_cnt[THREADS / ILCC_WAVE];                                        \
+  __shared__ uint32_t s_dead[kBoxTilesMax / 32];                                         \
+  __shared__ uint16_t s_live[kBoxSegment<THREADS>];                                      \
+  __shared__ uint32_t s_next;                                                            \
+  const GridLds l = grid_lds(c.grid_lds_points, 0, 0);                                   \
+  float2* s_ij = reinterpret_cast<float2*>(smem);                                        \
+  float* s_hw = lds_next<float>(smem, 0, l.hw);                                          \
+  float* s_ay = lds_next<float>(s_hw, l.hw, l.ay);                                       \
+  float* s_az = s_ay + pass.t.n_ty
+
+// k6_grid_cost_listed: a 1-D grid of G workgroups, workgroup b runs item b -- straight-line code, the registers of the (n_th, F)
+// launch (64 VGPRs, seven wavefronts per SIMD).  G is the host's estimate of the count (ilcc_api.cpp: full_pass_rule); a workgroup
+// past the count returns, and items past G are left to k6_grid_cost_listed_rest.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k6_grid_cost_listed(Ctx c, GridPass pass) {
+  K6_FULL_PASS_LDS(THREADS);
+  if (blockIdx.x < min(*pass.work_count, c.n_frames * pass.blocks))   // (the list holds no more items than records)
+    listed_item<THREADS>(c, pass, blockIdx.x, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next);
+}
+
+// k6_grid_cost_listed_rest: the items from `first` (= the G of the launch in front of it) on, when the batch listed more than the host
+// expected: workgroup b runs items first + b, first + b + (its grid), ... with a workgroup barrier in between, and retires behind
+// them.  Every workgroup returns at once in the usual case.  (A kernel of its own because of its registers: around the item LOOP the
+// compiler hoists everything that depends on the thread index alone and keeps it live through the body -- 93 VGPRs, five wavefronts
+// per SIMD, or scratch when held to 72.  Which of the two kernels runs an item never shows in its record.)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k6_grid_cost_listed_rest(Ctx c, GridPass pass, uint32_t first) {
+  K6_FULL_PASS_LDS(THREADS);
+  const uint32_t n_items = min(*pass.work_count, c.n_frames * pass.blocks);
+  for (uint32_t i = first + blockIdx.x; i < n_items; i += gridDim.x) {
+    listed_item<THREADS>(c, pass, i, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next);
+    __syncthreads();   // the next item reuses the workgroup's LDS (thread 0 reads the wavefronts' bests last)
+  }
+}
+#undef K6_FULL_PASS_LDS
 
 // -DILCC_K6_ISA_PROBE (tools/k6_isa_count.sh): the two terms alone, N chained calls on N different points per kernel.  The
 // VALU instructions of ONE evaluation = (instructions of the N = 3 kernel - instructions of the N = 1 kernel) / 2 -- counted
@@ -782,7 +851,9 @@ hipError_t set_kernel_attributes_k6() {
   hipError_t e = raise_grid_lds_limit({(const void*)k6_grid_cost<true, true, false, kGridThreads>, (const void*)k6_grid_cost<true, false, false, kGridThreads>,
                        (const void*)k6_grid_cost<false, true, false, kGridThreads>, (const void*)k6_grid_cost<false, false, false, kGridThreads>,
                        (const void*)k6_grid_cost<true, false, true, kGridThreads>,  (const void*)k6_grid_cost<false, false, true, kGridThreads>,
-                       (const void*)k6_grid_cost<true, false, true, kGridThreadsLarge>});
+                       (const void*)k6_grid_cost<true, false, true, kGridThreadsLarge>, (const void*)k6_grid_cost_listed<kGridThreads>,
+                       (const void*)k6_grid_cost_listed<kGridThreadsLarge>, (const void*)k6_grid_cost_listed_rest<kGridThreads>,
+                       (const void*)k6_grid_cost_listed_rest<kGridThreadsLarge>});
   if (e == hipSuccess) e = set_kernel_attributes_k6_group_prepass();
   if (e == hipSuccess) e = set_kernel_attributes_k6_locate();
   return e;
@@ -810,6 +881,27 @@ void launch_grid_cost(const Ctx& c, const GridPass& pass, hipStream_t s, int32_t
     else
       hipLaunchKernelGGL((k6_grid_cost<false, false, false, kGridThreads>), grid, block, lds, s, c, pass, cost_volume);
   }
+}
+
+// the pipeline's full pass (pruning, out-of-board term) on the items k6_group_prepass listed: `workgroups` (>= 1) of
+// k6_grid_cost_listed for the first as many items, and, unless that is one per record, kListedRest of k6_grid_cost_listed_rest for
+// whatever the batch lists beyond them
+constexpr uint32_t kListedRest = 1024;   // four per compute unit: enough to keep the chip busy on a batch the host's estimate missed
+void launch_grid_cost_listed(const Ctx& c, const GridPass& pass, hipStream_t s, uint32_t workgroups) {
+  const size_t lds = grid_lds_bytes(c.grid_lds_points, pass.t.n_ty, pass.t.n_tz);
+  const bool large = c.grid_lds_points > (uint32_t)kGridLargeFrom;
+  const dim3 block(large ? kGridThreadsLarge : kGridThreads);
+  if (large)
+    hipLaunchKernelGGL((k6_grid_cost_listed<kGridThreadsLarge>), dim3(workgroups), block, lds, s, c, pass);
+  else
+    hipLaunchKernelGGL((k6_grid_cost_listed<kGridThreads>), dim3(workgroups), block, lds, s, c, pass);
+  const uint32_t records = c.n_frames * pass.blocks;
+  if (workgroups >= records) return;
+  const dim3 rest(records - workgroups < kListedRest ? records - workgroups : kListedRest);
+  if (large)
+    hipLaunchKernelGGL((k6_grid_cost_listed_rest<kGridThreadsLarge>), rest, block, lds, s, c, pass, workgroups);
+  else
+    hipLaunchKernelGGL((k6_grid_cost_listed_rest<kGridThreads>), rest, block, lds, s, c, pass, workgroups);
 }
 
 }  // namespace ilcc

@@ -13,6 +13,22 @@ namespace ilcc {
 // out; the interval stays far narrower than a board).  Output per (frame, group): a state word -- 0: every tile rejected (the
 // group's full-pass workgroups exit on their first instructions), 1: a bit mask of the rejected tiles follows (their own
 // pre-pass starts from it and only looks at the rest), 2: no common pre-pass (conditions not met) -- and the mask.
+
+// The hand-over to the full pass (GridPass::work_list; one thread of the pre-pass workgroup): a group with something left to do --
+// state 1, or state 2 on a frame with status ILCC_OK -- lists its nk (frame, theta) workgroups; for every other group the pre-pass
+// writes the nk records a full-pass workgroup would have written on its first instructions.  Either way the full pass's records
+// are what the (n_th, F) launch alone leaves; the listed launch simply never starts the workgroups with nothing to do.
+__device__ __forceinline__ void hand_over_group(const GridPass& pass, uint32_t f, int k0, int nk, bool live) {
+  if (pass.work_list == nullptr) return;
+  const uint32_t first = f * pass.blocks + (uint32_t)k0;
+  if (live) {
+    const uint32_t at = atomicAdd(pass.work_count, (uint32_t)nk);   // (at most n_frames x blocks items over the launch: the list's size)
+    for (int t = 0; t < nk; ++t) pass.work_list[at + (uint32_t)t] = first + (uint32_t)t;
+  } else {
+    for (int t = 0; t < nk; ++t) no_candidate(&pass.out[first + (uint32_t)t]);
+  }
+}
+
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, GridPass pass) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -32,8 +48,12 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, GridPass pass
   const int nta = axis_tiles(n_ty), ntb = axis_tiles(n_tz), n_tiles = nta * ntb;
   const uint32_t Mi = lds ? c.walk_mi[f] : 0u;
   // (every condition is uniform over the workgroup)
-  if (!(c.res[f].status == ILCC_OK && lds && nk > 1 && pass.box_points != 0u && n_tiles <= kBoxTilesMax && Mall > Mi)) {
-    if (threadIdx.x == 0) pass.grp_alive[tr] = 2u;
+  const bool frame_ok = c.res[f].status == ILCC_OK;
+  if (!(frame_ok && lds && nk > 1 && pass.box_points != 0u && n_tiles <= kBoxTilesMax && Mall > Mi)) {
+    if (threadIdx.x == 0) {
+      pass.grp_alive[tr] = 2u;
+      hand_over_group(pass, f, k0, nk, frame_ok);   // (a frame that never reached the search: its full-pass workgroups only write no_candidate)
+    }
     return;
   }
   const int lane = lane_id();
@@ -85,6 +105,7 @@ __global__ __launch_bounds__(THREADS) void k6_group_prepass(Ctx c, GridPass pass
     for (int w = 0; w < THREADS / ILCC_WAVE; ++w) box_evals += s_iters[w];
     count_evals(c.grid_iters, f, kEvalsBox, box_evals);
     pass.grp_alive[tr] = any_alive ? 1u : 0u;
+    hand_over_group(pass, f, k0, nk, any_alive);
   }
 }
 

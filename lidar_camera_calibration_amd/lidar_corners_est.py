@@ -285,6 +285,23 @@ class LidarCornersBatch:
         if st != N.OK:
             raise IlccError(st, self._err())
 
+    def debug_full_pass_launch(self, mode: int, workgroups: int = 0):
+        """Diagnostic: force how the grid search's full pass is launched -- ``N.FULL_PASS_GRID`` (one workgroup per (frame, theta)),
+        ``N.FULL_PASS_LISTED`` with ``workgroups`` >= 1 (only the workgroups the common pre-pass listed) -- or give the choice back
+        to the rule (``N.FULL_PASS_RULE``).  Results are identical either way."""
+        st = self._lib.ilcc_debug_full_pass_launch(self._h, int(mode), int(workgroups))
+        if st != N.OK:
+            raise IlccError(st, self._err())
+
+    def debug_full_pass_last(self) -> dict:
+        """The form and workgroups of the handle's last full pass, and the live (frame, theta) workgroups the last completed batch
+        listed, with its frame count."""
+        out = (C.c_uint32 * N.FULL_PASS_LAST_WORDS)()
+        st = self._lib.ilcc_debug_full_pass_last(self._h, out)
+        if st != N.OK:
+            raise IlccError(st, self._err())
+        return dict(zip(("form", "workgroups", "live", "frames"), (int(v) for v in out)))
+
     def debug_cluster_home(self, home: int):
         """Diagnostic: force where K2 keeps the cell-sorted points (``N.CLUSTER_HOME_LDS`` / ``N.CLUSTER_HOME_L2``), or give the
         choice back to the per-launch rule (``N.CLUSTER_HOME_RULE``).  Results are identical either way."""
