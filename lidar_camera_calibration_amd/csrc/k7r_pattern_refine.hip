@@ -10,7 +10,44 @@
 
 #include "k7_common.h"
 
+#ifdef ILCC_K7R_TIMING
+#include <algorithm>
+#include <vector>
+#endif
+
 namespace ilcc {
+
+// -DILCC_K7R_TIMING: where a K7r wavefront's cycles go (cycle counter stamps around the phases of its life), one record per
+// wavefront in k7r_prof[], read back through ilcc_debug_k7r_profile (tools/dev_k7r_phases.py).  Without the switch the stamps
+// and the record compile away.
+enum RefineProfSlot {
+  kProfWritten = 0,   // 1: the record was written
+  kProfSetup,         // staging + grid_argmin + recount_near_ties + first_round_is_settled
+  kProfTrips,         // silence-test trips of the pattern rounds (the walk less its queued evaluations)
+  kProfEvals,         // queued evaluations (and the walks of sweeps that skip nothing)
+  kProfReduce,        // row reduction + LDS atomics
+  kProfBarrier,       // waiting at the two barriers of a pattern round's sweep
+  kProfDecide,        // decision step
+  kProfBasin,         // basin checks: their sweeps, barriers and decisions
+  kProfLife,          // entry to record
+  kProfRounds,        // pattern rounds swept
+  kProfTripCount,     // silence-test trips
+  kProfQueued,        // points queued for evaluation
+  kProfFrame,
+  kProfWave,
+  kProfWords = 16
+};
+#ifdef ILCC_K7R_TIMING
+constexpr int kRefineProfWaves = 1 << 14;
+__device__ unsigned long long k7r_prof[kRefineProfWaves * kProfWords];
+#define K7R_STAMP(name) const unsigned long long name = __builtin_readcyclecounter()
+#define K7R_SPENT(fr, slot, from, to) ((fr).prof[slot] += (to) - (from))
+#define K7R_COUNT(fr, slot, k) ((fr).prof[slot] += (unsigned long long)(k))
+#else
+#define K7R_STAMP(name)
+#define K7R_SPENT(fr, slot, from, to)
+#define K7R_COUNT(fr, slot, k)
+#endif
 
 constexpr double kCostQOne = 1099511627776.0;   // 2^40: quantum of the fixed-point cost (oracle: ORC_COST_Q_ONE)
 // wavefronts of the K7r workgroup: kRefineThreads / 64 in large batches, kRefineThreadsSmallBatch / 64 in small ones (the
@@ -150,6 +187,9 @@ struct Frame {
   uint32_t n;
   RefineShared& sh;
   int sweep;            // sweeps run so far
+#ifdef ILCC_K7R_TIMING
+  unsigned long long prof[kProfWords];   // this wavefront's record (begin_frame zeroes it)
+#endif
 };
 // (zeroes the first sweep's acc set: the caller's barrier publishes it)
 __device__ __forceinline__ Frame begin_frame(const Ctx& c, RefineShared& sh, const float2* yz, const uint8_t* lab, uint32_t n) {
@@ -222,7 +262,10 @@ __device__ __forceinline__ int stencil_sweep(Frame& fr, int n_th, const int32_t 
   const float2* yz = fr.yz;
   const uint8_t* lab = fr.lab;
   const uint32_t n = fr.n;
+  K7R_STAMP(t_begin);
   const int buf = sweep_begin(fr);
+  K7R_STAMP(t_open);
+  K7R_SPENT(fr, parity ? kProfBasin : kProfBarrier, t_begin, t_open);
   const int wid = __builtin_amdgcn_readfirstlane(wave_id());
   const int waves_per_theta = kRefineWaves / n_th;          // 3 wavefronts: one per theta of the stencil, or all three on the basin check's single theta
   const int it = wid % n_th, grp = wid / n_th;
@@ -291,21 +334,29 @@ __device__ __forceinline__ int stencil_sweep(Frame& fr, int n_th, const int32_t 
             active = !(one_cell && (lab[p] != 0) == white);
           }
           const unsigned long long m = __ballot(active);
+          K7R_COUNT(fr, kProfTripCount, 1);
           if (m != 0ull) {
             if (active) queue[(tail + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & (kActQueue - 1)] = p;
             tail += (uint32_t)__popcll(m);
+            K7R_COUNT(fr, kProfQueued, __popcll(m));
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // one wavefront: LDS executes its instructions in order; keep the compiler from reordering
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            K7R_STAMP(t_drain);
             while (tail - head >= (uint32_t)ILCC_WAVE) {
               eval_point(queue[(head + (uint32_t)lane) & (kActQueue - 1)]);
               head += ILCC_WAVE;
             }
+            K7R_STAMP(t_drained);
+            K7R_SPENT(fr, kProfEvals, t_drain, t_drained);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the reads above before the next round's writes
             __builtin_amdgcn_wave_barrier();
           }
         }
+        K7R_STAMP(t_rest);
         if ((uint32_t)lane < tail - head) eval_point(queue[(head + (uint32_t)lane) & (kActQueue - 1)]);
+        K7R_STAMP(t_rested);
+        K7R_SPENT(fr, kProfEvals, t_rest, t_rested);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // ... and before a second walk's
         __builtin_amdgcn_wave_barrier();
       } else {
@@ -313,6 +364,7 @@ __device__ __forceinline__ int stencil_sweep(Frame& fr, int n_th, const int32_t 
       }
     };
     unsigned long long tot[9];
+    K7R_STAMP(t_walk);
     {
       double acc[9];
       walk(acc);
@@ -329,6 +381,8 @@ __device__ __forceinline__ int stencil_sweep(Frame& fr, int n_th, const int32_t 
         for (int e = 0; e < 9; ++e) tot[e] = (unsigned long long)iacc[e];
       }
     }
+    K7R_STAMP(t_walked);
+    K7R_SPENT(fr, parity ? kProfBasin : kProfTrips, t_walk, t_walked);   // (the record takes the queued evaluations off the trips)
     // integer sums: any reduction order gives the same totals
 #pragma unroll
     for (int e = 0; e < 9; ++e) {
@@ -341,8 +395,13 @@ __device__ __forceinline__ int stencil_sweep(Frame& fr, int n_th, const int32_t 
       t += xor_lane_u64<1>(t);
       if ((lane & 15) == 0) atomicAdd(&fr.sh.acc[buf][it * 9 + e], t);
     }
+    K7R_STAMP(t_added);
+    K7R_SPENT(fr, parity ? kProfBasin : kProfReduce, t_walked, t_added);
   }
+  K7R_STAMP(t_close);
   sweep_end(fr);
+  K7R_STAMP(t_end);
+  K7R_SPENT(fr, parity ? kProfBasin : kProfBarrier, t_close, t_end);
   return buf;
 }
 
@@ -461,6 +520,29 @@ __device__ __forceinline__ bool first_round_is_settled(const Frame& fr, const Gr
   return !risk && !(flags & ILCC_FLAG_TIE_OVERFLOW) && gk > 0 && gk < c.p.n_th - 1 && ga > 0 && ga < n_ty - 1 && gb > 0 && gb < n_tz - 1;
 }
 
+// The least (cost, key) pair of lanes 0..31, cost first and then key, returned wave-uniform: five register-only exchanges
+// (comparisons of integers: the order of the reduction cannot change the pick).  Every wavefront runs it on its own copy, all
+// 64 lanes active; lanes that hold no entry pass (LLONG_MAX, 0xFFFFFFFF).
+template <int MASK>
+__device__ __forceinline__ void argmin_step(long long& cost, uint32_t& key) {
+  const long long oc = (long long)xor_lane_u64<MASK>((unsigned long long)cost);
+  const uint32_t ok = xor_lane_u32<MASK>(key);
+  const bool take = oc < cost || (oc == cost && ok < key);
+  cost = take ? oc : cost;
+  key = take ? ok : key;
+}
+__device__ __forceinline__ void argmin_lanes32(long long& cost, uint32_t& key) {
+  argmin_step<16>(cost, key);
+  argmin_step<8>(cost, key);
+  argmin_step<4>(cost, key);
+  argmin_step<2>(cost, key);
+  argmin_step<1>(cost, key);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(unsigned long long)cost);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)cost >> 32));
+  cost = (long long)(((unsigned long long)hi << 32) | lo);
+  key = (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
+}
+
 // orc_pattern_refine from st.lat / st.phase (st.skip_first: see first_round_is_settled), executed redundantly (and
 // identically) by every thread of the workgroup
 __device__ __forceinline__ void pattern_refine(Frame& fr, RefineState& st) {
@@ -489,20 +571,17 @@ __device__ __forceinline__ void pattern_refine(Frame& fr, RefineState& st) {
         tz[k] = st.lat[2] + (k - 1) * stride;
       }
       const int b = stencil_sweep(fr, 3, th, ty, tz, st.phase, false);
-      long long bc = LLONG_MAX;
-      int bd2 = 0, be = -1;
-      for (int e = 0; e < 27; ++e) {   // (dk, da, db) order; ties: nearer, then first
-        if (e == 13) continue;
-        const int dk = e / 9 - 1, da = (e / 3) % 3 - 1, db = e % 3 - 1;
-        if (fr.lat.theta_or_none(st.lat[0] + dk * stride) == kNoTheta) continue;
-        const long long cc = (long long)sh.acc[b][e];
-        const int d2 = dk * dk + da * da + db * db;
-        if (cc < bc || (cc == bc && d2 < bd2)) {
-          bc = cc;
-          bd2 = d2;
-          be = e;
-        }
-      }
+      K7R_STAMP(t_swept);
+      // lane e < 27 holds neighbour e in (dk, da, db) order; the pick is the oracle's: lower cost, then nearer (smaller d2), then
+      // first (lower e) -- the least (cost, d2 * 32 + e).  The centre and the thetas outside the table take no part; an entry
+      // of LLONG_MAX is never taken, as in a loop that starts from it.
+      const int le = min(lane_id(), 26);
+      const int ldk = le / 9 - 1, lda = (le / 3) % 3 - 1, ldb = le % 3 - 1;
+      const bool listed = lane_id() < 27 && le != 13 && fr.lat.theta_or_none(st.lat[0] + ldk * stride) != kNoTheta;
+      long long bc = listed ? (long long)sh.acc[b][le] : LLONG_MAX;
+      uint32_t bkey = listed ? (uint32_t)((ldk * ldk + lda * lda + ldb * ldb) * 32 + le) : 0xFFFFFFFFu;
+      argmin_lanes32(bc, bkey);
+      const int be = (bc == LLONG_MAX) ? -1 : (int)(bkey & 31u);
       const long long centre = (long long)sh.acc[b][13];
       ++r;
       if (be >= 0 && bc < centre) {
@@ -512,6 +591,9 @@ __device__ __forceinline__ void pattern_refine(Frame& fr, RefineState& st) {
       } else {
         stride >>= 1;
       }
+      K7R_STAMP(t_decided);
+      K7R_SPENT(fr, kProfDecide, t_swept, t_decided);
+      K7R_COUNT(fr, kProfRounds, 1);
     }
     st.rounds += r;
     if (refine && stride >= 1) st.capped = 1;   // left the loop on the round cap, not on the stride
@@ -521,18 +603,18 @@ __device__ __forceinline__ void pattern_refine(Frame& fr, RefineState& st) {
     const int32_t hz[3] = {st.lat[2] - c.refine_hop_z, st.lat[2], st.lat[2] + c.refine_hop_z};
     // ((da + db) & 1 with da, db in {-1, 0, 1} == (a + b) & 1 with a = da + 1, b = db + 1)
     const int b = stencil_sweep(fr, 1, th1, hy, hz, st.phase, true);
+    K7R_STAMP(t_basin);
     st.cost = (long long)sh.acc[b][4];
-    long long alt = LLONG_MAX;
-    int ae = -1;
-    for (int e = 0; e < 9; ++e) {
-      if (e == 4) continue;
-      const long long cc = (long long)sh.acc[b][e];
-      if (cc < alt) {
-        alt = cc;
-        ae = e;
-      }
-    }
+    // lane e < 9 holds basin e; the cheapest of the eight neighbours, the first of equals: the least (cost, e)
+    const int he = min(lane_id(), 8);
+    const bool neighbour = lane_id() < 9 && he != 4;
+    long long alt = neighbour ? (long long)sh.acc[b][he] : LLONG_MAX;
+    uint32_t akey = neighbour ? (uint32_t)he : 0xFFFFFFFFu;
+    argmin_lanes32(alt, akey);
+    const int ae = (int)(akey & 15u);   // (read only where alt < st.cost: a neighbour's)
     st.alt = alt;
+    K7R_STAMP(t_basin_read);
+    K7R_SPENT(fr, kProfBasin, t_basin, t_basin_read);
     if (alt < st.cost && st.hops < 2 && refine) {
       const int da = ae / 3 - 1, db = ae % 3 - 1;
       ++st.hops;
@@ -576,6 +658,7 @@ __device__ __forceinline__ void store_record(const Lattice& lat, const RefineSta
 // points every sweep reads)
 template <bool LDS_POINTS>
 __device__ __forceinline__ void refine_frame(const Ctx& c, SolveRec* rec, const StagedPoints& lds, RefineShared& sh) {
+  K7R_STAMP(t_entry);
   const uint32_t f = blockIdx.x;
   const uint64_t beg = c.off[f];
   SolveRec* out = &rec[2 * f];
@@ -603,8 +686,23 @@ __device__ __forceinline__ void refine_frame(const Ctx& c, SolveRec* rec, const 
   }
   const GridCell start = fr.lat.from_flat(b.flat);
   RefineState st = start_at(start.at, first_round_is_settled(fr, start, flags));
+  K7R_STAMP(t_start);
   pattern_refine(fr, st);
   if (threadIdx.x == 0) store_record(fr.lat, st, flags, n_ties, out);
+#ifdef ILCC_K7R_TIMING
+  if (lane_id() == 0) {   // one record per wavefront: the last batch that ran frame f keeps it
+    const unsigned long long t_done = __builtin_readcyclecounter();
+    const uint32_t wid = (uint32_t)wave_id();
+    unsigned long long* o = k7r_prof + (size_t)((f * (uint32_t)kRefineWaves + wid) & (uint32_t)(kRefineProfWaves - 1)) * kProfWords;
+    fr.prof[kProfWritten] = 1ull;
+    fr.prof[kProfSetup] = t_start - t_entry;
+    fr.prof[kProfTrips] -= fr.prof[kProfEvals];   // (the walk of a pattern round = its trips + its queued evaluations)
+    fr.prof[kProfLife] = t_done - t_entry;
+    fr.prof[kProfFrame] = f;
+    fr.prof[kProfWave] = wid;
+    for (int k = 0; k < kProfWords; ++k) o[k] = fr.prof[k];
+  }
+#endif
 }
 
 __global__ __launch_bounds__(kRefineThreadsSmallBatch) void k7r_pattern_refine(Ctx c, SolveRec* rec) {
@@ -655,5 +753,24 @@ void launch_pattern_refine(const Ctx& c, hipStream_t s) {
 void launch_pattern_refine_test(const Ctx& c, hipStream_t s, RefineOut* d_io) {
   hipLaunchKernelGGL(k7r_pattern_refine_test, dim3(1), dim3(kRefineThreads), 0, s, c, d_io);
 }
+
+#ifdef ILCC_K7R_TIMING
+// out: the written records (kProfWords words each, RefineProfSlot order), at most cap_records of them; returns their number
+extern "C" int ilcc_debug_k7r_profile(unsigned long long* out, int cap_records, int clear) {
+  static std::vector<unsigned long long> host((size_t)kRefineProfWaves * kProfWords);
+  if (hipMemcpyFromSymbol(host.data(), HIP_SYMBOL(k7r_prof), host.size() * sizeof(unsigned long long)) != hipSuccess) return -1;
+  int n = 0;
+  for (size_t w = 0; w < (size_t)kRefineProfWaves && n < cap_records; ++w)
+    if (host[w * kProfWords + kProfWritten] != 0ull) {
+      std::copy(host.begin() + w * kProfWords, host.begin() + (w + 1) * kProfWords, out + (size_t)n * kProfWords);
+      ++n;
+    }
+  if (clear) {
+    std::fill(host.begin(), host.end(), 0ull);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(k7r_prof), host.data(), host.size() * sizeof(unsigned long long)) != hipSuccess) return -1;
+  }
+  return n;
+}
+#endif
 
 }  // namespace ilcc
