@@ -404,7 +404,34 @@ int32_t ilcc_debug_reference_solve(ilcc_handle* h, const float* yz, const uint8_
 int32_t ilcc_debug_locate(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets, uint32_t n_frames,
                           uint32_t* records_out, uint32_t* bound_out);
 
-/* Diagnostic (ABI 5): the real timeline of the batches, without a profiler.  While enabled, every completed batch appends one row
+/* Diagnostic: the GRID back end as the pipeline launches it on a BATCH -- K5w, the launches that locate the minimum, the common
+ * pre-pass, the full pass, K7r and K7b -- on n_frames frames of caller-supplied labelled points (host buffers; frame f = points
+ * offsets[f] .. offsets[f + 1]).  It is to ilcc_grid_solve what ilcc_debug_reference_solve is to ilcc_get_theta_t: the frame count
+ * alone selects what a batch of that size runs -- k6_locate from 512 frames on (where the grid and the capacity take it), the
+ * 192-thread K7r above 64 frames, the full pass's launch form by the handle's rule or as ilcc_debug_full_pass_launch forced it.
+ * Staged in front of the launches: what K4/K5 leave behind (offsets, labelled counts, walk strides) and what K1 resets (a record per
+ * frame, zeroed but for status = status_in[f]: a frame whose status is not ILCC_OK is one the front end failed; an infinite bound
+ * and sub-bound and a zero near-tie count per frame; the batch's counter words).  The handle's LDS staging capacity is used as it is
+ * and never grown: frames with more labelled points take the global-memory forms beside staged ones in the same launches.
+ * Out, per frame f, from slot 2 f of the solve records (pre-filled with every bit set):
+ *   rec_f64[ILCC_GRID_REC_DOUBLES f ..] = theta, ty, tz;  rec_i64[ILCC_GRID_REC_INT64S f ..] = cost_q, alt_q (units of 2^-40);
+ *   rec_i32[ILCC_GRID_REC_INTS f ..] = rounds, hops, phase, valid, flags, ties (valid == 0: K7r had nothing to refine; a slot no
+ *   launch wrote keeps every bit set);
+ * results[f]: the frame's record after K7b, the part in front of `corners` (corners are not copied);
+ * info[ILCC_GRID_BATCH_INFO_WORDS] (may be NULL): [0] the LDS staging capacity the launches ran with (labelled points per frame),
+ * [1] how the minimum was located: 0 not at all (a grid too small), 1 seed + refinement + anchor launches, 2 k6_locate,
+ * [2] the form of the full pass (ILCC_FULL_PASS_GRID / _LISTED), [3] K7r's threads per workgroup.
+ * Refuses (nothing is launched): a busy ticket 0, a handle that is not in ILCC_SOLVER_GRID mode, more frames than max_frames, more
+ * points than the handle holds, offsets that do not start at 0 or that decrease, and null pointers. */
+#define ILCC_GRID_REC_DOUBLES 3
+#define ILCC_GRID_REC_INT64S 2
+#define ILCC_GRID_REC_INTS 6
+#define ILCC_GRID_BATCH_INFO_WORDS 4
+int32_t ilcc_debug_grid_solve_batch(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets,
+                                    const int32_t* status_in, uint32_t n_frames, double* rec_f64, int64_t* rec_i64, int32_t* rec_i32,
+                                    ilcc_result* results, uint32_t* info);
+
+/* Diagnostic (ABI 5): the real timeline of the batches, without a profiler. While enabled, every completed batch appends one row
  * of ILCC_TIMELINE_COLS doubles: slot, then the times in ms -- relative to a reference event recorded when the timeline was
  * enabled -- of the batch's HIP events: start, after K1's count pass, after K1, K2, K3, K4/K5, K5w, seed, refinement, anchor,
  * common pre-pass (= ready for the full pass), full pass start (behind the wait for the previous batch's full pass), full pass

@@ -37,6 +37,7 @@ EXPORTS = [
     "ilcc_debug_cluster_home", "ilcc_debug_cluster_launch", "ilcc_debug_reference_solve",
     "ilcc_debug_group_prepass", "ilcc_debug_solve_walk", "ilcc_debug_locate",
     "ilcc_debug_full_pass_launch", "ilcc_debug_full_pass_rule", "ilcc_debug_full_pass_last",
+    "ilcc_debug_grid_solve_batch",
 ]
 FULL_PASS_RULE, FULL_PASS_GRID, FULL_PASS_LISTED = 0, 1, 2
 FULL_PASS_LAST_WORDS = 4
@@ -45,6 +46,8 @@ RESULTS_FULL, RESULTS_COMPACT = 0, 1
 CLUSTER_HOME_RULE, CLUSTER_HOME_LDS, CLUSTER_HOME_L2 = 0, 1, 2
 CLUSTER_LAUNCH_WORDS = 6
 SOLVE_REC_DOUBLES, SOLVE_REC_INTS = 6, 4
+GRID_REC_DOUBLES, GRID_REC_INT64S, GRID_REC_INTS, GRID_BATCH_INFO_WORDS = 3, 2, 6, 4
+LOCATE_NONE, LOCATE_LAUNCHES, LOCATE_FUSED = 0, 1, 2   # ilcc_debug_grid_solve_batch: info[1]
 
 
 class Params(C.Structure):
@@ -250,6 +253,11 @@ def lib():
             L.ilcc_debug_full_pass_rule.restype = C.c_int32
             L.ilcc_debug_full_pass_last.argtypes = [vp, C.POINTER(C.c_uint32)]
             L.ilcc_debug_full_pass_last.restype = C.c_int32
+        if hasattr(L, "ilcc_debug_grid_solve_batch"):    # (likewise)
+            L.ilcc_debug_grid_solve_batch.argtypes = [vp, fp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_uint32,
+                                                      C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32), rp,
+                                                      C.POINTER(C.c_uint32)]
+            L.ilcc_debug_grid_solve_batch.restype = C.c_int32
         L.ilcc_fetch_results.argtypes = [vp, C.c_uint32, C.c_uint32, rp]
         L.ilcc_fetch_results.restype = C.c_int32
         _lib = L

@@ -723,6 +723,17 @@ LocatePlan locate_plan(const ilcc_handle* h, const Slot& sl, const Ctx& c) {
   return lp;
 }
 
+// How a batch of n_frames locates the minimum in front of the full pass: not at all (a grid too small to decimate), with the three
+// kinds of launches, or in one launch, one workgroup per frame (k6_locate), when the batch has the frames to fill the chip that way
+// and the plan's LDS fits.  The values are what ilcc_debug_grid_solve_batch reports.
+enum LocateForm { kLocateNone = 0, kLocateLaunches = 1, kLocateFused = 2 };
+LocateForm locate_form(const ilcc_handle* h, const LocatePlan& lp, uint32_t n_frames) {
+  if (!(h->seed_grid.n_th > 0 && h->p.n_th >= 8 && h->p.n_ty >= 8 && h->p.n_tz >= 8)) return kLocateNone;
+  const bool fused = n_frames >= (uint32_t)kLocateMinFrames && lp.seed.n_th <= 16 &&
+                     locate_lds_bytes(lp, h->grid.n_ty, h->grid.n_tz) <= (size_t)kLocateLdsMax;
+  return fused ? kLocateFused : kLocateLaunches;
+}
+
 // Locating the minimum with three kinds of launches (batches too small for k6_locate's one workgroup per frame): seed over the
 // decimated tables, refinement around its argmin, then kAnchorRounds anchor rounds, each re-centred on the previous round's argmin
 // -- a greedy descent on complete costs towards the grid minimum, for a tighter bound in front of the full pass.  Returns where
@@ -755,16 +766,14 @@ int32_t enqueue_grid_search(ilcc_handle* h, Slot& sl, const Ctx& c, hipStream_t 
   GridSeed located{};   // (records == nullptr: nothing located)
   // (grid_prune = 0 keeps the locate launches: they only initialise the frame's bound, which the cut-free full
   // pass still needs to recognise near ties; it never cuts a tile)
-  if (h->seed_grid.n_th > 0 && h->p.n_th >= 8 && h->p.n_ty >= 8 && h->p.n_tz >= 8) {
+  const LocatePlan lp = locate_plan(h, sl, c);
+  const LocateForm located_by = locate_form(h, lp, n_frames);
+  if (located_by != kLocateNone) {
     // These launches only have to LOCATE the minimum.  Seed and refinement therefore look at a prefix of the point walk (an
     // eighth of the frame's labelled points, at least ILCC_SEED_POINTS positions: a uniform sample of the board) and keep their
     // own bound word; the anchor evaluates what they found on EVERY point and publishes the frame's real bound.  (Round 2 ran
     // seed and refinement on all points: 16 % of the path's VALU instructions.)
-    const LocatePlan lp = locate_plan(h, sl, c);
-    // one launch, one workgroup per frame (k6_locate) when the batch has the frames to fill the chip that way
-    const bool fused = n_frames >= (uint32_t)kLocateMinFrames && lp.seed.n_th <= 16 &&
-                       locate_lds_bytes(lp, h->grid.n_ty, h->grid.n_tz) <= (size_t)kLocateLdsMax;
-    if (fused) {
+    if (located_by == kLocateFused) {
       launch_locate(c, s, lp);
       HIP_TRY(h, hipEventRecord(sl.ev[kEvSeeded], s));   // (the whole locate launch is accounted as the "seed" span)
       HIP_TRY(h, hipEventRecord(sl.ev[kEvRefined], s));
@@ -1778,8 +1787,7 @@ int32_t ilcc_debug_locate(ilcc_handle* h, const float* yz, const uint8_t* label,
   // the handle's capacities as they are (see ilcc_debug_reference_solve): the caller decides which frames the anchor stages
   const Ctx c = make_ctx(h, sl, nullptr, nullptr, n_frames, 1);
   const LocatePlan lp = locate_plan(h, sl, c);
-  if (!(h->seed_grid.n_th > 0 && h->p.n_th >= 8 && h->p.n_ty >= 8 && h->p.n_tz >= 8) || lp.seed.n_th > 16 ||
-      locate_lds_bytes(lp, h->grid.n_ty, h->grid.n_tz) > (size_t)kLocateLdsMax) {
+  if (locate_form(h, lp, (uint32_t)kLocateMinFrames) != kLocateFused) {
     h->err = "ilcc_debug_locate: this grid (or LDS capacity) does not take k6_locate";
     return ILCC_CAPACITY;
   }
@@ -1814,6 +1822,87 @@ int32_t ilcc_debug_locate(ilcc_handle* h, const float* yz, const uint8_t* label,
   HIP_TRY(h, hipMemcpyAsync(records_out, lp.out, sizeof(GridPartial) * n_frames, hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipMemcpyAsync(bound_out, sl.d_bound, sizeof(uint32_t) * n_frames, hipMemcpyDeviceToHost, s));
   ILCC_TRY(sync_own(h, s));
+  return ILCC_OK;
+}
+
+int32_t ilcc_debug_grid_solve_batch(ilcc_handle* h, const float* yz, const uint8_t* label, const uint64_t* offsets,
+                                    const int32_t* status_in, uint32_t n_frames, double* rec_f64, int64_t* rec_i64, int32_t* rec_i32,
+                                    ilcc_result* results, uint32_t* info) {
+  if (!h) return ILCC_BAD_ARGUMENT;
+  if (!status_in || !rec_f64 || !rec_i64 || !rec_i32 || !results) {
+    h->err = "ilcc_debug_grid_solve_batch: null status_in or output";
+    return ILCC_BAD_ARGUMENT;
+  }
+  Slot& sl = h->slots[0];
+  if (sl.busy) {
+    h->err = "diagnostic entry while ticket 0 is in flight";
+    return ILCC_BAD_ARGUMENT;
+  }
+  if (h->p.solver != ILCC_SOLVER_GRID) {
+    h->err = "ilcc_debug_grid_solve_batch needs ILCC_SOLVER_GRID";
+    return ILCC_BAD_ARGUMENT;
+  }
+  ILCC_TRY(check_offsets(h, offsets, n_frames));
+  const uint64_t total = offsets[n_frames];
+  if (total > 0 && (!yz || !label)) {
+    h->err = "ilcc_debug_grid_solve_batch: null points";
+    return ILCC_BAD_ARGUMENT;
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  const hipStream_t s = h->stream[take_stream(h)];
+  // what K4/K5 leave behind for the back end -- offsets, labelled counts (+ walk strides) -- and what K1 resets: a record per frame
+  // (zeroed but for the caller's status), an infinite bound and sub-bound and no near ties per frame, the batch's counters
+  std::vector<uint32_t> n_lab(n_frames), stride(n_frames), bound(n_frames, 0x7f800000u);
+  std::vector<ilcc_result> res(n_frames);
+  std::memset(res.data(), 0, sizeof(ilcc_result) * n_frames);
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    n_lab[f] = (uint32_t)(offsets[f + 1] - offsets[f]);
+    stride[f] = walk_stride(n_lab[f]);
+    res[f].status = status_in[f];
+  }
+  HIP_TRY(h, hipMemcpyAsync(sl.d_off, offsets, sizeof(uint64_t) * (n_frames + 1), hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_res, res.data(), sizeof(ilcc_result) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_nlab, n_lab.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_walk, stride.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_bound, bound.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(sl.d_bound_sub, bound.data(), sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemsetAsync(sl.d_tie_count, 0, sizeof(uint32_t) * n_frames, s));
+  HIP_TRY(h, hipMemsetAsync(sl.d_iters, 0, sizeof(unsigned long long) * kBatchWords, s));
+  if (total > 0) {
+    HIP_TRY(h, hipMemcpyAsync(sl.d_yz, yz, sizeof(float2) * total, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(sl.d_lab, label, total, hipMemcpyHostToDevice, s));
+  }
+  // (a record slot no launch writes comes back with every bit set: valid == -1, never 0 or 1)
+  HIP_TRY(h, hipMemsetAsync(sl.d_solverec, 0xFF, sizeof(SolveRec) * 2 * n_frames, s));
+  sl.n_frames = 0;   // the stage buffers no longer describe a batch
+  // the handle's capacities as they are (diagnostic_ctx would grow the staging to the frame): the caller decides which frames stay
+  // in global memory.  From here on the frame count alone selects what runs, as in enqueue_impl
+  const Ctx c = make_ctx(h, sl, nullptr, nullptr, n_frames, 1);
+  ILCC_TRY(enqueue_grid_search(h, sl, c, s, n_frames, /*chain=*/false));
+  launch_pattern_refine(c, s);
+  launch_corners(c, s, 1);
+  HIP_TRY(h, hipGetLastError());
+  std::vector<SolveRec> rec(2 * (size_t)n_frames);
+  std::vector<ilcc_result> back(n_frames);
+  HIP_TRY(h, hipMemcpyAsync(rec.data(), sl.d_solverec, sizeof(SolveRec) * rec.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipMemcpyAsync(back.data(), sl.d_res, sizeof(ilcc_result) * n_frames, hipMemcpyDeviceToHost, s));
+  ILCC_TRY(sync_own(h, s));
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    const SolveRec& r = rec[2 * (size_t)f];
+    const double d[ILCC_GRID_REC_DOUBLES] = {r.x[0], r.x[1], r.x[2]};
+    const int64_t q[ILCC_GRID_REC_INT64S] = {(int64_t)r.cost_q, (int64_t)r.alt_q};   // (not r.sel x 2^40: see ilcc_grid_solve)
+    const int32_t i[ILCC_GRID_REC_INTS] = {r.iters_a, r.iters_b, r.phase, r.valid, r.flags, r.ties};
+    std::memcpy(rec_f64 + ILCC_GRID_REC_DOUBLES * (size_t)f, d, sizeof(d));
+    std::memcpy(rec_i64 + ILCC_GRID_REC_INT64S * (size_t)f, q, sizeof(q));
+    std::memcpy(rec_i32 + ILCC_GRID_REC_INTS * (size_t)f, i, sizeof(i));
+    std::memcpy(&results[f], &back[f], offsetof(ilcc_result, corners));
+  }
+  if (info) {
+    info[0] = c.grid_lds_points;
+    info[1] = (uint32_t)locate_form(h, locate_plan(h, sl, c), n_frames);
+    info[2] = h->full_pass_last[0];
+    info[3] = (uint32_t)(n_frames <= (uint32_t)kSmallBatchFrames ? kRefineThreadsSmallBatch : kRefineThreads);
+  }
   return ILCC_OK;
 }
 

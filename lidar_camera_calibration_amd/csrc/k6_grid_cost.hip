@@ -137,10 +137,16 @@ __device__ __forceinline__ void publish_record(const Ctx& c, uint32_t f, Best be
 // read from the walk layout in L2 and rotated by the lane that needs it: only the few tiles that walk (almost) the whole frame get
 // there.  Same points, same order, same sums.  (Before: such a frame took the LDS-free body, which has no box pre-pass: a handful of
 // frames with 6 682 labelled points made config 5's full pass 5.6 ms instead of 0.74 ms per 128 frames.)
-template <bool OOB, bool VOLUME, bool LDS_POINTS, bool PRUNE, int THREADS, bool OVERFLOW = false>
+// OVERFLOW = 2 (staged_prefix = false): the interior class and the box pre-pass's sample do not fit the staging, so NOTHING is staged
+// and there is no box pre-pass -- every position comes from the walk layout in L2 -- but the walk, and with it every candidate's fp32
+// sum, stays the staged form's.  (Such a frame used to take the LDS-free body, which adds the points in another order: its grid
+// cost, and on a near tie the fp32 ranking, then depended on the handle's capacity.)
+// (A template value, not a run-time flag: with the flag the pipeline's kernels compiled to another schedule.)
+template <bool OOB, bool VOLUME, bool LDS_POINTS, bool PRUNE, int THREADS, int OVERFLOW = 0>
 __device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pass, float* volume, float2* s_ij, float* s_hw, Best* s_best,
                                                uint32_t* s_iters, uint32_t* s_cnt, float* s_ay, float* s_az, uint32_t* s_dead, uint16_t* s_live,
                                                uint32_t* s_next, const uint32_t kblk, const uint32_t f) {
+  constexpr bool staged_prefix = OVERFLOW != 2;
   // kblk: this workgroup's index within the frame, f: its frame (blockIdx.x, blockIdx.y of the (n_th, F) launch; from the item of the listed one)
   uint32_t k = kblk;   // theta index (a launch with a window: set from the seed below)
   [[maybe_unused]] const unsigned long long t_entry = K6_NOW();
@@ -223,7 +229,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pas
   uint32_t n_in, n_rm;
   walk_prefix(M, Mfull, Mi_all, n_rim_all, n_in, n_rm);
   auto walk_source = [&](uint32_t sl) { return layout_source(sl, n_in, n_rm, Mfull, Mi_all, n_rim_all); };
-  const uint32_t lds_n = OVERFLOW ? min(M, c.grid_lds_points) : M;   // walk positions [0, lds_n) live in LDS
+  const uint32_t lds_n = OVERFLOW ? (staged_prefix ? min(M, c.grid_lds_points) : 0u) : M;   // walk positions [0, lds_n) live in LDS
   auto stage_point = [&](uint32_t sl) {
     const uint32_t src = walk_source(sl);
     s_ij[sl] = rotate(wyz[src], cth, sth);
@@ -233,7 +239,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pas
     Mi = n_in;
     // The full pass stages the points its box pre-pass looks at first: a workgroup the pre-pass leaves no tile (half of
     // them: every theta more than a few steps from the minimum) never stages, or reads, the rest.
-    const bool box_first = PRUNE && OOB && pass.box_points != 0u && nta * ntb <= kBoxTilesMax && M > Mi;   // (= use_box below)
+    const bool box_first = PRUNE && OOB && pass.box_points != 0u && nta * ntb <= kBoxTilesMax && M > Mi && (!OVERFLOW || staged_prefix);   // (= use_box below)
     stage_lo = box_first ? Mi : 0u;
     stage_hi = box_first ? Mi + box_sample(pass.box_points, Mfull, M, Mi, kBoxShift) : lds_n;   // (OVERFLOW: the caller made sure the sample fits)
     for (uint32_t sl = stage_lo + threadIdx.x; sl < stage_hi; sl += THREADS) stage_point(sl);
@@ -270,7 +276,7 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pas
   bool use_box = false;
   unsigned long long box_evals = 0;   // (point, tile) evaluations of this workgroup's pre-pass
   if constexpr (PRUNE && LDS_POINTS && OOB) {
-    use_box = pass.box_points != 0u && n_tiles <= kBoxTilesMax && M > Mi;
+    use_box = pass.box_points != 0u && n_tiles <= kBoxTilesMax && M > Mi && (!OVERFLOW || staged_prefix);
     if (use_box) {
       const uint32_t n_pre = box_sample(pass.box_points, Mfull, M, Mi, kBoxShift);
       const bool any_alive = own_box_prepass<THREADS>(n_tiles, ntb, a_org, b_org, n_ty, n_tz, s_ay, s_az, s_ij, Mi, n_pre, gb_bits, s_dead0, s_dead, s_live, s_cnt,
@@ -295,19 +301,20 @@ __device__ __forceinline__ void grid_cost_body(const Ctx& c, const GridPass& pas
   constexpr int kFirstIn = 0, kFirstBd = 2;   // interior- / border-class (rim-first) points per lane in the first, register-resident block
   const bool first_block = LDS_POINTS && Mi >= (uint32_t)(kFirstIn * kSlices) && M - Mi >= (uint32_t)(kFirstBd * kSlices);
   PointTerms first_in[kFirstIn > 0 ? kFirstIn : 1], first_bd[kFirstBd > 0 ? kFirstBd : 1];
+  auto first_point = [&](uint32_t at) -> PointTerms {
+    if (OVERFLOW == 2 && at >= lds_n) {   // (nothing is staged)
+      const uint32_t src = walk_source(at);
+      const float2 v = rotate(wyz[src], cth, sth);
+      return PointTerms{v.x, v.y, wlab[src] ? 0.5f : 0.f};
+    }
+    const float2 v = s_ij[at];
+    return PointTerms{v.x, v.y, s_hw[at]};
+  };
   if (LDS_POINTS && first_block) {
 #pragma unroll
-    for (int u = 0; u < kFirstIn; ++u) {
-      const uint32_t ai = (uint32_t)(u * kSlices + my_s);
-      const float2 vi = s_ij[ai];
-      first_in[u] = PointTerms{vi.x, vi.y, s_hw[ai]};
-    }
+    for (int u = 0; u < kFirstIn; ++u) first_in[u] = first_point((uint32_t)(u * kSlices + my_s));
 #pragma unroll
-    for (int u = 0; u < kFirstBd; ++u) {
-      const uint32_t ab = Mi + (uint32_t)(u * kSlices + my_s);
-      const float2 vb = s_ij[ab];
-      first_bd[u] = PointTerms{vb.x, vb.y, s_hw[ab]};
-    }
+    for (int u = 0; u < kFirstBd; ++u) first_bd[u] = first_point(Mi + (uint32_t)(u * kSlices + my_s));
   }
 
   const bool whole_tiles = (n_ty % kTile) == 0 && (n_tz % kTile) == 0;   // (wave-uniform: a scalar branch per tile)
@@ -713,11 +720,14 @@ __global__ __launch_bounds__(THREADS) void k6_grid_cost(Ctx c, GridPass pass, fl
     if (pass.walk_limit == 0u && pass.box_points != 0u && Mall <= (uint32_t)kGridLdsPointsMax) {
       const uint32_t Mi = c.walk_mi[blockIdx.y];
       // (= box_sample, written out: called here, the helper compiles both pipeline instances to another schedule, + 24 instructions)
-      if (Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShift), Mall - Mi) <= c.grid_lds_points) {
-        grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS, true>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next,
-                                                                blockIdx.x, blockIdx.y);
-        return;
-      }
+      const bool staged_prefix = Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShift), Mall - Mi) <= c.grid_lds_points;
+      if (staged_prefix)
+        grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS, 1>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next,
+                                                             blockIdx.x, blockIdx.y);
+      else
+        grid_cost_body<OOB, VOLUME, true, PRUNE, THREADS, 2>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next,
+                                                             blockIdx.x, blockIdx.y);
+      return;
     }
   }
   grid_cost_body<OOB, VOLUME, false, PRUNE, THREADS>(c, pass, volume, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, &s_next, blockIdx.x, blockIdx.y);
@@ -742,10 +752,12 @@ __device__ __forceinline__ void listed_item(const Ctx& c, const GridPass& pass, 
   }
   if (pass.walk_limit == 0u && pass.box_points != 0u && Mall <= (uint32_t)kGridLdsPointsMax) {   // OVERFLOW: the same conditions as in k6_grid_cost
     const uint32_t Mi = c.walk_mi[f];
-    if (Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShiftOf<THREADS>), Mall - Mi) <= c.grid_lds_points) {
-      grid_cost_body<true, false, true, true, THREADS, true>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
-      return;
-    }
+    const bool staged_prefix = Mall > Mi && Mi + min(max(pass.box_points, Mall >> kBoxShiftOf<THREADS>), Mall - Mi) <= c.grid_lds_points;
+    if (staged_prefix)
+      grid_cost_body<true, false, true, true, THREADS, 1>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
+    else
+      grid_cost_body<true, false, true, true, THREADS, 2>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
+    return;
   }
   grid_cost_body<true, false, false, true, THREADS>(c, pass, nullptr, s_ij, s_hw, s_best, s_iters, s_cnt, s_ay, s_az, s_dead, s_live, s_next, kblk, f);
 }

@@ -607,6 +607,54 @@ class LidarCornersBatch:
                     iters_a=i[:, :, 0].copy(), iters_b=i[:, :, 1].copy(), phase=i[:, :, 2].copy(), valid=i[:, :, 3].copy(),
                     results=res, lds_points=int(lds.value))
 
+    def grid_solve_batch(self, frames, status_in=None) -> dict:
+        """The GRID back end as the pipeline launches it on a batch (K5w, locate, common pre-pass, full pass, K7r, K7b) on
+        caller-supplied labelled frames: ``frames`` is a sequence of (yz[m, 2], label[m]); ``status_in[f]`` != OK marks frame f
+        as failed by the front end.  The frame count alone selects the locate form, K7r's width and the full pass's form; the
+        handle's capacities are not grown.  -> dict of per-frame arrays: x[F, 3] (theta, ty, tz), lat[F, 3] (lattice coordinates
+        as grid_solve gives them; 0 where valid != 1), cost_q, alt_cost_q, rounds, hops, phase, valid (-1: no launch wrote the
+        slot), flags, ties; status, result_flags, grid_index, grid_cost (float32), grid_ties from the frames' records; results:
+        the records themselves (corners not copied); lds_points, locate (N.LOCATE_*), full_pass (N.FULL_PASS_*), k7r_threads.
+        Diagnostic entry."""
+        f = len(frames)
+        counts = [len(lab) for _, lab in frames]
+        offsets = np.zeros(f + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(counts, dtype=np.uint64)
+        yz = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 2) for a, _ in frames] or
+                                                 [np.zeros((0, 2), np.float32)]), dtype=np.float32)
+        label = np.ascontiguousarray(np.concatenate([np.asarray(b, np.uint8).reshape(-1) for _, b in frames] or
+                                                    [np.zeros(0, np.uint8)]), dtype=np.uint8)
+        status = np.ascontiguousarray(np.zeros(f, np.int32) if status_in is None else status_in, dtype=np.int32)
+        if len(status) != f:
+            raise IlccError(N.BAD_ARGUMENT, "grid_solve_batch: one status per frame")
+        d = np.zeros((f, N.GRID_REC_DOUBLES), dtype=np.float64)
+        q = np.zeros((f, N.GRID_REC_INT64S), dtype=np.int64)
+        i = np.zeros((f, N.GRID_REC_INTS), dtype=np.int32)
+        res = (N.Result * max(f, 1))()
+        info = (C.c_uint32 * N.GRID_BATCH_INFO_WORDS)()
+        st = self._lib.ilcc_debug_grid_solve_batch(self._h, N.fptr(yz), label.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   status.ctypes.data_as(C.POINTER(C.c_int32)), f,
+                                                   d.ctypes.data_as(C.POINTER(C.c_double)), q.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   i.ctypes.data_as(C.POINTER(C.c_int32)), res, info)
+        if st != N.OK:
+            raise IlccError(st, self._err())
+        p = self.params
+        div = float(p.refine_div if p.refine_div > 0 else 1)
+        valid = i[:, 3].copy()
+        lat = np.zeros((f, 3), dtype=np.int64)
+        ok = valid == 1
+        for k, (lo, step) in enumerate(((p.th_min, p.th_step), (p.ty_min, p.ty_step), (p.tz_min, p.tz_step))):
+            lat[ok, k] = np.rint((d[ok, k] - lo) / (step / div)).astype(np.int64)
+        return dict(x=d.copy(), lat=lat, cost_q=q[:, 0].copy(), alt_cost_q=q[:, 1].copy(), rounds=i[:, 0].copy(), hops=i[:, 1].copy(),
+                    phase=i[:, 2].copy(), valid=valid, flags=i[:, 4].copy(), ties=i[:, 5].copy(),
+                    status=np.array([res[k].status for k in range(f)], np.int32),
+                    result_flags=np.array([res[k].flags for k in range(f)], np.int32),
+                    grid_index=np.array([res[k].grid_index for k in range(f)], np.int32),
+                    grid_cost=np.array([res[k].grid_cost for k in range(f)], np.float32),
+                    grid_ties=np.array([res[k].grid_ties for k in range(f)], np.int32),
+                    results=res, lds_points=int(info[0]), locate=int(info[1]), full_pass=int(info[2]), k7r_threads=int(info[3]))
+
     def timing(self) -> N.Timing:
         t = N.Timing()
         self._lib.ilcc_get_timing(self._h, C.byref(t))

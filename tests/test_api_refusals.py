@@ -168,6 +168,8 @@ def test_synchronous_and_diagnostic_calls_are_refused_while_ticket_0_is_in_fligh
         lambda: L.ilcc_pattern_refine(h, N.fptr(yz), labp, 8, lat, C.byref(phase), None, None, None, None),
         lambda: L.ilcc_debug_reference_solve(h, N.fptr(yz), labp, (C.c_uint64 * 2)(0, 8), (C.c_int32 * 1)(0), 1, (C.c_double * 12)(),
                                              (C.c_int32 * 8)(), res, None),
+        lambda: L.ilcc_debug_grid_solve_batch(h, N.fptr(yz), labp, (C.c_uint64 * 2)(0, 8), (C.c_int32 * 1)(0), 1, (C.c_double * 3)(),
+                                              (C.c_int64 * 2)(), (C.c_int32 * 6)(), res, None),
     ]
     for call in calls:
         e.refused(call(), N.BAD_ARGUMENT)
@@ -308,3 +310,62 @@ def test_the_views_of_the_last_grid_solve_are_refused_while_a_batch_is_in_flight
     assert (dims[0], dims[1]) == (9, 4)        # the default grid: 61 thetas in groups of 7, 40 x 40 translations = 100 tiles of 4 x 4
     assert L.ilcc_debug_solve_walk(h, None, None, 0, counts) >= 0
     assert e.wait(e.accepted(*w.host)) == w.ref
+
+
+def test_grid_solve_batch_refusals_launch_nothing():
+    """ilcc_debug_grid_solve_batch refuses null pointers, offsets that do not describe a batch, more frames than max_frames, more
+    points than the handle holds and a handle that is not in ILCC_SOLVER_GRID mode -- each with its status and a text, the outputs
+    untouched and, on a handle that has run nothing yet, no full pass on record afterwards (ilcc_debug_full_pass_last: form 0);
+    then the same handle accepts a good call.  (A busy ticket 0: with the other diagnostic entries above.)"""
+    L = N.lib()
+    I32P, I64P, F64P, U32P = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+    FRAMES, POINTS = 3, 64
+    yz = np.zeros((POINTS + 1, 2), np.float32)
+    lab = np.zeros(POINTS + 1, np.uint8)
+    status = np.zeros(FRAMES + 1, np.int32)
+    d = np.full(3 * (FRAMES + 1), -7.0)
+    q = np.full(2 * (FRAMES + 1), -7, np.int64)
+    i = np.full(6 * (FRAMES + 1), -7, np.int32)
+    res = (N.Result * (FRAMES + 1))()
+    good = np.array([0, 16, 16, POINTS], np.uint64)
+
+    def call(h, off, n_frames, **null):
+        a = dict(yz=N.fptr(yz), lab=lab.ctypes.data_as(U8P), off=None if off is None else off.ctypes.data_as(U64P),
+                 status=status.ctypes.data_as(I32P), d=d.ctypes.data_as(F64P), q=q.ctypes.data_as(I64P), i=i.ctypes.data_as(I32P), res=res)
+        a.update({k: None for k in null})
+        return L.ilcc_debug_grid_solve_batch(h, a["yz"], a["lab"], a["off"], a["status"], n_frames, a["d"], a["q"], a["i"], a["res"], None)
+
+    def last_form(h):
+        out = (C.c_uint32 * N.FULL_PASS_LAST_WORDS)()
+        assert L.ilcc_debug_full_pass_last(h, out) == N.OK
+        return out[0]
+
+    e = Handle(FRAMES, POINTS)      # (the default parameters: ILCC_SOLVER_GRID)
+    try:
+        assert L.ilcc_debug_grid_solve_batch(None, None, None, None, None, 0, None, None, None, None, None) == N.BAD_ARGUMENT
+        four = np.array([0, 16, 16, 32, POINTS], np.uint64)
+        too_many_points = np.array([0, 16, 16, POINTS + 1], np.uint64)
+        not_from_0 = np.array([1, 16, 16, POINTS], np.uint64)
+        decreasing = np.array([0, 16, 15, POINTS], np.uint64)
+        cases = [(good, FRAMES, dict(status=1), N.BAD_ARGUMENT), (good, FRAMES, dict(d=1), N.BAD_ARGUMENT), (good, FRAMES, dict(q=1), N.BAD_ARGUMENT),
+                 (good, FRAMES, dict(i=1), N.BAD_ARGUMENT), (good, FRAMES, dict(res=1), N.BAD_ARGUMENT), (good, FRAMES, dict(yz=1), N.BAD_ARGUMENT),
+                 (good, FRAMES, dict(lab=1), N.BAD_ARGUMENT), (None, FRAMES, {}, N.BAD_ARGUMENT), (good, 0, {}, N.BAD_ARGUMENT),
+                 (four, FRAMES + 1, {}, N.CAPACITY), (too_many_points, FRAMES, {}, N.CAPACITY), (not_from_0, FRAMES, {}, N.BAD_ARGUMENT),
+                 (decreasing, FRAMES, {}, N.BAD_ARGUMENT)]
+        for off, n_frames, null, want in cases:
+            e.refused(call(e.h, off, n_frames, **null), want)
+            assert not e.busy(0) and last_form(e.h) == 0
+        assert (d == -7.0).all() and (q == -7).all() and (i == -7).all() and all(res[f].status == 0 and res[f].grid_index == 0 for f in range(FRAMES + 1))
+        assert call(e.h, good, FRAMES) == N.OK, e.err()
+        assert last_form(e.h) != 0 and (i[:6 * FRAMES] != -7).all() and (i[6 * FRAMES:] == -7).all()
+    finally:
+        e.close()
+    p = N.default_params()
+    p.solver = N.SOLVER_REFERENCE_LOCAL
+    h = L.ilcc_create(-1, C.byref(p), FRAMES, POINTS)
+    assert h
+    try:
+        assert call(h, good, FRAMES) == N.BAD_ARGUMENT and b"ILCC_SOLVER_GRID" in L.ilcc_last_error(h)
+        assert last_form(h) == 0
+    finally:
+        L.ilcc_destroy(h)
