@@ -162,7 +162,8 @@ int32_t ilcc_image_sequence_cut(const uint64_t* raw_bytes, uint32_t n, uint64_t 
  * large as the largest batch, allocated once per call).
  * CONTRACT: every record's status, rows, cols and xy equal what K11 + ilcc_find_chessboard_device give for that image alone, so
  * record 0 with first = 0 equals ilcc_bag_find_chessboard.
- * Refusals, on the host: a topic with CompressedImage only (ILCC_BAD_ARGUMENT); an image of another size or encoding class
+ * Refusals, on the host: a topic with CompressedImage only (ILCC_BAD_ARGUMENT; ilcc_bag_corners_all_compressed_images of
+ * ilcc_jpeg_sequence.h takes it); an image of another size or encoding class
  * (mono / colour / Bayer pattern: the encoding itself) than the first selected one, or of another size than camera's
  * (ILCC_BAD_ARGUMENT, the text names the message); an image smaller than K10 takes (ILCC_BAD_ARGUMENT); one image above a budget
  * (ILCC_CAPACITY); per_image_out (cap records; may be NULL with cap 0) smaller than the selection (ILCC_CAPACITY with

@@ -105,7 +105,8 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
     Iterator compressed;
     if (ilcc_bag_topic_open(bag_path, topic, kCompressedImageMd5, &compressed.it) == ILCC_OK)
       return fail(ILCC_BAD_ARGUMENT, std::string("topic ") + topic +
-                                         " carries only sensor_msgs/CompressedImage: ilcc_bag_corners_all_images takes sensor_msgs/Image");
+                                         " carries only sensor_msgs/CompressedImage: ilcc_bag_corners_all_images takes sensor_msgs/Image, "
+                                         "ilcc_bag_corners_all_compressed_images (ilcc_jpeg_sequence.h) takes this topic");
     return ilcc_bag_topic_open(bag_path, topic, kImageMd5, &compressed.it);   // the first refusal, with its text
   }
   if (st != ILCC_OK) return st;

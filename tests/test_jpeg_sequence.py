@@ -1,0 +1,433 @@
+"""Camera corners from every CompressedImage of a bag, on the GPU (include/ilcc_jpeg_sequence.h): K13b against the single-image
+entry and the numpy restatement byte for byte (fixtures, constructed coefficients, seams, refusals), the decode pool against
+the restatement, and the chain bag -> fused board against ilcc_jpeg_decode_device + K11 + ilcc_find_chessboard_device message
+by message and against the restated fusion.  No tolerance anywhere; the expected value is never K13b's own."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import image_sequence_cases as K
+import image_sequence_ref as SR
+import jpeg_cases as J
+import jpeg_ref as R
+from lidar_camera_calibration_amd import _native as N
+from lidar_camera_calibration_amd import camera_image as CI
+from lidar_camera_calibration_amd import image_corners as IC
+from lidar_camera_calibration_amd import image_sequence as IS
+from lidar_camera_calibration_amd import jpeg
+from lidar_camera_calibration_amd import jpeg_sequence as JS
+from lidar_camera_calibration_amd import jpeg_write
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "lidar_camera_calibration_amd", "ilcc_image_corners")
+BOARD = (7, 5)
+FILL = 0xAB
+SIZES = ["1x1", "4x3", "7x5", "8x8", "16x16", "17x33", "31x16", "33x17", "50x35", "255x9", "257x9"]
+MODES = ["gray", "444", "422", "420"]
+COMPRESSED = ("sensor_msgs/CompressedImage", R.COMPRESSED_IMAGE_MD5)
+
+
+def _sampling(mode):
+    return None if mode == "gray" else mode
+
+
+# ---- K13b against the single entry and the restatement ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("kind", ["noise", "ramp"])
+def test_k13b_on_the_fixtures(kind, mode):
+    """q50 and q95 carry different tables, r0 and r2 the same coefficients behind another scan: five images, two table sets.
+    1x1 and 4x3 take the replicate upsamplers, 255x9 and 257x9 lie on either side of the 32-block workgroup, and with 4:2:0 the
+    chroma rows are half as many groups wide as the luma rows."""
+    for size in SIZES:
+        names = ["%s_%s_%s_%s.jpg" % (kind, size, mode, v) for v in ("q50_r0", "q50_r2", "q95_r0", "q95_r2")]
+        names.append(names[0])
+        infos = [jpeg.parse(J.data(n)) for n in names]
+        w, h = infos[0].width, infos[0].height
+        layout = jpeg.make_info(w, h, _sampling(mode))
+        assert all(i.coef_count == layout.coef_count and (i.width, i.height) == (w, h) for i in infos)
+        quants = np.stack([JS.quant_rows(i) for i in infos])
+        assert not np.array_equal(quants[0], quants[2]) and np.array_equal(quants[0], quants[4])
+        coefs = np.stack([J.restated(n)[1] for n in names])
+        got = JS.idct_batch(layout, quants, coefs).cpu().numpy()
+        for m, n in enumerate(names):
+            assert np.array_equal(got[m], J.restated(n)[2]), (n, m, "restatement")
+            assert np.array_equal(got[m], jpeg.idct(infos[m], coefs[m]).cpu().numpy()), (n, m, "single entry")
+
+
+def _constructed(w, h, mode, seed, tables):
+    """(single-entry info, restated info, [3, 64] table rows, coefficients): component c uses tables[c], each component's
+    amplitude chosen for its table so that the IDCT stays inside int32"""
+    q = np.stack([J.QUANTS[t] for t in tables])
+    info = jpeg.make_info(w, h, _sampling(mode), q)
+    rinfo = R.make_info(w, h, None if mode == "gray" else jpeg.SAMPLINGS[mode], q)
+    parts = []
+    for c, comp in enumerate(rinfo.comps):
+        info.comp[c].quant_index = c
+        comp.tq = c
+        parts.append(J.grid_coefficients(comp.blocks_w * comp.blocks_h * 64, 31 * seed + c, max(1, 1000 // int(q[c].max()))))
+    coef = np.concatenate(parts)
+    assert coef.size == info.coef_count == rinfo.coef_count
+    return info, rinfo, q, coef
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_k13b_on_constructed_coefficients(mode):
+    orders = [("ones", "255", "ramp"), ("ramp", "ones", "255"), ("255", "ramp", "ones")]      # permuted across the components
+    for bw, bh, w, h in J.GRIDS:
+        built = [_constructed(w, h, mode, seed, orders[seed]) for seed in range(3)]
+        layout = jpeg.make_info(w, h, _sampling(mode))
+        got = JS.idct_batch(layout, np.stack([b[2] for b in built]), np.stack([b[3] for b in built])).cpu().numpy()
+        for m, (info, rinfo, _, coef) in enumerate(built):
+            assert np.array_equal(got[m], R.pixels(rinfo, coef)), (w, h, m, "restatement")
+            assert np.array_equal(got[m], jpeg.idct(info, coef).cpu().numpy()), (w, h, m, "single entry")
+
+
+def test_k13b_single_coefficient_blocks_in_a_batch_of_two():
+    coef = J.single_coefficient_blocks()
+    q8 = np.full((3, 64), 8, np.uint16)
+    layout = jpeg.make_info(256 * 8, 8, None)
+    other = J.grid_coefficients(coef.size, 5, 100)
+    got = JS.idct_batch(layout, np.stack([q8, np.ones((3, 64), np.uint16)]), np.stack([coef, other])).cpu().numpy()
+    want = R.pixels(R.make_info(256 * 8, 8, None, q8[0]), coef)
+    bad = np.argwhere((got[0] != want).any(0).reshape(256, 8).any(1)).ravel()
+    assert bad.size == 0, "blocks (k + 64 * case) that differ: %s" % bad[:16]
+    assert np.array_equal(got[0], jpeg.idct(jpeg.make_info(256 * 8, 8, None, q8[0]), coef).cpu().numpy())
+    assert np.array_equal(got[1], R.pixels(R.make_info(256 * 8, 8, None, np.ones(64)), other))
+
+
+def _raw(layout, quant, coef, coef_pitch, n, dst, dst_pitch, stride, scratch, scratch_bytes):
+    import torch
+    return JS.lib().ilcc_jpeg_idct_batch_device(C.byref(layout) if layout is not None else None, C.c_void_p(quant), C.c_void_p(coef), coef_pitch, n,
+                                                C.c_void_p(dst), dst_pitch, stride, C.c_void_p(scratch), scratch_bytes,
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
+@pytest.mark.parametrize("mode,w,h", [("gray", 33, 17), ("420", 17, 33), ("422", 257, 9)])
+def test_k13b_seams(mode, w, h):
+    """Pitched coefficients with 0x7FFF in the gaps, padded rows, images back to back and apart by odd pitches (image 1 and 2 then
+    start at odd addresses and take the byte stores), base offsets 0 .. 3; not a byte outside the images' rows is written."""
+    import torch
+    n, bpp = 3, 1 if mode == "gray" else 3
+    built = [_constructed(w, h, mode, 10 + m, [("ones", "255", "ramp"), ("ramp", "ramp", "ones"), ("255", "ones", "ones")][m]) for m in range(n)]
+    want = [R.pixels(b[1], b[3]) for b in built]
+    layout = jpeg.make_info(w, h, _sampling(mode))
+    quants = np.stack([b[2] for b in built])
+    count = layout.coef_count
+    base_pitch = (count + 7) // 8 * 8
+    for coef_pitch in (base_pitch, base_pitch + 8, base_pitch + 4096):
+        coefs = np.full((n, coef_pitch), 0x7FFF, np.int16)
+        for m, b in enumerate(built):
+            coefs[m, :count] = b[3]
+        dcoefs = torch.from_numpy(coefs).cuda()
+        for stride in (bpp * w, bpp * w + 1, bpp * w + 13):
+            for pitch in (stride * h, stride * h + 1, stride * h + 257):
+                for offset in range(4):
+                    size = offset + n * pitch + 64
+                    buf = torch.full((size,), FILL, dtype=torch.uint8, device="cuda")
+                    shape, strides = ((n, h, w), (pitch, stride, 1)) if bpp == 1 else ((n, h, w, 3), (pitch, stride, 3, 1))
+                    JS.idct_batch(layout, quants, dcoefs, out=buf[offset:].as_strided(shape, strides))
+                    expect = np.full(size, FILL, np.uint8)
+                    for m in range(n):
+                        rows = expect[offset + m * pitch:offset + m * pitch + stride * h].reshape(h, stride)
+                        rows[:, :bpp * w] = want[m].reshape(h, bpp * w)
+                    assert np.array_equal(buf.cpu().numpy(), expect), (coef_pitch, stride, pitch, offset)
+    # one image is the single entry; no image is no launch
+    info, _, q, coef = built[0]
+    one = JS.idct_batch(layout, q[None], coef[None]).cpu().numpy()
+    assert np.array_equal(one[0], jpeg.idct(info, coef).cpu().numpy())
+    buf = torch.full((bpp * w * h,), FILL, dtype=torch.uint8, device="cuda")
+    scratch = torch.zeros(max(JS.batch_scratch_bytes(layout, n), 16), dtype=torch.uint8, device="cuda")
+    dq = torch.from_numpy(quants.view(np.int16)).cuda()
+    assert _raw(layout, dq.data_ptr(), dcoefs.data_ptr(), dcoefs.shape[1], 0, buf.data_ptr(), bpp * w * h, bpp * w, scratch.data_ptr(), scratch.numel()) == N.OK
+    torch.cuda.synchronize()
+    assert (buf == FILL).all()
+
+
+@pytest.mark.parametrize("mode", ["gray", "420"])
+def test_k13b_refuses_before_any_launch(mode):
+    import torch
+    w, h, n = 17, 9, 2
+    bpp = 1 if mode == "gray" else 3
+    layout = jpeg.make_info(w, h, _sampling(mode))
+    pitch = (layout.coef_count + 7) // 8 * 8
+    coef = torch.zeros((n, pitch), dtype=torch.int16, device="cuda")
+    quant = torch.ones((n, 3, 64), dtype=torch.int16, device="cuda")
+    out = torch.full((n, h, bpp * w), FILL, dtype=torch.uint8, device="cuda")
+    scratch = torch.zeros(max(JS.batch_scratch_bytes(layout, n), 16) + 16, dtype=torch.uint8, device="cuda")
+    good = dict(layout=layout, quant=quant.data_ptr(), coef=coef.data_ptr(), coef_pitch=pitch, n=n, dst=out.data_ptr(), dst_pitch=bpp * w * h,
+                stride=bpp * w, scratch=scratch.data_ptr(), scratch_bytes=JS.batch_scratch_bytes(layout, n))
+    forged = jpeg.make_info(w, h, _sampling(mode))
+    forged.comp[0].blocks_w += 1
+    moved = jpeg.make_info(w, h, _sampling(mode))
+    moved.coef_count += 64
+    calls = {
+        "null layout": dict(layout=None), "null quant": dict(quant=0), "null coef": dict(coef=0), "null dst": dict(dst=0),
+        "forged block count": dict(layout=forged), "forged coef_count": dict(layout=moved),
+        "too many images": dict(n=65536),
+        "coef_pitch short": dict(coef_pitch=layout.coef_count - 8), "coef_pitch not a multiple of 8": dict(coef_pitch=pitch + 4),
+        "misaligned coef": dict(coef=coef.data_ptr() + 2), "misaligned quant": dict(quant=quant.data_ptr() + 8),
+        "stride short": dict(stride=bpp * w - 1), "dst_pitch short": dict(dst_pitch=bpp * w * h - 1),
+    }
+    if bpp == 3:
+        calls.update({"null scratch": dict(scratch=0), "misaligned scratch": dict(scratch=scratch.data_ptr() + 8),
+                      "too little scratch": dict(scratch_bytes=good["scratch_bytes"] - 1)})
+    for what, kw in calls.items():
+        a = dict(good)
+        a.update(kw)
+        assert _raw(**a) == N.BAD_ARGUMENT, what
+        assert "ilcc_jpeg_idct_batch_device" in JS._last_error(), what
+    torch.cuda.synchronize()
+    assert (out == FILL).all()
+    assert JS.batch_scratch_bytes(forged, n) == 0
+    assert _raw(**good) == N.OK
+    torch.cuda.synchronize()
+    want = R.pixels(R.make_info(w, h, None if mode == "gray" else (2, 2), np.ones((2, 64))), np.zeros(layout.coef_count, np.int16))
+    assert all(np.array_equal(out[m].cpu().numpy().reshape(want.shape), want) for m in range(n))
+
+
+# ---- the decode pool ----------------------------------------------------------------------------------------------------------
+
+def test_entropy_decode_many_equals_the_restatement():
+    names = J.small_fixtures() + ["pointgrey1.jpg"]
+    jpgs = [J.data(n) for n in names]
+    for threads in (1, 3, 16):
+        coefs, statuses = JS.entropy_decode_many(jpgs, threads)
+        assert statuses == [N.OK] * len(names)
+        for n, c in zip(names, coefs):
+            assert np.array_equal(c, J.restated(n)[1]), (n, threads)
+
+
+def test_entropy_decode_many_reports_the_lowest_failing_job():
+    names = J.small_fixtures()[::9]
+    jpgs = [J.data(n) for n in names]
+    lower, upper = J.refusals()["four ZRL"], J.refusals()["cut inside the scan"]
+    jpgs.insert(3, lower[0])
+    jpgs.insert(11, upper[0])
+    names.insert(3, None)
+    names.insert(11, None)
+    for threads in (1, 3, 16):
+        coefs, statuses = JS.entropy_decode_many(jpgs, threads, raise_on_failure=False)
+        st, text = JS.entropy_decode_many.last
+        assert st == N.BAD_ARGUMENT and lower[2] in text and upper[2] not in text
+        assert statuses == [N.OK if n else N.BAD_ARGUMENT for n in names]
+        for n, c in zip(names, coefs):
+            if n:
+                assert np.array_equal(c, J.restated(n)[1]), (n, threads)
+    with pytest.raises(IS.ImageSequenceError) as e:
+        JS.entropy_decode_many(jpgs, 4)
+    assert e.value.status == N.BAD_ARGUMENT and lower[2] in str(e.value)
+
+
+# ---- the chain ----------------------------------------------------------------------------------------------------------------
+
+QUALITY = 95
+_jpgs, _alone_cache = {}, {}
+
+
+def chain_jpgs(mode, quality=QUALITY):
+    """the nine chain images as JPEG files by the project's writer, gray or bgr8 4:2:0; encoded once"""
+    key = (mode, quality)
+    if key not in _jpgs:
+        grays = [im for im, _ in K.chain_images()]
+        _jpgs[key] = [jpeg_write.encode(g if mode == "gray" else K.encode(g, "bgr8"), quality, "420") for g in grays]
+    return _jpgs[key]
+
+
+def messages(jpgs, fmt="jpeg"):
+    return [R.compressed_image_msg(j, fmt, seq=k, stamp=(100 + k, 7 * k)) for k, j in enumerate(jpgs)]
+
+
+def alone(jpg, camera=None, key=None):
+    """the single-image route on one file: ilcc_jpeg_decode_device + K11 + K10 + structure recovery -> (status, board, n_corners)"""
+    if key is None or key not in _alone_cache:
+        px = jpeg.decode(jpg)
+        mono = CI.to_mono8(px, "mono8" if px.dim() == 2 else "bgr8", camera)
+        n_corners = len(IC.find_corners(mono))
+        try:
+            got = (N.OK, IC.find_chessboard(mono, BOARD), n_corners)
+        except IC.BoardNotFound as e:
+            got = (e.status, None, n_corners)
+        if key is None:
+            return got
+        _alone_cache[key] = got
+    return _alone_cache[key]
+
+
+def _assert_records_equal_alone(records, jpgs, tag, camera=None, selected=None):
+    selected = selected if selected is not None else list(range(len(jpgs)))
+    assert [r.message for r in records] == selected
+    for r, k in zip(records, selected):
+        st, board, n_corners = alone(jpgs[k], camera, key=(tag, camera is not None, k))
+        assert (r.status, r.n_corners) == (st, n_corners), k
+        if st == N.OK:
+            assert (r.rows, r.cols) == board.shape[:2] and r.board().tobytes() == board.tobytes(), k
+        else:
+            assert (r.rows, r.cols, r.accepted, r.used) == (0, 0, 0, 0) and r.distance == -1
+        assert (r.stamp_sec, r.stamp_nsec, r.time_sec, r.time_nsec) == (100 + k, 7 * k, 50 + k, 0)
+
+
+def _assert_fusion_is_the_restatement(out, records, gate_px=0.0):
+    want = SR.fuse([r.board() for r in records], [r.status == N.OK for r in records], BOARD[0], BOARD[1], gate_px)
+    assert (out.status, out.n_images, out.n_ok, out.n_used, out.ref_image, out.rows, out.cols) == \
+        (want.status, want.n_images, want.n_ok, want.n_used, want.ref_image, want.rows, want.cols)
+    assert (out.gate, out.spread_rms, out.spread_max) == (want.gate, want.spread_rms, want.spread_max)
+    assert out.board().tobytes() == np.ascontiguousarray(want.xy).tobytes()
+    assert [bool(r.used) for r in records] == list(want.used) and [r.distance for r in records] == list(want.dist)
+    assert [bool(r.accepted) for r in records] == [r.status == N.OK for r in records]
+
+
+def _summary(out, records):
+    return ((out.status, out.n_images, out.n_ok, out.n_used, out.ref_image, out.rows, out.cols, out.gate, out.spread_rms, out.spread_max,
+             out.board().tobytes()), [bytes(r) for r in records])
+
+
+def _camera():
+    cam = K.chain_camera()
+    return CI.CameraModel.make(cam.fx, cam.cx, cam.fy, cam.cy, cam.d, cam.width, cam.height)
+
+
+@pytest.fixture(scope="module")
+def bags(tmp_path_factory):
+    d = tmp_path_factory.mktemp("jpeg_sequence")
+    return {mode: K.write_bag(d / ("nine_%s.bag" % mode), messages(chain_jpgs(mode)), per_chunk=4, conn=COMPRESSED) for mode in ("gray", "420")}
+
+
+@pytest.mark.parametrize("mode", ["gray", "420"])
+def test_chain_equals_the_single_route(bags, mode):
+    jpgs, bag = chain_jpgs(mode), bags[mode]
+    # the comparison must not pass on nine empty records: the single route alone finds most of the boards
+    found = [alone(j, key=(mode, False, k))[0] == N.OK for k, j in enumerate(jpgs)]
+    assert sum(found) >= 5, found
+    base = JS.bag_corners_all_compressed_images(bag, K.TOPIC, None, BOARD)
+    out, records = base
+    assert out.status == N.OK and out.n_images == 9 and out.n_batches == 1
+    _assert_records_equal_alone(records, jpgs, mode)
+    _assert_fusion_is_the_restatement(out, records)
+    assert records[0].status == N.OK
+    assert records[0].board().tobytes() == CI.bag_find_chessboard(bag, K.TOPIC, None, BOARD).tobytes()
+    # with a camera
+    cam = _camera()
+    out, records = JS.bag_corners_all_compressed_images(bag, K.TOPIC, cam, BOARD, raise_on_failure=False)
+    _assert_records_equal_alone(records, jpgs, mode, cam)
+    _assert_fusion_is_the_restatement(out, records)
+    if records[0].status == N.OK:
+        assert records[0].board().tobytes() == CI.bag_find_chessboard(bag, K.TOPIC, cam, BOARD).tobytes()
+    # selections
+    for first, stride, max_images in ((1, 2, 0), (2, 3, 2)):
+        sel = SR.select(9, first, stride, max_images)
+        out, records = JS.bag_corners_all_compressed_images(bag, K.TOPIC, None, BOARD, first=first, stride=stride, max_images=max_images,
+                                                            raise_on_failure=False)
+        assert out.n_images == len(sel)
+        _assert_records_equal_alone(records, jpgs, mode, selected=sel)
+        _assert_fusion_is_the_restatement(out, records)
+    # neither the cut nor the number of decode threads changes a byte
+    staged, device = JS.sequence_bytes(jpeg.parse(jpgs[0]))
+    seen = []
+    for staging, budget, threads in ((0, 0, 1), (5 * staged, 0, 4), (0, 5 * device, 1), (2 * staged, 0, 1), (0, 2 * device, 4)):
+        out, records = JS.bag_corners_all_compressed_images(bag, K.TOPIC, None, BOARD, staging_bytes=staging, device_bytes=budget, decode_threads=threads)
+        assert out.n_batches == len(IS.sequence_cut([staged] * 9, device, staging, budget)) - 1 == len(SR.cut([staged] * 9, device, staging, budget)) - 1
+        assert _summary(out, records) == _summary(*base), (staging, budget, threads)
+        seen.append(out.n_batches)
+    assert seen == [1, 2, 2, 5, 5]
+
+
+def test_chain_with_one_image_of_another_quality(tmp_path):
+    """message 1 was written at quality 80: its quantisation tables (and its Huffman statistics) differ from its neighbours'"""
+    jpgs = list(chain_jpgs("420")[:3])
+    jpgs[1] = chain_jpgs("420", 80)[1]
+    assert not np.array_equal(jpeg.parse(jpgs[0]).quant_array(), jpeg.parse(jpgs[1]).quant_array())
+    bag = K.write_bag(tmp_path / "mixed.bag", messages(jpgs), per_chunk=2, conn=COMPRESSED)
+    out, records = JS.bag_corners_all_compressed_images(bag, K.TOPIC, None, BOARD, raise_on_failure=False)
+    _assert_records_equal_alone(records, jpgs, "mixed")
+    _assert_fusion_is_the_restatement(out, records)
+    assert any(r.status == N.OK for r in records)
+
+
+def test_chain_refusals(tmp_path, bags):
+    def refused(path, status, *words, **kw):
+        with pytest.raises(IS.ImageSequenceError) as e:
+            JS.bag_corners_all_compressed_images(path, kw.pop("topic", K.TOPIC), kw.pop("camera", None), kw.pop("board", BOARD), **kw)
+        assert e.value.status == status, str(e.value)
+        for w in words:
+            assert w in str(e.value), str(e.value)
+
+    def bag(name, jpgs, fmts=None):
+        msgs = [R.compressed_image_msg(j, (fmts or {}).get(k, "jpeg"), seq=k, stamp=(100 + k, 7 * k)) for k, j in enumerate(jpgs)]
+        return K.write_bag(tmp_path / name, msgs, per_chunk=2, conn=COMPRESSED)
+
+    gray, colour = chain_jpgs("gray"), chain_jpgs("420")
+    staged, _ = JS.sequence_bytes(jpeg.parse(gray[0]))
+    raw = K.write_bag(tmp_path / "raw.bag", K.chain_messages()[:2])
+    refused(raw, N.BAD_ARGUMENT, "sensor_msgs/Image", "ilcc_bag_corners_all_images takes it")
+    refused(bags["gray"], N.BAD_ARGUMENT, topic="/no/such/topic")
+    refused(bag("png.bag", gray[:3], {1: "mono8; png compressed"}), N.BAD_ARGUMENT, "message 1", "png")
+    # message 2 opens the second batch; the first has run by then
+    progressive = bag("progressive.bag", gray[:2] + [J.refusals()["progressive"][0]] + gray[3:4])
+    refused(progressive, N.BAD_ARGUMENT, "message 2", "progressive", staging_bytes=2 * staged)
+    out, _ = JS.bag_corners_all_compressed_images(bags["gray"], K.TOPIC, None, BOARD, max_images=2)
+    assert out.status == N.OK                                  # the process is as good as before
+    # a scan that ends early is found by the pool, on a worker thread, while batch 0 is on the device
+    cut = gray[3][:jpeg.parse(gray[3]).scan_offset + 40]
+    refused(bag("cut.bag", gray[:3] + [cut]), N.BAD_ARGUMENT, "message 3", "ends early", staging_bytes=2 * staged, decode_threads=4)
+    refused(bag("cut0.bag", [cut] + gray[:1]), N.BAD_ARGUMENT, "message 0", "ends early")
+    out, _ = JS.bag_corners_all_compressed_images(bags["gray"], K.TOPIC, None, BOARD, max_images=2)
+    assert out.status == N.OK
+    img = K.chain_images()[0][0]
+    j422 = jpeg_write.encode(K.encode(img, "bgr8"), QUALITY, "422")
+    refused(bag("422.bag", colour[:2] + [j422]), N.BAD_ARGUMENT, "message 2", "sampling differs")
+    refused(bag("gray_after_colour.bag", colour[:1] + gray[1:2]), N.BAD_ARGUMENT, "message 1", "components differ")
+    small = jpeg_write.encode(np.ascontiguousarray(img[:300]), QUALITY)
+    refused(bag("size.bag", gray[:2] + [small]), N.BAD_ARGUMENT, "message 2", "differs from the first selected image's")
+    cam = K.chain_camera()
+    other = CI.CameraModel.make(cam.fx, cam.cx, cam.fy, cam.cy, cam.d, cam.width + 1, cam.height)
+    refused(bags["gray"], N.BAD_ARGUMENT, "camera's width / height", camera=other)
+    tiny = jpeg_write.encode(np.zeros((33, 64), np.uint8), QUALITY)
+    refused(bag("tiny.bag", [tiny]), N.BAD_ARGUMENT, "smaller than 34 px")
+    refused(bags["gray"], N.CAPACITY, "above staging_bytes or device_bytes", staging_bytes=1000)
+    refused(bags["gray"], N.CAPACITY, "above staging_bytes or device_bytes", device_bytes=1000)
+    refused(bags["gray"], N.BAD_ARGUMENT, "select no message", first=9)
+    refused(bags["gray"], N.BAD_ARGUMENT, "board", board=(2, 5))
+    # per_image_out too small: the number needed, nothing run
+    L = JS.lib()
+    sp = JS.default_params()
+    out = IS.ImageSequenceResult()
+    buf = (IS.ImageRecord * 4)()
+    args = (0, bags["gray"].encode(), K.TOPIC.encode(), None, 7, 5)
+    st = L.ilcc_bag_corners_all_compressed_images(*args, C.byref(sp), C.byref(out), buf, 4)
+    assert (st, out.status, out.n_images, out.n_batches) == (N.CAPACITY, N.CAPACITY, 9, 0) and not any(bytes(buf))
+    assert L.ilcc_bag_corners_all_compressed_images(*args, None, C.byref(out), buf, 4) == N.BAD_ARGUMENT
+    assert L.ilcc_bag_corners_all_compressed_images(*args, C.byref(sp), C.byref(out), None, 4) == N.BAD_ARGUMENT
+    # the sibling keeps its refusal of such a topic, status and words
+    with pytest.raises(IS.ImageSequenceError) as e:
+        IS.bag_corners_all_images(bags["gray"], K.TOPIC, None, BOARD)
+    assert e.value.status == N.BAD_ARGUMENT and "carries only sensor_msgs/CompressedImage" in str(e.value)
+
+
+# ---- the program ------------------------------------------------------------------------------------------------------------------
+
+def test_cli_all_images_on_a_compressed_topic(tmp_path, bags):
+    assert os.path.exists(CLI), "build() makes lidar_camera_calibration_amd/ilcc_image_corners"
+    yaml_path = tmp_path / "cam.yaml"
+    yaml_path.write_text(K.yaml_text(K.chain_camera()))
+    base = [CLI, "--bag", bags["gray"], "--topic", K.TOPIC, "--yaml", str(yaml_path)]
+    fused, report, want = tmp_path / "fused.txt", tmp_path / "report.txt", tmp_path / "want.txt"
+    r = subprocess.run(base + ["--out", str(fused), "--all-images", "--report", str(report), "--decode-threads", "2"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out, records = JS.bag_corners_all_compressed_images(bags["gray"], K.TOPIC, _camera(), BOARD)
+    IC.save_cam_corners(str(want), out.board())
+    assert fused.read_bytes() == want.read_bytes()
+    lines = report.read_text().split("\n")
+    assert lines[-1] == "" and len(lines) == 10
+    for k, rec in enumerate(records):
+        assert lines[k] == "image %d message %d stamp %d.%09d status %d accepted %d used %d distance_px %.3f" % (
+            k, rec.message, rec.stamp_sec, rec.stamp_nsec, rec.status, rec.accepted, rec.used, rec.distance if rec.distance >= 0 else -1.0)
+    assert "all images: status 0 images 9 accepted %d used %d batches 1" % (out.n_ok, out.n_used) in r.stdout
+    r = subprocess.run(base + ["--out", str(fused), "--decode-threads", "2"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "usage:" in r.stderr and "--decode-threads" in r.stderr
