@@ -1,5 +1,5 @@
 """Fixtures of the image-sequence tests: constructed boards for the fusion (each case named for what it is; the CPU tests check
-that it is that), K10b's batches of mixed content, and the nine-image bag of the chain."""
+that it is that), K10b's batches of mixed content and of hundreds of small images, and the nine-image bag of the chain."""
 import functools
 
 import numpy as np
@@ -119,6 +119,55 @@ BATCHES = {
 def seam_batch(w, h):
     """three images of w x h with different content on both sides of every seam"""
     return [_noise(w, h, 21), _squares(w, h, 22), _noise(w, h, 23)]
+
+
+# ---- K10b batches of hundreds of images ---------------------------------------------------------------------------------------------
+# k10b_offsets scans the batch's n * cpi chunk counts 256 at a time with a carry between the tiles (cpi: chunks of 256 scan blocks per
+# image), and one loop writes cand_offsets[0 .. n].  Square images of three sides give cpi 1, 2 and 3; each batch is drawn from eight
+# distinct images of its side, in a random -- so aperiodic -- order.
+MANY_SIDES = {1: 34, 2: 84, 3: 108}                     # cpi -> side; 34 is the smallest side the entry takes
+MANY_MEMBERS = ("noise_a", "noise_b", "noise_c", "noise_d", "squares_a", "squares_b", "constant_a", "constant_b")
+WITH_CANDIDATES = MANY_MEMBERS[:6]
+
+
+@functools.lru_cache(maxsize=None)
+def many_images(side):
+    return dict(noise_a=_noise(side, side, 40), noise_b=_noise(side, side, 41), noise_c=_noise(side, side, 42), noise_d=_noise(side, side, 43),
+                squares_a=_squares(side, side, 50), squares_b=_squares(side, side, 53),
+                constant_a=np.full((side, side), 77, np.uint8), constant_b=np.full((side, side), 200, np.uint8))
+
+
+def _draw(seed, names, n, with_candidates_at=()):
+    """n names in random order; at the given places (the two sides of a tile seam), images that have candidates"""
+    rng = np.random.Generator(np.random.Philox(key=seed))
+    out = [names[i] for i in rng.integers(0, len(names), n)]
+    for k in with_candidates_at:
+        out[k] = WITH_CANDIDATES[int(rng.integers(0, len(WITH_CANDIDATES)))]
+    return out
+
+
+def _constant_run():
+    """600 images: chunks 256 .. 511, the whole second tile of the scan, are constant images' (and some on both sides of it), with
+    images that have candidates before and behind the run"""
+    return _draw(5, WITH_CANDIDATES, 250) + _draw(6, MANY_MEMBERS[6:], 270) + _draw(7, WITH_CANDIDATES, 80)
+
+
+# name -> (cpi, member names)
+MANY_BATCHES = {
+    "cpi1_n256_all_with_candidates": (1, _draw(1, WITH_CANDIDATES, 256)),       # exactly one tile; cand_offsets[256] by the loop's second trip
+    "cpi1_n257": (1, _draw(2, MANY_MEMBERS, 257, (255, 256))),                              # a second tile of one chunk
+    "cpi1_n600": (1, _draw(3, MANY_MEMBERS, 600, (255, 256, 511, 512, 599))),                              # three tiles: the carry is applied twice
+    "cpi1_n600_constant_run": (1, _constant_run()),                             # a tile whose total is 0: the carry passes through it
+    "cpi1_n600_first_only": (1, ["noise_b"] + _draw(8, MANY_MEMBERS[6:], 599)),
+    "cpi1_n600_last_only": (1, _draw(9, MANY_MEMBERS[6:], 599) + ["noise_c"]),
+    "cpi3_n86": (3, _draw(4, MANY_MEMBERS, 86, (84, 85))),                                # 258 chunks: the seam lies inside image 85
+    "cpi2_n129": (2, _draw(10, MANY_MEMBERS, 129, (127, 128))),                             # 258 chunks: the seam lies between images 127 and 128
+}
+
+
+def many_batch(name):
+    cpi, names = MANY_BATCHES[name]
+    return [many_images(MANY_SIDES[cpi])[n] for n in names]
 
 
 # ---- the chain's bag ---------------------------------------------------------------------------------------------------------------

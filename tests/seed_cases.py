@@ -1,6 +1,6 @@
 """Inputs shared by tests/test_seed_cpu.py and tests/test_seed.py: the synthetic frames of the bench's configurations
-(generated once per session), clouds constructed from integer quanta for every path of K15, and the committed seeds of
-the closed-loop frames."""
+(generated once per session), clouds constructed from integer quanta for every path of K15, a batch of 600 ragged frames, a
+frame above 1024 x 256 points, and the committed seeds of the closed-loop frames."""
 import functools
 
 import numpy as np
@@ -199,6 +199,78 @@ def isolated(n_components, points_each=3):
     """n_components single-cell components three cells apart"""
     cells = np.array([[3 * k - 20, 4, -2] for k in range(n_components)])
     return cloud_of(np.repeat(cells, points_each, axis=0) * G.cq + 61)
+
+
+# ---- batches of hundreds of frames, and a frame whose lanes take a second point ----------------------------------------------------
+# The frame is blockIdx.y; k15_clear resets the 2 n_frames counters from inside its loop over slots.  600 frames whose sizes walk over
+# ragged_batch's in a random -- so aperiodic -- order, each drawn from a pool of at most eight distinct clouds of its size.
+MANY_FRAMES = 600
+MANY_SIZES = (0, 1, 63, 64, 65, 257)
+MANY_CHECKED = {0: 257, 255: 65, 256: 257, 257: 63, 599: 64}      # the frames compared word for word, and the sizes they are given
+MANY_MAX_COMPONENTS = 320                                         # above the cells a frame of 257 points can occupy
+
+
+def board_plate(k):
+    """257 points on a 0.9 m x 1.2 m rectangle, 16 x 16 and one twice: a component that passes the default gates of the finishing
+    (sides 0.9 and 1.2 sqrt(17 / 15), rms 0), normal to axis k in a place of its own"""
+    u, v = np.rint(np.linspace(0, 0.9 * 1024, 16)).astype(np.int64), np.rint(np.linspace(0, 1.2 * 1024, 16)).astype(np.int64)
+    uu, vv = np.meshgrid(u, v, indexing="ij")
+    q = np.zeros((257, 3), np.int64)
+    axes = [a for a in range(3) if a != k]
+    q[:256, axes[0]], q[:256, axes[1]] = uu.ravel(), vv.ravel()
+    return cloud_of(q + np.array([(-700, 300, -200), (400, -900, 100), (-300, -300, 500)][k]))
+
+
+def plates(n, k):
+    """the first n points of two_plates in every direction, adjacent and a cell apart, starting with direction k"""
+    steps = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, -1), (0, 1, 1), (1, 1, 1), (1, -1, 1), (-1, -1, -1)]
+    return np.concatenate([two_plates(steps[(k + i) % 9], 1 + i % 2) for i in range(9)])[:n]
+
+
+@functools.lru_cache(maxsize=None)
+def many_members(size):
+    """the pool of a frame size: random boxes, one cell, plates, and for 257 points the board-sized plates"""
+    if size == 0:
+        return [np.zeros((0, 4), np.float32)]
+    if size == 1:
+        return [random_box(1, 400 + k, -2.0, 2.0) for k in range(4)]
+    pool = [random_box(size, 200 + size, -0.6, 0.6), random_box(size, 300 + size, -3.0, -0.2), one_cell(size), plates(size, 0), plates(size, 4)]
+    if size == 257:
+        pool += [board_plate(k) for k in range(3)]
+    return pool
+
+
+def many_frames(pool=many_members, frames=MANY_FRAMES, seed=15):
+    """-> (points [total, 4], offsets [frames + 1], [(size, member of pool(size))] per frame)"""
+    rng = np.random.Generator(np.random.Philox(key=seed))
+    sizes = [MANY_CHECKED.get(f, MANY_SIZES[int(rng.integers(0, len(MANY_SIZES)))]) for f in range(frames)]
+    picks = [(s, int(rng.integers(0, len(pool(s))))) for s in sizes]
+    clouds = [pool(s)[k] for s, k in picks]
+    return np.concatenate(clouds), np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64), picks
+
+
+BIG_FRAME = 262144 + 257      # 1024 blocks of 256 lanes take 262 144 points a trip: a second trip of one full block and one point
+
+
+@functools.lru_cache(maxsize=None)
+def big_frame(n=BIG_FRAME):
+    """n points in 300 cells -- a flat sheet of 18 x 14 cells and a box of 4 x 4 x 3 beside it -- with 40 dropped points among them
+    -> (cloud, dropped)"""
+    rng = np.random.default_rng(21)
+    ij = np.stack(np.meshgrid(np.arange(18), np.arange(14), indexing="ij"), -1).reshape(-1, 2)
+    sheet = np.concatenate([ij - [9, 7], np.full((len(ij), 1), -2)], 1)
+    ijk = np.stack(np.meshgrid(np.arange(4), np.arange(4), np.arange(3), indexing="ij"), -1).reshape(-1, 3)
+    cells = np.concatenate([sheet, ijk + [12, -2, 1]])
+    assert len(cells) == 300
+    which = rng.integers(0, len(cells), n)
+    q = cells[which] * G.cq + rng.integers(0, G.cq, (n, 3))
+    flat = which < len(sheet)
+    q[flat, 2] = -2 * G.cq + 60                               # the sheet's points at one height
+    cloud = cloud_of(q)
+    dropped = rng.choice(n, 40, replace=False)
+    cloud[dropped[:20], rng.integers(0, 3, 20)] = np.float32(np.nan)
+    cloud[dropped[20:], rng.integers(0, 3, 20)] = np.float32(20.5)     # beyond the range
+    return cloud, len(dropped)
 
 
 def ragged_batch():

@@ -117,6 +117,24 @@ def isolated_plates(n_components):
     return cloud_of(np.concatenate([sheet(2, -2, (6 * k - 30, 3), (6 * k - 27, 6)) for k in range(n_components)]))
 
 
+# ---- batches of hundreds of frames (seed_cases.many_frames with plates and ells in the pool)
+
+@functools.lru_cache(maxsize=None)
+def many_members(size):
+    """seed_cases' pool of the size, and from 63 points on: that many points of the dense plate and of two ells, in random order"""
+    pool = list(K.many_members(size))
+    if size == 257:
+        pool = [pool[0], pool[2], pool[3], pool[5], pool[6]]          # a box, a cell, plates, two board-sized plates: eight with the three below
+    if size >= 63:
+        for k, cloud in enumerate((dense_plate(), ell(), ell(1, 0, (-9, -8, -7)))):
+            pool.append(cloud[np.random.default_rng(70 + k).permutation(len(cloud))[:size]])
+    return pool
+
+
+def many_frames():
+    return K.many_frames(many_members)
+
+
 # ---- scenes
 
 BOARD = synth.Board()

@@ -1,5 +1,6 @@
 """Inputs the sequence tests share: constructed corner sets for the fusion (every coordinate exactly representable, every sum
-exact), the synthetic twelve-scan sequences with two scans from a shifted board, and bags written from them."""
+exact), K0b's batches of hundreds of messages with the restated entry table and workgroup map, the synthetic twelve-scan sequences
+with two scans from a shifted board, and bags written from them."""
 import functools
 
 import numpy as np
@@ -75,6 +76,199 @@ def fusion_cases():
     sq = lattice(4, 4)
     cases.append(("square", stack([renumber(_noisy(sq, rng), 4, 4, (k + 1) % 4) for k in range(6)]), np.ones(6, np.uint8), 4, 4, G / 2))
     return cases
+
+
+# ---- K0b on hundreds of messages ------------------------------------------------------------------------------------------------
+# What a batch adds over K0 is the map workgroup -> (entry of the layout class, tile of it): find_entry's binary search, the classes'
+# places in the entry table, the table's size.  These batches give every kernel 1, 2, 3, 256 and 257 entries, and the classes the
+# tile patterns named below.  A batch is built from a pool of a few distinct messages (one per layout and point count, random
+# bytes), drawn in a random -- so aperiodic -- order; empty messages lie in between, so a message's row is never its entry index.
+F32 = W.FLOAT32
+XYZI16 = [("x", 0, F32, 1), ("y", 4, F32, 1), ("z", 8, F32, 1), ("intensity", 12, F32, 1)]
+VELO = [("x", 0, F32, 1), ("y", 4, F32, 1), ("z", 8, F32, 1), ("intensity", 16, F32, 1), ("ring", 20, W.UINT16, 1)]
+# name -> (layout class, point_step, fields, height, row_pad, alignment of data[] in the blob): the layouts of test_sequence._mixed_batch
+UNPACK_LAYOUTS = {
+    "step20": (0, 20, [("x", 0, F32, 1), ("y", 4, F32, 1), ("z", 8, F32, 1), ("intensity", 16, F32, 1)], 1, 0, 16),
+    "step80": (0, 80, [("x", 72, F32, 1), ("y", 4, F32, 1), ("z", 40, F32, 1), ("intensity", 76, F32, 1)], 1, 0, 16),
+    "odd_offsets": (0, 32, [("x", 2, F32, 1), ("y", 6, F32, 1), ("z", 10, F32, 1), ("intensity", 17, F32, 1)], 1, 0, 16),
+    "padded_rows": (0, 32, VELO, 4, 8, 16),
+    "unaligned": (0, 32, VELO, 1, 0, 4),
+    "xyzi16": (1, 16, XYZI16, 1, 0, 16),
+    "xyz16": (1, 16, XYZI16[:3], 1, 0, 16),
+    "velo": (2, 32, VELO, 1, 0, 16),
+    "velo_two_rows": (2, 32, VELO, 2, 0, 16),
+    "step48": (3, 48, [("intensity", 44, F32, 1), ("z", 0, F32, 1), ("y", 20, F32, 1), ("x", 24, F32, 1)], 1, 0, 16),
+    "step64": (4, 64, [("x", 60, F32, 1), ("y", 32, F32, 1), ("z", 4, F32, 1), ("intensity", 8, F32, 1)], 1, 0, 16),
+}
+UNPACK_CLASSES = 5
+UNPACK_ARGS_BYTES = 56         # sizeof(UnpackArgs): two pointers, a uint64, seven uint32, padded to 8
+UNPACK_COUNTS = (0, 1, 255, 256, 257, 1023, 1024, 1025, 2049, 3073)
+# the one count outside UNPACK_COUNTS: no count of that list has "hundreds of tiles".  201 tiles of the generic path (256 points each)
+UNPACK_BIG = 200 * 256 + 1
+ENTRY_COUNTS = (1, 2, 3, 256, 257)
+
+
+def tile_points(c):
+    """points per workgroup of layout class c (kUnpackThreads for the generic path, kUnpackTile for the tiled ones)"""
+    return 1024 if c else 256
+
+
+def _one_tile(c):
+    return [n for n in UNPACK_COUNTS if 0 < n <= tile_points(c)]
+
+
+def _several_tiles(c):
+    return [257, 1023, 1025] if c == 0 else [1025, 2049, 3073]
+
+
+# name -> {class: (tile pattern, entries)}.  The patterns:
+#   one_tile      every entry one tile: first_tile is the entry index
+#   several       every entry several tiles
+#   mixed         any count of UNPACK_COUNTS
+#   last_several  one-tile entries and a last one of several tiles: workgroups beyond the last first_tile
+#   big_first     a first entry of 201 tiles, then one-tile entries
+# Batches a .. e give class c the entry count ENTRY_COUNTS[(b + c) % 5]; f has no member of class 2 between populated classes 1 and 3.
+UNPACK_BATCHES = {
+    "a": {0: ("several", 1), 1: ("several", 2), 2: ("mixed", 3), 3: ("one_tile", 256), 4: ("last_several", 257)},
+    "b": {0: ("one_tile", 2), 1: ("mixed", 3), 2: ("last_several", 256), 3: ("one_tile", 257), 4: ("several", 1)},
+    "c": {0: ("mixed", 3), 1: ("one_tile", 256), 2: ("last_several", 257), 3: ("several", 1), 4: ("one_tile", 2)},
+    "d": {0: ("several", 256), 1: ("one_tile", 257), 2: ("one_tile", 1), 3: ("several", 2), 4: ("mixed", 3)},
+    "e": {0: ("big_first", 257), 1: ("several", 1), 2: ("several", 2), 3: ("mixed", 3), 4: ("one_tile", 256)},
+    "f": {0: ("big_first", 120), 1: ("last_several", 200), 3: ("several", 64), 4: ("mixed", 3)},
+}
+UNPACK_PADDED_TO_32 = "a"      # this batch is filled up with empty messages to a multiple of 32: 32 UnpackArgs are a multiple of 256 bytes
+
+
+@functools.lru_cache(maxsize=None)
+def unpack_member(layout, n):
+    """the pool's message of `layout` with n points of random bytes (every bit pattern, NaNs included)"""
+    import zlib
+    _, step, fields, height, row_pad, _ = UNPACK_LAYOUTS[layout]
+    rng = np.random.Generator(np.random.Philox(key=[zlib.crc32(layout.encode()), n]))
+    raw = rng.integers(0, 256, (n, step), dtype=np.uint8)
+    return W.pointcloud2(raw, fields, step, height=height if n else 1, row_pad=row_pad if n else 0)
+
+
+def _counts(rng, c, pattern, entries):
+    def draw(choices, k):
+        return [int(choices[i]) for i in rng.integers(0, len(choices), k)]
+
+    if pattern == "one_tile":
+        return draw(_one_tile(c), entries)
+    if pattern == "several":
+        return draw(_several_tiles(c), entries)
+    if pattern == "mixed":
+        return draw([n for n in UNPACK_COUNTS if n], entries)
+    if pattern == "last_several":
+        return draw(_one_tile(c), entries - 1) + [_several_tiles(c)[-1]]
+    assert pattern == "big_first" and c == 0
+    return [UNPACK_BIG] + draw(_one_tile(c), entries - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def unpack_batch(name):
+    """-> [(message, alignment of its data[] inside the blob)], as test_sequence.Device takes it"""
+    import zlib
+    spec = UNPACK_BATCHES[name]
+    rng = np.random.Generator(np.random.Philox(key=zlib.crc32(name.encode())))
+    counts = {c: _counts(rng, c, pattern, entries) for c, (pattern, entries) in spec.items()}
+    order = rng.permutation(np.concatenate([np.full(len(v), c) for c, v in counts.items()]))     # the classes' entries keep their own order
+    names = list(UNPACK_LAYOUTS)
+    batch, at = [], {c: 0 for c in counts}
+
+    def add(layout, n):
+        batch.append((unpack_member(layout, n), UNPACK_LAYOUTS[layout][5]))
+
+    def add_empty():
+        add(names[int(rng.integers(0, len(names)))], 0)
+
+    add_empty()
+    for c in order:
+        n = counts[int(c)][at[int(c)]]
+        at[int(c)] += 1
+        fits = [k for k, lay in UNPACK_LAYOUTS.items() if lay[0] == c and n % lay[3] == 0]
+        add(fits[int(rng.integers(0, len(fits)))], n)
+        if rng.integers(0, 4) == 0:
+            add_empty()
+    add_empty()
+    while name == UNPACK_PADDED_TO_32 and len(batch) % 32:
+        add_empty()
+    return batch
+
+
+def unpack_class(msg, align):
+    """k0_unpack.h's unpack_class restated on the message's own bytes, for data[] at an address that is `align` modulo 16"""
+    import sequence_ref as R
+    m = R.parse_pointcloud2(msg)
+    ps = m["point_step"]
+    tiled = ps % 16 == 0 and ps <= 64 and align % 16 == 0 and (m["height"] == 1 or m["row_step"] == m["width"] * ps)
+    tiled = tiled and all(o is None or o % 4 == 0 for o in m["off"])
+    return (ps // 16 if tiled else 0), m["height"] * m["width"]
+
+
+def unpack_table(batch):
+    """The entry table K0b builds for the batch, restated: per class (rows of its non-empty messages, their point counts, the first
+    tile of each, the class's tiles), and the running point count in front of every message."""
+    rows = [[] for _ in range(UNPACK_CLASSES)]
+    points = []
+    for m, (msg, align) in enumerate(batch):
+        c, n = unpack_class(msg, align)
+        points.append(n)
+        if n:
+            rows[c].append(m)
+    offsets = np.concatenate([[0], np.cumsum(points)]).astype(np.int64)
+    table = []
+    for c in range(UNPACK_CLASSES):
+        n = np.asarray([points[m] for m in rows[c]], np.int64)
+        tiles = -(-n // tile_points(c))
+        first = np.concatenate([[0], np.cumsum(tiles)[:-1]]).astype(np.int64) if len(n) else np.zeros(0, np.int64)
+        table.append((np.asarray(rows[c], np.int64), n, first, int(tiles.sum())))
+    return table, offsets
+
+
+FIND_ENTRY_RULES = ("right", "lt_for_le", "hi_is_n_minus_1", "returns_hi")
+
+
+def find_entry(first, w, rule="right"):
+    """k0b_unpack_batch.hip's find_entry for every workgroup w at once -> the entry's index, or len(first) where a wrong rule leaves
+    the table.  The wrong rules: `<` for `<=` in the comparison, hi = n - 1 at the start, and entries[hi] returned."""
+    n = len(first)
+    lo = np.zeros(len(w), np.int64)
+    hi = np.full(len(w), n - 1 if rule == "hi_is_n_minus_1" else n, np.int64)
+    while True:
+        live = hi - lo > 1
+        if not live.any():
+            break
+        mid = lo + (hi - lo) // 2
+        below = first[np.minimum(mid, n - 1)] < w if rule == "lt_for_le" else first[np.minimum(mid, n - 1)] <= w
+        lo, hi = np.where(live & below, mid, lo), np.where(live & ~below, mid, hi)
+    return hi if rule == "returns_hi" else lo
+
+
+def unpack_model(batch, want, rule="right", guard=0xCD):
+    """The bytes K0b's launches leave in an output of `guard` bytes when workgroups find their entry by `rule`; want: the numpy unpack
+    of the whole batch [points, 4] float32.  A workgroup whose tile lies outside its message writes nothing (as the kernels' bounds
+    say), and so does one whose entry lies outside the table."""
+    table, offsets = unpack_table(batch)
+    src = np.full(len(want), -1, np.int64)                  # the point of `want` that lands at each output point
+    for c, (rows, n, first, tiles) in enumerate(table):
+        if not tiles:
+            continue
+        w = np.arange(tiles, dtype=np.int64)
+        e = find_entry(first, w, rule)
+        inside = e < len(first)
+        e = np.minimum(e, len(first) - 1)
+        p0 = (w - first[e]) * tile_points(c)
+        inside &= (p0 >= 0) & (p0 < n[e])
+        for wk in np.flatnonzero(inside):
+            k = e[wk]
+            cnt = min(tile_points(c), n[k] - p0[wk])
+            at = offsets[rows[k]] + p0[wk]
+            src[at:at + cnt] = np.arange(at, at + cnt)
+    out = np.full((len(want), 16), guard, np.uint8)
+    hit = src >= 0
+    out[hit] = want.view(np.uint8).reshape(-1, 16)[src[hit]]
+    return out, src
 
 
 # ---- the synthetic sequences: fixture pose p, twelve scans with frame seeds 9000 + 50 p + s, scans 0 and 5 from the board shifted by

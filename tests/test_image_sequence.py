@@ -214,6 +214,50 @@ def test_candidate_order_equals_the_restatement():
         assert np.array_equal(cand[off[m]:off[m + 1], 1:], single(im)[1])
 
 
+# ---- hundreds of images: the tiles of k10b_offsets and its carry ----------------------------------------------------------------
+
+def _check_many(images, plan):
+    """corners, candidate offsets and the candidate list itself against the single entry, image by image"""
+    n, (h, w) = len(images), images[0].shape
+    assert_batch_equals_single(images, plan=plan)
+    assert plan.launches <= 8
+    cand, off = plan.candidates(n)
+    alone = [single(im)[1] for im in images]
+    assert list(off) == list(np.concatenate([[0], np.cumsum([len(c) for c in alone])]))
+    want = np.concatenate([np.column_stack([np.full(len(c), m), c]) for m, c in enumerate(alone)] + [np.zeros((0, 3))]).astype(np.int32)
+    assert cand.tobytes() == want.tobytes()                  # the single entry's own (scan) order, image by image
+    keys = [(m, R.block_id(u, v, h)) for m, u, v in cand]
+    assert keys == sorted(keys) and len(set(keys)) == len(keys)
+    return off
+
+
+@pytest.mark.parametrize("name", list(K.MANY_BATCHES))
+def test_hundreds_of_images_equal_the_single_entry(name):
+    """256 chunk counts to a tile of k10b_offsets: one tile exactly, a second of one chunk, three, a seam inside an image and between
+    two, a tile without a candidate.  What each batch is, tests/test_image_sequence_cpu.py holds against the restated chunk counts."""
+    cpi, names = K.MANY_BATCHES[name]
+    for member, im in K.many_images(K.MANY_SIDES[cpi]).items():
+        assert (len(single(im)[1]) > 0) == (member in K.WITH_CANDIDATES), member
+    images = K.many_batch(name)
+    with IS.CornerPlan(len(images), K.MANY_SIDES[cpi], K.MANY_SIDES[cpi]) as plan:
+        off = _check_many(images, plan)
+        assert (np.diff(off.astype(np.int64)) > 0).tolist() == [n in K.WITH_CANDIDATES for n in names]
+        assert plan.launches == 8
+
+
+def test_a_large_batch_and_then_a_smaller_one_of_smaller_images_on_one_plan():
+    """counts[], cand_offsets[] and the min / max words of 86 images of 108 x 108 (258 chunks) lie under the 40 images of 34 x 34
+    that follow them on the same plan, and under the three constant ones after those"""
+    side = K.MANY_SIDES[3]
+    with IS.CornerPlan(86, side, side) as plan:
+        _check_many(K.many_batch("cpi3_n86"), plan)
+        small = K.many_batch("cpi1_n600")[100:140]
+        _check_many(small, plan)
+        off = _check_many([K.many_images(K.MANY_SIDES[1])["constant_a"]] * 3, plan)
+        assert off[-1] == 0 and plan.launches == 7
+        _check_many(K.many_batch("cpi2_n129")[:86], plan)
+
+
 # ---- the chain ---------------------------------------------------------------------------------------------------------------------
 
 def _alone(raw, encoding, camera=None):

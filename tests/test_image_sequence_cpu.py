@@ -137,6 +137,65 @@ def test_scratch_bytes_equal_the_restatement():
     assert R.nms_blocks(160) * R.nms_blocks(128) == 1008
 
 
+# ---- the K10b batches of hundreds of images: each is what tests/test_image_sequence.py takes it for ----------------------------------
+
+def _nms_blocks(side):
+    """scan blocks of nonMaximumSuppression.m along a side: starts 9, 13, .. while the block's last pixel, start + 3, is <= side - 5"""
+    return len(range(9, side - 8 + 1, 4))
+
+
+def _cpi(side):
+    return -(-_nms_blocks(side) ** 2 // 256)
+
+
+def test_many_image_sizes_have_the_chunks_per_image_they_are_named_for():
+    assert [(s, _nms_blocks(s), _cpi(s)) for s in K.MANY_SIDES.values()] == [(34, 5, 1), (84, 17, 2), (108, 23, 3)]
+    assert all(R.nms_blocks(s) == _nms_blocks(s) for s in range(30, 200)) and _nms_blocks(36) == 5 < _nms_blocks(37)
+    assert all(K.MANY_SIDES[cpi] == side for cpi, side in ((1, 34), (2, 84), (3, 108)))
+
+
+def test_many_image_members_with_and_without_candidates():
+    """the restated likelihood and non-maximum suppression: every noise and squares image has maxima, no two of a side equally many
+    in the same blocks, and a constant image has none"""
+    import cbdetect_ref
+    for side in K.MANY_SIDES.values():
+        found = {}
+        for name, im in K.many_images(side).items():
+            assert im.shape == (side, side) and im.dtype == np.uint8
+            if name.startswith("constant"):
+                assert im.min() == im.max()            # no contrast: the likelihood is nowhere above the threshold (the GPU test holds the count 0)
+                continue
+            found[name] = cbdetect_ref.nms(cbdetect_ref.likelihood(im))[0]
+            assert len(found[name]) >= 3, (side, name)
+        assert sorted(found) == sorted(K.WITH_CANDIDATES) and len({tuple(v) for v in found.values()}) == len(found)
+
+
+def test_many_image_batches_put_the_seams_where_they_are_named():
+    def tiles(name):
+        cpi, names = K.MANY_BATCHES[name]
+        assert len(set(names)) <= len(K.MANY_MEMBERS) and K.many_batch(name)[0].shape == (K.MANY_SIDES[cpi],) * 2
+        has = np.repeat([n in K.WITH_CANDIDATES for n in names], cpi)          # per chunk: its image has candidates
+        return cpi, names, has, -(-len(has) // 256)
+
+    cpi, names, has, n_tiles = tiles("cpi1_n256_all_with_candidates")
+    assert (len(names), n_tiles) == (256, 1) and has.all()
+    cpi, names, has, n_tiles = tiles("cpi1_n257")
+    assert (len(names), n_tiles) == (257, 2) and has[255] and has[256] and not has.all()
+    cpi, names, has, n_tiles = tiles("cpi1_n600")
+    assert (len(names), n_tiles) == (600, 3) and has[[255, 256, 511, 512, 599]].all() and not has.all()
+    assert all(names[s:] != names[:-s] for s in range(1, 257))              # no period: no shift up to a tile maps the order onto itself
+    cpi, names, has, n_tiles = tiles("cpi1_n600_constant_run")
+    assert (len(names), n_tiles) == (600, 3) and not has[256:512].any() and has[:250].all() and has[520:].all()
+    cpi, names, has, n_tiles = tiles("cpi1_n600_first_only")
+    assert (len(names), n_tiles) == (600, 3) and has[0] and not has[1:].any()
+    cpi, names, has, n_tiles = tiles("cpi1_n600_last_only")
+    assert (len(names), n_tiles) == (600, 3) and has[-1] and not has[:-1].any()
+    cpi, names, has, n_tiles = tiles("cpi3_n86")
+    assert (cpi, len(has), n_tiles) == (3, 258, 2) and 256 // cpi == 85 and 256 % cpi == 1 and names[85] in K.WITH_CANDIDATES     # inside image 85
+    cpi, names, has, n_tiles = tiles("cpi2_n129")
+    assert (cpi, len(has), n_tiles) == (2, 258, 2) and 256 % cpi == 0 and has[255] and has[256]         # between images 127 and 128
+
+
 @pytest.mark.parametrize("first,stride,max_images", [(0, 1, 0), (2, 3, 0), (1, 2, 3), (10, 1, 0), (0, 0, 4)])
 def test_selection_and_cut_on_a_bag(tmp_path, first, stride, max_images):
     """The lengths the chain cuts with are the messages' own, read through the topic iterator; image 4 has padded rows, so the

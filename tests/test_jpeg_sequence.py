@@ -149,6 +149,58 @@ def test_k13b_seams(mode, w, h):
     assert (buf == FILL).all()
 
 
+MANY_TABLES = [("ones", "255", "ramp"), ("ramp", "ones", "255"), ("255", "ramp", "ones"), ("ramp", "255", "255")]
+
+
+def _many(mode, w, h, n):
+    """n images drawn in random -- so aperiodic -- order from four distinct (coefficients, table set) members
+    -> (layout, quants [n, 3, 64], coefs [n, coef_count], the restatement's pixels [n, ...], the single entry's pixels [n, ...])"""
+    built = [_constructed(w, h, mode, 40 + k, MANY_TABLES[k]) for k in range(4)]
+    restated = np.stack([R.pixels(b[1], b[3]) for b in built])
+    alone = np.stack([jpeg.idct(b[0], b[3]).cpu().numpy() for b in built])
+    assert len({r.tobytes() for r in restated}) == 4                          # a swap of two members would show
+    pick = np.random.Generator(np.random.Philox(key=n)).integers(0, 4, n)
+    return (jpeg.make_info(w, h, _sampling(mode)), np.stack([b[2] for b in built])[pick], np.stack([b[3] for b in built])[pick],
+            restated[pick], alone[pick])
+
+
+@pytest.mark.parametrize("n", [256, 257, 1000])
+@pytest.mark.parametrize("mode,w,h", [("gray", 9, 7), ("420", 17, 33)])
+def test_k13b_on_hundreds_of_images(mode, w, h, n):
+    """The image is blockIdx.z: m * coef_pitch, m * dst_pitch and (3 m + c) * 64 at m in the hundreds.  The coefficients are pitched
+    by 8 above coef_count with 0x7FFF in the gap, the images by stride * h + 1 in a buffer of FILL: odd addresses from image 1 on."""
+    import torch
+    layout, quants, coefs, restated, alone = _many(mode, w, h, n)
+    bpp = 1 if mode == "gray" else 3
+    count = layout.coef_count
+    pitched = np.full((n, (count + 7) // 8 * 8 + 8), 0x7FFF, np.int16)
+    pitched[:, :count] = coefs
+    stride = bpp * w
+    pitch = stride * h + 1
+    buf = torch.full((n * pitch + 64,), FILL, dtype=torch.uint8, device="cuda")
+    shape, strides = ((n, h, w), (pitch, stride, 1)) if bpp == 1 else ((n, h, w, 3), (pitch, stride, 3, 1))
+    JS.idct_batch(layout, quants, torch.from_numpy(pitched).cuda(), out=buf.as_strided(shape, strides))
+    got = buf.cpu().numpy()
+    for want, what in ((restated, "restatement"), (alone, "single entry")):
+        expect = np.full(n * pitch + 64, FILL, np.uint8)
+        expect[:n * pitch].reshape(n, pitch)[:, :stride * h] = want.reshape(n, stride * h)
+        bad = np.flatnonzero((got[:n * pitch].reshape(n, pitch) != expect[:n * pitch].reshape(n, pitch)).any(1))
+        assert bad.size == 0, "%s: images %s differ, or the byte behind them" % (what, bad[:8])
+        assert np.array_equal(got, expect), what                              # and the buffer outside the images' rows is still FILL
+
+
+def test_k13b_on_65535_images_the_grid_s_limit():
+    """gridDim.z at its maximum: 65535 gray images of 8 x 8, one block each, from the same four members."""
+    n = 65535
+    layout, quants, coefs, restated, alone = _many("gray", 8, 8, n)
+    assert layout.coef_count == 64 and coefs.shape == (n, 64)
+    got = JS.idct_batch(layout, quants, coefs).cpu().numpy()
+    assert got.shape == (n, 8, 8)
+    bad = np.flatnonzero((got != restated).any((1, 2)))
+    assert bad.size == 0, "images %s differ from the restatement" % bad[:8]
+    assert np.array_equal(got, alone)
+
+
 @pytest.mark.parametrize("mode", ["gray", "420"])
 def test_k13b_refuses_before_any_launch(mode):
     import torch

@@ -148,6 +148,71 @@ def test_scratch_of_0xff_and_then_dirty(est):
     check_records(est, a, sp, scratch=scratch.data_ptr())
 
 
+# ---- hundreds of frames in one batch, and a frame above 1024 x 256 points
+
+MANY_SP = K.small_params(max_components=K.MANY_MAX_COMPONENTS)
+_restated_seeds = {}
+
+
+@pytest.fixture(scope="module")
+def est_many():
+    e = LidarCornersBatch(1024, POINTS // 1024, N.default_params())      # 1024 frames of the same 2^20 points in all: R.grid(sp, POINTS) as above
+    yield e
+    e.close()
+
+
+def _assert_seeds_are_the_restatement_s(got, picks):
+    """frame by frame: no frame over capacity, the restatement's seeds in its order (computed once per distinct cloud)"""
+    assert len(got) == len(picks)
+    for f, (pick, seeds) in enumerate(zip(picks, got)):
+        if pick not in _restated_seeds:
+            recs = R.components(K.many_members(pick[0])[pick[1]], MANY_SP, R.grid(MANY_SP, POINTS))
+            _restated_seeds[pick] = [(s.key, s.n, tuple(float(v) for v in s.centroid)) for s in R.finish(recs, MANY_SP)]
+        assert seeds is not None, f
+        assert [(s.key, s.n, tuple(s.centroid_array().tolist())) for s in seeds] == _restated_seeds[pick], f
+
+
+def test_600_frames_in_one_batch(est_many):
+    points, offsets, picks = K.many_frames()
+    got = S.propose_seeds(est_many, points, offsets, native(MANY_SP))
+    _assert_seeds_are_the_restatement_s(got, picks)
+    assert sum(len(s) == 1 for s in got) >= 20 and len({s[0].key for s in got if s}) == 3        # the frames that hold a board-sized plate
+    for f, size in K.MANY_CHECKED.items():
+        frame = points[int(offsets[f]):int(offsets[f + 1])]
+        recs = check_records(est_many, points, MANY_SP, offsets, f, frame)
+        assert sum(r[1] for r in recs) == len(frame) == size
+
+
+def test_600_frames_with_scratch_of_0xff_and_then_dirty(est_many):
+    """the counters of all 600 frames are reset by k15_clear alone: a frame whose record counter kept 0xFFFFFFFF, or the count of the
+    call before, would be over capacity or hold other records"""
+    import torch
+    points, offsets, picks = K.many_frames()
+    nsp = native(MANY_SP)
+    scratch = torch.full((S.scratch_bytes(len(picks), len(points), nsp),), 0xFF, dtype=torch.uint8, device="cuda")
+    d_points = torch.from_numpy(points).cuda()
+    torch.cuda.synchronize()
+    assert scratch.data_ptr() % 256 == 0
+    for _ in range(2):                                         # 0xFF everywhere, then dirty from the calls before
+        _assert_seeds_are_the_restatement_s(S.propose_seeds_device(est_many, d_points.data_ptr(), offsets, nsp, scratch.data_ptr()), picks)
+        for f in (599, 256):
+            check_records(est_many, points, MANY_SP, offsets, f, points[int(offsets[f]):int(offsets[f + 1])], scratch=scratch.data_ptr())
+
+
+def test_a_frame_of_262144_and_257_points_beside_one_of_65(est_many):
+    """gridDim.x is capped at 1024 blocks of 256: the large frame's lanes take a second point in k15_insert and k15_moments, and
+    the last trip of k15_moments is one full block and one block of a single point, whose other lanes still exchange values"""
+    big, dropped = K.big_frame()
+    small = K.random_box(65, 165, -0.6, 0.6)
+    assert len(big) == 1024 * 256 + 257
+    points = np.concatenate([big, small])
+    offsets = np.array([0, len(big), len(big) + len(small)], np.uint64)
+    recs = check_records(est_many, points, K.small_params(), offsets, 0, big)
+    assert len(recs) == 2 and sum(r[1] for r in recs) == len(big) - dropped
+    recs = check_records(est_many, points, K.small_params(), offsets, 1, small)
+    assert sum(r[1] for r in recs) == len(small)
+
+
 def test_host_refusals_leave_the_outputs_untouched(est):
     import torch
     L = S.lib()

@@ -75,6 +75,42 @@ def test_restated_components_of_constructed_plates():
         assert [r[1] for r in near] == [50] and sorted(r[1] for r in far) == [25, 25], step
 
 
+def _assert_many_frames(points, offsets, picks, pool):
+    """the 600-frame batch is what the GPU tests take it for: ragged sizes in no periodic order, few distinct clouds"""
+    sizes = np.diff(offsets.astype(np.int64))
+    assert len(picks) == K.MANY_FRAMES == 600 and offsets[0] == 0 and offsets[-1] == len(points)
+    assert set(sizes) == set(K.MANY_SIZES) == {0, 1, 63, 64, 65, 257} and 40_000 <= len(points) <= 60_000
+    assert [int(sizes[f]) for f in K.MANY_CHECKED] == list(K.MANY_CHECKED.values()) and set(K.MANY_CHECKED) == {0, 255, 256, 257, 599}
+    assert all(sizes[s:].tolist() != sizes[:-s].tolist() for s in range(1, 300))          # no shift maps the walk onto itself
+    assert all(picks[s:] != picks[:-s] for s in range(1, 300))
+    for size in K.MANY_SIZES:
+        assert 1 <= len(pool(size)) <= 8 and all(len(c) == size and c.dtype == np.float32 for c in pool(size))
+        assert {k for s, k in picks if s == size} == set(range(len(pool(size))))             # every member is drawn
+    for f, (size, k) in enumerate(picks):
+        assert points[int(offsets[f]):int(offsets[f + 1])].tobytes() == pool(size)[k].tobytes()
+
+
+def test_many_frames_are_what_the_gpu_test_takes_them_for():
+    points, offsets, picks = K.many_frames()
+    _assert_many_frames(points, offsets, picks, K.many_members)
+    sp = K.small_params(max_components=K.MANY_MAX_COMPONENTS)
+    for k in range(3):                                          # a board-sized plate is one component and one seed, under the default gates
+        seeds = R.propose(K.board_plate(k), sp)
+        assert [(s.n, round(s.l1, 2), round(s.l2, 2)) for s in seeds] == [(257, 0.96, 1.28)] and seeds[0].rms < 1e-6
+    assert sum((size, k) in ((257, 5), (257, 6), (257, 7)) for size, k in picks) >= 20
+    assert max(len(R.components(c, sp)) for size in K.MANY_SIZES for c in K.many_members(size)) <= K.MANY_MAX_COMPONENTS
+
+
+def test_big_frame_takes_two_trips_and_few_cells():
+    cloud, dropped = K.big_frame()
+    assert len(cloud) == K.BIG_FRAME == 1024 * 256 + 257 and dropped == 40
+    keep, q = R.quantise(cloud, K.G)
+    assert keep.sum() == len(cloud) - dropped
+    assert 200 <= len(np.unique(q // K.G.cq, axis=0)) <= 300
+    recs = R.components(cloud, K.small_params())
+    assert len(recs) == 2 and sum(r[1] for r in recs) == len(cloud) - dropped
+
+
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
     """The stand-alone program: tests/seed_host_check.cpp + csrc/seed_host.cpp only, under ASan and UBSan."""

@@ -148,6 +148,67 @@ def test_scratch_of_0xff_then_dirty_and_shared_with_the_ordinary_path(est):
     assert st == N.OK and plain.tolist() == R.components(b, SP, R.grid(SP, POINTS))
 
 
+# ---- hundreds of frames in one batch, and a frame above 1024 x 256 points (the planar twins of tests/test_seed.py's)
+
+MANY_SP = K.small_params(max_components=K.K.MANY_MAX_COMPONENTS)
+_restated_seeds = {}
+
+
+@pytest.fixture(scope="module")
+def est_many():
+    e = LidarCornersBatch(1024, POINTS // 1024, N.default_params())      # 1024 frames of the same 2^20 points in all: R.grid(sp, POINTS) as above
+    yield e
+    e.close()
+
+
+def _assert_seeds_are_the_restatement_s(got, picks):
+    """frame by frame: no frame over capacity, the restatement's seeds in its order (computed once per distinct cloud)"""
+    assert len(got) == len(picks)
+    for f, (pick, seeds) in enumerate(zip(picks, got)):
+        if pick not in _restated_seeds:
+            recs = P.components(K.many_members(pick[0])[pick[1]], MANY_SP, K.PP, R.grid(MANY_SP, POINTS))
+            _restated_seeds[pick] = [(s.key, s.n, tuple(float(v) for v in s.centroid)) for s in R.finish(recs, MANY_SP)]
+        assert seeds is not None, f
+        assert [(s.key, s.n, tuple(s.centroid_array().tolist())) for s in seeds] == _restated_seeds[pick], f
+
+
+def test_600_frames_in_one_batch(est_many):
+    points, offsets, picks = K.many_frames()
+    got = S.propose_seeds_planar(est_many, points, offsets, *native(MANY_SP))
+    _assert_seeds_are_the_restatement_s(got, picks)
+    assert sum(len(s) == 1 for s in got) >= 10 and len({s[0].key for s in got if s}) == 2        # the frames that hold a board-sized plate
+    for f, size in K.K.MANY_CHECKED.items():
+        frame = points[int(offsets[f]):int(offsets[f + 1])]
+        assert len(frame) == size
+        check_records(est_many, points, MANY_SP, offsets, f, frame)
+
+
+def test_600_frames_with_scratch_of_0xff_and_then_dirty(est_many):
+    import torch
+    points, offsets, picks = K.many_frames()
+    nsp, npp = native(MANY_SP)
+    scratch = torch.full((S.planar_scratch_bytes(len(picks), len(points), nsp),), 0xFF, dtype=torch.uint8, device="cuda")
+    d_points = torch.from_numpy(points).cuda()
+    torch.cuda.synchronize()
+    assert scratch.data_ptr() % 256 == 0
+    for _ in range(2):                                         # 0xFF everywhere, then dirty from the calls before
+        _assert_seeds_are_the_restatement_s(S.propose_seeds_planar_device(est_many, d_points.data_ptr(), offsets, nsp, npp, scratch.data_ptr()), picks)
+        for f in (599, 256):
+            check_records(est_many, points, MANY_SP, offsets, f, points[int(offsets[f]):int(offsets[f + 1])], scratch=scratch.data_ptr())
+
+
+def test_a_frame_of_262144_and_257_points_beside_one_of_65(est_many):
+    """the large frame's lanes take a second point in k15_insert and k15_moments; its sheet is one core component, its box none"""
+    big, _ = K.K.big_frame()
+    small = K.many_members(65)[5]
+    assert len(big) == 1024 * 256 + 257 and len(small) == 65
+    points = np.concatenate([big, small])
+    offsets = np.array([0, len(big), len(big) + len(small)], np.uint64)
+    recs = check_records(est_many, points, SP, offsets, 0, big)
+    assert len(recs) == 1 and recs[0][1] > 200_000
+    check_records(est_many, points, SP, offsets, 1, small)
+
+
 def test_one_frame_over_capacity_leaves_the_others_intact(est):
     sp = K.small_params(cluster_min=3, max_components=8)
     over, fits, other = K.isolated_plates(9), K.isolated_plates(8), K.dense_plate()

@@ -91,6 +91,20 @@ def test_one_cell_and_empty_clouds():
     assert P.components(np.zeros((0, 4), np.float32), SP, C.PP) == []
 
 
+def test_many_frames_are_what_the_gpu_test_takes_them_for():
+    from test_seed_cpu import _assert_many_frames
+    points, offsets, picks = C.many_frames()
+    _assert_many_frames(points, offsets, picks, C.many_members)
+    sp = C.small_params(max_components=C.K.MANY_MAX_COMPONENTS)
+    seeds = {pick: [s.key for s in R.finish(P.components(C.many_members(pick[0])[pick[1]], sp, C.PP), sp)] for pick in set(picks)}
+    assert {pick for pick, s in seeds.items() if s} == {(257, 3), (257, 4)}              # the two board-sized plates: all their cells are core
+    assert sum(pick in ((257, 3), (257, 4)) for pick in picks) >= 10
+    # the large frame: its flat sheet is one component of core cells, its box of points has none
+    big, dropped = C.K.big_frame()
+    recs = P.components(big, SP, C.PP)
+    assert len(recs) == 1 and 200_000 < recs[0][1] < len(big) - dropped and P.frame_fits(len(big), C.G)
+
+
 def test_committed_scene_frames_hold_the_conditions_they_were_chosen_by(ob):
     """(c) on every committed frame; (a) and (b), which need the oracle, on the first two of each list"""
     import sys

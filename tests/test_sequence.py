@@ -83,9 +83,11 @@ class Device:
         return bool((self.host(self.out) == 0xCD).all())
 
 
-def _check_batch(batch, want_launches):
+def _check_batch(batch, want_launches, plan=None):
+    """plan: the caller's own (left open); without one, a plan of exactly the batch's size"""
     d = Device(batch)
-    plan = sequence.UnpackPlan(max(1, len(batch)))
+    own = plan is None
+    plan = sequence.UnpackPlan(max(1, len(batch))) if own else plan
     offsets = sequence.unpack_batch_device(d.d_blob.data_ptr(), d.blob_bytes, d.layouts, d.src, d.out.data_ptr(), d.cap, plan)
     assert plan.launches == want_launches
     assert list(offsets) == list(np.concatenate([[0], np.cumsum([lay.n_points for lay in d.layouts])]))
@@ -99,7 +101,8 @@ def _check_batch(batch, want_launches):
     d.out.fill_(0xCD)
     sequence.unpack_batch_device(d.d_blob.data_ptr(), d.blob_bytes, d.layouts, d.src, d.out.data_ptr(), d.cap, plan)
     assert d.host(d.out).tobytes() == got.tobytes()
-    plan.close()
+    if own:
+        plan.close()
     return d
 
 
@@ -112,6 +115,27 @@ def test_k0b_on_one_message_and_on_empty_messages():
     rng = np.random.Generator(np.random.Philox(key=7))
     _check_batch([(_msg(rng, 1500, 32, VELO), 16)], 1)
     _check_batch([(_msg(rng, 0, 32, VELO), 16), (_msg(rng, 0, 20, VELO[:4]), 16), (_msg(rng, 0, 16, XYZI16), 4)], 0)
+
+
+@pytest.mark.parametrize("name", list(K.UNPACK_BATCHES))
+def test_k0b_on_batches_of_hundreds_of_messages(name):
+    """Every kernel with 1, 2, 3, 256 and 257 entries over the batches; what each batch is, tests/test_sequence_cpu.py holds against
+    the restated entry table.  The plan is of exactly the batch's size; batch a's is a multiple of 32 messages, so its entries
+    start right behind the UnpackArgs, the others' behind padding."""
+    batch = K.unpack_batch(name)
+    d = _check_batch(batch, len(K.UNPACK_BATCHES[name]))                      # one launch per populated class
+    assert d.d_blob.data_ptr() % 16 == 0                                      # a message's layout class depends on it
+    assert d.points == K.unpack_table(batch)[1][-1]
+
+
+def test_k0b_plan_larger_than_the_batch_then_a_small_batch_on_it():
+    """Nothing of the larger table shows through the smaller one: 15 messages after 690-odd on the same plan."""
+    big = K.unpack_batch("e")
+    plan = sequence.UnpackPlan(len(big) + 37)
+    _check_batch(big, 5, plan)
+    _check_batch(_mixed_batch(), 5, plan)
+    _check_batch(K.unpack_batch("f"), 4, plan)
+    plan.close()
 
 
 def test_k0b_refusals_launch_nothing_and_leave_the_output_untouched():

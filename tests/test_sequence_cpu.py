@@ -213,6 +213,83 @@ def test_committed_oracle_corners_are_the_oracle_s(golden_dir, solver):
     assert corners.dtype == np.float32 and np.abs(corners - want_corners).max() <= 1e-6
 
 
+# ---- the K0b batches of hundreds of messages: each is what tests/test_sequence.py takes it for ------------------------------------
+
+def test_unpack_batches_have_the_entry_counts_and_tile_patterns_they_are_named_for():
+    seen = {c: set() for c in range(K.UNPACK_CLASSES)}
+    patterns = set()
+    plan_bytes = set()
+    for name, spec in K.UNPACK_BATCHES.items():
+        batch = K.unpack_batch(name)
+        table, offsets = K.unpack_table(batch)
+        points = np.diff(offsets)
+        assert 300 <= len(batch) <= 1100 and 150_000 <= offsets[-1] <= 340_000, (name, len(batch), offsets[-1])
+        assert set(points) <= set(K.UNPACK_COUNTS) | {K.UNPACK_BIG}
+        assert len({id(m) for m, _ in batch}) <= 8 * len(K.UNPACK_COUNTS)                # a pool of few distinct members
+        plan_bytes.add(len(batch) * K.UNPACK_ARGS_BYTES % 256 == 0)
+        assert points[0] == 0 and points[-1] == 0 and (points == 0).sum() >= len(batch) // 8
+        for c, (rows, n, first, tiles) in enumerate(table):
+            pattern, entries = spec.get(c, (None, 0))
+            assert len(rows) == entries, (name, c)
+            if not entries:
+                continue
+            seen[c].add(entries)
+            patterns.add(pattern)
+            tiles_of = -(-n // K.tile_points(c))
+            assert first[0] == 0 and np.array_equal(first[1:], np.cumsum(tiles_of)[:-1]) and tiles == tiles_of.sum()
+            assert (rows != np.arange(entries)).all()                                     # no message's row is its entry index
+            if entries > 3:
+                assert (np.diff(rows) > 1).any() and (points[rows[0]:rows[-1]] == 0).any()   # other classes' and empty messages in between
+            if pattern == "one_tile":
+                assert (tiles_of == 1).all() and np.array_equal(first, np.arange(entries))
+            elif pattern == "several":
+                assert (tiles_of > 1).all()
+            elif pattern == "last_several":
+                assert (tiles_of[:-1] == 1).all() and tiles_of[-1] > 1 and tiles > first[-1] + 1
+            elif pattern == "big_first":
+                assert tiles_of[0] == 201 and (tiles_of[1:] == 1).all() and first[1] == 201
+            else:
+                assert pattern == "mixed"
+        if name == "f":
+            assert [len(t[0]) > 0 for t in table] == [True, True, False, True, True]     # an absent class between two populated ones
+    for c in range(K.UNPACK_CLASSES):
+        assert seen[c] >= set(K.ENTRY_COUNTS), (c, seen[c])                               # every kernel: 1, 2, 3, 2^8 and 2^8 + 1 entries
+    assert patterns == {"one_tile", "several", "mixed", "last_several", "big_first"}
+    assert plan_bytes == {True, False}               # tables whose UnpackArgs part is and is not a multiple of 256 bytes
+    assert len(K.unpack_batch(K.UNPACK_PADDED_TO_32)) % 32 == 0
+
+
+def test_restated_layout_class_is_the_pool_s():
+    for layout, (c, step, _, height, _, align) in K.UNPACK_LAYOUTS.items():
+        n = 1024
+        assert K.unpack_class(K.unpack_member(layout, n), align) == (c, n), layout
+        assert ingest.parse_pointcloud2(K.unpack_member(layout, n)).point_step == step
+    assert K.unpack_class(K.unpack_member("velo", 1024), 4) == (0, 1024)                 # the source's alignment decides too
+    assert sorted({lay[0] for lay in K.UNPACK_LAYOUTS.values()}) == list(range(K.UNPACK_CLASSES))
+
+
+@pytest.mark.parametrize("name", list(K.UNPACK_BATCHES))
+def test_unpack_batches_tell_the_wrong_entry_searches_from_the_right_one(name):
+    """The map workgroup -> (entry, tile) as a numpy model, with find_entry's rule and with three wrong ones: on every batch each
+    wrong rule leaves other bytes in the output than the right one, which leaves the numpy unpack."""
+    batch = K.unpack_batch(name)
+    unpacked = {m: R.unpack(m) for m in dict.fromkeys(m for m, _ in batch)}              # the distinct members, once each
+    whole = np.concatenate([unpacked[m] for m, _ in batch])
+    right, src = K.unpack_model(batch, whole, "right")
+    assert right.tobytes() == whole.tobytes() and np.array_equal(src, np.arange(len(whole)))
+    for rule in K.FIND_ENTRY_RULES[1:]:
+        wrong, _ = K.unpack_model(batch, whole, rule)
+        assert wrong.tobytes() != right.tobytes(), rule
+    # ... and every class with two entries or more does so by itself
+    table, _ = K.unpack_table(batch)
+    for c, (rows, n, first, tiles) in enumerate(table):
+        w = np.arange(tiles)
+        for rule in K.FIND_ENTRY_RULES[1:]:
+            assert len(rows) < 2 or not np.array_equal(K.find_entry(first, w, rule), K.find_entry(first, w)), (c, rule)
+        if len(rows):
+            assert np.array_equal(K.find_entry(first, w), np.searchsorted(first, w, side="right") - 1)
+
+
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
     """The stand-alone program: tests/sequence_host_check.cpp + csrc/sequence_host.cpp only, under ASan and UBSan."""
