@@ -126,7 +126,8 @@ int32_t ilcc_image_parse_any(const uint8_t* msg, uint64_t msg_bytes, ilcc_image_
 
 /* K11: pixels of `encoding` in device memory (rows src_step bytes apart) -> 8-bit grayscale in device
  * memory (rows dst_stride bytes apart): cv::undistort(mono8(src), K, d, K) with a camera, mono8(src)
- * with camera == NULL.  On hip_stream (a hipStream_t, NULL = default stream); asynchronous.  Checked on
+ * with camera == NULL.  On hip_stream (a hipStream_t, NULL = default stream); asynchronous; *camera is read
+ * before the call returns (in this entry and in the two below).  Checked on
  * the host before any launch (ILCC_BAD_ARGUMENT): null pointers, width / height outside 1 .. 65536,
  * strides shorter than a row, an unknown encoding, a Bayer image below 3 x 3, a camera of another size or with fx or fy not
  * finite and non-zero, source and destination ranges that overlap (the kernel gathers). */

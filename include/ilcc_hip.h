@@ -267,7 +267,11 @@ int32_t ilcc_extract_batch_device(ilcc_handle* h, const float* d_xyzi, const uin
  * count is the host's setting.  Three streams plus the host's own need 4 queues, HIP's default; ilcc_create prints a
  * one-time note when fewer are configured.)
  * Tickets must be waited for in submission order once all slots are taken (ILCC_CAPACITY otherwise).
- * The inputs must stay valid and unchanged until the matching ilcc_wait returns. */
+ * The inputs must stay valid and unchanged until the matching ilcc_wait returns.
+ * The entry takes no stream: the batch runs on one of the handle's own three streams, which are non-blocking and wait for no
+ * stream of the caller's, the null stream included.  So d_xyzi and d_clicks must be COMPLETE in device memory when the call is
+ * made -- whatever produced them (a copy, K0b, a kernel of the caller's) has to have finished, by a host wait on its stream or
+ * event, not merely been enqueued.  offsets is copied before the call returns.  ilcc_extract_batch_device is the same. */
 int32_t ilcc_submit_batch_device(ilcc_handle* h, const float* d_xyzi, const uint64_t* offsets,
                                  uint32_t n_frames, const float* d_clicks, int32_t* ticket);
 /* The same with HOST inputs (SURVEY.md 8d counts this copy): the batch's H2D copy is enqueued on the batch's

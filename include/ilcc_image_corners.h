@@ -66,7 +66,8 @@ int32_t ilcc_image_corners_device(const void* d_image, int32_t width, int32_t he
 int32_t ilcc_chessboard_from_corners(const ilcc_image_corner* corners, int32_t n_corners, int32_t board_w,
                                      int32_t board_h, int32_t* rows, int32_t* cols, int32_t* board_index);
 
-/* Both steps: the board's 0-based (u, v) per matrix entry, row-major, in xy[rows * cols * 2]. */
+/* Both steps: the board's 0-based (u, v) per matrix entry, row-major, in xy[rows * cols * 2].  Synchronous on return like
+ * the first step; the kernels and copies of both entries run on hip_stream. */
 int32_t ilcc_find_chessboard_device(const void* d_image, int32_t width, int32_t height, int32_t stride,
                                     int32_t board_w, int32_t board_h, int32_t* rows, int32_t* cols, double* xy,
                                     void* hip_stream);

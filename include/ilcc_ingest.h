@@ -53,7 +53,8 @@ int32_t ilcc_bag_first_message(const char* bag_path, const char* topic, const ch
 int32_t ilcc_pointcloud2_parse(const uint8_t* msg, uint64_t msg_bytes, ilcc_pointcloud2_layout* out);
 
 /* K0: data[] (device pointer) -> packed float4 {x, y, z, intensity} (device pointer, height*width
- * records), on hip_stream (a hipStream_t, NULL = default stream); asynchronous. */
+ * records), on hip_stream (a hipStream_t, NULL = default stream); asynchronous.  *layout is read before the call
+ * returns (it travels in the kernel's arguments): the caller may change or free it at once. */
 int32_t ilcc_pointcloud2_unpack_device(const void* d_data, const ilcc_pointcloud2_layout* layout, void* d_xyzi,
                                        void* hip_stream);
 

@@ -108,8 +108,9 @@ int32_t ilcc_jpeg_idct_device(const ilcc_jpeg_info* info, const int16_t* d_coef,
 
 /* parse -> entropy decode -> upload -> K13 on the current device, one hipMalloc / hipFree for coefficients and scratch.
  * *width, *height and *encoding (ILCC_ENCODING_MONO8 or ILCC_ENCODING_BGR8: the file's own) are set whenever the
- * headers parse; cap_bytes < (height - 1) * dst_stride + bpp * width is ILCC_CAPACITY with nothing written.  Returns
- * after the kernels were queued on hip_stream (the coefficient buffer is freed behind them). */
+ * headers parse; cap_bytes < (height - 1) * dst_stride + bpp * width is ILCC_CAPACITY with nothing written.  The
+ * kernels run on hip_stream; the call waits for that stream before it returns (its coefficient buffer is freed on return), so
+ * `jpg` has been read and the pixels are in d_dst when it does. */
 int32_t ilcc_jpeg_decode_device(const uint8_t* jpg, uint64_t bytes, void* d_dst, int32_t dst_stride, uint64_t cap_bytes, int32_t* width,
                                 int32_t* height, int32_t* encoding, void* hip_stream);
 

@@ -39,7 +39,8 @@ extern "C" {
  *          sample planes at d_scratch + m * ilcc_jpeg_scratch_bytes(layout).
  * CONTRACT: every byte of image m equals what ilcc_jpeg_idct_device writes for (layout + image m's tables, image m's coefficients);
  * not a byte outside [row * dst_stride, row * dst_stride + bpp * width) of any image is written.  Asynchronous on hip_stream, no
- * allocation, no host wait.  n_images == 0: ILCC_OK, no launch.
+ * allocation, no host wait; *layout is read before the call returns.  d_scratch belongs to the call until its launches have run.
+ * n_images == 0: ILCC_OK, no launch.
  *
  * Launches, whatever n_images is: ONE k13b_idct for all components of all images (the image is blockIdx.z, the (component,
  * block row) pair is flattened into blockIdx.y, blockIdx.x is the 32-block group sized for the widest component), and for 3

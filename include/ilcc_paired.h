@@ -64,7 +64,8 @@ int32_t ilcc_pair_by_stamp(const uint64_t* cloud_ns, uint64_t n_clouds, const ui
  * travel through memory the plan owns (page-locked host copy, device copy, one asynchronous upload on hip_stream in front of
  * the launches).  Asynchronous on hip_stream; ilcc_colourise_plan_finish waits for the plan's last call and copies the offsets
  * out.  A plan serves one call at a time: a call first waits for the plan's previous call to have finished on the device.
- * Destroy it only after its last call has finished.
+ * Destroy it only after its last call has finished.  offsets, d_images_bgr, image_steps, image_of_scan and *cam are read
+ * before the call returns (the tables built from them are the plan's): the caller may change or free them at once.
  *
  * Refusals -- all on the host, nothing launched or copied, d_xyzrgb untouched: null pointers / more scans or points than the plan
  * holds / decreasing offsets / an image_of_scan outside its range / an image step < 3 * width / width or height <= 0 / more than

@@ -58,7 +58,8 @@ int32_t ilcc_project_intensity_device(const void* d_xyzi, uint32_t n_points, con
 
 /* rgblidar: XYZRGB cloud (input order) of the points that pass spaceToPlane, colour = the BGR pixel
  * at (int)u, (int)v of d_image_bgr (rows image_step bytes apart).  Output records are 16 bytes:
- * float x, y, z and PCL's packed rgb (uint32 r << 16 | g << 8 | b, stored in the 4th float's bits). */
+ * float x, y, z and PCL's packed rgb (uint32 r << 16 | g << 8 | b, stored in the 4th float's bits).  Synchronous on
+ * return like the entry above (*n_out is a host value); both read *cam before they launch. */
 int32_t ilcc_colourise_device(const void* d_xyzi, uint32_t n_points, const ilcc_projection* cam,
                               double distance_valid, const void* d_image_bgr, uint32_t image_step, void* d_xyzrgb,
                               uint32_t* n_out, void* hip_stream);
@@ -68,7 +69,8 @@ int32_t ilcc_colourise_device(const void* d_xyzi, uint32_t n_points, const ilcc_
  * hit k = 0 .. n_hits-1 and every stamp offset (dx, dy), bytes 0, 1, 2 of pixel (x+dx, y+dy) become (r, g, b) when that
  * pixel is inside the image; a later hit overwrites an earlier one, each stamp pixel is clipped on its own, and x, y may be
  * any int32.  d_scratch: ilcc_draw_hits_scratch_bytes(width, height) bytes of device memory, contents irrelevant on
- * entry.  stamp_xy == NULL: the reference's stamp; else n_stamp (1..64) pairs (dx, dy) of int8 in HOST memory.
+ * entry.  stamp_xy == NULL: the reference's stamp; else n_stamp (1..64) pairs (dx, dy) of int8 in HOST memory, read
+ * before the call returns.  d_scratch belongs to the call until its launches have run: two calls in flight need two.
  * Asynchronous on hip_stream; the result does not depend on thread order.  ILCC_BAD_ARGUMENT before any launch: null
  * pointers, width / height outside 1..65536, stride < 3 * width, n_stamp outside 1..64 with a stamp given,
  * n_hits > 2^32 - 2, d_hits or d_scratch not 4-byte aligned.  n_hits == 0: ILCC_OK, nothing is touched. */

@@ -50,7 +50,8 @@ void ilcc_bag_topic_close(ilcc_bag_topic* it);
  *
  * The per-message table travels through memory the plan owns (page-locked host copy, device copy, one asynchronous upload on
  * hip_stream in front of the launches).  A plan serves one call at a time: a call first waits for the plan's previous call to
- * have finished on the device.  Destroy it only after its last call has finished.
+ * have finished on the device.  Destroy it only after its last call has finished.  layouts and src_offsets are read, and
+ * offsets_out is written, before the call returns: the caller may change or free the three arrays at once.
  *
  * Refusals -- all on the host, nothing launched or copied, d_xyzi and offsets_out untouched: null pointers / more messages than the
  * plan holds / a layout whose steps or fields do not fit its data_bytes (ILCC_BAD_ARGUMENT); a big-endian message
