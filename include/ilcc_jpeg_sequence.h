@@ -66,7 +66,9 @@ int32_t ilcc_jpeg_entropy_decode_many(const uint8_t* const* jpg, const uint64_t*
 typedef struct ilcc_jpeg_sequence_params {
   ilcc_image_sequence_params seq;   /* first / stride / max_images / gate_px / staging_bytes / device_bytes, as documented there */
   uint32_t decode_threads;          /* 0: 8; above 16 is read as 16 */
-  uint32_t reserved0;
+  uint32_t reserved0;               /* the route of the Huffman decode: 0 (the default) the host pool below; 1 K16 on the device
+                                     * (ilcc_jpeg_huffman.h: the pool's threads then only prepare the scans); anything else is
+                                     * ILCC_BAD_ARGUMENT.  The records do not depend on it. */
 } ilcc_jpeg_sequence_params;
 void    ilcc_default_jpeg_sequence_params(ilcc_jpeg_sequence_params*);
 

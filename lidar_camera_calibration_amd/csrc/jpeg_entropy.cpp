@@ -8,6 +8,7 @@
 #include "ilcc_hip.h"
 #include "ilcc_jpeg.h"
 #include "jpeg_entropy.h"
+#include "jpeg_tables.h"
 
 namespace ilcc {
 
@@ -42,39 +43,9 @@ constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25,
                                  41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-constexpr int kLookBits = 9;
-
-struct Huffman {
-  bool defined = false;
-  uint8_t values[256];
-  int32_t maxcode[17];               // largest code of each length, -1: none
-  int32_t first[17];                 // index in values[] of the first code of each length, minus that code
-  uint16_t look[1 << kLookBits];     // kLookBits-bit prefix -> length << 8 | symbol, 0: longer than kLookBits
-
-  // counts[16] and the symbols behind them; false: more codes of a length than that length has
-  bool define(const uint8_t* counts, const uint8_t* symbols, int total) {
-    std::memcpy(values, symbols, (size_t)total);
-    std::memset(look, 0, sizeof(look));
-    int32_t code = 0, k = 0;
-    for (int len = 1; len <= 16; ++len) {
-      const int n = counts[len - 1];
-      first[len] = k - code;
-      if (code + n > (1 << len)) return false;
-      for (int i = 0; i < n; ++i, ++k, ++code)
-        if (len <= kLookBits)
-          for (int fill = 0; fill < (1 << (kLookBits - len)); ++fill)
-            look[(code << (kLookBits - len)) | fill] = (uint16_t)((len << 8) | values[k]);
-      maxcode[len] = n ? code - 1 : -1;
-      code <<= 1;
-    }
-    defined = true;
-    return true;
-  }
-};
-
-struct Tables {
-  Huffman dc[4], ac[4];
-};
+constexpr int kLookBits = ilcc::kJpegLookBits;
+using Huffman = ilcc::JpegHuffman;   // csrc/jpeg_tables.h: shared with csrc/jpeg_scan_prepare.cpp
+using Tables = ilcc::JpegTables;
 
 struct Reader {
   const uint8_t* m;
@@ -427,6 +398,10 @@ int32_t ilcc_jpeg_entropy_decode(const uint8_t* jpg, uint64_t bytes, const ilcc_
 }
 
 }  // extern "C"
+
+int32_t ilcc::jpeg_read_headers(const uint8_t* jpg, uint64_t bytes, ilcc_jpeg_info* info, JpegTables* tables) {
+  return read_headers(jpg, bytes, info, tables);
+}
 
 bool ilcc::jpeg_laid_out(const ilcc_jpeg_info& I) {
   ilcc_jpeg_info L = I;

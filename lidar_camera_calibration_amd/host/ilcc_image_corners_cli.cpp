@@ -5,11 +5,12 @@
 //                      [--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]
 //   ilcc_image_corners --jpg pointgrey1.jpg [--yaml pointgrey.yaml] [--board 7x5] --out pointgrey1.txt [--device N]
 //   ilcc_image_corners --bag ... --topic ... --yaml ... --out pointgrey1.txt --all-images [--first N] [--stride N] [--max-images N]
-//                      [--gate PX] [--report FILE] [--decode-threads N]
+//                      [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu]
 // --all-images reads EVERY sensor_msgs/Image of the topic (include/ilcc_image_sequence.h): the boards of the images that hold one
 // are fused into ONE board, written in the same format; --report writes one line per image.  It takes no --jpg, --jpg-out or --pgm.
 // A topic that carries no sensor_msgs/Image but sensor_msgs/CompressedImage goes through include/ilcc_jpeg_sequence.h instead
-// (the same output); --decode-threads is the number of host threads its Huffman decode runs on (0: 8, at most 16).
+// (the same output); --decode-threads is the number of host threads its Huffman decode runs on (0: 8, at most 16), and
+// --huffman gpu decodes the scans on the device instead (K16, include/ilcc_jpeg_huffman.h; the threads then only prepare them).
 // --jpg takes the image from a JPEG file instead (libcbdetect/demo_all_pic.m:8-19 on one file).  Without --yaml the file
 // is taken as already undistorted, as the reference's process_data/<camera><i>.jpg are, and the board is --board's
 // (corners along x by corners along y, 7x5 when not given); with it, both come from the yaml as for a bag.
@@ -39,7 +40,7 @@ const char* kUsage =
     "[--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]\n"
     "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n"
     "       ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt --all-images "
-    "[--first N] [--stride N] [--max-images N] [--gate PX] [--report FILE] [--decode-threads N] [--device N]\n";
+    "[--first N] [--stride N] [--max-images N] [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] [--device N]\n";
 
 // true when the topic carries no sensor_msgs/Image but sensor_msgs/CompressedImage
 bool compressed_only(const std::string& bag_path, const std::string& topic) {
@@ -55,13 +56,15 @@ bool compressed_only(const std::string& bag_path, const std::string& topic) {
 
 // --all-images: every image of the topic, the fused board into out_path
 int run_all_images(int device, const std::string& bag_path, const std::string& topic, const ilcc_camera_model& cam, int32_t board_w, int32_t board_h,
-                   const ilcc_image_sequence_params& sp, uint32_t decode_threads, const std::string& out_path, const std::string& report) {
+                   const ilcc_image_sequence_params& sp, uint32_t decode_threads, uint32_t huffman, const std::string& out_path,
+                   const std::string& report) {
   ilcc_image_sequence_result r;
   std::vector<ilcc_image_record> images(1);
   ilcc_jpeg_sequence_params jp;
   ilcc_default_jpeg_sequence_params(&jp);
   jp.seq = sp;
   jp.decode_threads = decode_threads;
+  jp.reserved0 = huffman;   // the route of the Huffman decode: 0 the host pool, 1 K16
   const bool compressed = compressed_only(bag_path, topic);
   auto run = [&](uint32_t cap) {
     return compressed ? ilcc_bag_corners_all_compressed_images(device, bag_path.c_str(), topic.c_str(), &cam, board_w, board_h, &jp, &r, images.data(), cap)
@@ -106,7 +109,7 @@ int main(int argc, char** argv) {
   std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path, jpg_out_path, report;
   int device = 0, quality = 95;
   bool all_images = false, sequence_option = false;
-  uint32_t decode_threads = 0;
+  uint32_t decode_threads = 0, huffman = 0;
   ilcc_image_sequence_params sp;
   ilcc_default_image_sequence_params(&sp);
   int32_t board_w = 7, board_h = 5;
@@ -129,7 +132,10 @@ int main(int argc, char** argv) {
     else if (a == "--gate" && i + 1 < argc) { sp.gate_px = std::atof(argv[++i]); sequence_option = true; }
     else if (a == "--report" && i + 1 < argc) { report = argv[++i]; sequence_option = true; }
     else if (a == "--decode-threads" && i + 1 < argc) { decode_threads = (uint32_t)std::strtoul(argv[++i], nullptr, 10); sequence_option = true; }
-    else {
+    else if (a == "--huffman" && i + 1 < argc && (std::string(argv[i + 1]) == "host" || std::string(argv[i + 1]) == "gpu")) {
+      huffman = std::string(argv[++i]) == "gpu" ? 1u : 0u;
+      sequence_option = true;
+    } else {
       std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
       return 2;
     }
@@ -142,7 +148,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (all_images ? (from_jpg || !jpg_out_path.empty() || !pgm_path.empty() || out_path.empty()) : sequence_option) {
-    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate, --report and --decode-threads need it\n", kUsage);
+    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate, --report, --decode-threads and --huffman need it\n", kUsage);
     return 2;
   }
   ilcc_camera_model cam{};
@@ -166,7 +172,7 @@ int main(int argc, char** argv) {
     return 2;
   }
 
-  if (all_images) return run_all_images(device, bag_path, topic, cam, board_w, board_h, sp, decode_threads, out_path, report);
+  if (all_images) return run_all_images(device, bag_path, topic, cam, board_w, board_h, sp, decode_threads, huffman, out_path, report);
 
   if (!pgm_path.empty()) {
     int32_t w = 0, h = 0;

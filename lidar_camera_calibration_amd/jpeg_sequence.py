@@ -154,10 +154,11 @@ def default_params() -> JpegSequenceParams:
 
 
 def bag_corners_all_compressed_images(bag_path, topic, camera=None, board=(7, 5), first=0, stride=1, max_images=0, gate_px=0.0, staging_bytes=0,
-                                      device_bytes=0, decode_threads=0, device=0, raise_on_failure=True):
+                                      device_bytes=0, decode_threads=0, device=0, raise_on_failure=True, huffman="host"):
     """Every selected CompressedImage of the bag's topic -> (ImageSequenceResult, [ImageRecord]).  Raises BoardNotFound when the
     fusion finds no board and ImageSequenceError on a refusal, unless raise_on_failure is False (then the result's status says
-    so; the records are complete for the two fusion statuses)."""
+    so; the records are complete for the two fusion statuses).  huffman: "host", the decode pool, or "gpu", K16 (jpeg_huffman); the
+    records are the same."""
     L = lib()
     sp = default_params()
     sp.seq.first, sp.seq.stride, sp.seq.max_images, sp.seq.gate_px = int(first), int(stride), int(max_images), float(gate_px)
@@ -166,6 +167,7 @@ def bag_corners_all_compressed_images(bag_path, topic, camera=None, board=(7, 5)
     if device_bytes:
         sp.seq.device_bytes = int(device_bytes)
     sp.decode_threads = int(decode_threads)
+    sp.reserved0 = {"host": 0, "gpu": 1}[huffman] if isinstance(huffman, str) else int(huffman)
     out = ImageSequenceResult()
     cam = C.byref(camera) if camera is not None else None
     args = (int(device), os.fsencode(bag_path), topic.encode(), cam, int(board[0]), int(board[1]), C.byref(sp), C.byref(out))
