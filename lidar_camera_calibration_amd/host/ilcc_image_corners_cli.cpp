@@ -5,12 +5,15 @@
 //                      [--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]
 //   ilcc_image_corners --jpg pointgrey1.jpg [--yaml pointgrey.yaml] [--board 7x5] --out pointgrey1.txt [--device N]
 //   ilcc_image_corners --bag ... --topic ... --yaml ... --out pointgrey1.txt --all-images [--first N] [--stride N] [--max-images N]
-//                      [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu]
+//                      [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] [--jpg-out-all PREFIX] [--quality 95]
 // --all-images reads EVERY sensor_msgs/Image of the topic (include/ilcc_image_sequence.h): the boards of the images that hold one
 // are fused into ONE board, written in the same format; --report writes one line per image.  It takes no --jpg, --jpg-out or --pgm.
 // A topic that carries no sensor_msgs/Image but sensor_msgs/CompressedImage goes through include/ilcc_jpeg_sequence.h instead
 // (the same output); --decode-threads is the number of host threads its Huffman decode runs on (0: 8, at most 16), and
 // --huffman gpu decodes the scans on the device instead (K16, include/ilcc_jpeg_huffman.h; the threads then only prepare them).
+// --jpg-out-all PREFIX (with --all-images) writes every selected image, undistorted, as PREFIX<message index, 6 digits>.jpg
+// (include/ilcc_jpeg_write_sequence.h: each file is what --jpg-out writes for that message alone); the Huffman coding runs on the
+// device (K17) unless --huffman host is given.  With it --out may be left out: the corners are then not searched.
 // --jpg takes the image from a JPEG file instead (libcbdetect/demo_all_pic.m:8-19 on one file).  Without --yaml the file
 // is taken as already undistorted, as the reference's process_data/<camera><i>.jpg are, and the board is --board's
 // (corners along x by corners along y, 7x5 when not given); with it, both come from the yaml as for a bag.
@@ -31,6 +34,7 @@
 #include "ilcc_jpeg.h"
 #include "ilcc_jpeg_sequence.h"
 #include "ilcc_jpeg_write.h"
+#include "ilcc_jpeg_write_sequence.h"
 #include "ilcc_sequence.h"
 
 namespace {
@@ -40,7 +44,8 @@ const char* kUsage =
     "[--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]\n"
     "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n"
     "       ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt --all-images "
-    "[--first N] [--stride N] [--max-images N] [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] [--device N]\n";
+    "[--first N] [--stride N] [--max-images N] [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] "
+    "[--jpg-out-all PREFIX] [--quality 95] [--device N]\n";
 
 // true when the topic carries no sensor_msgs/Image but sensor_msgs/CompressedImage
 bool compressed_only(const std::string& bag_path, const std::string& topic) {
@@ -103,12 +108,34 @@ int run_all_images(int device, const std::string& bag_path, const std::string& t
   return rc;
 }
 
+// --jpg-out-all: every selected image of the topic, undistorted, as <prefix><message index>.jpg
+int run_save_all(int device, const std::string& bag_path, const std::string& topic, const ilcc_camera_model& cam, const ilcc_image_sequence_params& sp,
+                 uint32_t route, int quality, const std::string& prefix) {
+  ilcc_jpeg_write_sequence_params wp;
+  ilcc_default_jpeg_write_sequence_params(&wp);
+  wp.first = sp.first;
+  wp.stride = sp.stride;
+  wp.max_images = sp.max_images;
+  wp.staging_bytes = sp.staging_bytes;
+  wp.device_bytes = sp.device_bytes;
+  wp.route = route;
+  ilcc_jpeg_write_sequence_result r;
+  const int32_t st = ilcc_bag_save_jpeg_all(device, bag_path.c_str(), topic.c_str(), &cam, prefix.c_str(), quality, &wp, &r, nullptr, 0);
+  if (st != ILCC_OK) {
+    std::fprintf(stderr, "can't write %s*.jpg: %s: %s\n", prefix.c_str(), ilcc_strerror(st), ilcc_last_error(nullptr));
+    return 1;
+  }
+  std::printf("all images: %d files %llu bytes batches %d host_encoded %d -> %s*.jpg\n", r.n_images, (unsigned long long)r.file_bytes, r.n_batches,
+              r.n_host_encoded, prefix.c_str());
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path, jpg_out_path, report;
+  std::string bag_path, topic, yaml_path, out_path, pgm_path, jpg_path, jpg_out_path, jpg_out_all, report;
   int device = 0, quality = 95;
-  bool all_images = false, sequence_option = false;
+  bool all_images = false, sequence_option = false, huffman_given = false;
   uint32_t decode_threads = 0, huffman = 0;
   ilcc_image_sequence_params sp;
   ilcc_default_image_sequence_params(&sp);
@@ -123,6 +150,7 @@ int main(int argc, char** argv) {
     else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
     else if (a == "--pgm" && i + 1 < argc) pgm_path = argv[++i];
     else if (a == "--jpg-out" && i + 1 < argc) jpg_out_path = argv[++i];
+    else if (a == "--jpg-out-all" && i + 1 < argc) { jpg_out_all = argv[++i]; sequence_option = true; }
     else if (a == "--quality" && i + 1 < argc) quality = std::atoi(argv[++i]);
     else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
     else if (a == "--all-images") all_images = true;
@@ -134,7 +162,7 @@ int main(int argc, char** argv) {
     else if (a == "--decode-threads" && i + 1 < argc) { decode_threads = (uint32_t)std::strtoul(argv[++i], nullptr, 10); sequence_option = true; }
     else if (a == "--huffman" && i + 1 < argc && (std::string(argv[i + 1]) == "host" || std::string(argv[i + 1]) == "gpu")) {
       huffman = std::string(argv[++i]) == "gpu" ? 1u : 0u;
-      sequence_option = true;
+      sequence_option = huffman_given = true;
     } else {
       std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
       return 2;
@@ -143,12 +171,12 @@ int main(int argc, char** argv) {
   const bool from_jpg = !jpg_path.empty();
   const bool bag_ok = !bag_path.empty() && !topic.empty() && !yaml_path.empty();
   const bool jpg_ok = bag_path.empty() && topic.empty() && pgm_path.empty() && jpg_out_path.empty();
-  if ((out_path.empty() && (from_jpg || jpg_out_path.empty())) || (from_jpg ? !jpg_ok : !bag_ok)) {
+  if ((out_path.empty() && (from_jpg || (jpg_out_path.empty() && jpg_out_all.empty()))) || (from_jpg ? !jpg_ok : !bag_ok)) {
     std::fprintf(stderr, "%s", kUsage);
     return 2;
   }
-  if (all_images ? (from_jpg || !jpg_out_path.empty() || !pgm_path.empty() || out_path.empty()) : sequence_option) {
-    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate, --report, --decode-threads and --huffman need it\n", kUsage);
+  if (all_images ? (from_jpg || !jpg_out_path.empty() || !pgm_path.empty() || (out_path.empty() && jpg_out_all.empty())) : sequence_option) {
+    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate, --report, --decode-threads and --huffman need it, and so does --jpg-out-all, with which --out may be left out\n", kUsage);
     return 2;
   }
   ilcc_camera_model cam{};
@@ -172,6 +200,10 @@ int main(int argc, char** argv) {
     return 2;
   }
 
+  if (all_images && !jpg_out_all.empty()) {   // the files are coded on the device unless --huffman host says otherwise
+    const int rc = run_save_all(device, bag_path, topic, cam, sp, huffman_given && huffman == 0 ? 1u : 0u, quality, jpg_out_all);
+    if (rc != 0 || out_path.empty()) return rc;
+  }
   if (all_images) return run_all_images(device, bag_path, topic, cam, board_w, board_h, sp, decode_threads, huffman, out_path, report);
 
   if (!pgm_path.empty()) {
