@@ -16,7 +16,8 @@
  *   cv::imshow (:87)                                                       ilcc_save_ppm_bgr; CLI ilcc_pcd2image
  *
  * Deviation, documented: the reference pairs image and cloud by ApproximateTime; this entry takes the first message of
- * each topic, like every other bag entry of this library.  Quirk, kept: Scalar(r, g, b) on a bgr8 image puts r into
+ * each topic, like every other bag entry of this library.  For every time-paired scan and image of a recording, drawn in one
+ * batch, see ilcc_overlay_sequence.h (K12b).  Quirk, kept: Scalar(r, g, b) on a bgr8 image puts r into
  * byte 0, so the reference's window shows red and blue swapped; ilcc_save_ppm_bgr writes B,G,R as R,G,B, so the file
  * shows what that window showed.
  *

@@ -20,7 +20,7 @@
 #include "host_util.h"
 #include "ilcc_internal.h"
 #include "ilcc_project.h"
-#include "k8_space_to_plane.h"   // space_to_plane, kProjThreads, kProjChunk: shared with K8b
+#include "k8_space_to_plane.h"   // space_to_plane, kProjThreads, kProjChunk: shared with K8b; intensity_rgb: shared with K12b
 
 namespace ilcc {
 
@@ -36,30 +36,6 @@ struct ProjArgs {
   void* out;
   uint32_t* total;
 };
-
-// float -> unsigned char the way an x86-64 build converts (cvttss2si, low byte)
-__device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)(int32_t)v; }
-// double -> int as cvttsd2si: NaN / out of range give INT_MIN ("integer indefinite"), not saturation
-__device__ __forceinline__ int32_t x86_d2i(double v) {
-  return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : (int32_t)0x80000000;
-}
-
-// HSVtoRGB (:373-428) with s = v = 100
-__device__ __forceinline__ void hsv_to_rgb(int32_t h, int32_t s, int32_t v, uint8_t& r, uint8_t& g, uint8_t& b) {
-  const float rgb_max = v * 2.55f;
-  const float rgb_min = rgb_max * (100 - s) / 100.0f;
-  const int32_t i = h / 60;
-  const int32_t difs = h % 60;
-  const float adj = (rgb_max - rgb_min) * difs / 60.0f;
-  switch (i) {
-    case 0: r = to_u8(rgb_max); g = to_u8(rgb_min + adj); b = to_u8(rgb_min); break;
-    case 1: r = to_u8(rgb_max - adj); g = to_u8(rgb_max); b = to_u8(rgb_min); break;
-    case 2: r = to_u8(rgb_min); g = to_u8(rgb_max); b = to_u8(rgb_min + adj); break;
-    case 3: r = to_u8(rgb_min); g = to_u8(rgb_max - adj); b = to_u8(rgb_max); break;
-    case 4: r = to_u8(rgb_min + adj); g = to_u8(rgb_min); b = to_u8(rgb_max); break;
-    default: r = to_u8(rgb_max); g = to_u8(rgb_min); b = to_u8(rgb_max - adj); break;
-  }
-}
 
 __global__ __launch_bounds__(kProjThreads) void k8_count(ProjArgs a) {
   const uint32_t beg = blockIdx.x * kProjChunk;
@@ -112,13 +88,10 @@ __global__ __launch_bounds__(kProjThreads) void k8_scatter(ProjArgs a) {
         const uint32_t rgb = sample_bgr_as_rgb(a.image, a.image_step, px, py);
         reinterpret_cast<float4*>(a.out)[running + rank] = make_float4(q.x, q.y, q.z, __uint_as_float(rgb));
       } else {
-        const double h = ((double)q.w - a.lo) / (a.hi - a.lo) * 255;   // pcd2image.cpp:71
-        uint8_t r, g, b;
-        hsv_to_rgb(x86_d2i(h), 100, 100, r, g, b);
         uint4 rec;
         rec.x = (uint32_t)px;
         rec.y = (uint32_t)py;
-        rec.z = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+        rec.z = intensity_rgb(q.w, a.lo, a.hi);
         rec.w = i;
         reinterpret_cast<uint4*>(a.out)[running + rank] = rec;
       }
