@@ -1,6 +1,8 @@
 // What the host chains (bag -> parser -> one hipMalloc -> kernels -> result) share: the last-error text behind a status,
 // the 256-byte alignment of the parts of a device buffer, a device buffer freed on scope exit, the device check, the first
-// message of a bag topic in a vector, and the std_msgs/Header every ROS message starts with.  Internal, not installed.
+// message of a bag topic in a vector, and the std_msgs/Header every ROS message starts with; and what the chains over every
+// message of a topic share: the scope guards, the md5 sums of the two image types, message i in a vector, the first / stride / max
+// selection and the image-topic open with its CompressedImage refusal.  Internal, not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +14,7 @@
 
 #include "ilcc_hip.h"
 #include "ilcc_ingest.h"
+#include "ilcc_sequence.h"   // the topic iterator
 
 namespace ilcc {
 
@@ -54,6 +57,65 @@ inline int32_t read_first_message(const char* bag_path, const char* topic, const
     return fail(ILCC_IO_ERROR, "out of memory for the bag's message");
   }
   return ilcc_bag_first_message(bag_path, topic, md5, msg->data(), bytes, &bytes);
+}
+
+// ---- what the chains over every message of a topic share (the six *_api.cpp chain files)
+
+constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";             // sensor_msgs/Image
+constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";   // sensor_msgs/CompressedImage
+
+inline uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
+inline uint64_t stamp_ns(uint32_t sec, uint32_t nsec) { return (uint64_t)sec * 1000000000ull + nsec; }
+
+struct Iterator {
+  ilcc_bag_topic* it = nullptr;
+  ~Iterator() { ilcc_bag_topic_close(it); }
+};
+struct Stream {
+  hipStream_t s = nullptr;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+struct Pinned {
+  uint8_t* p = nullptr;
+  ~Pinned() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+// whatever made the call end, the stream's work must have finished before the buffers it uses go away: declared behind them
+struct InFlight {
+  hipStream_t s = nullptr;
+  ~InFlight() {
+    if (s) (void)hipStreamSynchronize(s);
+  }
+};
+
+// the message `i` of the topic in `msg` (never empty, so that data() is an address), its length in *bytes
+inline int32_t read_message(ilcc_bag_topic* it, uint64_t i, std::vector<uint8_t>* msg, uint64_t* bytes) {
+  const int32_t st = ilcc_bag_topic_read(it, i, nullptr, 0, bytes);
+  if (st != ILCC_OK && st != ILCC_CAPACITY) return st;
+  msg->resize(*bytes ? *bytes : 1);
+  return ilcc_bag_topic_read(it, i, msg->data(), *bytes, bytes);
+}
+
+// the message indices first, first + stride, ... of the topic, at most max of them (0: all); max_word names max in the refusal
+inline int32_t select_messages(ilcc_bag_topic* it, uint64_t first, uint64_t stride, uint64_t max, const char* max_word, std::vector<uint64_t>* selected) {
+  const uint64_t count = ilcc_bag_topic_count(it);
+  for (uint64_t i = first; i < count && (max == 0 || selected->size() < max); i += stride ? stride : 1) selected->push_back(i);
+  if (selected->empty()) return fail(ILCC_BAD_ARGUMENT, std::string("first / stride / ") + max_word + " select no message of the topic");
+  return ILCC_OK;
+}
+
+// opens the topic's sensor_msgs/Image messages; a topic that carries only the compressed type is refused in `entry`'s name, with
+// `hint` (a sentence that starts with ", ", or "") behind it
+inline int32_t open_image_topic(const char* bag_path, const char* topic, const char* entry, const char* hint, ilcc_bag_topic** it) {
+  const int32_t st = ilcc_bag_topic_open(bag_path, topic, kImageMd5, it);
+  if (st != ILCC_BAD_ARGUMENT) return st;
+  Iterator compressed;   // no sensor_msgs/Image there: say so when the topic carries the compressed type instead
+  if (ilcc_bag_topic_open(bag_path, topic, kCompressedImageMd5, &compressed.it) == ILCC_OK)
+    return fail(ILCC_BAD_ARGUMENT, std::string("topic ") + topic + " carries only sensor_msgs/CompressedImage: " + entry + " takes sensor_msgs/Image" + hint);
+  return ilcc_bag_topic_open(bag_path, topic, kImageMd5, &compressed.it);   // the first refusal, with its text
 }
 
 inline bool read_u32(const uint8_t* m, uint64_t n, uint64_t* at, uint32_t* v) {

@@ -3,7 +3,8 @@
 // (bag_reader.cpp), the Image parser and K11 (camera_image_host.cpp, k11_camera_image.hip), K10b (k10b_image_corners_batch.hip),
 // ilcc_chessboard_from_corners (image_corners_host.cpp), the cut and the fusion (image_sequence_host.cpp).  This file owns the
 // batching: the two sets of buffers, and the order of the calls that lets a host thread recover batch k's boards while the
-// device works on batch k + 1.  Failures below are reported through ilcc_last_error(NULL).
+// device works on batch k + 1.  The guards, the selection, "message i in a vector" and the image-topic open are host_util.h's.
+// Failures below are reported through ilcc_last_error(NULL).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,21 +23,8 @@ using namespace ilcc;
 
 namespace {
 
-constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
-constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 constexpr uint64_t kDefaultStagingBytes = 256ull << 20, kDefaultDeviceBytes = 512ull << 20;
 constexpr int32_t kFirstCapacity = 1024;   // corners per image; a batch with a fuller image runs again with room for it
-
-struct Iterator {
-  ilcc_bag_topic* it = nullptr;
-  ~Iterator() { ilcc_bag_topic_close(it); }
-};
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
 
 // one of the two sets of buffers
 struct BatchBuffers {
@@ -100,20 +88,11 @@ void recover(const BatchBuffers* B, int32_t board_w, int32_t board_h, ilcc_image
 int32_t all_images(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera, int32_t board_w, int32_t board_h,
                    const ilcc_image_sequence_params& sp, ilcc_image_sequence_result* out, ilcc_image_record* per_image_out, uint32_t cap) {
   Iterator iter;
-  int32_t st = ilcc_bag_topic_open(bag_path, topic, kImageMd5, &iter.it);
-  if (st == ILCC_BAD_ARGUMENT) {   // no sensor_msgs/Image there: say so when the topic carries the compressed type instead
-    Iterator compressed;
-    if (ilcc_bag_topic_open(bag_path, topic, kCompressedImageMd5, &compressed.it) == ILCC_OK)
-      return fail(ILCC_BAD_ARGUMENT, std::string("topic ") + topic +
-                                         " carries only sensor_msgs/CompressedImage: ilcc_bag_corners_all_images takes sensor_msgs/Image, "
-                                         "ilcc_bag_corners_all_compressed_images (ilcc_jpeg_sequence.h) takes this topic");
-    return ilcc_bag_topic_open(bag_path, topic, kImageMd5, &compressed.it);   // the first refusal, with its text
-  }
+  int32_t st = open_image_topic(bag_path, topic, "ilcc_bag_corners_all_images", ", ilcc_bag_corners_all_compressed_images (ilcc_jpeg_sequence.h) takes this topic",
+                                &iter.it);
   if (st != ILCC_OK) return st;
   std::vector<uint64_t> selected;
-  const uint64_t count = ilcc_bag_topic_count(iter.it), stride = sp.stride ? sp.stride : 1;
-  for (uint64_t i = sp.first; i < count && (sp.max_images == 0 || selected.size() < sp.max_images); i += stride) selected.push_back(i);
-  if (selected.empty()) return fail(ILCC_BAD_ARGUMENT, "first / stride / max_images select no message of the topic");
+  if ((st = select_messages(iter.it, sp.first, sp.stride, sp.max_images, "max_images", &selected)) != ILCC_OK) return st;
   const uint32_t n_sel = (uint32_t)selected.size();
   out->n_images = (int32_t)n_sel;
   if (cap < n_sel && (per_image_out || cap)) return fail(ILCC_CAPACITY, "per_image_out holds fewer records than images were selected");
@@ -122,10 +101,8 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   std::vector<uint8_t> msg;
   auto read = [&](uint32_t k, ilcc_image_layout* L) -> int32_t {
     uint64_t bytes = 0;
-    int32_t s = ilcc_bag_topic_read(iter.it, selected[k], nullptr, 0, &bytes);
-    if (s != ILCC_OK && s != ILCC_CAPACITY) return s;
-    msg.resize(bytes ? bytes : 1);
-    if ((s = ilcc_bag_topic_read(iter.it, selected[k], msg.data(), bytes, &bytes)) != ILCC_OK) return s;
+    int32_t s = read_message(iter.it, selected[k], &msg, &bytes);
+    if (s != ILCC_OK) return s;
     if ((s = ilcc_image_parse_any(msg.data(), bytes, L)) != ILCC_OK) return fail(s, message_name(selected[k]) + ": " + ilcc_last_error(nullptr));
     return ILCC_OK;
   };

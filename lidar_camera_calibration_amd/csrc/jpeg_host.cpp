@@ -21,8 +21,6 @@ using namespace ilcc;
 
 namespace {
 
-constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
-constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 
 // the refusals of jpeg_entropy.cpp, which knows nothing of the library, arrive in ilcc_last_error
 const bool g_sink_set = (jpeg_error_sink = [](const char* text) { set_global_error(text); }, true);

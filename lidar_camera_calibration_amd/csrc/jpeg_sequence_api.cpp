@@ -5,7 +5,8 @@
 // (k10b_image_corners_batch.hip), ilcc_chessboard_from_corners (image_corners_host.cpp), the cut and the fusion
 // (image_sequence_host.cpp).  This file owns the batching, as image_sequence_api.cpp does for raw images: the two sets of
 // buffers, and the order of the calls that lets the pool decode batch k + 1 and a host thread recover batch k - 1's boards
-// while the device works on batch k.  Failures below are reported through ilcc_last_error(NULL).
+// while the device works on batch k.  The guards, the selection and "message i in a vector" are host_util.h's.  Failures below
+// are reported through ilcc_last_error(NULL).
 // With sp->reserved0 == 1 the Huffman decode is K16's (k16_jpeg_huffman.hip): the pool's threads only run ilcc_jpeg_scan_prepare
 // (jpeg_scan_prepare.cpp) into the blob, which then holds files' scans instead of coefficients.
 #include <hip/hip_runtime.h>
@@ -29,21 +30,8 @@ using namespace ilcc;
 
 namespace {
 
-constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
-constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 constexpr int32_t kFirstCapacity = 1024;   // corners per image; a batch with a fuller image runs again with room for it
 constexpr uint64_t kQuantBytes = 3 * 64 * sizeof(uint16_t);   // an image's table rows
-
-struct Iterator {
-  ilcc_bag_topic* it = nullptr;
-  ~Iterator() { ilcc_bag_topic_close(it); }
-};
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
 
 // what one image takes, in bytes; every part a multiple of 256
 struct Sizes {
@@ -239,9 +227,7 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   }
   if (st != ILCC_OK) return st;
   std::vector<uint64_t> selected;
-  const uint64_t count = ilcc_bag_topic_count(iter.it), stride = sp.stride ? sp.stride : 1;
-  for (uint64_t i = sp.first; i < count && (sp.max_images == 0 || selected.size() < sp.max_images); i += stride) selected.push_back(i);
-  if (selected.empty()) return fail(ILCC_BAD_ARGUMENT, "first / stride / max_images select no message of the topic");
+  if ((st = select_messages(iter.it, sp.first, sp.stride, sp.max_images, "max_images", &selected)) != ILCC_OK) return st;
   const uint32_t n_sel = (uint32_t)selected.size();
   out->n_images = (int32_t)n_sel;
   if (cap < n_sel && (per_image_out || cap)) return fail(ILCC_CAPACITY, "per_image_out holds fewer records than images were selected");
@@ -249,10 +235,8 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   // message k of the selection and its two headers
   auto read = [&](uint32_t k, std::vector<uint8_t>* msg, ilcc_compressed_image_layout* L, ilcc_jpeg_info* I) -> int32_t {
     uint64_t bytes = 0;
-    int32_t s = ilcc_bag_topic_read(iter.it, selected[k], nullptr, 0, &bytes);
-    if (s != ILCC_OK && s != ILCC_CAPACITY) return s;
-    msg->resize(bytes ? bytes : 1);
-    if ((s = ilcc_bag_topic_read(iter.it, selected[k], msg->data(), bytes, &bytes)) != ILCC_OK) return s;
+    int32_t s = read_message(iter.it, selected[k], msg, &bytes);
+    if (s != ILCC_OK) return s;
     if ((s = ilcc_compressed_image_parse(msg->data(), bytes, L)) != ILCC_OK) return fail(s, message_name(selected[k]) + ": " + ilcc_last_error(nullptr));
     if ((s = ilcc_jpeg_parse(msg->data() + L->data_offset, L->data_bytes, I)) != ILCC_OK)
       return fail(s, message_name(selected[k]) + ": " + ilcc_last_error(nullptr));
@@ -262,11 +246,9 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   // message k of the selection, whose size is known to be at least `expect` bytes, without parsing anything
   auto read_bytes = [&](uint32_t k, std::vector<uint8_t>* msg, uint64_t expect) -> int32_t {
     uint64_t bytes = 0;
-    int32_t s = ilcc_bag_topic_read(iter.it, selected[k], nullptr, 0, &bytes);
-    if (s != ILCC_OK && s != ILCC_CAPACITY) return s;
-    if (bytes < expect) return fail(ILCC_IO_ERROR, message_name(selected[k]) + ": the message changed while the bag was read");
-    msg->resize(bytes ? bytes : 1);
-    return ilcc_bag_topic_read(iter.it, selected[k], msg->data(), bytes, &bytes);
+    const int32_t s = read_message(iter.it, selected[k], msg, &bytes);
+    if (s != ILCC_OK) return s;
+    return bytes < expect ? fail(ILCC_IO_ERROR, message_name(selected[k]) + ": the message changed while the bag was read") : ILCC_OK;
   };
 
   // the first selected image decides size, component count and sampling

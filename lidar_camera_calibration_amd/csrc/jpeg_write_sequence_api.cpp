@@ -2,10 +2,11 @@
 // through K11, K14b and K17 into one .jpg each.  The layers below do the work: the topic iterator (bag_reader.cpp), the message and
 // JPEG header parsers (camera_image_host.cpp, jpeg_host.cpp, jpeg_entropy.cpp), for a CompressedImage topic the host decode pool and
 // K13b (jpeg_decode_pool.cpp, k13b_jpeg_batch.hip), K11 (k11_camera_image.hip), K14b (k14b_jpeg_write_batch.hip), K17
-// (k17_jpeg_huffman_enc.hip), the headers and the host encoder (jpeg_entropy_enc.cpp), the cut (image_sequence_host.cpp).  This
-// file owns the batching: one set of buffers sized by the largest batch, one stream, and per batch one H2D copy of the staged
-// messages, the launches, the rows back, and ONE copy of the scans that were produced.  Failures below are reported through
-// ilcc_last_error(NULL).
+// (k17_jpeg_huffman_enc.hip), the cut (image_sequence_host.cpp), and "rows and scans of a batch -> each image's file" with the
+// headers and the host encoder (jpeg_finish.h, jpeg_entropy_enc.cpp).  This file owns the batching: one set of buffers sized by
+// the largest batch, one stream, and per batch one H2D copy of the staged messages, the launches, the rows back, and ONE copy of
+// the scans that were produced.  The guards, the selection and "message i in a vector" are host_util.h's.  Failures below are
+// reported through ilcc_last_error(NULL).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,35 +22,13 @@
 #include "ilcc_jpeg_write_sequence.h"
 #include "ilcc_sequence.h"
 #include "jpeg_entropy.h"
+#include "jpeg_finish.h"
 
 using namespace ilcc;
 
 namespace {
 
-constexpr const char* kImageMd5 = "060021388200f6f0f447d0fcd9c64743";
-constexpr const char* kCompressedImageMd5 = "8f7a12909da2c9d3332d540a0977563f";
 constexpr uint64_t kQuantBytes = 3 * 64 * sizeof(uint16_t);   // a decoded image's table rows
-constexpr uint64_t kHeaderRoom = 1024;                        // above the 629 bytes the headers can take
-
-struct Iterator {
-  ilcc_bag_topic* it = nullptr;
-  ~Iterator() { ilcc_bag_topic_close(it); }
-};
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-struct Pinned {
-  uint8_t* p = nullptr;
-  ~Pinned() {
-    if (p) (void)hipHostFree(p);
-  }
-};
-
-uint64_t up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
-
 std::string message_name(uint64_t message) { return "message " + std::to_string(message); }
 
 // what one written image takes on the device, every part a multiple of 256
@@ -60,9 +39,9 @@ struct Sizes {
 bool sizes_of(const ilcc_jpeg_info& I, uint64_t out_per_image, Sizes* S) {
   S->mono = align256((uint64_t)I.width * (uint64_t)I.height);
   S->coef = align256(I.coef_count * sizeof(int16_t));
-  S->out = align256(up16(out_per_image));
+  S->out = align256(align16(out_per_image));
   S->rows = 256;
-  S->scratch = ilcc_jpeg_huffman_encode_scratch_bytes(&I, 1, up16(out_per_image));
+  S->scratch = ilcc_jpeg_huffman_encode_scratch_bytes(&I, 1, align16(out_per_image));
   S->device = S->mono + S->coef + S->out + S->rows + S->scratch;
   return S->scratch != 0;
 }
@@ -88,9 +67,7 @@ int32_t save_all(int32_t device, const char* bag_path, const char* topic, const 
   }
   if (st != ILCC_OK) return st;
   std::vector<uint64_t> selected;
-  const uint64_t count = ilcc_bag_topic_count(iter.it), stride = sp.stride ? sp.stride : 1;
-  for (uint64_t i = sp.first; i < count && (sp.max_images == 0 || selected.size() < sp.max_images); i += stride) selected.push_back(i);
-  if (selected.empty()) return fail(ILCC_BAD_ARGUMENT, "first / stride / max_images select no message of the topic");
+  if ((st = select_messages(iter.it, sp.first, sp.stride, sp.max_images, "max_images", &selected)) != ILCC_OK) return st;
   const uint32_t n_sel = (uint32_t)selected.size();
   out->n_images = (int32_t)n_sel;
   if (cap < n_sel && (records_out || cap)) return fail(ILCC_CAPACITY, "records holds fewer rows than images were selected");
@@ -104,10 +81,8 @@ int32_t save_all(int32_t device, const char* bag_path, const char* topic, const 
   };
   auto read = [&](uint32_t k, Parsed* P) -> int32_t {
     uint64_t bytes = 0;
-    int32_t s = ilcc_bag_topic_read(iter.it, selected[k], nullptr, 0, &bytes);
-    if (s != ILCC_OK && s != ILCC_CAPACITY) return s;
-    msg.resize(bytes ? bytes : 1);
-    if ((s = ilcc_bag_topic_read(iter.it, selected[k], msg.data(), bytes, &bytes)) != ILCC_OK) return s;
+    int32_t s = read_message(iter.it, selected[k], &msg, &bytes);
+    if (s != ILCC_OK) return s;
     if (!compressed) s = ilcc_image_parse_any(msg.data(), bytes, &P->L);
     else if ((s = ilcc_compressed_image_parse(msg.data(), bytes, &P->C)) == ILCC_OK) s = ilcc_jpeg_parse(msg.data() + P->C.data_offset, P->C.data_bytes, &P->J);
     return s == ILCC_OK ? ILCC_OK : fail(s, message_name(selected[k]) + ": " + ilcc_last_error(nullptr));
@@ -123,7 +98,7 @@ int32_t save_all(int32_t device, const char* bag_path, const char* topic, const 
     return fail(ILCC_BAD_ARGUMENT, message_name(selected[0]) + ": the camera's width / height differ from the image's");
   ilcc_jpeg_info I;   // of every file written: one component, no restart markers, as ilcc_bag_save_jpeg writes
   if ((st = ilcc_jpeg_write_info(w, h, 1, 1, 1, quality, 0, &I)) != ILCC_OK) return st;
-  const uint64_t out_per_image = up16(sp.out_bytes_per_image ? sp.out_bytes_per_image : (uint64_t)w * (uint64_t)h);
+  const uint64_t out_per_image = align16(sp.out_bytes_per_image ? sp.out_bytes_per_image : (uint64_t)w * (uint64_t)h);
   Sizes S;
   if (!sizes_of(I, out_per_image, &S)) return fail(ILCC_BAD_ARGUMENT, message_name(selected[0]) + ": image too large for K17");
   // a CompressedImage is decoded as in ilcc_jpeg_sequence.h: its coefficients and table rows are staged, K13b makes the pixels
@@ -175,52 +150,25 @@ int32_t save_all(int32_t device, const char* bag_path, const char* topic, const 
   const uint64_t coef_at = mono_at + S.mono * images_cap, out_at = coef_at + S.coef * images_cap, rows_at = out_at + align256(out_cap_max);
   const uint64_t scratch_at = rows_at + align256(sizeof(ilcc_jpeg_encode_row) * images_cap);
   DeviceBuffer d_all;
-  Pinned h_blob, h_back;   // h_back: [ rows | scans ] on route 0, one image's coefficients on route 1 and in the fallback
+  Pinned h_blob, h_back;   // h_back: [ rows | scans ]
   const uint64_t back_rows = align256(sizeof(ilcc_jpeg_encode_row) * images_cap);
-  const uint64_t back_bytes = back_rows + std::max<uint64_t>(out_cap_max, I.coef_count * sizeof(int16_t));
   if ((e = hipMalloc(&d_all.p, scratch_at + k17_scratch)) != hipSuccess || (e = hipHostMalloc((void**)&h_blob.p, blob_cap, hipHostMallocDefault)) != hipSuccess ||
-      (e = hipHostMalloc((void**)&h_back.p, back_bytes, hipHostMallocDefault)) != hipSuccess)
+      (e = hipHostMalloc((void**)&h_back.p, back_rows + out_cap_max, hipHostMallocDefault)) != hipSuccess)
     return hip_fail(e);
   uint8_t* base = (uint8_t*)d_all.p;
-  auto* h_rows = reinterpret_cast<ilcc_jpeg_encode_row*>(h_back.p);
-  uint8_t* h_payload = h_back.p + back_rows;
 
-  uint8_t headers[kHeaderRoom];
-  uint64_t header_bytes = 0;
-  if ((st = ilcc_jpeg_write_headers(&I, headers, sizeof(headers), &header_bytes)) != ILCC_OK) return st;
-  const uint8_t eoi[2] = {0xFF, 0xD9};
-  std::vector<uint8_t> file;   // of an image the host encodes
-
-  auto path_of = [&](uint32_t k) {
-    char number[16];
-    std::snprintf(number, sizeof(number), "%06u", (unsigned)selected[k]);
-    return std::string(prefix) + number + ".jpg";
-  };
-  // route 1 for image m of the batch that starts at selection index `at`: its coefficients to the host, the host encoder, the file
-  auto host_encode = [&](uint32_t at, uint32_t m) -> int32_t {
-    const uint64_t bytes = I.coef_count * sizeof(int16_t);
-    hipError_t err = hipMemcpyAsync(h_payload, base + coef_at + S.coef * m, bytes, hipMemcpyDeviceToHost, stream.s);
-    if (err == hipSuccess) err = hipStreamSynchronize(stream.s);
-    if (err != hipSuccess) return hip_fail(err);
-    out->d2h_bytes += bytes;
-    const uint64_t bound = ilcc_jpeg_file_bound(&I);
-    uint64_t room = std::min<uint64_t>(1024 + I.coef_count, bound), n = 0;   // a byte per coefficient holds any file an image compresses into
-    for (;;) {
-      file.resize(room);
-      const int32_t s = ilcc_jpeg_entropy_encode(&I, reinterpret_cast<const int16_t*>(h_payload), file.data(), room, &n);
-      if (s == ILCC_CAPACITY && room < bound) {
-        room = bound;
-        continue;
-      }
-      if (s != ILCC_OK) return fail(s, message_name(selected[at + m]) + ": " + ilcc_last_error(nullptr));
-      break;
-    }
-    ilcc_jpeg_write_record& r = records[at + m];
-    r.route = 1;
-    r.file_bytes = n;
-    ++out->n_host_encoded;
-    return write_file(path_of(at + m), file.data(), n, nullptr, 0, nullptr, 0);
-  };
+  JpegFinisher files;   // K17's rows and scans of a batch -> each image's file
+  files.info = &I;
+  files.stream = stream.s;
+  files.d_coef = base + coef_at;
+  files.coef_pitch = S.coef;
+  files.d_scans = base + out_at;
+  files.d_rows = reinterpret_cast<const ilcc_jpeg_encode_row*>(base + rows_at);
+  files.out_per_image = out_per_image;
+  files.h_back = h_back.p;
+  files.back_rows = back_rows;
+  if ((st = files.init()) != ILCC_OK) return st;
+  std::vector<uint8_t> encoded;   // of an image the host encodes
 
   std::vector<Parsed> parsed(images_cap);
   std::vector<uint64_t> at(images_cap);
@@ -307,10 +255,7 @@ int32_t save_all(int32_t device, const char* bag_path, const char* topic, const 
     fj.n_images = n;
     fj.hip_stream = stream.s;
     if ((st = ilcc_jpeg_fdct_batch_device(&fj)) != ILCC_OK) return st;
-    if (sp.route == 1) {
-      for (uint32_t m = 0; m < n; ++m)
-        if ((st = host_encode(b0, m)) != ILCC_OK) return st;
-    } else {
+    if (sp.route == 0) {
       ilcc_jpeg_huffman_encode_job hj{};
       hj.layout = &I;
       hj.d_coef = fj.d_coef;
@@ -324,35 +269,25 @@ int32_t save_all(int32_t device, const char* bag_path, const char* topic, const 
       hj.hip_stream = stream.s;
       if ((st = ilcc_jpeg_huffman_encode_batch_device(&hj)) != ILCC_OK) return st;
       // the rows, then one copy of the scans that were produced
-      if ((e = hipMemcpyAsync(h_rows, hj.d_rows, sizeof(ilcc_jpeg_encode_row) * n, hipMemcpyDeviceToHost, stream.s)) != hipSuccess ||
-          (e = hipStreamSynchronize(stream.s)) != hipSuccess)
-        return hip_fail(e);
-      out->d2h_bytes += sizeof(ilcc_jpeg_encode_row) * n;
-      uint64_t span = 0;
-      for (uint32_t m = 0; m < n; ++m)
-        if (h_rows[m].status == 0) span = std::max(span, h_rows[m].offset + h_rows[m].bytes);
-      if (span > hj.out_cap) return fail(ILCC_HIP_ERROR, "internal error: K17 placed a scan past its output");
-      if (span) {
-        if ((e = hipMemcpyAsync(h_payload, hj.d_out, span, hipMemcpyDeviceToHost, stream.s)) != hipSuccess || (e = hipStreamSynchronize(stream.s)) != hipSuccess)
-          return hip_fail(e);
-        out->d2h_bytes += span;
-      }
-      for (uint32_t m = 0; m < n; ++m) {
-        if (h_rows[m].status != 0) continue;
-        ilcc_jpeg_write_record& r = records[b0 + m];
-        r.route = 0;
-        r.file_bytes = header_bytes + h_rows[m].bytes + 2;
-        if ((st = write_file(path_of(b0 + m), headers, header_bytes, h_payload + h_rows[m].offset, h_rows[m].bytes, eoi, 2)) != ILCC_OK) return st;
-      }
-      // what K17 did not place: an image without room is finished by the host encoder; a range refusal is the host encoder's to word
-      for (uint32_t m = 0; m < n; ++m) {
-        if (h_rows[m].status == 0) continue;
-        if ((st = host_encode(b0, m)) != ILCC_OK) return st;
-        if (h_rows[m].status & (ILCC_JPEG_ENCODE_DC_RANGE | ILCC_JPEG_ENCODE_AC_RANGE))
-          return fail(ILCC_HIP_ERROR, message_name(selected[b0 + m]) + ": internal error: K17 refused coefficients (status " + std::to_string(h_rows[m].status) +
-                                          ") that the host encoder accepts");
-      }
+      if ((st = files.rows_back(n)) != ILCC_OK) return st;
+      if ((e = hipStreamSynchronize(stream.s)) != hipSuccess) return hip_fail(e);
+      bool queued = false;
+      if ((st = files.scans_back(n, &queued)) != ILCC_OK) return st;
+      if (queued && (e = hipStreamSynchronize(stream.s)) != hipSuccess) return hip_fail(e);
     }
+    for (uint32_t m = 0; m < n; ++m) {   // the file's spans go to fwrite as they are: nothing assembles them
+      JpegFile f;
+      if ((st = files.file(m, sp.route, message_name(selected[b0 + m]), &encoded, &f)) != ILCC_OK) return st;
+      ilcc_jpeg_write_record& r = records[b0 + m];
+      r.route = f.route;
+      r.file_bytes = f.bytes();
+      char number[16];
+      std::snprintf(number, sizeof(number), "%06u", (unsigned)selected[b0 + m]);
+      st = write_file(std::string(prefix) + number + ".jpg", f.part[0], f.part_bytes[0], f.part[1], f.part_bytes[1], f.part[2], f.part_bytes[2]);
+      if (st != ILCC_OK) return st;
+    }
+    out->d2h_bytes = files.d2h_bytes;
+    out->n_host_encoded = files.n_host_encoded;
     ++out->n_batches;
   }
   for (uint32_t k = 0; k < n_sel; ++k) {
@@ -374,7 +309,7 @@ uint64_t ilcc_jpeg_write_sequence_bytes(int32_t width, int32_t height, uint64_t 
   ilcc_jpeg_info I;
   Sizes S;
   if (ilcc_jpeg_write_info(width, height, 1, 1, 1, 95, 0, &I) != ILCC_OK) return 0;
-  return sizes_of(I, up16(out_bytes_per_image ? out_bytes_per_image : (uint64_t)width * (uint64_t)height), &S) ? S.device : 0;
+  return sizes_of(I, align16(out_bytes_per_image ? out_bytes_per_image : (uint64_t)width * (uint64_t)height), &S) ? S.device : 0;
 }
 
 int32_t ilcc_bag_save_jpeg_all(int32_t device, const char* bag_path, const char* topic, const ilcc_camera_model* camera, const char* path_prefix,

@@ -2,7 +2,8 @@
 // pipeline, then ilcc_fuse_corners.  The layers below do the work: the topic iterator (bag_reader.cpp), K0b (k0b_unpack_batch.hip),
 // ilcc_submit_batch_device / ilcc_wait (ilcc_api.cpp), the fusion (sequence_host.cpp).  This file owns the batching: which scans
 // form a batch, the two sets of staging buffers, and the order of the calls that lets the host read the next batch while the
-// device works on this one.  Failures below are reported through ilcc_last_error(NULL).
+// device works on this one.  The guards, the selection and "message i in a vector" are host_util.h's.  Failures below are
+// reported through ilcc_last_error(NULL).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,19 +22,6 @@ namespace {
 
 constexpr uint64_t kDefaultStagingBytes = 256ull << 20;
 
-inline uint64_t align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
-
-struct Iterator {
-  ilcc_bag_topic* it = nullptr;
-  ~Iterator() { ilcc_bag_topic_close(it); }
-};
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
 // one of the two sets of staging buffers, and the batch it currently carries
 struct BatchBuffers {
   uint8_t* h_blob = nullptr;   // page-locked
@@ -50,12 +38,13 @@ struct BatchBuffers {
   uint32_t scans() const { return (uint32_t)layouts.size(); }
 };
 
-// a batch the pipeline still works on must be waited for before its buffers go away, whatever made the call end
-struct InFlight {
+// a batch the pipeline still works on must be waited for before its buffers go away, whatever made the call end (host_util.h's
+// InFlight waits for a stream; this one for the pipeline's ticket)
+struct TicketInFlight {
   ilcc_handle* h;
   int32_t ticket = -1;
   std::vector<ilcc_result> sink;
-  ~InFlight() {
+  ~TicketInFlight() {
     if (ticket >= 0 && !sink.empty()) (void)ilcc_wait(h, ticket, sink.data());
   }
 };
@@ -76,10 +65,8 @@ struct Chain {
 
   int32_t fetch(uint32_t scan) {   // message of selected scan `scan` -> msg, pending
     uint64_t bytes = 0;
-    int32_t st = ilcc_bag_topic_read(it, selected[scan], nullptr, 0, &bytes);
-    if (st != ILCC_OK && st != ILCC_CAPACITY) return st;
-    msg.resize(bytes ? bytes : 1);
-    if ((st = ilcc_bag_topic_read(it, selected[scan], msg.data(), bytes, &bytes)) != ILCC_OK) return st;
+    int32_t st = read_message(it, selected[scan], &msg, &bytes);
+    if (st != ILCC_OK) return st;
     if ((st = ilcc_pointcloud2_parse(msg.data(), bytes, &pending)) != ILCC_OK) return st;
     have_pending = true;
     return ILCC_OK;
@@ -142,9 +129,7 @@ int32_t all_scans(ilcc_handle* h, const char* bag_path, const char* topic, const
   c.h = h;
   c.hv = handle_view(h);
   c.it = iter.it;
-  const uint64_t count = ilcc_bag_topic_count(iter.it), stride = sp.stride ? sp.stride : 1;
-  for (uint64_t i = sp.first; i < count && (sp.max_scans == 0 || c.selected.size() < sp.max_scans); i += stride) c.selected.push_back(i);
-  if (c.selected.empty()) return fail(ILCC_BAD_ARGUMENT, "first / stride / max_scans select no message of the topic");
+  if ((st = select_messages(iter.it, sp.first, sp.stride, sp.max_scans, "max_scans", &c.selected)) != ILCC_OK) return st;
   const uint32_t n_sel = (uint32_t)c.selected.size();
   out->n_scans = (int32_t)n_sel;
   if (per_scan_out && cap < n_sel) return fail(ILCC_CAPACITY, "per_scan_out holds fewer records than scans were selected");
@@ -233,7 +218,7 @@ int32_t all_scans(ilcc_handle* h, const char* bag_path, const char* topic, const
   // the batches: while the pipeline works on batch k the host reads, inflates, stages, copies and unpacks batch k + 1
   std::vector<ilcc_result> results(n_sel);
   std::memset(static_cast<void*>(results.data()), 0, sizeof(ilcc_result) * n_sel);
-  InFlight flying;
+  TicketInFlight flying;
   flying.h = h;
   flying.sink.resize(c.frames_cap);
   int cur = 0;

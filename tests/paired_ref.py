@@ -39,6 +39,64 @@ def pair_by_stamp(cloud_ns, image_ns, max_dt_ns):
     return image_of, dt
 
 
+MAX_BATCH_POINTS = 2 ** 32 - 2
+
+
+class CutRefused(Exception):
+    """kind: "CAPACITY" or "BAD_ARGUMENT"."""
+    def __init__(self, kind):
+        Exception.__init__(self, kind)
+        self.kind = kind
+
+
+def cut_paired(scans, image_raw, bgr_bytes, staging, image, device=0, per_member=0, member_cap=0, stage_unpaired=False):
+    """The batch cut of the paired chains (csrc/paired_cut.h), restated from the two loops the chains had.
+    scans: [(data_bytes, points, pair)] per selected scan, pair -1 for an unpaired one; image_raw[j], bgr_bytes: multiples of 256.
+    stage_unpaired: ilcc_bag_rgblidar_all_scans stages and unpacks every scan; ilcc_bag_pcd2image_all_pairs (False) counts an unpaired
+    scan's data[] against `staging` but neither stages it nor counts its points, and has the device budget and the member cap.
+    -> (batches, largest): a batch is a dict(first_scan, scans, members, blob_bytes, points, raw_bytes, bgr_bytes,
+    images=[(image, raw_at, bgr_at)]); largest a dict of the maxima.  Raises CutRefused."""
+    up16 = lambda v: (v + 15) // 16 * 16
+    if device and per_member > device:
+        raise CutRefused("CAPACITY")
+    batches, s = [], 0
+    while s < len(scans):
+        first, members, blob, points, counted, seen = s, [], 0, 0, 0, []
+        while s < len(scans):
+            data, pts, j = scans[s]
+            member = stage_unpaired or j >= 0
+            new_image = j >= 0 and j not in seen
+            extra = image_raw[j] + bgr_bytes if new_image else 0
+            if data > staging or extra > image:
+                raise CutRefused("CAPACITY")
+            if member and points + pts > MAX_BATCH_POINTS:
+                if not members:
+                    raise CutRefused("BAD_ARGUMENT")
+                break
+            cost = sum(image_raw[i] + bgr_bytes for i in seen)
+            full = member and ((device and (len(members) + 1) * per_member > device) or (member_cap and len(members) >= member_cap))
+            if s > first and (up16(counted) + data > staging or cost + extra > image or full):
+                break
+            counted = up16(counted) + data
+            if member:
+                blob = up16(blob) + data
+                points += pts
+                members.append(s)
+            if new_image:
+                seen.append(j)
+            s += 1
+        b = dict(first_scan=first, scans=s - first, members=members, blob_bytes=blob, points=points, raw_bytes=0, bgr_bytes=0, images=[])
+        for j in seen:                                           # an image shared with another batch is charged to both
+            b["images"].append((j, b["raw_bytes"], b["bgr_bytes"]))
+            b["raw_bytes"] += image_raw[j]
+            b["bgr_bytes"] += bgr_bytes
+        batches.append(b)
+    largest = dict(members=max(len(b["members"]) for b in batches) if batches else 0)
+    for key in ("blob_bytes", "points", "raw_bytes", "bgr_bytes"):
+        largest[key] = max((b[key] for b in batches), default=0)
+    return batches, largest
+
+
 def pcd_bytes(xyzrgb):
     """The file ilcc_save_pcd_xyzrgb writes for (n, 4) float32 records."""
     a = np.ascontiguousarray(xyzrgb, dtype=np.float32).reshape(-1, 4)
