@@ -18,6 +18,7 @@
  *   chessboardEnergy.m                                            ilcc_chessboard_from_corners (host)
  *   plotChessboards.m:48-68 (dlmwrite of the X then Y block)      ilcc_save_cam_corners
  *   (a batch of images in one go, every image of a bag fused)     ilcc_image_sequence.h (K10b: the same stage bodies)
+ *   (the boards of a batch of corner lists in two launches)        ilcc_image_structure.h (K18: one wavefront per seed corner)
  *
  * Corner positions are 0-based pixels (findCorners.m:124-125); the file adds 1 back, as the
  * reference's dump does.  Not here: multi-board output.  The undistorted image itself

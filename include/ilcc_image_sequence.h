@@ -114,7 +114,9 @@ typedef struct ilcc_image_sequence_params {
   uint32_t first;               /* first message of the topic that is taken (time order) */
   uint32_t stride;              /* every stride-th from there (0 is read as 1) */
   uint32_t max_images;          /* at most this many (0: all) */
-  uint32_t reserved0;
+  uint32_t reserved0;           /* the route of structure recovery: 0 ilcc_chessboard_from_corners on a host thread; 1 K18 on the */
+                                /*   call's stream right after the batch's K10b (ilcc_image_structure.h): the same records; above 1: */
+                                /*   ILCC_BAD_ARGUMENT, refused with the other host-side refusals before anything is allocated */
   double gate_px;               /* <= 0: half a square of the median board (rule 4 above) */
   uint64_t staging_bytes;       /* raw message data per batch; 0: 256 MiB */
   uint64_t device_bytes;        /* mono8 images + K10b scratch per batch; 0: 512 MiB */
@@ -141,7 +143,7 @@ typedef struct ilcc_image_sequence_result {
   int32_t n_batches;
   double gate;
   double spread_rms, spread_max;
-  double host_recovery_ms;      /* wall time spent in ilcc_chessboard_from_corners, all images */
+  double host_recovery_ms;      /* wall time spent recovering boards, all images, whichever route (reserved0) did it */
   double xy[ILCC_MAX_CORNERS * 2];
 } ilcc_image_sequence_result;
 

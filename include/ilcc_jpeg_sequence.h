@@ -64,7 +64,8 @@ int32_t ilcc_jpeg_entropy_decode_many(const uint8_t* const* jpg, const uint64_t*
 
 /* ---- 3. the chain ---------------------------------------------------------------------------------------------------------- */
 typedef struct ilcc_jpeg_sequence_params {
-  ilcc_image_sequence_params seq;   /* first / stride / max_images / gate_px / staging_bytes / device_bytes, as documented there */
+  ilcc_image_sequence_params seq;   /* first / stride / max_images / gate_px / staging_bytes / device_bytes and reserved0 (the route
+                                     * of structure recovery: 0 the host thread, 1 K18), as documented there */
   uint32_t decode_threads;          /* 0: 8; above 16 is read as 16 */
   uint32_t reserved0;               /* the route of the Huffman decode: 0 (the default) the host pool below; 1 K16 on the device
                                      * (ilcc_jpeg_huffman.h: the pool's threads then only prepare the scans); anything else is

@@ -12,6 +12,7 @@
 #include "host_util.h"
 #include "ilcc_hip.h"
 #include "ilcc_image_corners.h"
+#include "ilcc_image_structure.h"   // ilcc_chessboard_seed_board
 
 namespace ilcc {
 
@@ -188,25 +189,32 @@ Board grow(const Board& b, const Corners& C, int border) {
   return n;
 }
 
+// the board seed i grows to while the energy falls (empty: initChessboard rejected it, or its 3 x 3 board is above 0)
+Board seed_board(const Corners& C, int i) {
+  Board b = init_board(C, i);
+  if (b.empty() || energy(b, C) > 0) return Board();
+  for (;;) {
+    const double e = energy(b, C);
+    Board prop[4];
+    double pe[4];
+    for (int j = 0; j < 4; ++j) {
+      prop[j] = grow(b, C, j + 1);
+      pe[j] = energy(prop[j], C);
+    }
+    int mi = 0;
+    for (int j = 1; j < 4; ++j)
+      if (pe[j] < pe[mi]) mi = j;
+    if (pe[mi] < e) b = prop[mi];
+    else break;
+  }
+  return b;
+}
+
 std::vector<Board> chessboards_from_corners(const Corners& C) {
   std::vector<Board> boards;
   for (int i = 0; i < (int)C.p.size(); ++i) {
-    Board b = init_board(C, i);
-    if (b.empty() || energy(b, C) > 0) continue;
-    for (;;) {
-      const double e = energy(b, C);
-      Board prop[4];
-      double pe[4];
-      for (int j = 0; j < 4; ++j) {
-        prop[j] = grow(b, C, j + 1);
-        pe[j] = energy(prop[j], C);
-      }
-      int mi = 0;
-      for (int j = 1; j < 4; ++j)
-        if (pe[j] < pe[mi]) mi = j;
-      if (pe[mi] < e) b = prop[mi];
-      else break;
-    }
+    const Board b = seed_board(C, i);
+    if (b.empty()) continue;
     const double eb = energy(b, C);
     if (!(eb < -10)) continue;
     std::vector<int> over;
@@ -266,6 +274,29 @@ extern "C" int32_t ilcc_chessboard_from_corners(const ilcc_image_corner* corners
   *rows = hit->rows;
   *cols = hit->cols;
   for (size_t k = 0; k < hit->idx.size(); ++k) board_index[k] = hit->idx[k];
+  return ILCC_OK;
+}
+
+extern "C" int32_t ilcc_chessboard_seed_board(const ilcc_image_corner* corners, int32_t n_corners, int32_t seed, int32_t* rows,
+                                              int32_t* cols, int32_t* index, int32_t cap, double* energy) {
+  if (!corners || n_corners <= 0 || seed < 0 || seed >= n_corners || !rows || !cols || !energy || cap < 0 || (cap > 0 && !index))
+    return ilcc::fail(ILCC_BAD_ARGUMENT, "ilcc_chessboard_seed_board: bad argument");
+  ilcc::Corners C;
+  for (int i = 0; i < n_corners; ++i) {
+    C.p.push_back({corners[i].u, corners[i].v});
+    C.v1.push_back({corners[i].v1[0], corners[i].v1[1]});
+    C.v2.push_back({corners[i].v2[0], corners[i].v2[1]});
+  }
+  const ilcc::Board b = ilcc::seed_board(C, seed);
+  *rows = b.rows;
+  *cols = b.cols;
+  *energy = b.empty() ? 0.0 : ilcc::energy(b, C);
+  if (b.empty()) {
+    *rows = *cols = 0;
+    return ILCC_OK;
+  }
+  if ((size_t)cap < b.idx.size()) return ilcc::fail(ILCC_CAPACITY, "ilcc_chessboard_seed_board: the board has more cells than index holds");
+  for (size_t k = 0; k < b.idx.size(); ++k) index[k] = b.idx[k];
   return ILCC_OK;
 }
 

@@ -1,7 +1,7 @@
 // image_sequence_api.cpp -- ilcc_bag_corners_all_images (include/ilcc_image_sequence.h): every image of a bag topic through K11 and
 // K10b, structure recovery per image, then ilcc_fuse_image_corners.  The layers below do the work: the topic iterator
 // (bag_reader.cpp), the Image parser and K11 (camera_image_host.cpp, k11_camera_image.hip), K10b (k10b_image_corners_batch.hip),
-// ilcc_chessboard_from_corners (image_corners_host.cpp), the cut and the fusion (image_sequence_host.cpp).  This file owns the
+// ilcc_chessboard_from_corners (image_corners_host.cpp) or K18 (structure_route.h), the cut and the fusion (image_sequence_host.cpp).  This file owns the
 // batching: the two sets of buffers, and the order of the calls that lets a host thread recover batch k's boards while the
 // device works on batch k + 1.  The guards, the selection, "message i in a vector" and the image-topic open are host_util.h's.
 // Failures below are reported through ilcc_last_error(NULL).
@@ -18,6 +18,7 @@
 #include "host_util.h"
 #include "ilcc_image_sequence.h"
 #include "ilcc_sequence.h"
+#include "structure_route.h"
 
 using namespace ilcc;
 
@@ -151,6 +152,7 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   if ((e = hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e);
   BatchBuffers B[2];
   Worker worker;   // after B: it is joined before the buffers it reads go away
+  StructureRoute structure;   // reserved0 == 1: K18 recovers the boards instead of the host thread
   const int n_sets = n_batches > 1 ? 2 : 1;
   for (int k = 0; k < n_sets; ++k) {
     BatchBuffers& b = B[k];
@@ -208,6 +210,12 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
     }
     if (st != ILCC_OK) return st;
     ++out->n_batches;
+    if (sp.reserved0 == 1) {   // structure recovery of this batch on the device (K18), on the call's stream
+      if ((st = structure.recover(now.corners.data(), now.capacity, now.n_corners.data(), now.count, images_cap, board_w, board_h,
+                                  records.data() + now.first, stream.s)) != ILCC_OK)
+        return st;
+      continue;
+    }
     // structure recovery of this batch on a host thread, while the next batch is staged and runs
     worker.join();
     if (worker.status != ILCC_OK) return fail(worker.status, worker.error);
@@ -215,7 +223,7 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   }
   worker.join();
   if (worker.status != ILCC_OK) return fail(worker.status, worker.error);
-  out->host_recovery_ms = worker.ms;
+  out->host_recovery_ms = worker.ms + structure.ms;
 
   // fusion of the boards that were found
   const uint32_t N2 = (uint32_t)(2 * board_w * board_h);
@@ -279,6 +287,8 @@ int32_t ilcc_bag_corners_all_images(int32_t device, const char* bag_path, const 
     st = fail(ILCC_BAD_ARGUMENT, "the board must have 3 x 3 .. ILCC_MAX_CORNERS corners");
   } else if (!std::isfinite(sp->gate_px)) {
     st = fail(ILCC_BAD_ARGUMENT, "gate_px is not finite");
+  } else if (sp->reserved0 > 1) {
+    st = fail(ILCC_BAD_ARGUMENT, "reserved0 (the route of structure recovery) must be 0, the host thread, or 1, K18");
   } else {
     try {   // no exception crosses the C-ABI
       st = all_images(device, bag_path, topic, camera, board_w, board_h, *sp, out, per_image_out, cap);

@@ -25,6 +25,7 @@
 #include "ilcc_jpeg_sequence.h"
 #include "ilcc_sequence.h"
 #include "jpeg_entropy.h"
+#include "structure_route.h"
 
 using namespace ilcc;
 
@@ -324,6 +325,7 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   if ((e = hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e);
   BatchBuffers B[2];
   Worker decoder, worker;   // after B: they are joined before the buffers they use go away
+  StructureRoute structure;   // seq.reserved0 == 1: K18 recovers the boards instead of the host thread
   const int n_sets = n_batches > 1 ? 2 : 1;
   // route 1: [ blob | coefficients | K16's statuses and counters | planes | pixels | mono8 ]
   const uint64_t coef_at = k16 ? blob_cap : 0, k16_at = coef_at + (k16 ? S.coef * images_cap : 0);
@@ -506,6 +508,12 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
     }
     if (st != ILCC_OK) return st;
     ++out->n_batches;
+    if (jp.seq.reserved0 == 1) {   // structure recovery of this batch on the device (K18), on the call's stream
+      if ((st = structure.recover(now.corners.data(), now.capacity, now.n_corners.data(), now.count, images_cap, board_w, board_h,
+                                  records.data() + now.first, stream.s)) != ILCC_OK)
+        return st;
+      continue;
+    }
     // structure recovery of this batch on a host thread, while the next batch runs
     worker.join();
     if (worker.status != ILCC_OK) return fail(worker.status, worker.error);
@@ -513,7 +521,7 @@ int32_t all_images(int32_t device, const char* bag_path, const char* topic, cons
   }
   worker.join();
   if (worker.status != ILCC_OK) return fail(worker.status, worker.error);
-  out->host_recovery_ms = worker.ms;
+  out->host_recovery_ms = worker.ms + structure.ms;
 
   // fusion of the boards that were found
   const uint32_t N2 = (uint32_t)(2 * board_w * board_h);
@@ -597,6 +605,8 @@ int32_t ilcc_bag_corners_all_compressed_images(int32_t device, const char* bag_p
     st = fail(ILCC_BAD_ARGUMENT, "gate_px is not finite");
   } else if (sp->reserved0 > 1) {
     st = fail(ILCC_BAD_ARGUMENT, "reserved0 (the route of the Huffman decode) must be 0, the host pool, or 1, K16");
+  } else if (sp->seq.reserved0 > 1) {
+    st = fail(ILCC_BAD_ARGUMENT, "seq.reserved0 (the route of structure recovery) must be 0, the host thread, or 1, K18");
   } else {
     try {   // no exception crosses the C-ABI
       st = all_images(device, bag_path, topic, camera, board_w, board_h, *sp, out, per_image_out, cap);

@@ -5,12 +5,15 @@
 //                      [--pgm undistorted.pgm] [--jpg-out <camera><i>.jpg] [--quality 95] [--device N]
 //   ilcc_image_corners --jpg pointgrey1.jpg [--yaml pointgrey.yaml] [--board 7x5] --out pointgrey1.txt [--device N]
 //   ilcc_image_corners --bag ... --topic ... --yaml ... --out pointgrey1.txt --all-images [--first N] [--stride N] [--max-images N]
-//                      [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] [--jpg-out-all PREFIX] [--quality 95]
+//                      [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] [--structure host|gpu]
+//                      [--jpg-out-all PREFIX] [--quality 95]
 // --all-images reads EVERY sensor_msgs/Image of the topic (include/ilcc_image_sequence.h): the boards of the images that hold one
 // are fused into ONE board, written in the same format; --report writes one line per image.  It takes no --jpg, --jpg-out or --pgm.
 // A topic that carries no sensor_msgs/Image but sensor_msgs/CompressedImage goes through include/ilcc_jpeg_sequence.h instead
 // (the same output); --decode-threads is the number of host threads its Huffman decode runs on (0: 8, at most 16), and
 // --huffman gpu decodes the scans on the device instead (K16, include/ilcc_jpeg_huffman.h; the threads then only prepare them).
+// --structure gpu recovers every image's board on the device (K18, include/ilcc_image_structure.h) instead of a host thread: the
+// same boards, the same files.
 // --jpg-out-all PREFIX (with --all-images) writes every selected image, undistorted, as PREFIX<message index, 6 digits>.jpg
 // (include/ilcc_jpeg_write_sequence.h: each file is what --jpg-out writes for that message alone); the Huffman coding runs on the
 // device (K17) unless --huffman host is given.  With it --out may be left out: the corners are then not searched.
@@ -45,7 +48,7 @@ const char* kUsage =
     "       ilcc_image_corners --jpg file.jpg [--yaml camera.yaml] [--board 7x5] --out <camera><i>.txt [--device N]\n"
     "       ilcc_image_corners --bag file.bag --topic /camera/image_raw --yaml camera.yaml --out <camera><i>.txt --all-images "
     "[--first N] [--stride N] [--max-images N] [--gate PX] [--report FILE] [--decode-threads N] [--huffman host|gpu] "
-    "[--jpg-out-all PREFIX] [--quality 95] [--device N]\n";
+    "[--structure host|gpu] [--jpg-out-all PREFIX] [--quality 95] [--device N]\n";
 
 // true when the topic carries no sensor_msgs/Image but sensor_msgs/CompressedImage
 bool compressed_only(const std::string& bag_path, const std::string& topic) {
@@ -163,6 +166,9 @@ int main(int argc, char** argv) {
     else if (a == "--huffman" && i + 1 < argc && (std::string(argv[i + 1]) == "host" || std::string(argv[i + 1]) == "gpu")) {
       huffman = std::string(argv[++i]) == "gpu" ? 1u : 0u;
       sequence_option = huffman_given = true;
+    } else if (a == "--structure" && i + 1 < argc && (std::string(argv[i + 1]) == "host" || std::string(argv[i + 1]) == "gpu")) {
+      sp.reserved0 = std::string(argv[++i]) == "gpu" ? 1u : 0u;   // the route of structure recovery: 0 the host thread, 1 K18
+      sequence_option = true;
     } else {
       std::fprintf(stderr, "unknown or incomplete argument: %s\n", a.c_str());
       return 2;
@@ -176,7 +182,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (all_images ? (from_jpg || !jpg_out_path.empty() || !pgm_path.empty() || (out_path.empty() && jpg_out_all.empty())) : sequence_option) {
-    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate, --report, --decode-threads and --huffman need it, and so does --jpg-out-all, with which --out may be left out\n", kUsage);
+    std::fprintf(stderr, "%s--all-images takes a bag and --out, no --jpg, --jpg-out or --pgm; --first, --stride, --max-images, --gate, --report, --structure, --decode-threads and --huffman need it, and so does --jpg-out-all, with which --out may be left out\n", kUsage);
     return 2;
   }
   ilcc_camera_model cam{};

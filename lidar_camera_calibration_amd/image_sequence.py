@@ -3,7 +3,11 @@
 ``find_corners_batch`` is K10b (findCorners on a batch of equal-sized images in at most eight launches, byte for byte what
 ``image_corners.find_corners`` gives image by image), ``fuse_image_corners`` merges per-image boards on the host, and
 ``bag_corners_all_images`` is the chain bag -> fused ``<camera><i>.txt`` board.  ``tests/image_sequence_ref.py`` restates the
-fusion, the batch cut and the candidate order."""
+fusion, the batch cut and the candidate order.
+
+``chessboards_from_corners_batch`` is K18 (``include/ilcc_image_structure.h``): the boards of a batch of corner lists in two
+launches, each what ``image_corners.chessboard_from_corners`` gives for that list alone; ``seed_board`` is its stage output, from
+the device or from the host code.  ``structure="gpu"`` sends a chain's structure recovery through it."""
 import ctypes as C
 import os
 
@@ -18,6 +22,20 @@ IMAGE_SEQUENCE_EXPORTS = ["ilcc_image_corner_plan_create", "ilcc_image_corner_pl
                           "ilcc_image_corner_plan_launches", "ilcc_image_corner_plan_allocations", "ilcc_image_corner_plan_candidates",
                           "ilcc_image_corner_scratch_bytes", "ilcc_fuse_image_corners", "ilcc_default_image_sequence_params",
                           "ilcc_image_sequence_cut", "ilcc_bag_corners_all_images"]
+IMAGE_STRUCTURE_EXPORTS = ["ilcc_structure_plan_create", "ilcc_structure_plan_destroy", "ilcc_chessboards_from_corners_batch",
+                           "ilcc_structure_plan_launches", "ilcc_structure_plan_fallbacks", "ilcc_structure_plan_allocations",
+                           "ilcc_structure_plan_seed_board", "ilcc_chessboard_seed_board"]
+STRUCTURE_MAX_CORNERS = 4096     # ILCC_STRUCTURE_MAX_CORNERS: corners of one image on the device path
+STRUCTURE_ROUTES = {"host": 0, "gpu": 1}
+
+
+def structure_route(structure) -> int:
+    """reserved0 of ImageSequenceParams for `structure`: "host" / "gpu", or the number itself (the C entry refuses one above 1)"""
+    if isinstance(structure, str):
+        if structure not in STRUCTURE_ROUTES:
+            raise ValueError('structure must be "host" or "gpu", got %r' % (structure,))
+        return STRUCTURE_ROUTES[structure]
+    return int(structure)
 
 
 class FusedImageCorners(C.Structure):
@@ -125,6 +143,20 @@ def lib():
                                                   C.POINTER(ImageSequenceParams), C.POINTER(ImageSequenceResult), C.POINTER(ImageRecord),
                                                   C.c_uint32]
         L.ilcc_bag_corners_all_images.restype = C.c_int32
+        L.ilcc_structure_plan_create.argtypes = [C.c_uint32, C.c_uint32]
+        L.ilcc_structure_plan_create.restype = vp
+        L.ilcc_structure_plan_destroy.argtypes = [vp]
+        L.ilcc_structure_plan_destroy.restype = None
+        L.ilcc_chessboards_from_corners_batch.argtypes = [vp, C.c_int32, i32p, C.c_uint32, C.c_int32, C.c_int32, i32p, i32p, i32p, i32p, vp, vp]
+        L.ilcc_chessboards_from_corners_batch.restype = C.c_int32
+        for name in ("launches", "fallbacks", "allocations"):
+            fn = getattr(L, "ilcc_structure_plan_" + name)
+            fn.argtypes = [vp]
+            fn.restype = C.c_uint32
+        L.ilcc_structure_plan_seed_board.argtypes = [vp, C.c_uint32, C.c_uint32, i32p, i32p, i32p, C.c_int32, f64p]
+        L.ilcc_structure_plan_seed_board.restype = C.c_int32
+        L.ilcc_chessboard_seed_board.argtypes = [vp, C.c_int32, C.c_int32, i32p, i32p, i32p, C.c_int32, f64p]
+        L.ilcc_chessboard_seed_board.restype = C.c_int32
         _ready = True
     return L
 
@@ -241,6 +273,106 @@ def find_corners_batch(images, plan=None, capacity=8192):
     return [out[m, :cnt[m]].copy() for m in range(n)]
 
 
+class StructurePlan:
+    """A K18 plan on the current device: all scratch for up to `max_images` corner lists of up to `max_corners` corners.  One call
+    at a time; ``close()`` (or the context manager) frees it."""
+
+    def __init__(self, max_images, max_corners):
+        self._p = lib().ilcc_structure_plan_create(int(max_images), int(max_corners))
+        if not self._p:
+            raise ImageSequenceError(_native.HIP_ERROR, _last_error())
+        self.max_images, self.max_corners = int(max_images), int(max_corners)
+
+    def fits(self, n, corners):
+        return self._p and n <= self.max_images and corners <= self.max_corners
+
+    @property
+    def launches(self):
+        return lib().ilcc_structure_plan_launches(self._p)
+
+    @property
+    def fallbacks(self):
+        return lib().ilcc_structure_plan_fallbacks(self._p)
+
+    @property
+    def allocations(self):
+        return lib().ilcc_structure_plan_allocations(self._p)
+
+    def close(self):
+        if self._p:
+            lib().ilcc_structure_plan_destroy(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+_structure_plan = None
+
+
+def chessboards_from_corners_batch(corners_per_image, board=(7, 5), plan=None, capacity=None, stream=None):
+    """K18: the board of every corner list of a batch -> (statuses [n] int32, [index matrix or None]): image m's status and
+    (rows, cols) int32 matrix of corner indices are what ``image_corners.chessboard_from_corners`` gives for its list alone
+    (None without ILCC_OK).  `corners_per_image`: a list of structured arrays of CORNER_DTYPE.  `capacity`: the row length of the
+    [n, capacity] array the lists are laid in (the longest list when not given).  `stream`: a torch stream (the current one when
+    not given).  Without `plan`, a module-level plan is kept and reused while the batches fit it."""
+    global _structure_plan
+    import torch
+    n = len(corners_per_image)
+    a, b = int(board[0]), int(board[1])
+    counts = np.array([len(c) for c in corners_per_image], np.int32)
+    longest = int(counts.max()) if n else 0
+    cap = longest if capacity is None else int(capacity)
+    if plan is None:
+        if _structure_plan is None or not _structure_plan.fits(n, max(longest, 1)):
+            if _structure_plan is not None:
+                _structure_plan.close()
+            _structure_plan = StructurePlan(max(n, 1), max(longest, 1))
+        plan = _structure_plan
+    table = np.zeros((max(n, 1), max(cap, 1)), CORNER_DTYPE)
+    for m, c in enumerate(corners_per_image):
+        table[m, :min(len(c), cap)] = np.asarray(c, CORNER_DTYPE)[:cap]
+    cells = max(a * b, 1)
+    status, rows, cols = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    index = np.full((max(n, 1), cells), -1, np.int32)
+    i32p = C.POINTER(C.c_int32)
+    s = stream if stream is not None else torch.cuda.current_stream()
+    st = lib().ilcc_chessboards_from_corners_batch(table.ctypes.data_as(C.c_void_p), cap, counts.ctypes.data_as(i32p) if n else None, n, a, b,
+                                                   status.ctypes.data_as(i32p), rows.ctypes.data_as(i32p), cols.ctypes.data_as(i32p),
+                                                   index.ctypes.data_as(i32p), plan._p, C.c_void_p(s.cuda_stream))
+    if st != _native.OK:
+        raise ImageSequenceError(st, _last_error())
+    boards = [index[m, :rows[m] * cols[m]].reshape(rows[m], cols[m]).copy() if status[m] == _native.OK else None for m in range(n)]
+    return status[:n].copy(), boards
+
+
+def seed_board(corners=None, seed=0, plan=None, image=0):
+    """The board a seed corner grows to BEFORE the overlap rule -> ((rows, cols) int32 index matrix or None, energy).  With
+    `corners` (a structured array of CORNER_DTYPE) from the host code, ilcc_chessboard_seed_board; with `plan` and `image` from
+    K18's stage output of the plan's last call, ilcc_structure_plan_seed_board."""
+    rows, cols, energy = C.c_int32(0), C.c_int32(0), C.c_double(0)
+    index = np.zeros(MAX_CORNERS, np.int32)
+    i32p = C.POINTER(C.c_int32)
+    if plan is not None:
+        st = lib().ilcc_structure_plan_seed_board(plan._p, int(image), int(seed), C.byref(rows), C.byref(cols), index.ctypes.data_as(i32p),
+                                                  index.size, C.byref(energy))
+    else:
+        c = np.ascontiguousarray(corners, CORNER_DTYPE)
+        st = lib().ilcc_chessboard_seed_board(c.ctypes.data_as(C.c_void_p), len(c), int(seed), C.byref(rows), C.byref(cols),
+                                              index.ctypes.data_as(i32p), index.size, C.byref(energy))
+    if st != _native.OK:
+        raise ImageSequenceError(st, _last_error())
+    if rows.value == 0:
+        return None, float(energy.value)
+    return index[:rows.value * cols.value].reshape(rows.value, cols.value).copy(), float(energy.value)
+
+
 def fuse_image_corners(boards, accepted, board=(7, 5), gate_px=0.0):
     """ilcc_fuse_image_corners: `boards` is a list of (rows, cols, 2) arrays (None or anything for a non-accepted image).
     -> (FusedImageCorners, used flags, distances)."""
@@ -290,12 +422,14 @@ def sequence_cut(raw_bytes, device_bytes_per_image, staging_bytes=0, device_byte
 
 
 def bag_corners_all_images(bag_path, topic, camera=None, board=(7, 5), first=0, stride=1, max_images=0, gate_px=0.0, staging_bytes=0,
-                           device_bytes=0, device=0, raise_on_failure=True):
+                           device_bytes=0, device=0, raise_on_failure=True, structure="host"):
     """Every selected image of the bag's topic -> (ImageSequenceResult, [ImageRecord]).  Raises BoardNotFound when the fusion finds
     no board (none accepted, or no majority within the gate) and ImageSequenceError on a refusal, unless raise_on_failure is
-    False (then the result's status says so; the records are complete for the two fusion statuses)."""
+    False (then the result's status says so; the records are complete for the two fusion statuses).  structure: "host", a host
+    thread, or "gpu", K18 (chessboards_from_corners_batch), recovers the boards; the records are the same."""
     L = lib()
     sp = default_params()
+    sp.reserved0 = structure_route(structure)
     sp.first, sp.stride, sp.max_images, sp.gate_px = int(first), int(stride), int(max_images), float(gate_px)
     if staging_bytes:
         sp.staging_bytes = int(staging_bytes)

@@ -12,7 +12,7 @@ import numpy as np
 from . import _native
 from .camera_image import CameraImageError, CameraModel
 from .image_corners import BoardNotFound
-from .image_sequence import ImageRecord, ImageSequenceError, ImageSequenceParams, ImageSequenceResult
+from .image_sequence import ImageRecord, ImageSequenceError, ImageSequenceParams, ImageSequenceResult, structure_route
 from .jpeg import Info, parse
 
 JPEG_SEQUENCE_EXPORTS = ["ilcc_jpeg_batch_scratch_bytes", "ilcc_jpeg_idct_batch_device", "ilcc_jpeg_entropy_decode_many",
@@ -154,13 +154,14 @@ def default_params() -> JpegSequenceParams:
 
 
 def bag_corners_all_compressed_images(bag_path, topic, camera=None, board=(7, 5), first=0, stride=1, max_images=0, gate_px=0.0, staging_bytes=0,
-                                      device_bytes=0, decode_threads=0, device=0, raise_on_failure=True, huffman="host"):
+                                      device_bytes=0, decode_threads=0, device=0, raise_on_failure=True, huffman="host", structure="host"):
     """Every selected CompressedImage of the bag's topic -> (ImageSequenceResult, [ImageRecord]).  Raises BoardNotFound when the
     fusion finds no board and ImageSequenceError on a refusal, unless raise_on_failure is False (then the result's status says
     so; the records are complete for the two fusion statuses).  huffman: "host", the decode pool, or "gpu", K16 (jpeg_huffman); the
-    records are the same."""
+    records are the same.  structure: "host" or "gpu" (K18), as in ``image_sequence.bag_corners_all_images``."""
     L = lib()
     sp = default_params()
+    sp.seq.reserved0 = structure_route(structure)
     sp.seq.first, sp.seq.stride, sp.seq.max_images, sp.seq.gate_px = int(first), int(stride), int(max_images), float(gate_px)
     if staging_bytes:
         sp.seq.staging_bytes = int(staging_bytes)
