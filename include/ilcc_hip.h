@@ -482,11 +482,13 @@ int32_t ilcc_debug_full_pass_last(const ilcc_handle* h, uint32_t out[ILCC_FULL_P
  * are identical either way.  No batch may be in flight.
  * ilcc_debug_cluster_launch reports the last K2 launch of the handle (the online caller: its first tier) and the limits the rule
  * works from: out[0] home used (ILCC_CLUSTER_HOME_LDS / _L2; 0: no launch yet), [1] dynamic LDS bytes per workgroup, [2] threads
- * per workgroup, [3] the kernel's static LDS bytes, [4] the device's LDS bytes per compute unit, [5] its compute units. */
+ * per workgroup, [3] the kernel's static LDS bytes, [4] the device's LDS bytes per compute unit, [5] its compute units, [6] the
+ * frames of the last FINISHED batch that the LDS cell grid could not hold and the fallback launch clustered (hashed cells, point
+ * level; 0 for the online caller, whose second tier takes such frames), [7] the most workgroups a fallback launch has. */
 #define ILCC_CLUSTER_HOME_RULE 0
 #define ILCC_CLUSTER_HOME_LDS 1
 #define ILCC_CLUSTER_HOME_L2 2
-#define ILCC_CLUSTER_LAUNCH_WORDS 6
+#define ILCC_CLUSTER_LAUNCH_WORDS 8
 int32_t ilcc_debug_cluster_home(ilcc_handle* h, int32_t home);
 int32_t ilcc_debug_cluster_launch(const ilcc_handle* h, uint32_t out[ILCC_CLUSTER_LAUNCH_WORDS]);
 

@@ -44,7 +44,7 @@ FULL_PASS_LAST_WORDS = 4
 ABI_VERSION = 5            # the layout of Params / Result / Timing below is ILCC_ABI_VERSION 5 of include/ilcc_hip.h
 RESULTS_FULL, RESULTS_COMPACT = 0, 1
 CLUSTER_HOME_RULE, CLUSTER_HOME_LDS, CLUSTER_HOME_L2 = 0, 1, 2
-CLUSTER_LAUNCH_WORDS = 6
+CLUSTER_LAUNCH_WORDS = 8
 SOLVE_REC_DOUBLES, SOLVE_REC_INTS = 6, 4
 GRID_REC_DOUBLES, GRID_REC_INT64S, GRID_REC_INTS, GRID_BATCH_INFO_WORDS = 3, 2, 6, 4
 LOCATE_NONE, LOCATE_LAUNCHES, LOCATE_FUSED = 0, 1, 2   # ilcc_debug_grid_solve_batch: info[1]

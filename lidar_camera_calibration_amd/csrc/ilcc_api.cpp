@@ -80,6 +80,7 @@ struct Slot {
   uint32_t *d_flags = nullptr, *d_nfinite = nullptr, *d_counts_fin = nullptr;   // the online caller's two tiers (Ctx::frame_flags, n_finite, crop_fin)
   uint32_t* h_online = nullptr;   // pinned: flags then finite counts of the last online batch
   uint32_t* d_list = nullptr;     // tier 2: [0] count, [1..] listed frames
+  uint32_t* d_fallback = nullptr; // K2: the frames k2_seeded_cluster hands to k2_fallback_cluster (Ctx::fallback_list; their count is a batch word)
   void* d_list_frames = nullptr;  // tier 2: kListedFrameBytes per frame
   GridPartial *d_partial = nullptr, *d_partial2 = nullptr, *d_partial3 = nullptr, *d_partial4 = nullptr;
   SolveRec* d_solverec = nullptr;
@@ -159,6 +160,7 @@ struct ilcc_handle {
   ClusterLimits cluster_limits{};    // K2's residency limits on this device (launch_cluster's rule for the home of the sorted points)
   int32_t cluster_home = kClusterHomeRule;   // ilcc_debug_cluster_home: the rule, or one home forced
   ClusterLaunch cluster_last{};      // what the last k2_seeded_cluster launch used (ilcc_debug_cluster_launch)
+  uint32_t cluster_fallback_last = 0;   // frames of the last finished batch that k2_seeded_cluster handed to k2_fallback_cluster (likewise)
   std::vector<double> tl_rows;
   std::string err;
 };
@@ -330,6 +332,7 @@ auto slot_device_buffers(const ilcc_handle* h, Slot& sl) {
       buffer(sl.d_flags, mf),
       buffer(sl.d_nfinite, mf),
       buffer(sl.d_list, mf + 1),
+      buffer(sl.d_fallback, mf),
       Buffer{&sl.d_list_frames, kListedFrameBytes * mf},
       buffer(sl.d_masks, chunks * (kCropChunk / 64)),
       buffer(sl.d_parent, np),
@@ -550,6 +553,7 @@ Ctx make_ctx(ilcc_handle* h, Slot& sl, const float4* d_xyzi, const float* d_clic
   c.cluster_cells_cap = h->cluster_cells_cap;
   c.wide = 0u;
   c.cluster_bits = cluster_bits_default();
+  c.fallback_list = sl.d_fallback;
   c.online_tier = 0u;
   c.online_window = 0.f;
   c.frame_flags = sl.d_flags;
@@ -1124,7 +1128,7 @@ void raise_capacities(ilcc_handle* h, uint32_t grid_points, uint32_t cluster_poi
 // K2's one-workgroup LDS path likewise (ROI points per frame, steps of 512): what it does not hold of a CU's 160 KiB is room for K6
 // workgroups of other batches.  Its per-cell arrays: the most occupied cells a frame of the batch needed (+ 1/8), steps of 256.
 // Frames the LDS cell grid cannot hold at any capacity (bounding grid too large: un-cropped clouds; more cells than the largest
-// capacity) take the hashed-cell path of their own workgroup (k2_cluster.hip, k2_hashed.h).
+// capacity) take the hashed-cell path in the fallback launch (k2_fallback.hip, k2_hashed.h).
 constexpr int kGridStaticLds = 3072;   // static LDS of a full-pass workgroup (bests, counters, the box pre-pass's mask and list), rounded up
 // the largest multiple of 256 staged points with which two full-pass workgroups on an n_ty x n_tz grid fit a CU's LDS (0: none)
 constexpr uint32_t grid_points_two_per_cu(int n_ty, int n_tz) {
@@ -1147,6 +1151,7 @@ int32_t finish(ilcc_handle* h, Slot& sl, ilcc_result* out, float* out_compact = 
   const BatchCounts n = count_batch(h, sl);
   ILCC_TRY(account_timing(h, sl, n.evals));
   grow_capacities(h, n, sl.h_iters[3 * kIterSlots]);
+  h->cluster_fallback_last = (uint32_t)sl.h_iters[kFallbackWord];
   if (sl.grid && sl.listed) {   // the batch's live count came back with its counters: the next submits size their full pass by it
     note_live(h, sl.h_iters[kLiveWord], sl.n_frames);
     h->full_pass_last[2] = (uint32_t)sl.h_iters[kLiveWord];
@@ -2000,6 +2005,8 @@ int32_t ilcc_debug_cluster_launch(const ilcc_handle* h, uint32_t out[ILCC_CLUSTE
   out[3] = h->cluster_limits.static_lds;
   out[4] = h->cluster_limits.lds_per_cu;
   out[5] = h->cluster_limits.cus;
+  out[6] = h->cluster_fallback_last;
+  out[7] = kFallbackGrid;
   return ILCC_OK;
 }
 

@@ -13,7 +13,7 @@ namespace ilcc {
 
 // The LDS of a CU, and the bounds derived from it (the library is built for gfx950 only)
 constexpr int kCuLdsBytes = 160 * 1024;
-constexpr int kClusterLdsMax = kCuLdsBytes - 4 * 1024;   // K2: dynamic LDS the handle lets k2_seeded_cluster's capacities grow to (fit_cluster_lds); its limit in a build with the timers' static LDS
+constexpr int kClusterLdsMax = kCuLdsBytes - 4 * 1024;   // K2: dynamic LDS the handle lets k2_seeded_cluster's capacities grow to (fit_cluster_lds)
 constexpr int kLocateLdsMax = 3 * (kCuLdsBytes / 8);     // K6: dynamic LDS up to which a batch takes k6_locate (60 KiB: two of its workgroups share a CU); above, the separate launches
 constexpr int kSolveLdsMax = kCuLdsBytes - 16 * 1024;    // K7a: dynamic LDS bound (144 KiB = two frames staged at kGridLdsPointsMax, k7_common.h)
 
@@ -74,8 +74,9 @@ constexpr int kTieCap = 256;           // K6 -> K7r: near-tie candidates kept pe
 constexpr float kTieEps = 2e-5f;       // relative cost window of a near-tie (fp32 sums of ~1e3 terms agree to ~1e-6)
 constexpr int kCoverageCellsMax = 1024;   // K7b: board squares tracked by the coverage mask (board_w x board_h)
 constexpr int kIterSlots = 64;         // K6 executed-iteration counters (spread to avoid one hot atomic); [0,64): all points, [64,128): interior-class points, [128,192): (point, tile) evaluations of the box pre-pass
-constexpr int kBatchWords = 3 * kIterSlots + 2;   // Ctx::grid_iters: the K6 counters, then K2's: [192] most occupied cells a frame's LDS cell grid needed, then [193]:
+constexpr int kBatchWords = 3 * kIterSlots + 3;   // Ctx::grid_iters: the K6 counters, then K2's: [192] most occupied cells a frame's LDS cell grid needed, then [193]:
 constexpr int kLiveWord = 3 * kIterSlots + 1;     // the live (frame, theta) workgroups k6_group_prepass listed for the full pass (its low 32 bits are the list's count word)
+constexpr int kFallbackWord = 3 * kIterSlots + 2; // [194]: the frames k2_seeded_cluster listed in Ctx::fallback_list for k2_fallback_cluster (reset with kLiveWord, by K1 / the diagnostic entries)
 constexpr int kClusterHashSize = 1 << 17;    // K2: hash buckets per frame (global memory)
 constexpr int kClusterLdsPointsMax = 4096;   // K2: largest LDS capacity for the cell-sorted points (ROI points per frame); larger frames keep them in HBM/L2
 constexpr int kClusterLdsPointsMin = 1024;   // K2: smallest (the handle grows it in steps of 512 with the ROI sizes it sees)
@@ -191,6 +192,7 @@ struct Ctx {
   uint32_t cluster_cells_cap;    // K2: occupied cells per frame the workgroup's LDS arrays hold; frames with more take the hashed-cell path (hashed_cluster_frame)
   uint32_t wide;             // per-frame kernels at their small-batch (latency) widths whatever the batch size: synchronous calls nothing overlaps with (the online caller)
   uint32_t cluster_bits;     // K2: cells of the padded bounding grid the LDS bitmap holds (a multiple of 64)
+  uint32_t* fallback_list;   // K2: n_frames words: the frames the LDS grid could not hold, in no particular order; their count is grid_iters[kFallbackWord]
   // The online caller (get_chessboard_by_point on un-cropped clouds) in two tiers.  online_tier 1: K1 crops a window of
   // +-online_window around the predicted point, K2 clusters it on the LDS cell grid and VERIFIES that the result is the one the
   // whole cloud gives (see fine_cluster_frame); frames it cannot vouch for get frame_flags[f] = 1.  online_tier 2: K1 (unbounded
@@ -345,7 +347,13 @@ struct ClusterLaunch {   // what a k2_seeded_cluster launch used
   uint32_t lds_bytes, threads;
 };
 hipError_t cluster_limits(int device, ClusterLimits* out);
-ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& lim, int32_t home);   // k2_cluster.hip: every frame, tiers 0 and 1
+ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& lim, int32_t home);   // k2_cluster.hip: every frame, tiers 0 and 1; tier 0: launch_cluster_fallback behind it
+// k2_fallback.hip: the frames k2_seeded_cluster listed (hashed cells, point level), a fixed grid of kFallbackGrid workgroups of `threads`
+void launch_cluster_fallback(const Ctx& c, hipStream_t s, uint32_t threads);
+#ifndef ILCC_K2_FALLBACK_GRID
+#define ILCC_K2_FALLBACK_GRID 1024   // (A/B builds: tools/build_variant.sh; the choice: DESIGN.md section 4)
+#endif
+constexpr uint32_t kFallbackGrid = ILCC_K2_FALLBACK_GRID;
 void launch_cluster_listed(const Ctx& c, hipStream_t s);   // k2h_listed.hip: the online caller's second tier, the k2h_* chain on the flagged frames
 constexpr size_t kListedFrameBytes = 64;   // of Ctx::list_frames per frame: one ListedFrame (k2h_listed.hip)
 hipError_t set_kernel_attributes_k2();   // once per (process, device), as those of K6 and K7 below

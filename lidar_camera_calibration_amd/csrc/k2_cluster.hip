@@ -1,9 +1,8 @@
-// k2_cluster.hip -- K2's per-frame launch, k2_seeded_cluster: one workgroup per frame on the LDS cell grid (fine_cluster_frame),
-// on hashed cells for a frame the grid cannot hold (hashed_cluster_frame, the phases of k2_hashed.h) and on points beyond that
-// (k2_point_level.h); its LDS size, device limits and launcher (launch_cluster).  The cell argument and which frame takes which
-// path: k2_common.h.  The online caller's second tier is k2h_listed.hip.
-#include "k2_hashed.h"
-#include "k2_point_level.h"
+// k2_cluster.hip -- K2's per-frame launch, k2_seeded_cluster: one workgroup per frame on the LDS cell grid (fine_cluster_frame);
+// a frame the grid cannot hold is listed for k2_fallback_cluster (k2_fallback.hip: hashed cells, and points beyond that), which
+// launch_cluster launches right behind it.  Its LDS size, device limits and launcher (launch_cluster).  The cell argument and
+// which frame takes which path: k2_common.h.  The online caller's second tier is k2h_listed.hip.
+#include "k2_common.h"
 
 namespace ilcc {
 
@@ -233,7 +232,7 @@ __device__ __forceinline__ void fine_components(const FineLds& L, uint32_t C) {
 }
 
 // The steps by the frame's workgroup, with the barriers between them.  Returns false (uniformly, and before any word of the
-// frame's result is written) when the frame does not fit the grid / the cell capacity: the caller takes the hashed-cell path.
+// frame's result is written) when the frame does not fit the grid / the cell capacity: the caller hands the frame to the fallback launch.
 // (The tail stays written out here: as a step of its own it cost the kernel 86 scalar instructions and 16 SGPR spills.)
 template <bool PTS_LDS>
 __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
@@ -322,93 +321,6 @@ __device__ bool fine_cluster_frame(const Ctx& c, uint32_t f, const FineLds& L) {
   return true;
 }
 
-// ------------------------------------------------------------------ hashed cells by the frame's own workgroup
-// -DILCC_K2_TIMING: counters of the one-workgroup path's edge search (union-find hops, cell pairs tested, thread-cycles per part).
-// Device globals, so defined in this file only; the k2h_* chain runs with NoClock.
-#ifdef ILCC_K2_TIMING
-__device__ unsigned long long g_k2_hops, g_k2_finds, g_k2_pairs, g_k2_hits, g_k2_t[6];
-struct EdgeClock {
-  unsigned long long t[6] = {0, 0, 0, 0, 0, 0}, last = __builtin_readcyclecounter();
-  __device__ void lap(int k) {
-    const unsigned long long now = __builtin_readcyclecounter();
-    t[k] += now - last;
-    last = now;
-  }
-  __device__ void pair() { atomicAdd(&g_k2_pairs, 1ull); }
-  __device__ void hit() { atomicAdd(&g_k2_hits, 1ull); }
-  __device__ void flush() {
-    for (int k = 0; k < 6; ++k) atomicAdd(&g_k2_t[k], t[k]);
-  }
-  static __device__ void find() { atomicAdd(&g_k2_finds, 1ull); }
-  static __device__ void hop() { atomicAdd(&g_k2_hops, 1ull); }
-};
-#else
-using EdgeClock = NoClock;
-#endif
-using FrameScope = WgScope<EdgeClock>;
-
-// The phases by the frame's own workgroup.  Returns false (uniformly) when the frame is outside this path's limits: the caller
-// takes the point-level path.
-__device__ bool hashed_cluster_frame(const Ctx& c, uint32_t f, uint32_t* sc) {
-  const HashViews v = hash_views(c, f);
-  const uint32_t M = v.M, tid = threadIdx.x, kT = blockDim.x;
-#ifdef ILCC_K2_TIMING
-  __shared__ unsigned long long hmark[12];
-#define HC_MARK(k) do { __syncthreads(); if (threadIdx.x == 0) hmark[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define HC_MARK(k) do {} while (0)
-#endif
-  HC_MARK(0);
-  HashFrame g;
-  if (!hash_setup(c, f, v, reinterpret_cast<float*>(sc), g)) return false;
-  HC_MARK(1);
-  hash_reset(v, g);
-  wg_phase();
-  HC_MARK(2);
-  for (uint32_t i = tid; i < M; i += kT) hash_insert<FrameScope>(v, g, i);
-  wg_phase();
-  HC_MARK(3);
-  const uint32_t C = hash_blocks(v, g, sc);
-  wg_phase();
-  HC_MARK(4);
-  for (uint32_t i = tid; i < M; i += kT) hash_cell<FrameScope>(v, i);
-  wg_phase();
-  HC_MARK(5);
-  hash_starts(v, C, sc);
-  wg_phase();
-  for (uint32_t i = tid; i < M; i += kT) hash_place<FrameScope>(v, i);
-  wg_phase();
-  HC_MARK(6);
-  {
-    const float tol2 = (float)(c.p.cluster_tol * c.p.cluster_tol);
-    FrameScope::Clock clk;
-    for (uint32_t A = tid; A < C; A += kT) hash_edges<FrameScope>(v, g, A, tol2, clk);
-    clk.flush();
-  }
-  wg_phase();
-  HC_MARK(7);
-  for (uint32_t t0 = 0; t0 < C; t0 += kT) {
-    const uint32_t A = t0 + tid;
-    uint32_t root = 0;
-    if (A < C) root = FrameScope::find(v.cpar, A);
-    wg_phase();   // (path halving rewrites parents: finish every find of the tile before the roots are stored)
-    if (A < C) hash_root<FrameScope>(v, A, root);
-  }
-  wg_phase();
-  HC_MARK(8);
-  hash_tail(c, f, v, C, sc);
-  HC_MARK(9);
-#ifdef ILCC_K2_TIMING
-  if (tid == 0)
-    printf("K2 counters (all frames so far): finds %llu hops %llu cell pairs tested %llu hits %llu; thread-cycles lookups %llu masks+findA %llu window %llu find/unite %llu tests %llu loop %llu\n", g_k2_finds, g_k2_hops, g_k2_pairs, g_k2_hits, g_k2_t[0], g_k2_t[1], g_k2_t[2], g_k2_t[3], g_k2_t[4], g_k2_t[5]);
-  if (tid == 0)
-    printf("K2 hashed M=%u C=%u table %u cycles: bbox %llu reset %llu insert %llu blocks %llu cells %llu sort %llu edges %llu comps %llu nn+compact %llu\n",
-           M, C, g.mask + 1u, hmark[1] - hmark[0], hmark[2] - hmark[1], hmark[3] - hmark[2], hmark[4] - hmark[3], hmark[5] - hmark[4], hmark[6] - hmark[5],
-           hmark[7] - hmark[6], hmark[8] - hmark[7], hmark[9] - hmark[8]);
-#endif
-  return true;
-}
-
 // ------------------------------------------------------------------ the kernel, its LDS and its launcher
 uint32_t cluster_bits_default() { return (uint32_t)kFineBits; }
 uint32_t cluster_bits_online() { return (uint32_t)kFineBitsOnline; }
@@ -443,22 +355,17 @@ __global__ __launch_bounds__(1024) void k2_seeded_cluster(Ctx c) {
     if (threadIdx.x == 0) c.frame_flags[f] = 1u;
     return;
   }
-  // the LDS cell grid cannot hold this frame: the same components on cells with the cells in a hash table (global memory) ...
-  __syncthreads();
-  if (hashed_cluster_frame(c, f, L.sc)) return;
-  // ... and beyond that path's limits (> 65 536 ROI points in one frame, a bounding grid of > 2^32 blocks): point-level search
-  __syncthreads();
-  point_level_cluster_frame(c, f, L.sc);
+  // The LDS cell grid cannot hold this frame: k2_fallback_cluster, launched behind this kernel, clusters it on hashed cells or on
+  // points.  fine_cluster_frame returned false before it wrote any word of the frame's result (record, `cluster`), so the
+  // frame reaches that launch as K1 left it.  The fallback's code is kept out of this kernel for the registers it costs every
+  // wavefront here: 113 VGPRs with it inlined, 59 without.
+  if (threadIdx.x == 0) c.fallback_list[atomicAdd(c.grid_iters + kFallbackWord, 1ull)] = f;
 }
 
 // up to a CU's whole LDS as dynamic LDS (> the 64 KiB default cap).  Called by ilcc_create for the handle's device: the attribute
 // is kept per (function, device).
 hipError_t set_kernel_attributes_k2() {
-#ifdef ILCC_K2_TIMING
-  return hipFuncSetAttribute((const void*)k2_seeded_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, kClusterLdsMax);   // (the timers' static LDS)
-#else
   return hipFuncSetAttribute((const void*)k2_seeded_cluster, hipFuncAttributeMaxDynamicSharedMemorySize, kCuLdsBytes);
-#endif
 }
 
 hipError_t cluster_limits(int device, ClusterLimits* out) {
@@ -496,6 +403,8 @@ ClusterLaunch launch_cluster(const Ctx& c, hipStream_t s, const ClusterLimits& l
   if (home == kClusterHomeL2) k.cluster_lds_points = 0u;   // no frame fits "the capacity": fine_cluster_frame<false> for all
   const size_t lds = cluster_lds_bytes(k.cluster_lds_points, k.cluster_cells_cap, k.cluster_bits);
   hipLaunchKernelGGL(k2_seeded_cluster, dim3(k.n_frames), dim3(threads), lds, s, k);
+  // (the online caller's first tier flags the frames the grid cannot hold for its second tier instead of listing them)
+  if (c.online_tier == 0u) launch_cluster_fallback(c, s, (uint32_t)threads);
   return ClusterLaunch{home, (uint32_t)lds, (uint32_t)threads};
 }
 

@@ -31,10 +31,11 @@
 // the exact 1-NN of the click wins, otherwise index 0.  Members are emitted in index order.  Every path ends in the same
 // choice and compaction (choose_cluster, compact_cluster).
 //
-// The files: k2_cluster.hip (the per-frame launch k2_seeded_cluster: the LDS-grid path, the hashed cells by the frame's own
-// workgroup, the launcher), k2h_listed.hip (the k2h_* chain and its launcher), k2_hashed.h (the hashed-cell phases both run),
+// The files: k2_cluster.hip (the per-frame launch k2_seeded_cluster: the LDS-grid path, the list of the frames it cannot hold,
+// the launcher), k2_fallback.hip (k2_fallback_cluster behind it: a listed frame's hashed cells by one workgroup, the point-level
+// search), k2h_listed.hip (the k2h_* chain and its launcher), k2_hashed.h (the hashed-cell phases those two run),
 // k2_point_level.h (the last resort of both) and this header: the union-find, the block-wide helpers, the reference's distance
-// and the tail every path ends in.  Included by the two .hip files (through k2_hashed.h and k2_point_level.h).
+// and the tail every path ends in.  Included by the three .hip files (the last two through k2_hashed.h and k2_point_level.h).
 #pragma once
 
 #include "ilcc_internal.h"

@@ -1,5 +1,5 @@
 // k2_hashed.h -- components on cells with the cells in a HASH TABLE in global memory (round 5): the phases hash_setup ...
-// hash_tail, their types and the two memory-scope policies they are instantiated with.  Included by k2_cluster.hip
+// hash_tail, their types and the two memory-scope policies they are instantiated with.  Included by k2_fallback.hip
 // (hashed_cluster_frame: one workgroup per frame, WgScope) and by k2h_listed.hip (the k2h_* chain, AgentScope).
 //
 // Frames the LDS cell grid cannot hold -- the un-cropped clouds of the online caller (get_chessboard_by_point,
@@ -95,7 +95,7 @@ __device__ __forceinline__ void wg_phase() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (buffer_inv: invalidates the CU's L1)
 }
 // The counters of the edge search and of the one-workgroup union-find, as a policy: nothing here.  A -DILCC_K2_TIMING build of
-// k2_cluster.hip gives the one-workgroup path a clock that counts (EdgeClock there, beside the device globals it adds to).
+// k2_fallback.hip gives the one-workgroup path a clock that counts (EdgeClock there, beside the device globals it adds to).
 struct NoClock {
   __device__ void lap(int) {}
   __device__ void pair() {}

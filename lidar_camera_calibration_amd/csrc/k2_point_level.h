@@ -1,5 +1,5 @@
 // k2_point_level.h -- the point-level spatial hash of rounds 1-3 by one workgroup: the last resort for a frame beyond the limits
-// of both cell paths (k2_common.h).  Called by k2_seeded_cluster (k2_cluster.hip) and by k2h_finish (k2h_listed.hip).
+// of both cell paths (k2_common.h).  Called by k2_fallback_cluster (k2_fallback.hip) and by k2h_finish (k2h_listed.hip).
 #pragma once
 
 #include "k2_common.h"

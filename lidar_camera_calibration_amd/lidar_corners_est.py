@@ -311,12 +311,13 @@ class LidarCornersBatch:
 
     def debug_cluster_launch(self) -> dict:
         """What the handle's last K2 launch used and the limits the rule works from: home, dynamic LDS bytes and threads per
-        workgroup; the kernel's static LDS bytes, the device's LDS bytes per compute unit and its compute units."""
+        workgroup; the kernel's static LDS bytes, the device's LDS bytes per compute unit and its compute units; the frames of
+        the last finished batch that went to K2's fallback launch, and the most workgroups that launch has."""
         out = (C.c_uint32 * N.CLUSTER_LAUNCH_WORDS)()
         st = self._lib.ilcc_debug_cluster_launch(self._h, out)
         if st != N.OK:
             raise IlccError(st, self._err())
-        return dict(zip(("home", "lds_bytes", "threads", "static_lds_bytes", "lds_per_cu", "cus"), (int(v) for v in out)))
+        return dict(zip(("home", "lds_bytes", "threads", "static_lds_bytes", "lds_per_cu", "cus", "fallback_frames", "fallback_grid"), (int(v) for v in out)))
 
     def wait_compact(self, ticket) -> np.ndarray:
         """The batch's compact records: [n_frames, RECORD_HEADER + 3 * board corners] float32 (layout:
